@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: P1 Laplace apply() on level-8 macro-cells, DoF-updates/s + HBM roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--level L] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--level L] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--regions R]]
+
+A plain run sets up, warms up, times ONE region of exactly K steps and prints the result line (value, ms_per_step and the
+roofline figures of that region).  --full adds everything that takes runs of its own: R = 25 regions (the headline is then
+the median region), the copy floor, the Infinity-Cache-sized ring, an event pair around every step, the level-9 supporting
+figure and the CPU baseline.  --dump-outputs DIR writes the destination arrays of the last timed step as DIR/*.npy.
 
 A "step" is ONE P1ConstantLaplaceOperator::apply(src, dst, level, Inner, Replace) through the C++ host layer
 (hyteg_amd/host, the mirror of HyTeG's operator API), which calls the HIP kernels through the C-ABI.  Inputs are
@@ -111,6 +116,23 @@ def cpu_baseline(level: int, w, budget_s: float = 10.0, threads: int = 16):
     }
 
 
+DUMP_BYTES = 60_000_000  # below the 64 MB the option promises, .npy headers included
+
+
+def dump_outputs(outputs, out_dir, world):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64; an array beyond its share of DUMP_BYTES (all ranks
+    together) is written as a fixed sample, the entries at sorted indices drawn with seed 0 (the same on every run)"""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // 8 // (world * max(1, len(outputs)))
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(out_dir / f"{name}.npy", a)
+
+
 MESH_FOR_WORLD = {1: "tet_1el", 2: "pyramid_2el", 4: "pyramid_4el", 8: "regular_octahedron_8el"}
 
 
@@ -150,11 +172,18 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--level", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--regions", type=int, default=25,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: 25 regions by default, copy floor, Infinity-Cache ring, "
+                         "per-step events, level-9 supporting figure, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--regions", type=int, default=None,
                     help="the timed K-step region is repeated this many times (each one bracketed by barrier + synchronize); "
-                         "value / ms_per_step / launch_us are the MEDIAN region, min and first region are reported beside it")
+                         "value / ms_per_step / launch_us are the MEDIAN region, min and first region are reported beside it "
+                         "(default: 25 with --full, else 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the destination arrays of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    n_regions = max(1, args.regions if args.regions is not None else (25 if args.full else 1))
 
     import numpy as np
     import torch
@@ -307,8 +336,8 @@ def main():
 
     ev0, ev1 = capi.event_create_timing(), capi.event_create_timing()
 
-    def region(fn):
-        """EXACTLY K steps between barrier + synchronize on both sides (wall clock) and between two HIP events recorded on
+    def region(fn, steps=None):
+        """EXACTLY K steps (or `steps`) between barrier + synchronize on both sides (wall clock) and between two HIP events recorded on
         the launch stream by the C loop that issues the K steps, directly before the first and after the last launch (device
         time; an event recorded from Python sits 5-8 us of interpreter time in front of the first launch, which a K = 20
         region of an otherwise idle GPU sees as 0.3 us per step: profiles/r03_k20_probe.txt)"""
@@ -317,7 +346,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        fn(0, args.steps, ev0, ev1)
+        fn(0, args.steps if steps is None else steps, ev0, ev1)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -331,23 +360,33 @@ def main():
         # buffer falls into the timed region; then the W warm-up steps of the contract
         apply_steps(0, pre_warm)
         apply_steps(0, args.warmup)
+        if not args.full:
+            # untimed: one region of the same shape (barriers, events, the same C loop, at most 2000 steps) in front of the
+            # timed one, which would otherwise be the first region of the run -- in runs of 25 regions the first one is
+            # the slowest (K = 20: 18.5 us per step against 15.1 for the median, BENCH_r03.json)
+            region(apply_steps, min(args.steps, 2000))
         # R regions of K steps each.  The copy floor (N = 1) is measured by R more regions AFTER the apply regions, not between
         # them: a copy region in front of an apply region changes what the Infinity Cache holds and made short (K = 20) apply
         # regions 19 % slower (profiles/r03_region_probe.txt)
         walls, devs, copies = [], [], []
-        for r in range(max(1, args.regions)):
+        for r in range(n_regions):
             w_, d_ = region(apply_steps)
             walls.append(w_)
             devs.append(d_)
+        # what the caller of the last timed step receives: the destination of ring pair (K - 1) % nbuf
+        outputs = ({f"dst_rank{rank}_cell{c}": dsts[(args.steps - 1) % nbuf].download_cell(c, level)
+                    for c in range(storage.n_local_cells)} if args.dump_outputs else None)
+        small.clear()
+        if not args.full:
+            return walls, devs, copies, None, outputs
         if world == 1 and os.environ.get("HYTEG_BENCH_COPY", "1") != "0":
             copy_steps(0, nbuf)
-            for r in range(max(1, args.regions)):
+            for r in range(n_regions):
                 copies.append(region(copy_steps)[1])
         # the ring of rounds 1-2 (sources fit into the Infinity Cache), for continuity: NOT the headline
-        small.clear()
         if world == 1 and os.environ.get("HYTEG_BENCH_SMALL_RING", "1") != "0":
             apply_steps_small_ring(0, 4 * nbuf_small)
-            for r in range(min(9, max(1, args.regions))):
+            for r in range(min(9, n_regions)):
                 small.append(region(apply_steps_small_ring)[1])
 
         # the same K steps once more, every step between its own pair of events (reported beside the region mean: an upper
@@ -359,14 +398,14 @@ def main():
             evs[k + 1].record(stream)
         torch.cuda.synchronize()
         per_step_us = sorted(evs[k].elapsed_time(evs[k + 1]) * 1e3 for k in range(args.steps))
-        return walls, devs, copies, per_step_us
+        return walls, devs, copies, per_step_us, outputs
 
     # untimed, before the W warm-up steps: the GPU's clocks follow the load over tens of milliseconds, and a run of 25 regions of
     # K = 20 steps is 5 ms of work after seconds of set-up -- without this its regions measure the ramp (10.1-10.3 us per launch
     # against 9.5 with it and 9.3 for K = 2000, same box; HYTEG_BENCH_PREWARM=0 switches it off, at least 2 * nbuf applies remain)
     small = []
     pre_warm = max(2 * nbuf, int(os.environ.get("HYTEG_BENCH_PREWARM", "10000")))
-    walls, devs, copies, per_step_us = measure()
+    walls, devs, copies, per_step_us, outputs = measure()
     if world > 1 and ctx.transport == "p2p":
         ok, err = True, ""
         try:
@@ -377,9 +416,11 @@ def main():
             ok, err = False, repr(e)
         if not all_ranks(ok):
             ctx.disable_p2p(f"peer-to-peer exchange failed its check after the timed region {err}: measured again on {ctx.inner_transport}")
-            walls, devs, copies, per_step_us = measure()
+            walls, devs, copies, per_step_us, outputs = measure()
     p2p["verified_on_check_pairs"] = world > 1 and ctx.transport == "p2p"
-    median_us = per_step_us[len(per_step_us) // 2]
+    median_us = per_step_us[len(per_step_us) // 2] if per_step_us else float("nan")
+    if outputs is not None:
+        dump_outputs(outputs, Path(args.dump_outputs), world)
 
     if dist is not None:
         # MAX over ranks, region by region
@@ -441,6 +482,8 @@ def main():
                 "pre_warm_note": "untimed applies BEFORE the W warm-up steps of the contract: two passes over the buffer ring (no first access "
                                  "inside the timed region) and, by default, 10000 applies (~0.1 s) that bring the GPU's clocks up; "
                                  "HYTEG_BENCH_PREWARM=0 leaves only the ring passes (K = 20: 10.1-10.3 us per launch instead of 9.5, DESIGN 3.1)",
+                "full": args.full,
+                "warmup_region_steps": 0 if args.full else min(args.steps, 2000),
                 "mesh_note": "1/2/4/8 GPUs run tet_1el / pyramid_2el / pyramid_4el / regular_octahedron_8el (one macro-cell per GPU);"
                              " they stand in for the MultigridStudies cube, whose 6 or 24 cells do not give one cell per GPU",
                 "halo_exchange": (f"transport '{ctx.transport}': "
@@ -475,8 +518,8 @@ def main():
                 "copy_us_min_region": (min(copies) * 1e3 / args.steps / storage.n_local_cells) if copies else None,
                 "copy_bytes_per_launch": 16 * n if copies else None,
                 "frac_of_copy": (copy_us / launch_us) if copy_us else None,
-                "per_step_event_median_us": median_us,
-                "per_step_event_min_us": per_step_us[0],
+                "per_step_event_median_us": median_us if per_step_us else None,
+                "per_step_event_min_us": per_step_us[0] if per_step_us else None,
                 "algorithmic_bytes_per_launch": algo_bytes,
                 "infinity_cache_assisted": ({
                     "launch_us": sorted(small)[len(small) // 2] * 1e3 / args.steps,
@@ -508,14 +551,14 @@ def main():
                 "copy_us_all": [round(d * 1e3 / args.steps / storage.n_local_cells, 3) for d in copies],
             },
         }
-        if world == 1 and level == 8 and os.environ.get("HYTEG_BENCH_LEVEL9", "1") != "0":
+        if args.full and world == 1 and level == 8 and os.environ.get("HYTEG_BENCH_LEVEL9", "1") != "0":
             # supporting figure, NOT the headline: the same kernel one refinement level up, where one launch lasts long enough
             # for the fixed cost per launch (start and tail of the grid, ~3 us) to stop mattering
             try:
                 out["roofline"]["level9_supporting"] = level9_supporting(host, capi, storage, stream, region, rng)
             except Exception as e:  # noqa: BLE001 -- never costs the headline line
                 out["roofline"]["level9_supporting"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(level, list(w))
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -505,11 +505,8 @@ def ref_fenics():
     """ctypes handle on oracle/_ref/libhyteg_ref_fenics.so or None if it was never built
     (it can only be built where /root/reference is mounted)."""
     so = _HERE / "_ref" / "libhyteg_ref_fenics.so"
-    if not so.exists():
-        if Path("/root/reference/src/hyteg/forms/form_fenics_generated").is_dir():
-            subprocess.run(["make", "-C", str(_HERE), "ref"], check=True, capture_output=True)
-        if not so.exists():
-            return None
+    if not so.exists():  # build() makes it (make -C oracle ref) where the reference is mounted
+        return None
     l = C.CDLL(str(so))
     for n in ("ref_p1_tet_diffusion", "ref_p1_tet_mass", "ref_p2_tet_diffusion", "ref_p1_tet_pspg"):
         if not hasattr(l, n):

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import ref_golden
 from conftest import OCT_TET, REF_TET, SKEW_TET
 from oracle import p1_oracle as po
 
@@ -61,9 +62,7 @@ def test_every_micro_cell_touches_ten_distinct_valid_dofs_and_every_dof_is_touch
 
 @pytest.mark.parametrize("tet", [REF_TET, OCT_TET, SKEW_TET])
 def test_p2_element_matrix_equals_the_references_generated_form(tet):
-    ref = po.ref_fenics()
-    if ref is None or not hasattr(ref, "ref_p2_tet_diffusion"):
-        pytest.skip("oracle/_ref not built (reference not mounted)")
+    ref = ref_golden.ref_fenics()
     c = np.ascontiguousarray(tet, dtype=np.float64).reshape(12)
     R = np.empty(100)
     ref.ref_p2_tet_diffusion(R.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_double)))

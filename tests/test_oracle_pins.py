@@ -3,6 +3,7 @@ properties for the P1 hot path.  CPU only."""
 import numpy as np
 import pytest
 
+import ref_golden
 from oracle import p1_oracle as po
 from conftest import OCT_TET, REF_TET, SKEW_TET
 
@@ -56,16 +57,13 @@ def test_on_cell_primitive_classification():
 
 # (tolerance 2e-14 relative: the generated code uses 16-digit decimal literals such as 0.1666666666666667)
 # ---- element matrix vs the reference's generated FEniCS code, compiled in place (oracle/_ref) ----
-def _ref_or_skip():
-    ref = po.ref_fenics()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference not mounted)")
-    return ref
+def _reference_forms():
+    return ref_golden.ref_fenics()  # the library where it is built, its recorded outputs everywhere (tests/ref_golden.py)
 
 
 @pytest.mark.parametrize("tet", [REF_TET, OCT_TET, SKEW_TET])
 def test_element_matrices_match_reference_fenics(tet):
-    ref = _ref_or_skip()
+    ref = _reference_forms()
     c = np.asarray(tet, dtype=np.float64).reshape(12)
     A = np.empty(16)
     ref.ref_p1_tet_diffusion(po._p(A), po._p(c))
@@ -82,7 +80,7 @@ def test_stokes_block_element_matrices_match_reference_fenics(tet, form):
     """div x/y/z, divT x/y/z, PSPG (the blocks of src/mixed_operator/P1P1StokesOperator.hpp:51-64) against the reference's
     generated p1_tet_div_tet.h / p1_tet_divt_tet.h / p1_tet_pspg_tet.h compiled in place; these matrices are NOT
     symmetric, so this also pins the index convention A[test][trial] (row-major, P1FenicsForm.hpp:96-124 reads row 0)"""
-    ref = _ref_or_skip()
+    ref = _reference_forms()
     A = po.ref_element_matrix(ref, tet, form)
     mine = po.element_matrix(tet, form)
     assert np.abs(A).max() > 0
@@ -138,7 +136,7 @@ _MICRO_TETS = [
 @pytest.mark.parametrize("level", [2, 5, 8])
 @pytest.mark.parametrize("form", [0, 2, 3, 4, 5, 6, 7, 8])
 def test_cell_stencil_matches_assembly_from_reference_element_matrices(tet, level, form):
-    ref = _ref_or_skip()
+    ref = _reference_forms()
     w = dict.fromkeys(po.STENCIL_NAMES, 0.0)
     for cellspec in _MICRO_TETS:
         names = cellspec.split()

@@ -5,6 +5,7 @@ as src/mixed_operator/P2ToP1ConstantOperator.hpp:90-97 and P1ToP2ConstantOperato
 import numpy as np
 import pytest
 
+import ref_golden
 from conftest import SKEW_TET
 from oracle import p1_oracle as po
 
@@ -17,9 +18,7 @@ TETS = [np.asarray(SKEW_TET, dtype=np.float64).reshape(12), np.array([0, 0, 0, 1
 def test_mixed_forms_are_the_reference_fenics_forms(which, k):
     from hyteg_amd import host
 
-    ref = po.ref_fenics()
-    if ref is None or not hasattr(ref, "ref_p2_to_p1_tet_div"):
-        pytest.skip("oracle/_ref was not built (the reference is not mounted)")
+    ref = ref_golden.ref_fenics()
     host.lib()
     for co in TETS:
         M = host.taylor_hood_form_element_matrix(which, k, co)

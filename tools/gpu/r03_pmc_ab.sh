@@ -8,7 +8,7 @@ for v in 0 1; do
  for C in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_WRITE_sum"; do
   N=$(echo $C | tr " " "_" | cut -c1-24)
   export $VAR=$v
-  timeout -k 10 200 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/v${v}_$N -- python3 $R/bench.py --steps 100 --warmup 20 --regions 2 --no-cpu-baseline > $O/v${v}_$N.log 2>&1 || echo "pass $v $N failed"
+  timeout -k 10 200 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/v${v}_$N -- python3 $R/bench.py --full --steps 100 --warmup 20 --regions 2 --no-cpu-baseline > $O/v${v}_$N.log 2>&1 || echo "pass $v $N failed"
  done
 done
 python3 - <<PY

@@ -82,7 +82,7 @@ out = {
     "read_bytes": int(round(read_b)),
     "write_bytes": int(round(write_b)),
     "kernel_as_rocprof_names_it": kname,
-    "method": "rocprofv3 --kernel-trace --pmc, separate passes for FETCH_SIZE and WRITE_SIZE over `python3 bench.py --steps 100 "
+    "method": "rocprofv3 --kernel-trace --pmc, separate passes for FETCH_SIZE and WRITE_SIZE over `python3 bench.py --full --steps 100 "
               f"--warmup 20 --regions 2 --no-cpu-baseline` ({nf} / {nw} dispatches, level 8, rotating buffers); counters are in KiB "
               "(tools/profile_bench.sh, tools/pmc_traffic.py)",
     "raw": {"FETCH_SIZE_avg_KiB": fetch, "WRITE_SIZE_avg_KiB": write, "calib_FETCH_SIZE_avg_KiB": cfetch, "calib_WRITE_SIZE_avg_KiB": cwrite},
