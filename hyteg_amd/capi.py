@@ -78,6 +78,8 @@ SIGNATURES = {
     "hyteg_hip_convert_f32_to_f64": (_i, [_vp, _vp, _sz, _vp]),
     "hyteg_hip_axpy_f32_into_f64": (_i, [_vp, _vp, _d, _sz, _vp]),
     "hyteg_hip_p1_jacobi_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _d, _vp]),
+    "hyteg_hip_p1_chebyshev_start_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _vp]),
+    "hyteg_hip_p1_chebyshev_step_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _d, _d, _i, _vp]),
     "hyteg_hip_p1_sor_cell": (_i, [_vp, _vp, _i, _dp, _d, _i, _vp]),
     "hyteg_hip_p1_residual_cell": (_i, [_vp, _vp, _vp, _i, _dp, _vp]),
     "hyteg_hip_p1_sor_cell_sweeps": (_i, [_vp, _vp, _i, _dp, _d, _i, _i, _vp]),
@@ -353,6 +355,17 @@ def p1_apply_cell(dst, src, level, w, update=REPLACE, stream=0):
 def p1_jacobi_cell(dst, rhs, src, level, w, relax, invdiag=None, stream=0):
     check(lib().hyteg_hip_p1_jacobi_cell(dst, rhs, src, invdiag, level, _w15(w), float(relax), stream),
           "p1_jacobi_cell")
+
+
+def p1_chebyshev_start_cell(t_out, rhs, x, level, w, invdiag=None, stream=0):
+    """t_out = invDiag .* (rhs - A x) on the cell interior (x is not updated: the next step applies the deferred update)"""
+    check(lib().hyteg_hip_p1_chebyshev_start_cell(t_out, rhs, x, invdiag, level, _w15(w), stream), "p1_chebyshev_start_cell")
+
+
+def p1_chebyshev_step_cell(t_out, x, t_in, level, w, c_prev, c_cur, has_prev=True, invdiag=None, stream=0):
+    """t_out = invDiag .* (A t_in); x = (x + c_prev t_in) + c_cur t_out (first term only if has_prev), one launch"""
+    check(lib().hyteg_hip_p1_chebyshev_step_cell(t_out, x, t_in, invdiag, level, _w15(w), float(c_prev), float(c_cur),
+                                                 int(bool(has_prev)), stream), "p1_chebyshev_step_cell")
 
 
 SOR_AUTO, SOR_PLANES, SOR_BLOCKS, SOR_DATAFLOW = 0, 1, 2, 3

@@ -136,7 +136,10 @@ enum ApplyMode
    // the two fused steps of the mixed-precision Jacobi smoother (double arrays in, float arrays out, and back):
    APPLY_RESIDUAL_F32OUT = 4, // double arithmetic: r = rhs - A src; dst (float) = r, dst2 (float) = relax * r / centre  (= the first Jacobi
                               //   sweep on A e = r from e = 0)
-   APPLY_JACOBI_ACCUM = 5     // float arithmetic: e = src + relax * ( rhs - A src ) / centre (src, rhs float); xacc (double) += e; e is not stored
+   APPLY_JACOBI_ACCUM = 5,    // float arithmetic: e = src + relax * ( rhs - A src ) / centre (src, rhs float); xacc (double) += e; e is not stored
+   // the two fused steps of the Chebyshev smoother (host/chebyshev.hpp ChebyshevSmoother::solve):
+   APPLY_CHEB_START = 6, // dst = invdiag .* ( rhs - A src )                                           (src = x, not updated here)
+   APPLY_CHEB_STEP  = 7  // dst = invdiag .* ( A src );  xacc = ( xacc + relax2 * src ) + relax * dst  (first term only if `flag`)
 };
 
 struct Stencil15

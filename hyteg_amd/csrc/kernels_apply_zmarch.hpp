@@ -2,6 +2,8 @@
 // Replaces apply_3D_macrocell_vertexdof_to_vertexdof_{replace,add} (reference:
 // src/constant_stencil_operator/P1generatedKernels/apply_3D_macrocell_vertexdof_to_vertexdof_replace.cpp:34-78)
 // and the 1 apply + 3 vector passes of P1Operator::smooth_jac (src/hyteg/p1functionspace/P1Operator.hpp:429-447).
+// and, per step of ChebyshevSmoother::solve (src/hyteg/solvers/ChebyshevSmoother.hpp:165-212), the apply, the multiplication with
+// the inverse diagonal and the update of the iterate (modes APPLY_CHEB_START / APPLY_CHEB_STEP).
 //
 // One WAVE owns a brick of NY rows x 64 x-positions (lanes 1..62 produce outputs) x LZ slices and marches in +z.
 // Slice z+1's rows are loaded ONCE and serve as "up" rows for slice z, centre rows for z+1 and "down" rows for z+2
@@ -55,9 +57,9 @@ struct ZMarchArgs
    void*            dst;
    const void*      src;
    const void*      rhs;     // JACOBI / RESIDUAL modes
-   const void*      invdiag; // JACOBI only, may be null
+   const void*      invdiag; // JACOBI / CHEB_START / CHEB_STEP, may be null
    void*            dst2;    // RESIDUAL_F32OUT: second float output (the first Jacobi iterate of the error equation)
-   double*          xacc;    // JACOBI_ACCUM: the double array the last float sweep is added to
+   double*          xacc;    // JACOBI_ACCUM: the double array the last float sweep is added to; CHEB_STEP: the iterate x
    const BrickTask* tasks;   // table mode (DEC == false)
    int              ntasks;
    unsigned         bytes;     // size of the cell array in bytes (buffer range): entries x sizeof( value type )
@@ -66,6 +68,8 @@ struct ZMarchArgs
    double           relax;
    Stencil15        st;
    int              zs[kZMarchMaxZChunks]; // decode mode: first task of z-chunk k (entries past the last chunk = ntasks)
+   double           relax2; // CHEB_STEP: coefficient of the deferred update x += relax2 * src ...
+   int              flag;   // ... which is applied only if flag != 0
 };
 
 #ifndef HYTEG_ZM_WAVES_PER_BLOCK
@@ -228,15 +232,18 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
    constexpr int kStAux = ST_AUX; // 2 = nontemporal (the default; 1 = sc0, 16 = sc1: measured variants)
    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc( const_cast< void* >( A.src ), 0, A.bytes, 0x00020000 );
    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc( A.dst, 0, MODE == APPLY_RESIDUAL_F32OUT ? A.bytes / 2 : A.bytes, 0x00020000 );
-   constexpr bool kHasRhs = MODE == APPLY_JACOBI || MODE == APPLY_RESIDUAL || MODE == APPLY_RESIDUAL_F32OUT || MODE == APPLY_JACOBI_ACCUM;
+   constexpr bool kHasRhs = MODE == APPLY_JACOBI || MODE == APPLY_RESIDUAL || MODE == APPLY_RESIDUAL_F32OUT || MODE == APPLY_JACOBI_ACCUM ||
+                            MODE == APPLY_CHEB_START;
+   constexpr bool kHasInv = MODE == APPLY_JACOBI || MODE == APPLY_CHEB_START || MODE == APPLY_CHEB_STEP; // pointwise inverse diagonal (or 1 / centre)
+   static_assert( MODE != APPLY_CHEB_STEP || SZ == 8, "the Chebyshev step updates a double iterate" );
    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc( const_cast< void* >( kHasRhs ? A.rhs : A.src ), 0, A.bytes, 0x00020000 );
    // mixed-precision modes: float outputs of a double kernel (half the bytes), the double accumulator of a float kernel (twice)
    const __amdgpu_buffer_rsrc_t rd2 =
        __builtin_amdgcn_make_buffer_rsrc( MODE == APPLY_RESIDUAL_F32OUT ? A.dst2 : A.dst, 0, MODE == APPLY_RESIDUAL_F32OUT ? A.bytes / 2 : A.bytes, 0x00020000 );
    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-       MODE == APPLY_JACOBI_ACCUM ? (void*) A.xacc : A.dst, 0, MODE == APPLY_JACOBI_ACCUM ? A.bytes * 2 : A.bytes, 0x00020000 );
+       ( MODE == APPLY_JACOBI_ACCUM || MODE == APPLY_CHEB_STEP ) ? (void*) A.xacc : A.dst, 0, MODE == APPLY_JACOBI_ACCUM ? A.bytes * 2 : A.bytes, 0x00020000 );
    const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-       const_cast< void* >( ( MODE == APPLY_JACOBI && A.invdiag ) ? A.invdiag : A.src ), 0, A.bytes, 0x00020000 );
+       const_cast< void* >( ( kHasInv && A.invdiag ) ? A.invdiag : A.src ), 0, A.bytes, 0x00020000 );
 
    const int lane_off = lane * SZ;
    const int ym       = t.y0 - 1; // first row held per slice
@@ -300,8 +307,8 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
    // whole memory round trip at its first store of every slice -- 16.9 us for the fused Jacobi against 9.7 us for the apply,
    // i.e. 7 us for 23 MB more).
    T          EX0[LZ][NY], EX1[LZ][NY];
-   double     EXD[LZ][NY]; // JACOBI_ACCUM: the accumulator's old values
-   const bool hasInv = MODE == APPLY_JACOBI && A.invdiag != nullptr;
+   double     EXD[LZ][NY]; // JACOBI_ACCUM: the accumulator's old values; CHEB_STEP: the iterate's
+   const bool hasInv = kHasInv && A.invdiag != nullptr;
    auto       load_extra = [&]( auto sc ) {
       constexpr int s = decltype( sc )::value;
       constexpr int q = s + 1;
@@ -314,10 +321,13 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
          {
             const int last8 = ( W - ( t.y0 + j ) - 1 - t.xb ) * SZ;
             const int vo    = min( lane_off, last8 );
-            EX0[s][j]       = MODE == APPLY_ADD ? zm_load2< T, EX_AUX >( rd, vo, ie * SZ ) : zm_load2< T, EX_AUX >( rr, vo, ie * SZ );
+            if constexpr ( MODE == APPLY_CHEB_STEP )
+               EXD[s][j] = zm_load2< double, 0 >( rx, vo, ie * 8 ); // x: read and rewritten by this lane only; the next step re-reads it
+            else
+               EX0[s][j] = MODE == APPLY_ADD ? zm_load2< T, EX_AUX >( rd, vo, ie * SZ ) : zm_load2< T, EX_AUX >( rr, vo, ie * SZ );
             if constexpr ( MODE == APPLY_JACOBI_ACCUM )
                EXD[s][j] = zm_load2< double, 2 >( rx, min( lane * 8, last8 * 2 ), ie * 8 ); // read once, rewritten right after: nontemporal
-            if constexpr ( MODE == APPLY_JACOBI )
+            if constexpr ( kHasInv )
             {
                T v = invc; // scalar inverse diagonal unless a function was given (wave-uniform branch)
                if ( hasInv )
@@ -381,6 +391,10 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
             out = EX0[s][j] - acc; // the bits of assign( { 1, -1 }, { rhs, A src } ): one rounding of rhs - acc either way
          else if ( MODE == APPLY_JACOBI_ACCUM )
             out = a0 + relax * ( invc * ( EX0[s][j] - acc ) );
+         else if ( MODE == APPLY_CHEB_START )
+            out = EX1[s][j] * ( EX0[s][j] - acc ); // multElementwise( invDiag, assign( { 1, -1 }, { rhs, A x } ) )
+         else if ( MODE == APPLY_CHEB_STEP )
+            out = EX1[s][j] * acc;
          else
             out = a0 + relax * ( EX1[s][j] * ( EX0[s][j] - acc ) );
          if constexpr ( XS == 62 )
@@ -398,6 +412,17 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
             }
             else if constexpr ( MODE == APPLY_JACOBI_ACCUM )
                zm_store2< double, kStAux >( rx, on ? lane * 8 : -8, io * 8, EXD[s][j] + (double) out );
+            else if constexpr ( MODE == APPLY_CHEB_STEP )
+            {
+               // x = ( x + c_prev t_in ) + c_cur t_out: the update the previous launch deferred (x was its stencil source or t_in did
+               // not exist yet), then this step's; t_in's centre value is the register the stencil read it into
+               double xn = EXD[s][j];
+               if ( A.flag ) // wave-uniform
+                  xn = xn + (double) A.relax2 * (double) a0;
+               xn = xn + (double) relax * (double) out;
+               zm_store2< T, kStAux >( rd, on ? lane_off : -8, io * SZ, out );
+               zm_store2< double, kStAux >( rx, on ? lane * 8 : -8, io * 8, xn );
+            }
             else
                zm_store2< T, kStAux >( rd, on ? lane_off : -8, io * SZ, out );
          }
@@ -410,6 +435,7 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
             lo     = lo == 8 ? 4 : lo;
             const int hi  = s < t.nz ? min( lo + 56, R - 1 - t.xb ) : 0;
             const int lo1 = t.xb == 0 ? 1 : lo;
+            static_assert( MODE != APPLY_CHEB_STEP, "the Chebyshev step has no aligned-window form" );
             zm_store2< T, kStAux >( rd, (unsigned) ( lane - lo1 ) < (unsigned) max( hi - lo1, 0 ) ? lane_off : -8, io * SZ, out );
          }
          io += R;

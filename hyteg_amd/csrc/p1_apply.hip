@@ -42,10 +42,11 @@ inline BrickShape default_shape( int mode, int level, bool f32 )
    return BrickShape{ 4, 4, 2 };
 }
 
-// `extra`: the second float output of APPLY_RESIDUAL_F32OUT / the double accumulator of APPLY_JACOBI_ACCUM
+// `extra`: the second float output of APPLY_RESIDUAL_F32OUT / the double accumulator of APPLY_JACOBI_ACCUM / the iterate of APPLY_CHEB_STEP
+// (whose deferred update is relax2, applied if flag != 0)
 template < int MODE, int NY, int LZ, int PFD, typename T >
 int launch_zmarch_shape( void* dst, const T* src, const T* rhs, const T* invdiag, int level, const double* w, double relax, hipStream_t stream,
-                         void* extra = nullptr )
+                         void* extra = nullptr, double relax2 = 0.0, int flag = 0 )
 {
    BrickTable bt;
    int        rc = get_bricks( level, NY, LZ, &bt );
@@ -65,6 +66,8 @@ int launch_zmarch_shape( void* dst, const T* src, const T* rhs, const T* invdiag
    A.N       = ( 1 << level ) + 1;
    A.bytes   = (unsigned) ( tet64( A.N ) * (int64_t) sizeof( T ) );
    A.relax   = relax;
+   A.relax2  = relax2;
+   A.flag    = flag;
    for ( int k = 0; k < 15; ++k )
       A.st.w[k] = w[k];
    int nblocks = ( bt.count + kZMarchWavesPerBlock - 1 ) / kZMarchWavesPerBlock;
@@ -121,14 +124,16 @@ inline BrickShape current_shape( int mode, int level, bool f32 )
 
 template < int MODE, typename T = double >
 int launch_zmarch( void* dst, const T* src, const T* rhs, const T* invdiag, int level, const double* w, double relax, hipStream_t stream,
-                   void* extra = nullptr )
+                   void* extra = nullptr, double relax2 = 0.0, int flag = 0 )
 {
-   // the fused mixed-precision steps take the shapes of the kernels they replace (residual / float Jacobi)
-   const int        shapeMode = MODE == APPLY_RESIDUAL_F32OUT ? APPLY_RESIDUAL : ( MODE == APPLY_JACOBI_ACCUM ? APPLY_JACOBI : MODE );
+   // the fused mixed-precision steps take the shapes of the kernels they replace (residual / float Jacobi); the Chebyshev steps
+   // stream three / four arrays like the Jacobi sweep and take its shapes
+   const int shapeMode = MODE == APPLY_RESIDUAL_F32OUT ? APPLY_RESIDUAL :
+                                                         ( ( MODE == APPLY_JACOBI_ACCUM || MODE == APPLY_CHEB_START || MODE == APPLY_CHEB_STEP ) ? APPLY_JACOBI : MODE );
    const BrickShape s         = current_shape( shapeMode, level, !std::is_same< T, double >::value );
 #define HH_X( NY_, LZ_, PFD_ ) \
    if ( s == BrickShape{ NY_, LZ_, PFD_ } ) \
-      return launch_zmarch_shape< MODE, NY_, LZ_, PFD_, T >( dst, src, rhs, invdiag, level, w, relax, stream, extra );
+      return launch_zmarch_shape< MODE, NY_, LZ_, PFD_, T >( dst, src, rhs, invdiag, level, w, relax, stream, extra, relax2, flag );
    HYTEG_ZM_SHAPES( HH_X )
 #undef HH_X
    return fail( HYTEG_HIP_EINVAL, "apply: brick shape not compiled in" );
@@ -272,6 +277,86 @@ HYTEG_HIP_API int hyteg_hip_p1_jacobi_accumulate_f32( double*            x,
    HH_REQUIRE( level >= HYTEG_HIP_MIN_LEVEL && level <= 10, "p1_jacobi_accumulate_f32: level out of range [2,10]" );
    HH_REQUIRE( w[7] != 0.0, "p1_jacobi_accumulate_f32: zero centre weight" );
    return launch_zmarch< APPLY_JACOBI_ACCUM, float >( nullptr, e_f32, rhs_f32, (const float*) nullptr, level, w, relax, as_stream( stream ), x );
+}
+
+// ---- the two fused steps of the Chebyshev smoother (host/chebyshev.hpp ChebyshevSmoother::solve) ----
+// Level 11 (byte offsets beyond the 32-bit buffer addressing of the z-march kernel) composes the step from the entry points it fuses.
+HYTEG_HIP_API int hyteg_hip_p1_chebyshev_start_cell( double*            t_out,
+                                                     const double*      rhs,
+                                                     const double*      x,
+                                                     const double*      invdiag,
+                                                     int                level,
+                                                     const double*      w,
+                                                     hyteg_hip_stream_t stream )
+{
+   HH_REQUIRE( t_out && rhs && x && w, "p1_chebyshev_start_cell: null pointer" );
+   HH_REQUIRE( level_ok( level ), "p1_chebyshev_start_cell: level out of range [2,11]" );
+   HH_REQUIRE( t_out != x && t_out != rhs && t_out != invdiag, "p1_chebyshev_start_cell: t_out must not alias x, rhs or invdiag" );
+   HH_REQUIRE( w[7] != 0.0, "p1_chebyshev_start_cell: zero centre weight" );
+   if ( tet64( ( 1 << level ) + 1 ) * 8 < ( (int64_t) 1 << 31 ) )
+      return launch_zmarch< APPLY_CHEB_START >( t_out, x, rhs, invdiag, level, w, 0.0, as_stream( stream ) );
+   int rc = hyteg_hip_p1_apply_cell( t_out, x, level, w, HYTEG_HIP_REPLACE, stream );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   const double* diff[2] = { rhs, t_out };
+   const double  pm[2]   = { 1.0, -1.0 };
+   rc                    = hyteg_hip_p1_assign_cell( t_out, 2, diff, pm, level, stream );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   if ( invdiag )
+   {
+      const double* prod[2] = { invdiag, t_out };
+      return hyteg_hip_p1_mult_cell( t_out, 2, prod, level, stream );
+   }
+   const double* one[1] = { t_out };
+   const double  inv[1] = { 1.0 / w[7] };
+   return hyteg_hip_p1_assign_cell( t_out, 1, one, inv, level, stream );
+}
+
+HYTEG_HIP_API int hyteg_hip_p1_chebyshev_step_cell( double*            t_out,
+                                                    double*            x,
+                                                    const double*      t_in,
+                                                    const double*      invdiag,
+                                                    int                level,
+                                                    const double*      w,
+                                                    double             c_prev,
+                                                    double             c_cur,
+                                                    int                has_prev,
+                                                    hyteg_hip_stream_t stream )
+{
+   HH_REQUIRE( t_out && x && t_in && w, "p1_chebyshev_step_cell: null pointer" );
+   HH_REQUIRE( level_ok( level ), "p1_chebyshev_step_cell: level out of range [2,11]" );
+   HH_REQUIRE( t_out != t_in && t_out != x && x != t_in, "p1_chebyshev_step_cell: t_out, x and t_in must be three different arrays" );
+   HH_REQUIRE( invdiag != t_out && invdiag != x, "p1_chebyshev_step_cell: invdiag must not alias an output" );
+   HH_REQUIRE( w[7] != 0.0, "p1_chebyshev_step_cell: zero centre weight" );
+   if ( tet64( ( 1 << level ) + 1 ) * 8 < ( (int64_t) 1 << 31 ) )
+      return launch_zmarch< APPLY_CHEB_STEP >( t_out, t_in, (const double*) nullptr, invdiag, level, w, c_cur, as_stream( stream ), x, c_prev,
+                                               has_prev ? 1 : 0 );
+   int rc = hyteg_hip_p1_apply_cell( t_out, t_in, level, w, HYTEG_HIP_REPLACE, stream );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   if ( invdiag )
+   {
+      const double* prod[2] = { invdiag, t_out };
+      rc                    = hyteg_hip_p1_mult_cell( t_out, 2, prod, level, stream );
+   }
+   else
+   {
+      const double* one[1] = { t_out };
+      const double  inv[1] = { 1.0 / w[7] };
+      rc                   = hyteg_hip_p1_assign_cell( t_out, 1, one, inv, level, stream );
+   }
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   if ( has_prev )
+   {
+      const double* s[1] = { t_in };
+      rc                 = hyteg_hip_p1_add_cell( x, 1, s, &c_prev, level, stream );
+      if ( rc != HYTEG_HIP_OK )
+         return rc;
+   }
+   const double* s[1] = { t_out };
+   return hyteg_hip_p1_add_cell( x, 1, s, &c_cur, level, stream );
 }
 
 HYTEG_HIP_API int hyteg_hip_p1_apply_kernel_name( int level, int update, char* buf, size_t buflen )

@@ -14,6 +14,7 @@ _LIB_PATH = _PKG / "lib" / "libhyteg_host.so"
 Inner, DirichletBoundary, NeumannBoundary, FreeslipBoundary, All, Boundary = 1, 2, 4, 8, 15, 14
 Replace, Add = 0, 1
 JACOBI, GAUSS_SEIDEL, SOR, JACOBI_FP32 = 0, 1, 2, 3  # JACOBI_FP32: MixedPrecisionJacobiSmoother (float sweeps on cell interiors)
+CHEBYSHEV = 4  # ChebyshevSmoother: not a code of hyteg_host_gmg_create (it has its own entry points: Solver.chebyshev / gmg_chebyshev)
 
 _vp, _i, _d, _u = C.c_void_p, C.c_int, C.c_double, C.c_uint
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
@@ -114,6 +115,11 @@ SIGNATURES = {
     "hyteg_host_prolongate": (_i, [_vp, _i, _i]),
     "hyteg_host_prolongate_and_add": (_i, [_vp, _i, _i]),
     "hyteg_host_gmg_create": (_i, [_vp, _i, _i, _i, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_chebyshev_coefficients": (_i, [_i, _d, _d, _dp]),
+    "hyteg_host_chebyshev_estimate_radius": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(_d)]),
+    "hyteg_host_chebyshev_create": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, C.POINTER(_vp)]),
+    "hyteg_host_chebyshev_set_fused": (_i, [_vp, _i]),
+    "hyteg_host_gmg_create_chebyshev": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_gmg_set_use_graphs": (_i, [_vp, _i]),
     "hyteg_host_cg_set_use_device_scalars": (_i, [_vp, _i]),
     "hyteg_host_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
@@ -129,6 +135,10 @@ SIGNATURES = {
     "hyteg_host_p2function_interpolate_constant": (_i, [_vp, _d, _i, _i]),
     "hyteg_host_p2function_assign": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_vp), _i, _i]),
     "hyteg_host_p2function_add": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_vp), _i, _i]),
+    "hyteg_host_p2function_mult_elementwise": (_i, [_vp, _i, C.POINTER(_vp), _i, _i]),
+    "hyteg_host_p2_chebyshev_estimate_radius": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(_d)]),
+    "hyteg_host_p2_chebyshev_create": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2_gmg_create_chebyshev": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_p2function_dot": (_i, [_vp, _vp, _i, _i, C.POINTER(_d)]),
     "hyteg_host_p2operator_create_constant": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "hyteg_host_p2_prolongate": (_i, [_vp, _i, _i, _i]),
@@ -187,6 +197,30 @@ def _ck(rc, what):
             exc, _hook_exception = _hook_exception, None
             raise HytegHostError(msg) from exc
         raise HytegHostError(msg)
+
+
+def _radii(radii):
+    r = np.atleast_1d(np.asarray(radii, dtype=np.float64)).copy()
+    return r, r.ctypes.data_as(_dp), int(r.size)
+
+
+def chebyshev_coefficients(order: int, lower: float, upper: float) -> np.ndarray:
+    """chebyshev::coefficients: monomial coefficients c[0..order-1] of p in
+    1 - l p(l) = T_n((theta - l) / delta) / T_n(theta / delta); needs no GPU"""
+    if order < 1:
+        raise ValueError("chebyshev_coefficients: order must be at least 1")
+    out = np.empty(int(order))
+    _ck(lib().hyteg_host_chebyshev_coefficients(int(order), float(lower), float(upper), out.ctypes.data_as(_dp)), "chebyshev_coefficients")
+    return out
+
+
+def estimate_radius(op, level: int, max_iter: int, x, tmp) -> float:
+    """chebyshev::estimateRadius: spectral radius of D^-1 A by max_iter power iterations from the start vector x (overwritten);
+    op: P1ConstantOperator with P1Functions, or a P2 Laplace operator with P2Functions (inverse diagonal computed)"""
+    r = _d()
+    fn = lib().hyteg_host_p2_chebyshev_estimate_radius if isinstance(op, P2ElementwiseLaplaceOperator) else lib().hyteg_host_chebyshev_estimate_radius
+    _ck(fn(op.h, int(level), int(max_iter), x.h, tmp.h, C.byref(r)), "chebyshev_estimate_radius")
+    return r.value
 
 
 def cell_size(level: int) -> int:
@@ -540,10 +574,35 @@ class Solver:
     @classmethod
     def gmg(cls, storage, min_level, max_level, smoother=JACOBI, relax=2.0 / 3.0, pre=3, post=3, wcycle=False, cg_max_iter=1000,
             cg_tol=1e-14):
+        if smoother == CHEBYSHEV:
+            raise ValueError("Solver.gmg: the Chebyshev smoother needs an order and spectral radii, use Solver.gmg_chebyshev")
         h = _vp()
         _ck(lib().hyteg_host_gmg_create(storage.h, min_level, max_level, smoother, float(relax), pre, post, int(wcycle),
                                         cg_max_iter, float(cg_tol), C.byref(h)), "gmg_create")
         return cls(h)
+
+    @classmethod
+    def chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3):
+        """hyteg::ChebyshevSmoother< P1ConstantLaplaceOperator >; radii: spectral radius of D^-1 A, one for all levels or one per level"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_chebyshev_create(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), C.byref(h)),
+            "chebyshev_create")
+        return cls(h)
+
+    @classmethod
+    def gmg_chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3, pre=1, post=1, wcycle=False, cg_max_iter=1000,
+                      cg_tol=1e-14):
+        """GeometricMultigridSolver smoothing with ChebyshevSmoother( order ): pre / post smoother calls per level"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_gmg_create_chebyshev(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), pre, post,
+                                                  int(wcycle), cg_max_iter, float(cg_tol), C.byref(h)), "gmg_create_chebyshev")
+        return cls(h)
+
+    def set_fused(self, on: bool) -> None:
+        """ChebyshevSmoother::setFused (of a multigrid solver: its smoother's): fused steps (default) or apply + multElementwise + assign"""
+        _ck(lib().hyteg_host_chebyshev_set_fused(self.h, int(bool(on))), "chebyshev_set_fused")
 
     @classmethod
     def cg(cls, storage, min_level, max_level, max_iter=1000, tol=1e-14):
@@ -739,6 +798,10 @@ class P2Function:
     def add(self, scalars, funcs, level, flag=All):
         self._vec(lib().hyteg_host_p2function_add, scalars, funcs, level, flag)
 
+    def mult_elementwise(self, funcs, level, flag=All):
+        hs = (_vp * len(funcs))(*[f.h for f in funcs])
+        _ck(lib().hyteg_host_p2function_mult_elementwise(self.h, len(funcs), hs, level, flag), "P2Function.mult_elementwise")
+
     def dot(self, other, level, flag=All):
         r = _d()
         _ck(lib().hyteg_host_p2function_dot(self.h, other.h, level, flag, C.byref(r)), "P2Function.dot")
@@ -815,6 +878,27 @@ class P2Solver:
         _ck(lib().hyteg_host_p2_gmg_create(storage.h, min_level, max_level, kind, float(relax), pre, post, int(bool(wcycle)), cg_max_iter,
                                            float(cg_tol), C.byref(h)), "P2 gmg")
         self.h = h
+
+    @classmethod
+    def chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3):
+        """hyteg::ChebyshevSmoother< P2ElementwiseLaplaceOperator > on its own (solve = one smoother call)"""
+        self = cls.__new__(cls)
+        self.storage, self.h = storage, _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_p2_chebyshev_create(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower),
+                                                 C.byref(self.h)), "P2 chebyshev")
+        return self
+
+    @classmethod
+    def gmg_chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3, pre=1, post=1, wcycle=False, cg_max_iter=1000,
+                      cg_tol=1e-14):
+        """the multigrid solver of this class smoothing with ChebyshevSmoother( order )"""
+        self = cls.__new__(cls)
+        self.storage, self.h = storage, _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_p2_gmg_create_chebyshev(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), pre, post,
+                                                     int(bool(wcycle)), cg_max_iter, float(cg_tol), C.byref(self.h)), "P2 gmg chebyshev")
+        return self
 
     def solve(self, op, x: "P2Function", b: "P2Function", level):
         _ck(lib().hyteg_host_p2_solver_solve(self.h, op.h, x.h, b.h, level), "P2 solve")

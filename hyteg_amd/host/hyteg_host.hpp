@@ -9,6 +9,7 @@
 //   P1ConstantOperator< Form >   src/constant_stencil_operator/P1ConstantOperator.hpp:33-168 + P1Operator.hpp:192-447
 //   P1toP1LinearRestriction / P1toP1LinearProlongation   src/hyteg/gridtransferoperators/
 //   WeightedJacobiSmoother, GaussSeidelSmoother, SORSmoother, CGSolver, GeometricMultigridSolver  src/hyteg/solvers/
+//   ChebyshevSmoother, chebyshev::estimateRadius, InvDiagOperatorWrapper                         src/hyteg/solvers/ChebyshevSmoother.hpp
 //
 // Data model: one device array per (macro-cell, level) in HyTeG's cell layout.  The DoFs
 // of macro-faces/edges/vertices are the boundary entries of every adjacent cell array and are kept bit-identical
@@ -31,5 +32,6 @@
 #include "p2gridtransfer.hpp"
 #include "gridtransfer.hpp"
 #include "solvers.hpp"
+#include "chebyshev.hpp"
 #include "stokes.hpp"
 #include "taylorhood.hpp"

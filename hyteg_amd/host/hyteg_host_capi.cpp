@@ -77,6 +77,20 @@ std::vector< std::reference_wrapper< const P1Function< double > > > refs( int n,
       r.push_back( std::cref( F( fs[i] ) ) );
    return r;
 }
+// ChebyshevSmoother with its coefficients set up (one spectral radius for all levels, or one per level)
+template < class Op >
+std::shared_ptr< ChebyshevSmoother< Op > > makeChebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                          double lower )
+{
+   if ( !radii || ( nRadii != 1 && nRadii != maxL - minL + 1 ) )
+      throw std::runtime_error( "chebyshev: pass one spectral radius, or one per level" );
+   auto sm = std::make_shared< ChebyshevSmoother< Op > >( static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL );
+   if ( nRadii == 1 )
+      sm->setupCoefficients( (uint_t) order, radii[0], upper, lower );
+   else
+      sm->setupCoefficients( (uint_t) order, std::vector< double >( radii, radii + nRadii ), upper, lower );
+   return sm;
+}
 } // namespace
 
 extern "C" {
@@ -573,6 +587,51 @@ HYTEG_HOST_API int hyteg_host_cg_create( hh_storage_t s, int minL, int maxL, int
                                                                                      (uint_t) maxIter, tol, tol ) };
    } );
 }
+/* ---- ChebyshevSmoother (src/hyteg/solvers/ChebyshevSmoother.hpp) ---- */
+HYTEG_HOST_API int hyteg_host_chebyshev_coefficients( int order, double lower, double upper, double* out )
+{
+   return guarded( [&] {
+      if ( order < 1 || !out )
+         throw std::runtime_error( "chebyshev_coefficients: order >= 1 and an output array are needed" );
+      const auto c = chebyshev::coefficients( (uint_t) order, lower, upper );
+      std::copy( c.begin(), c.end(), out );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_chebyshev_estimate_radius( hh_operator_t op, int level, int maxIter, hh_function_t x, hh_function_t tmp, double* radius )
+{
+   return guarded( [&] { WITH_OP( op, *radius = chebyshev::estimateRadius( A, (uint_t) level, (uint_t) maxIter, A.getStorage(), F( x ), F( tmp ) ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_chebyshev_create( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                double lower, hh_solver_t* out )
+{
+   return guarded( [&] { *out = new SolverH{ makeChebyshev< P1ConstantLaplaceOperator >( s, minL, maxL, order, radii, nRadii, upper, lower ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_chebyshev_set_fused( hh_solver_t solver, int on )
+{
+   return guarded( [&] {
+      using Op = P1ConstantLaplaceOperator;
+      auto sp  = static_cast< SolverH* >( solver )->p;
+      if ( auto g = std::dynamic_pointer_cast< GeometricMultigridSolver< Op > >( sp ) )
+         sp = g->getSmoother();
+      auto ch = std::dynamic_pointer_cast< ChebyshevSmoother< Op > >( sp );
+      if ( !ch )
+         throw std::runtime_error( "chebyshev_set_fused: neither a Chebyshev smoother nor a multigrid solver that smooths with one" );
+      ch->setFused( on != 0 );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_gmg_create_chebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                    double lower, int pre, int post, int wcycle, int cgMaxIter, double cgTol, hh_solver_t* out )
+{
+   return guarded( [&] {
+      using Op     = P1ConstantLaplaceOperator;
+      auto storage = static_cast< StorageH* >( s )->p;
+      auto sm      = makeChebyshev< Op >( s, minL, maxL, order, radii, nRadii, upper, lower );
+      auto coarse  = std::make_shared< CGSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) cgMaxIter, cgTol, cgTol );
+      *out         = new SolverH{ std::make_shared< GeometricMultigridSolver< Op > >(
+          storage, sm, coarse, std::make_shared< P1toP1LinearRestriction >(), std::make_shared< P1toP1LinearProlongation >(), (uint_t) minL,
+          (uint_t) maxL, (uint_t) pre, (uint_t) post, 0, wcycle ? CycleType::WCYCLE : CycleType::VCYCLE ) };
+   } );
+}
 HYTEG_HOST_API int hyteg_host_solver_solve( hh_solver_t solver, hh_operator_t laplace, hh_function_t x, hh_function_t b, int level )
 {
    return guarded( [&] {
@@ -833,6 +892,10 @@ HYTEG_HOST_API int hyteg_host_p2function_add( hh_p2function_t dst, int n, const 
 {
    return guarded( [&] { F2( dst ).add( std::vector< double >( scalars, scalars + n ), refs2( n, srcs ), (uint_t) level, DoFType( flag ) ); } );
 }
+HYTEG_HOST_API int hyteg_host_p2function_mult_elementwise( hh_p2function_t dst, int n, const hh_p2function_t* srcs, int level, int flag )
+{
+   return guarded( [&] { F2( dst ).multElementwise( refs2( n, srcs ), (uint_t) level, DoFType( flag ) ); } );
+}
 HYTEG_HOST_API int hyteg_host_p2function_dot( hh_p2function_t a, hh_p2function_t b, int level, int flag, double* result )
 {
    return guarded( [&] { *result = F2( a ).dotGlobal( F2( b ), (uint_t) level, DoFType( flag ) ); } );
@@ -934,6 +997,33 @@ HYTEG_HOST_API int hyteg_host_p2_gmg_create( hh_storage_t s, int minL, int maxL,
       *out          = new P2SolverH{ std::make_shared< GeometricMultigridSolver< Op, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation > >(
           storage, smoother, coarse, std::make_shared< P2toP2QuadraticRestriction >(), std::make_shared< P2toP2QuadraticProlongation >(),
           (uint_t) minL, (uint_t) maxL, (uint_t) pre, (uint_t) post, 0, wcycle ? CycleType::WCYCLE : CycleType::VCYCLE ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2_chebyshev_estimate_radius( hh_p2operator_t op, int level, int maxIter, hh_p2function_t x, hh_p2function_t tmp,
+                                                            double* radius )
+{
+   return guarded( [&] {
+      const auto& A = *static_cast< P2OperatorH* >( op )->p;
+      *radius       = chebyshev::estimateRadius( A, (uint_t) level, (uint_t) maxIter, F2( x ).getStorage(), F2( x ), F2( tmp ) );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2_chebyshev_create( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                   double lower, hh_p2solver_t* out )
+{
+   return guarded(
+       [&] { *out = new P2SolverH{ makeChebyshev< P2ElementwiseLaplaceOperator >( s, minL, maxL, order, radii, nRadii, upper, lower ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_p2_gmg_create_chebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                       double lower, int pre, int post, int wcycle, int cgMaxIter, double cgTol, hh_p2solver_t* out )
+{
+   return guarded( [&] {
+      using Op     = P2ElementwiseLaplaceOperator;
+      auto storage = static_cast< StorageH* >( s )->p;
+      auto sm      = makeChebyshev< Op >( s, minL, maxL, order, radii, nRadii, upper, lower );
+      auto coarse  = std::make_shared< CGSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) cgMaxIter, cgTol, cgTol );
+      *out         = new P2SolverH{ std::make_shared< GeometricMultigridSolver< Op, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation > >(
+          storage, sm, coarse, std::make_shared< P2toP2QuadraticRestriction >(), std::make_shared< P2toP2QuadraticProlongation >(), (uint_t) minL,
+          (uint_t) maxL, (uint_t) pre, (uint_t) post, 0, wcycle ? CycleType::WCYCLE : CycleType::VCYCLE ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_p2_solver_solve( hh_p2solver_t solver, hh_p2operator_t op, hh_p2function_t x, hh_p2function_t b, int level )

@@ -196,6 +196,73 @@ class P1ConstantOperator
       } );
    }
 
+   // ---- the steps of ChebyshevSmoother::solve (ChebyshevSmoother.hpp:165-212), fused like smooth_jac: one launch per step on
+   // the interiors the mask selects (hyteg_hip_p1_chebyshev_{start,step}_cell, scalar inverse diagonal = what
+   // computeInverseDiagonalOperatorValues stores there), this cell's shares of the shell points, sumSharedCopies, then the masked
+   // vector kernels for invDiag .* and the update of x on the shell.  Used on the levels the storage does not batch (the batched
+   // levels take the smoother's generic sequence, whose apply and vector kernels are one launch for all cells).
+   bool chebyshevFusable( uint_t level ) const { return !storage_->useBatch( level ) && level >= HYTEG_HIP_MIN_LEVEL; }
+   // t = invDiag .* ( b - A x ) on the selected points; on the shell also x += c0 t.  On the interiors x is this launch's stencil
+   // source: its update x += c0 t is carried out by the following chebyshevStep( ..., hasPrev = true ) or by chebyshevFinish.
+   void chebyshevStart( const P1Function< double >& t, const P1Function< double >& b, const P1Function< double >& x, double c0, uint_t level,
+                        DoFType flagIn ) const
+   {
+      ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerCheb( storage_->getTimingTree(), "chebyshev" );
+      const DoFType flag = x.effectiveFlag( flagIn );
+      if ( &t == &x || &t == &b )
+         throw std::runtime_error( "chebyshevStart: t must differ from x and b" );
+      forCells( [&]( uint_t c, const MacroCell& cell ) {
+         const auto&    S    = getCellStencils( cell.id, level );
+         const unsigned mask = storage_->maskFor( cell, flag );
+         if ( mask & HYTEG_HIP_MASK_INNER )
+            hipCheck( hyteg_hip_p1_chebyshev_start_cell( t.getCellPointer( c, level ), b.getCellPointer( c, level ), x.getCellPointer( c, level ),
+                                                         nullptr, (int) level, S.inner, storage_->stream() ),
+                      "chebyshevStart: cell" );
+         hipCheck( hyteg_hip_p1_apply_cell_boundary( t.getCellPointer( c, level ), x.getCellPointer( c, level ), (int) level, &S.slots[0][0], mask,
+                                                     HYTEG_HIP_REPLACE, storage_->stream() ),
+                   "chebyshevStart: boundary" );
+      } );
+      t.sumSharedCopies( level, flag );
+      chebyshevShell( t, &b, x, c0, level, flag );
+   }
+   // tOut = invDiag .* ( A tIn ) on the selected points; x = ( x + cPrev tIn ) + cCur tOut on the interiors (first term only if
+   // hasPrev: the update chebyshevStart left open), x += cCur tOut on the shell
+   void chebyshevStep( const P1Function< double >& tOut, const P1Function< double >& x, const P1Function< double >& tIn, double cPrev, double cCur,
+                       bool hasPrev, uint_t level, DoFType flagIn ) const
+   {
+      ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerCheb( storage_->getTimingTree(), "chebyshev" );
+      const DoFType flag = x.effectiveFlag( flagIn );
+      if ( &tOut == &tIn || &tOut == &x || &x == &tIn )
+         throw std::runtime_error( "chebyshevStep: tOut, x and tIn must be three different functions" );
+      forCells( [&]( uint_t c, const MacroCell& cell ) {
+         const auto&    S    = getCellStencils( cell.id, level );
+         const unsigned mask = storage_->maskFor( cell, flag );
+         if ( mask & HYTEG_HIP_MASK_INNER )
+            hipCheck( hyteg_hip_p1_chebyshev_step_cell( tOut.getCellPointer( c, level ), x.getCellPointer( c, level ), tIn.getCellPointer( c, level ),
+                                                        nullptr, (int) level, S.inner, cPrev, cCur, hasPrev ? 1 : 0, storage_->stream() ),
+                      "chebyshevStep: cell" );
+         hipCheck( hyteg_hip_p1_apply_cell_boundary( tOut.getCellPointer( c, level ), tIn.getCellPointer( c, level ), (int) level, &S.slots[0][0],
+                                                     mask, HYTEG_HIP_REPLACE, storage_->stream() ),
+                   "chebyshevStep: boundary" );
+      } );
+      tOut.sumSharedCopies( level, flag );
+      chebyshevShell( tOut, nullptr, x, cCur, level, flag );
+   }
+   // x += c t on the interiors: closes a smoother call of order 1 (no step follows the start)
+   void chebyshevFinish( const P1Function< double >& x, const P1Function< double >& t, double c, uint_t level, DoFType flagIn ) const
+   {
+      const DoFType flag = x.effectiveFlag( flagIn );
+      forCells( [&]( uint_t ci, const MacroCell& cell ) {
+         const unsigned inner = storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER;
+         if ( !inner )
+            return;
+         double*       d     = x.getCellPointer( ci, level );
+         const double* u[2]  = { d, t.getCellPointer( ci, level ) };
+         const double  sc[2] = { 1.0, c };
+         hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, u, sc, (int) level, inner, storage_->stream() ), "chebyshevFinish" );
+      } );
+   }
+
    // `steps` consecutive sweeps of smooth_sor (what a multigrid cycle's pre- / post-smoothing loop does,
    // GeometricMultigridSolver.hpp:209-215).  Where no shared or boundary point is swept (every macro-cell's shell is fixed: one
    // macro-cell with Dirichlet values, or cells whose common faces are not selected by the flag) the sweeps of a cell do not
@@ -301,6 +368,31 @@ class P1ConstantOperator
    }
 
  private:
+   // shell points of a Chebyshev step, after the shares of A t have been summed into t: t = b - t (start only), t = invDiag .* t,
+   // x = x + c t -- the reference's passes with their operands in its order
+   void chebyshevShell( const P1Function< double >& t, const P1Function< double >* b, const P1Function< double >& x, double c, uint_t level,
+                        DoFType flag ) const
+   {
+      const auto& invDiag = *getInverseDiagonalValues();
+      forCells( [&]( uint_t ci, const MacroCell& cell ) {
+         const unsigned shell = storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL;
+         if ( !shell )
+            return;
+         double* d = t.getCellPointer( ci, level );
+         if ( b )
+         {
+            const double* a[2]  = { b->getCellPointer( ci, level ), d };
+            const double  s1[2] = { 1.0, -1.0 };
+            hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, a, s1, (int) level, shell, storage_->stream() ), "chebyshev: residual" );
+         }
+         const double* m[2] = { invDiag.getCellPointer( ci, level ), d };
+         hipCheck( hyteg_hip_p1_vector_cell_masked( 2, d, 2, m, nullptr, (int) level, shell, storage_->stream() ), "chebyshev: scale" );
+         double*       xd    = x.getCellPointer( ci, level );
+         const double* u[2]  = { xd, d };
+         const double  s2[2] = { 1.0, c };
+         hipCheck( hyteg_hip_p1_vector_cell_masked( 0, xd, 2, u, s2, (int) level, shell, storage_->stream() ), "chebyshev: update" );
+      } );
+   }
    void launchSorCells( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flag,
                         bool backwards ) const
    {

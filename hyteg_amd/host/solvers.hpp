@@ -450,6 +450,7 @@ class GeometricMultigridSolver : public Solver< OperatorType >
    // used for storages distributed over several ranks (the exchange hooks are host callbacks).
    void setUseGraphs( bool on ) { useGraphs_ = on; }
    std::shared_ptr< Solver< OperatorType > > getCoarseSolver() const { return coarseSolver_; }
+   std::shared_ptr< Solver< OperatorType > > getSmoother() const { return smoother_; }
    bool usesGraphs() const { return graphsUsable(); }
    // number of cycles that were replayed from a recording (tests)
    uint_t replayedCycles() const { return replayed_; }

@@ -197,6 +197,39 @@ HYTEG_HIP_API int hyteg_hip_p1_jacobi_cell( double*            dst,
                                             double             relax,
                                             hyteg_hip_stream_t stream );
 
+/* ---- a4 / a13: the steps of a Chebyshev smoother, fused ------------------------------------------------------
+ * replaces, per step of ChebyshevSmoother::solve (src/hyteg/solvers/ChebyshevSmoother.hpp:165-212), the apply
+ * (P1Operator.hpp:192-320), the assign of the residual (first step only), the multElementwise with the inverse diagonal
+ * (ApplyFunctionMultiplicationWrapper::apply, src/hyteg/solvers/ApplyInverseDiagonalWrapper.hpp) and
+ * the assign x = x + c t (VertexDoFFunction.cpp:1088-1128) on the cell interior: one launch instead of four,
+ * 40 instead of 72 bytes per DoF (32 with the scalar inverse diagonal).
+ *   start:  t_out = invDiag .* ( rhs - A x ).  x is the stencil source of this launch and is NOT updated here (other waves
+ *           still read its old values): the update x += c_0 t_out is deferred to the next step (or to hyteg_hip_p1_add_cell
+ *           for a smoother of order 1).
+ *   step:   t_out = invDiag .* ( A t_in ), and at the same point x = ( x + c_prev t_in ) + c_cur t_out, the first term only
+ *           if has_prev != 0.  x is read and written by the same lane at the same address only (in place).
+ * invdiag: cell array of inverse diagonal values or NULL for the constant 1/w[7], as in hyteg_hip_p1_jacobi_cell.
+ * t_out must alias neither x, rhs, t_in nor invdiag, and x not t_in (EINVAL).  Every point sums the 15 terms in the order
+ * of hyteg_hip_p1_apply_cell, multiplies by the inverse diagonal and updates x: the composition's values up to the
+ * contraction of x + c t into one FMA.  Levels 2..11 (level 11 is composed from the entry points above inside the library). */
+HYTEG_HIP_API int hyteg_hip_p1_chebyshev_start_cell( double*            t_out,
+                                                     const double*      rhs,
+                                                     const double*      x,
+                                                     const double*      invdiag /* device or NULL */,
+                                                     int                level,
+                                                     const double*      w /* host, 15 */,
+                                                     hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p1_chebyshev_step_cell( double*            t_out,
+                                                    double*            x,
+                                                    const double*      t_in,
+                                                    const double*      invdiag /* device or NULL */,
+                                                    int                level,
+                                                    const double*      w /* host, 15 */,
+                                                    double             c_prev,
+                                                    double             c_cur,
+                                                    int                has_prev,
+                                                    hyteg_hip_stream_t stream );
+
 /* Selects how hyteg_hip_p1_sor_cell / hyteg_hip_p1_sor_cells execute the sweep.  Every form visits the points in an
  * order that respects the reference's lexicographic (z,y,x) dependencies (sor_3D_macrocell_P1.cpp:48-88), so the results
  * agree up to the rounding of the 15-term sum.  Process-wide; meant for tests and benchmarks.

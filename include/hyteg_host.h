@@ -154,6 +154,28 @@ HYTEG_HOST_API int hyteg_host_prolongate_and_add( hh_function_t f, int source_le
  * smoother: 0 = weighted Jacobi (relax), 1 = Gauss-Seidel, 2 = SOR (relax).  Coarse grid: CG. */
 HYTEG_HOST_API int hyteg_host_gmg_create( hh_storage_t s, int min_level, int max_level, int smoother, double relax, int pre, int post,
                                           int wcycle, int cg_max_iter, double cg_tol, hh_solver_t* out );
+/* ---- ChebyshevSmoother (replaces src/hyteg/solvers/ChebyshevSmoother.hpp:40-555 at its call sites) ----
+ * coefficients: replaces setupCoefficientsInternal (ChebyshevSmoother.hpp:329-552) for any order 1..8: out[0 .. order-1] are the
+ *   monomial coefficients of p in 1 - l p( l ) = T_n( ( theta - l ) / delta ) / T_n( theta / delta ), theta = ( upper + lower ) / 2,
+ *   delta = ( upper - lower ) / 2.  Touches no GPU.
+ * estimate_radius: replaces chebyshev::estimateRadius (ChebyshevSmoother.hpp:655-666; power iteration of
+ *   src/hyteg/numerictools/SpectrumEstimation.hpp:56-84 on D^-1 A, flag All).  x: start vector (overwritten), tmp: work function;
+ *   needs compute_inverse_diagonal.
+ * create: a ChebyshevSmoother of the given order for hyteg_host_solver_solve; radii: one spectral radius of D^-1 A for all levels
+ *   (n_radii = 1) or one per level min_level..max_level; bounds upper * radius and lower * radius (the reference's defaults: 1.2, 0.3;
+ *   setupCoefficients, ChebyshevSmoother.hpp:243-316).  The operator needs compute_inverse_diagonal before the first solve.
+ * set_fused: ChebyshevSmoother::setFused of the smoother itself or of a multigrid solver's smoother (default on: one launch per
+ *   step on the cell interiors; off: apply + multElementwise + assign).
+ * gmg_create_chebyshev: hyteg_host_gmg_create with that smoother (pre / post = smoother calls per level). */
+HYTEG_HOST_API int hyteg_host_chebyshev_coefficients( int order, double lower, double upper, double* out /* order */ );
+HYTEG_HOST_API int hyteg_host_chebyshev_estimate_radius( hh_operator_t op, int level, int max_iter, hh_function_t x, hh_function_t tmp,
+                                                         double* radius );
+HYTEG_HOST_API int hyteg_host_chebyshev_create( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                double upper, double lower, hh_solver_t* out );
+HYTEG_HOST_API int hyteg_host_chebyshev_set_fused( hh_solver_t solver, int on );
+HYTEG_HOST_API int hyteg_host_gmg_create_chebyshev( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                    double upper, double lower, int pre, int post, int wcycle, int cg_max_iter, double cg_tol,
+                                                    hh_solver_t* out );
 /* launch graphs of the cycle (hyteg_host.hpp, GeometricMultigridSolver::setUseGraphs): opt-in, storages of one rank;
  * replayed_cycles counts the cycles that ran from a recording */
 HYTEG_HOST_API int hyteg_host_gmg_set_use_graphs( hh_solver_t solver, int on );
@@ -215,6 +237,8 @@ HYTEG_HOST_API int hyteg_host_p2function_download( hh_p2function_t f, int local_
 HYTEG_HOST_API int hyteg_host_p2function_interpolate_constant( hh_p2function_t f, double value, int level, int flag );
 HYTEG_HOST_API int hyteg_host_p2function_assign( hh_p2function_t dst, int n, const double* scalars, const hh_p2function_t* srcs, int level, int flag );
 HYTEG_HOST_API int hyteg_host_p2function_add( hh_p2function_t dst, int n, const double* scalars, const hh_p2function_t* srcs, int level, int flag );
+/* P2Function::multElementwise (src/hyteg/p2functionspace/P2Function.cpp: vertex- and edge-DoF parts separately) */
+HYTEG_HOST_API int hyteg_host_p2function_mult_elementwise( hh_p2function_t dst, int n, const hh_p2function_t* srcs, int level, int flag );
 HYTEG_HOST_API int hyteg_host_p2function_dot( hh_p2function_t a, hh_p2function_t b, int level, int flag, double* result );
 HYTEG_HOST_API int hyteg_host_p2operator_create( hh_storage_t s, int min_level, int max_level, hh_p2operator_t* out );
 /* P2toP2QuadraticProlongation::prolongate / prolongateAndAdd (add != 0) from source_level to source_level + 1 and
@@ -249,6 +273,16 @@ HYTEG_HOST_API int hyteg_host_p2operator_smooth_sor( hh_p2operator_t op, hh_p2fu
                                                      int backwards );
 HYTEG_HOST_API int hyteg_host_p2_gmg_create( hh_storage_t s, int min_level, int max_level, int smoother, double relax, int pre, int post, int wcycle,
                                              int cg_max_iter, double cg_tol, hh_p2solver_t* out );
+/* ChebyshevSmoother< P2ElementwiseLaplaceOperator > (ChebyshevSmoother.hpp:40-555; the generic sequence apply, multElementwise,
+ * assign) on its own, its radius estimate (ChebyshevSmoother.hpp:655-666) and as the smoother of the multigrid solver above;
+ * arguments as for the P1 entries hyteg_host_chebyshev_create / _estimate_radius / hyteg_host_gmg_create_chebyshev */
+HYTEG_HOST_API int hyteg_host_p2_chebyshev_estimate_radius( hh_p2operator_t op, int level, int max_iter, hh_p2function_t x, hh_p2function_t tmp,
+                                                            double* radius );
+HYTEG_HOST_API int hyteg_host_p2_chebyshev_create( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                   double upper, double lower, hh_p2solver_t* out );
+HYTEG_HOST_API int hyteg_host_p2_gmg_create_chebyshev( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                       double upper, double lower, int pre, int post, int wcycle, int cg_max_iter, double cg_tol,
+                                                       hh_p2solver_t* out );
 HYTEG_HOST_API int hyteg_host_p2_solver_solve( hh_p2solver_t solver, hh_p2operator_t op, hh_p2function_t x, hh_p2function_t b, int level );
 HYTEG_HOST_API int hyteg_host_p2_solver_destroy( hh_p2solver_t solver );
 /* CGSolver< P2ElementwiseLaplaceOperator > on one level, flags Inner | NeumannBoundary as in the reference's CGSolver */

@@ -113,6 +113,23 @@ def main():
            24 * inner, inner)
     timeit("Jacobi fused (inverse-diagonal function)",
            lambda k: capi.p1_jacobi_cell(p(B, k), p(Cc, k), p(A, k), L, w, 0.66, p(Cc, k + 1), sh), 32 * inner, inner)
+    # one step of the Chebyshev smoother: t_out = invDiag .* (A t_in), x += c_prev t_in + c_cur t_out -- fused into one launch,
+    # and composed from the kernels of the smoother's generic path (apply, multElementwise, assign) on rings of their own
+    X = [torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)]
+    timeit("Chebyshev step, fused (scalar inverse diagonal)",
+           lambda k: capi.p1_chebyshev_step_cell(p(B, k), p(X, k), p(A, k), L, w, 0.5, -0.1, True, None, sh), 32 * inner, inner)
+    timeit("Chebyshev step, fused (inverse-diagonal function)",
+           lambda k: capi.p1_chebyshev_step_cell(p(B, k), p(X, k), p(A, k), L, w, 0.5, -0.1, True, p(Cc, k), sh), 40 * inner, inner)
+    timeit("Chebyshev start, fused (inverse-diagonal function)",
+           lambda k: capi.p1_chebyshev_start_cell(p(B, k), p(X, k), p(A, k), L, w, p(Cc, k), sh), 32 * inner, inner)
+
+    def chebyshev_step_composed(k):
+        capi.p1_apply_cell(p(B, k), p(A, k), L, w, 0, sh)
+        capi.p1_mult_cell(p(B, k), [p(Cc, k), p(B, k)], L, sh)
+        capi.p1_assign_cell(p(X, k), [1.0, -0.1], [p(X, k), p(B, k)], L, sh)
+
+    timeit("Chebyshev step, composed (apply + multElementwise + assign)", chebyshev_step_composed, 64 * inner, inner)
+    del X
     timeit("assign 1 source", lambda k: capi.p1_assign_cell(p(B, k), [2.0], [p(A, k)], L, sh), 16 * inner, inner)
     timeit("assign 2 sources", lambda k: capi.p1_assign_cell(p(B, k), [2.0, -1.0], [p(A, k), p(Cc, k)], L, sh), 24 * inner, inner)
     timeit("add 1 source", lambda k: capi.p1_add_cell(p(B, k), [2.0], [p(A, k)], L, sh), 24 * inner, inner)
@@ -203,10 +220,17 @@ def main():
         for o in (u6, r6, A6, s6):
             o.close()
     # V-cycles through the host layer
+    # Chebyshev rows: ( order, fused ) instead of a smoother code; V(1,1), spectral radius 1.97 on every level (the time per cycle
+    # does not depend on the bounds)
     for mesh, lo, hi, smoother, name in (("tet_1el", 2, L, host.JACOBI, "Jacobi(2/3)"), ("tet_1el", 2, L, host.JACOBI_FP32, "Jacobi fp32"),
                                           ("tet_1el", 2, min(L, 7), host.GAUSS_SEIDEL, "GS"),
+                                          ("tet_1el", 2, L, (3, True), "Chebyshev(3)"), ("tet_1el", 2, L, (2, True), "Chebyshev(2)"),
+                                          ("tet_1el", 2, L, (3, False), "Chebyshev(3) composed"),
+                                          ("tet_1el", 2, min(L, 7), (3, True), "Chebyshev(3)"),
                                           ("regular_octahedron_8el", 2, min(L, 6), host.JACOBI, "Jacobi(2/3)"),
-                                          ("regular_octahedron_8el", 0, min(L, 6), host.GAUSS_SEIDEL, "GS")):
+                                          ("regular_octahedron_8el", 0, min(L, 6), host.GAUSS_SEIDEL, "GS"),
+                                          ("regular_octahedron_8el", 2, min(L, 6), (3, True), "Chebyshev(3)"),
+                                          ("regular_octahedron_8el", 2, min(L, 6), (2, True), "Chebyshev(2)")):
         s2 = host.Storage.from_gmsh(ROOT / f"hyteg_amd/data/meshes/{mesh}.msh")
         s2.set_stream(sh)
         A2 = host.P1ConstantOperator(s2, lo, hi)
@@ -219,7 +243,12 @@ def main():
             x.upload_cell(c, hi, rng.random(capi.cell_size(hi)))
         x.sync_shared(hi, host.All)
         x.interpolate(0.0, hi, host.DirichletBoundary)
-        gmg = host.Solver.gmg(s2, lo, hi, smoother=smoother, relax=2.0 / 3.0, pre=3, post=3, cg_max_iter=50, cg_tol=1e-10)
+        if isinstance(smoother, tuple):
+            gmg = host.Solver.gmg_chebyshev(s2, lo, hi, smoother[0], 1.97, pre=1, post=1, cg_max_iter=50, cg_tol=1e-10)
+            gmg.set_fused(smoother[1])
+        else:
+            gmg = host.Solver.gmg(s2, lo, hi, smoother=smoother, relax=2.0 / 3.0, pre=3, post=3, cg_max_iter=50, cg_tol=1e-10)
+        vnu = "V(1,1)" if isinstance(smoother, tuple) else "V(3,3)"
         for _ in range(3):
             gmg.solve(A2, x, b, hi)
         torch.cuda.synchronize()
@@ -229,8 +258,8 @@ def main():
             gmg.solve(A2, x, b, hi)
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) * 1e3 / ncyc
-        rows.append(dict(kernel=f"V(3,3) {name} {mesh} L{lo}-{hi}", ms=ms, inner_dofs=dofs))
-        print(f"V(3,3) {name:12s} {mesh:24s} levels {lo}-{hi}: {ms:9.2f} ms/cycle, {dofs:.0f} inner DoFs "
+        rows.append(dict(kernel=f"{vnu} {name} {mesh} L{lo}-{hi}", ms=ms, inner_dofs=dofs))
+        print(f"{vnu} {name:21s} {mesh:24s} levels {lo}-{hi}: {ms:9.2f} ms/cycle, {dofs:.0f} inner DoFs "
               f"({dofs / ms * 1e-6:.2f} GDoF/s per cycle)", flush=True)
     # P1-P1 Stokes: the reference's P1P1Stokes3DUzawaConvergenceTest configuration (cube_24el, levels 2-5, V(3,3) increment 2, Uzawa)
     s3 = host.Storage.from_gmsh(ROOT / "hyteg_amd/data/meshes/cube_24el.msh")
