@@ -37,6 +37,7 @@ SIGNATURES = {
     "hyteg_hip_stream_create": (_i, [C.POINTER(_vp)]),
     "hyteg_hip_stream_destroy": (_i, [_vp]),
     "hyteg_hip_stream_synchronize": (_i, [_vp]),
+    "hyteg_hip_stream_is_capturing": (_i, [_vp, C.POINTER(_i)]),
     "hyteg_hip_event_create": (_i, [C.POINTER(_vp)]),
     "hyteg_hip_event_create_timing": (_i, [C.POINTER(_vp)]),
     "hyteg_hip_event_elapsed_ms": (_i, [_vp, _vp, C.POINTER(C.c_float)]),

@@ -343,6 +343,15 @@ HYTEG_HIP_API int hyteg_hip_graph_abort_capture( hyteg_hip_stream_t stream )
    return HYTEG_HIP_OK;
 }
 
+HYTEG_HIP_API int hyteg_hip_stream_is_capturing( hyteg_hip_stream_t stream, int* capturing )
+{
+   HH_REQUIRE( capturing != nullptr, "stream_is_capturing: null out pointer" );
+   hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+   HH_CHECK_HIP( hipStreamIsCapturing( as_stream( stream ), &status ) );
+   *capturing = status != hipStreamCaptureStatusNone ? 1 : 0;
+   return HYTEG_HIP_OK;
+}
+
 HYTEG_HIP_API int hyteg_hip_graph_launch( hyteg_hip_graph_t graph, hyteg_hip_stream_t stream )
 {
    if ( graph == nullptr )

@@ -32,6 +32,10 @@ SIGNATURES = {
     "hyteg_host_storage_set_boundary_type": (_i, [_vp, _i]),
     "hyteg_host_storage_set_stream": (_i, [_vp, _vp]),
     "hyteg_host_storage_set_batch_max_level": (_i, [_vp, _i]),
+    "hyteg_host_storage_set_apply_lanes": (_i, [_vp, _i]),
+    "hyteg_host_storage_set_apply_cell_lanes_min": (_i, [_vp, _i]),
+    "hyteg_host_storage_lanes_seen": (_i, [_vp, C.POINTER(C.c_uint)]),
+    "hyteg_host_lane_plan": (_i, [_i, _i, _ip, C.POINTER(C.c_ulonglong), _ip, C.POINTER(C.c_ulonglong), _ip, C.POINTER(_u)]),
     "hyteg_host_storage_set_hooks": (_i, [_vp, EXCHANGE_CB, EXCHANGE_CB, ALLREDUCE_CB, _vp]),
     "hyteg_host_storage_use_rccl": (_i, [_vp, C.c_char_p]),
     "hyteg_host_storage_use_p2p": (_i, [_vp, C.c_size_t, C.c_char_p, C.POINTER(C.c_int)]),
@@ -277,6 +281,21 @@ class Storage:
     def set_batch_max_level(self, level):
         """levels <= level run the batched kernels (one launch for all local cells); -1: per-cell kernels everywhere"""
         _ck(lib().hyteg_host_storage_set_batch_max_level(self.h, level), "set_batch_max_level")
+
+    def set_apply_lanes(self, lanes):
+        """stream lanes for independent interior launches inside one host-layer call (apply_cycle); 1: one stream, 0: default
+        (HYTEG_AMD_APPLY_LANES, else 2)"""
+        _ck(lib().hyteg_host_storage_set_apply_lanes(self.h, lanes), "set_apply_lanes")
+
+    def set_apply_cell_lanes_min(self, cells):
+        """multi-cell P1 apply: the cells' interior kernels alternate between the lanes from `cells` local cells on; 0: never"""
+        _ck(lib().hyteg_host_storage_set_apply_cell_lanes_min(self.h, cells), "set_apply_cell_lanes_min")
+
+    def lanes_seen(self):
+        """bit l: lane l carried a launch in the storage's last lane scope (0: its lanes were off)"""
+        m = C.c_uint()
+        _ck(lib().hyteg_host_storage_lanes_seen(self.h, C.byref(m)), "lanes_seen")
+        return m.value
 
     def set_stream(self, stream):
         _ck(lib().hyteg_host_storage_set_stream(self.h, stream), "set_stream")

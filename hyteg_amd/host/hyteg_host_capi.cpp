@@ -157,6 +157,38 @@ HYTEG_HOST_API int hyteg_host_storage_set_batch_max_level( hh_storage_t s, int l
 {
    return guarded( [&] { S( s ).setBatchMaxLevel( level ); } );
 }
+HYTEG_HOST_API int hyteg_host_storage_set_apply_lanes( hh_storage_t s, int lanes )
+{
+   return guarded( [&] { S( s ).setApplyLanes( lanes ); } );
+}
+HYTEG_HOST_API int hyteg_host_storage_set_apply_cell_lanes_min( hh_storage_t s, int cells )
+{
+   return guarded( [&] { S( s ).setApplyCellLanesMin( cells ); } );
+}
+HYTEG_HOST_API int hyteg_host_storage_lanes_seen( hh_storage_t s, unsigned* mask )
+{
+   return guarded( [&] { *mask = S( s ).lanesSeen(); } );
+}
+HYTEG_HOST_API int hyteg_host_lane_plan( int lanes, int nsteps, const int* read_ptr, const unsigned long long* read_ids, const int* write_ptr,
+                                         const unsigned long long* write_ids, int* lane_out, unsigned* waits_out )
+{
+   return guarded( [&] {
+      if ( nsteps < 0 || ( nsteps > 0 && ( !read_ptr || !write_ptr || !lane_out || !waits_out ) ) )
+         throw std::runtime_error( "lane_plan: null argument" );
+      LanePlanner                 planner( lanes );
+      std::vector< const void* > r, w;
+      for ( int k = 0; k < nsteps; ++k )
+      {
+         r.clear(), w.clear();
+         for ( int i = read_ptr[k]; i < read_ptr[k + 1]; ++i )
+            r.push_back( reinterpret_cast< const void* >( (uintptr_t) read_ids[i] ) );
+         for ( int i = write_ptr[k]; i < write_ptr[k + 1]; ++i )
+            w.push_back( reinterpret_cast< const void* >( (uintptr_t) write_ids[i] ) );
+         const auto p = planner.place( r.data(), (int) r.size(), w.data(), (int) w.size() );
+         lane_out[k] = p.lane, waits_out[k] = p.waits;
+      }
+   } );
+}
 HYTEG_HOST_API int hyteg_host_storage_use_rccl( hh_storage_t s, const unsigned char* unique_id )
 {
    return guarded( [&] {
@@ -417,11 +449,16 @@ HYTEG_HOST_API int hyteg_host_operator_apply_cycle( hh_operator_t op, int npairs
                                                     int flag, int update, int first, int steps )
 {
    return guarded( [&] {
+      if ( steps <= 0 || npairs <= 0 )
+         return;
+      // consecutive applies on different pairs are independent: they overlap on the storage's lanes (PrimitiveStorage::LaneScope)
+      PrimitiveStorage::LaneScope lanes( *F( srcs[0] ).getStorage() );
       for ( int k = 0; k < steps; ++k )
       {
          const int j = ( first + k ) % npairs;
          WITH_OP( op, A.apply( F( srcs[j] ), F( dsts[j] ), (uint_t) level, DoFType( flag ), update ? Add : Replace ) );
       }
+      lanes.join();
    } );
 }
 HYTEG_HOST_API int hyteg_host_operator_apply_cycle_timed( hh_operator_t op, int npairs, const hh_function_t* srcs, const hh_function_t* dsts,
@@ -435,10 +472,15 @@ HYTEG_HOST_API int hyteg_host_operator_apply_cycle_timed( hh_operator_t op, int 
       hyteg_hip_stream_t stream = F( srcs[0] ).getStorage()->stream();
       if ( evStart )
          hipCheck( hyteg_hip_event_record( evStart, stream ), "apply_cycle_timed: record" );
-      for ( int k = 0; k < steps; ++k )
       {
-         const int j = ( first + k ) % npairs;
-         WITH_OP( op, A.apply( F( srcs[j] ), F( dsts[j] ), (uint_t) level, DoFType( flag ), update ? Add : Replace ) );
+         // evStart in front of the fork, evStop behind the join: both on the storage's stream, the lanes in between
+         PrimitiveStorage::LaneScope lanes( *F( srcs[0] ).getStorage() );
+         for ( int k = 0; k < steps; ++k )
+         {
+            const int j = ( first + k ) % npairs;
+            WITH_OP( op, A.apply( F( srcs[j] ), F( dsts[j] ), (uint_t) level, DoFType( flag ), update ? Add : Replace ) );
+         }
+         lanes.join();
       }
       if ( evStop )
          hipCheck( hyteg_hip_event_record( evStop, stream ), "apply_cycle_timed: record" );

@@ -49,6 +49,29 @@ class P1ConstantOperator
       const DoFType flag = dst.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       if ( &src == &dst )
          throw std::runtime_error( "P1ConstantOperator::apply: src and dst must differ (P1Operator.hpp:198)" );
+      if ( storage_->lanesOpen() )
+      {
+         // inside a lane scope (the loop of apply_cycle): an apply that consists of interior launches only -- each reads src's
+         // cell array and writes dst's -- goes where the planner puts it, next to the applies it does not depend on; every
+         // other apply runs behind all lanes, as ever
+         if ( pureInterior( level, flag ) )
+         {
+            forCells( [&]( uint_t c, const MacroCell& cell ) {
+               if ( !( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER ) )
+                  return;
+               double*            d    = dst.getCellPointer( c, level );
+               const double*      u    = src.getCellPointer( c, level );
+               const void*        r[1] = { u };
+               const void*        w[1] = { d };
+               hyteg_hip_stream_t lane = storage_->laneFor( r, 1, w, 1 );
+               hipCheck( hyteg_hip_p1_apply_cell( d, u, (int) level, getCellStencils( cell.id, level ).inner,
+                                                  updateType == Replace ? HYTEG_HIP_REPLACE : HYTEG_HIP_ADD, lane ),
+                         "apply: cell" );
+            } );
+            return;
+         }
+         storage_->joinLanes();
+      }
       if ( storage_->useBatch( level ) )
       {
          applyBatched( src, dst, level, flag, updateType );
@@ -67,7 +90,12 @@ class P1ConstantOperator
       // 3. the interior stencil while the exchange is in flight, 4. reduce the shares.  1, 2 and 4 only touch shared points:
       // with a stream-agnostic transport they can form a chain on a side stream next to 3 (PrimitiveStorage::SideChain;
       // opt-in, measured slower than one stream).
-      PrimitiveStorage::SideChain chain( *storage_, storage_->sideChainUsable( (int) level, flag, 0 ) );
+      const bool                  sideChain = storage_->sideChainUsable( (int) level, flag, 0 );
+      PrimitiveStorage::SideChain chain( *storage_, sideChain );
+      // the interiors of the cells are independent launches: with enough cells they alternate between the lanes of the storage
+      // (one fork behind the shell kernels, one join in front of the reduction of the shares), see PrimitiveStorage::applyCellLanesMin()
+      PrimitiveStorage::LaneScope cellLanes( *storage_, !sideChain && storage_->applyCellLanesMin() > 0 && storage_->getNumberOfLocalCells() >= storage_->applyCellLanesMin() &&
+                                                            level >= HYTEG_HIP_MIN_LEVEL );
       // a rank with ONE macro-cell that exchanges peer to peer: the share kernel stores the shares into the peers' slots itself
       PrimitiveStorage::ShareSend send;
       const bool bySharesKernel = shellDst->beginSumSharedCopiesByShares( level, flag, send );
@@ -97,9 +125,12 @@ class P1ConstantOperator
          if ( ( mask & HYTEG_HIP_MASK_INNER ) && level >= HYTEG_HIP_MIN_LEVEL )
             hipCheck( hyteg_hip_p1_apply_cell( dst.getCellPointer( c, level ), src.getCellPointer( c, level ), (int) level,
                                                getCellStencils( cell.id, level ).inner,
-                                               updateType == Replace ? HYTEG_HIP_REPLACE : HYTEG_HIP_ADD, storage_->stream() ),
+                                               updateType == Replace ? HYTEG_HIP_REPLACE : HYTEG_HIP_ADD,
+                                               // the first cell on lane 1: forked before any interior is on the storage's stream
+                                               cellLanes.active() ? storage_->laneStream( (int) c + 1 ) : storage_->stream() ),
                       "apply: cell" );
       } );
+      cellLanes.join();
       chain.toSide();
       shellDst->endSumSharedCopies( level, flag );
       chain.join();
@@ -860,6 +891,16 @@ class P1ConstantOperator
                t.faceW[f][k] = faceTot[c.faces[f]][k];
       }
       return T;
+   }
+   // an apply without any shell point selected on any local cell (residual()'s test): its launches are the cells' interior
+   // kernels and nothing else
+   bool pureInterior( uint_t level, DoFType flag ) const
+   {
+      if ( storage_->numRanks() > 1 || storage_->useBatch( level ) || level < HYTEG_HIP_MIN_LEVEL )
+         return false;
+      bool anyShell = false;
+      forCells( [&]( uint_t, const MacroCell& cell ) { anyShell = anyShell || ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL ); } );
+      return !anyShell;
    }
    bool hasSharedPoints( uint_t level, DoFType flag ) const
    {

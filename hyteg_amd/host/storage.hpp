@@ -4,6 +4,7 @@
 #pragma once
 
 #include "comm.hpp"
+#include "lanes.hpp"
 #include "mesh.hpp"
 #include "timing.hpp"
 
@@ -130,6 +131,18 @@ class PrimitiveStorage
          hyteg_hip_free( dotWorkspace_ );
       for ( void* p : scratchAll_ )
          hyteg_hip_free( p );
+      for ( int l = 1; l < LanePlanner::kMaxLanes; ++l )
+         if ( laneStreams_[l] )
+         {
+            hyteg_hip_stream_synchronize( laneStreams_[l] );
+            hyteg_hip_event_destroy( laneEvents_[l] );
+            hyteg_hip_stream_destroy( laneStreams_[l] );
+         }
+      if ( laneFork_ )
+      {
+         hyteg_hip_event_destroy( laneFork_ );
+         hyteg_hip_event_destroy( laneEvents_[0] ); // created together (useLane)
+      }
       if ( sideStream_ )
       {
          hyteg_hip_stream_synchronize( sideStream_ );
@@ -255,8 +268,9 @@ class PrimitiveStorage
    {
       void* p = nullptr;
       hipCheck( hyteg_hip_malloc( &p, std::max< size_t >( 8, bytes ) ), "uploadTable: malloc" );
-      hipCheck( hyteg_hip_upload( p, h, bytes, stream_ ), "uploadTable: upload" );
-      hipCheck( hyteg_hip_stream_synchronize( stream_ ), "uploadTable: sync" );
+      hyteg_hip_stream_t s = stream();
+      hipCheck( hyteg_hip_upload( p, h, bytes, s ), "uploadTable: upload" );
+      hipCheck( hyteg_hip_stream_synchronize( s ), "uploadTable: sync" );
       scratchAll_.push_back( p );
       return p;
    }
@@ -275,6 +289,7 @@ class PrimitiveStorage
 
    void              setStream( hyteg_hip_stream_t s )
    {
+      joinLanes();
       stream_ = s;
       if ( timingTree_ )
          timingTree_->setStream( s );
@@ -293,7 +308,157 @@ class PrimitiveStorage
       timingTree_->setSynchronize( synchronize, stream_ );
    }
    TimingTree* getTimingTree() const { return timingTree_.get(); }
-   hyteg_hip_stream_t stream() const { return stream_; }
+   // the stream every launch of this layer goes on.  Inside an open LaneScope whoever asks for it is not lane-aware: the lanes
+   // are joined first, so that what follows on the stream sees everything issued so far (see LaneScope below)
+   hyteg_hip_stream_t stream() const
+   {
+      if ( laneUsed_ )
+         joinLanes();
+      return stream_;
+   }
+
+   // ---- stream lanes for independent interior launches -------------------------------------------------------------
+   // Inside one host-layer call that knows every array its launches read and write (the loop of apply_cycle, the cell loop of
+   // a multi-cell apply) independent launches go on a few in-order streams ("lanes"; lane 0 is the storage's stream) and
+   // dependent ones are ordered exactly as the single stream would order them (LanePlanner, lanes.hpp).  A level-8 apply
+   // then starts while the last waves of the previous one drain: profiles/apply_lanes_level8.txt.  LaneScope is the RAII
+   // bracket: the first use of a lane >= 1 forks it off the storage's stream (one event), join() -- also the destructor,
+   // and stream() for everybody who is not lane-aware -- records one event on every used lane and makes the storage's
+   // stream wait for each.  Between two host-layer calls nothing is ever left on a lane, so what a caller observes on its
+   // stream is what it observed with one stream.  A scope inside a scope shares the outer one's lanes.
+   // Lanes stay OFF (every launch on the storage's stream, in today's order) with a lane count of 1, on a storage of several
+   // ranks (their exchanges order themselves on streams of their own), with the timing tree enabled (its ranges wait for the
+   // storage's stream only), and while the stream is recorded into a graph; the batched levels never ask for them.
+   // Lane count: setApplyLanes(), else HYTEG_AMD_APPLY_LANES, else 2.
+   void setApplyLanes( int lanes )
+   {
+      if ( lanes < 0 || lanes > LanePlanner::kMaxLanes )
+         throw std::runtime_error( "setApplyLanes: 0 (default) to " + std::to_string( LanePlanner::kMaxLanes ) + " lanes" );
+      if ( laneDepth_ > 0 )
+         throw std::runtime_error( "setApplyLanes: a lane scope is open" );
+      laneCount_ = lanes == 0 ? -1 : lanes;
+   }
+   int applyLanes() const
+   {
+      if ( laneCount_ < 0 )
+      {
+         static const int fromEnv = [] {
+            const char* e = std::getenv( "HYTEG_AMD_APPLY_LANES" );
+            const int   n = e ? std::atoi( e ) : 2;
+            return std::min( std::max( n, 1 ), (int) LanePlanner::kMaxLanes );
+         }();
+         laneCount_ = fromEnv;
+      }
+      return laneCount_;
+   }
+   // Lanes for the cell loop of a multi-cell apply from this many local cells on; 0 = never.  Default 24: at level 8 two lanes
+   // take 559.7 -> 546.7 us per apply on 24 cells (-2.3 %) but 132.0 -> 141.3 us on 6 (+7 %), three lanes are slower on both
+   // (profiles/apply_lanes_level8.txt, section 4); setApplyCellLanesMin(), else HYTEG_AMD_APPLY_CELL_LANES_MIN read once.
+   void   setApplyCellLanesMin( int cells ) { cellLanesMin_ = cells < 0 ? -1 : cells; }
+   uint_t applyCellLanesMin() const
+   {
+      if ( cellLanesMin_ < 0 )
+      {
+         static const int fromEnv = [] {
+            const char* e = std::getenv( "HYTEG_AMD_APPLY_CELL_LANES_MIN" );
+            return e ? std::max( 0, std::atoi( e ) ) : 24;
+         }();
+         cellLanesMin_ = fromEnv;
+      }
+      return (uint_t) cellLanesMin_;
+   }
+   // bit l: lane l carried a launch placed through laneFor() / laneStream() in the last outermost LaneScope (or the open one);
+   // 0 if its lanes were off.  What a test asks to know that a second stream was really used.
+   unsigned lanesSeen() const { return lanesSeen_; }
+   // true inside an open LaneScope whose lanes are on
+   bool lanesOpen() const { return laneDepth_ > 0 && lanesOn_; }
+   // the stream for a launch that reads the arrays `reads` and writes the arrays `writes` (device base pointers), ordered
+   // behind every earlier launch of the scope it conflicts with.  Only inside an open scope.
+   hyteg_hip_stream_t laneFor( const void* const* reads, int nReads, const void* const* writes, int nWrites ) const
+   {
+      if ( laneManual_ ) // launches the planner has not seen: behind all of them
+         joinLanes();
+      const LanePlanner::Placement p = planner_.place( reads, nReads, writes, nWrites );
+      hyteg_hip_stream_t           s = useLane( p.lane );
+      lanesSeen_ |= 1u << p.lane;
+      for ( int j = 0; j < planner_.lanes(); ++j )
+         if ( p.waits & ( 1u << j ) )
+         {
+            // a lane that is waited for has launches, so it has been forked
+            hipCheck( hyteg_hip_event_record( laneEvents_[j], j == 0 ? stream_ : laneStreams_[j] ), "lanes: record" );
+            hipCheck( hyteg_hip_stream_wait_event( s, laneEvents_[j] ), "lanes: wait" );
+         }
+      return s;
+   }
+   // the stream of lane `lane` for launches the CALLER knows to be independent of everything issued in the scope since the
+   // last join (the interiors of different macro-cells)
+   hyteg_hip_stream_t laneStream( int lane ) const
+   {
+      laneManual_ = true;
+      lane %= planner_.lanes();
+      lanesSeen_ |= 1u << lane;
+      return useLane( lane );
+   }
+   void joinLanes() const
+   {
+      const unsigned used = laneUsed_;
+      laneUsed_ = 0, laneManual_ = false;
+      planner_.reset();
+      for ( int l = 1; l < LanePlanner::kMaxLanes; ++l )
+         if ( used & ( 1u << l ) )
+         {
+            hipCheck( hyteg_hip_event_record( laneEvents_[l], laneStreams_[l] ), "lanes: record" );
+            hipCheck( hyteg_hip_stream_wait_event( stream_, laneEvents_[l] ), "lanes: wait" );
+         }
+   }
+   class LaneScope
+   {
+    public:
+      explicit LaneScope( const PrimitiveStorage& st, bool want = true )
+      : st_( st )
+      {
+         if ( st_.laneDepth_ == 0 )
+         {
+            st_.lanesSeen_ = 0;
+            st_.lanesOn_   = want && st_.nranks_ == 1 && st_.applyLanes() > 1 && !st_.mainStream_ && !st_.timingTree_;
+            if ( st_.lanesOn_ )
+            {
+               int capturing = 0;
+               if ( hyteg_hip_stream_is_capturing( st_.stream_, &capturing ) != HYTEG_HIP_OK || capturing )
+                  st_.lanesOn_ = false;
+            }
+            if ( st_.lanesOn_ && st_.planner_.lanes() != st_.applyLanes() )
+               st_.planner_.setLanes( st_.applyLanes() );
+            st_.planner_.reset();
+         }
+         ++st_.laneDepth_;
+         use_ = want && st_.lanesOn_;
+      }
+      // lanes are on in the enclosing scopes and wanted by this one
+      bool active() const { return use_; }
+      int  lanes() const { return use_ ? st_.planner_.lanes() : 1; }
+      void join() const { st_.joinLanes(); }
+      ~LaneScope()
+      {
+         --st_.laneDepth_;
+         if ( st_.laneUsed_ )
+         {
+            try
+            {
+               st_.joinLanes();
+            } catch ( ... ) // left by an exception after a failed call: nothing more can be ordered
+            {}
+         }
+         if ( st_.laneDepth_ == 0 )
+            st_.lanesOn_ = false;
+      }
+      LaneScope( const LaneScope& )            = delete;
+      LaneScope& operator=( const LaneScope& ) = delete;
+
+    private:
+      const PrimitiveStorage& st_;
+      bool                    use_ = false;
+   };
 
    // ---- side stream for the shared-point chain of an operator application -------------------------------------------
    // In apply() the chain boundary shares -> pack -> [exchange] -> reduce touches only shared points of dst and the interior
@@ -335,6 +500,7 @@ class PrimitiveStorage
       {
          if ( !open_ )
             return;
+         st_.joinLanes();
          if ( !st_.sideStream_ )
          {
             hipCheck( hyteg_hip_stream_create( &st_.sideStream_ ), "side chain: stream_create" );
@@ -415,14 +581,14 @@ class PrimitiveStorage
    void       checkTransport() const
    {
       if ( transport_ )
-         transport_->check( stream_ );
+         transport_->check( stream() );
    }
    // at the points where the host reads device results anyway (downloads of cell arrays): only the peer-to-peer transport has
    // something to check there (the status word of its device-side arrival waits)
    void checkTransportAtHostRead() const
    {
       if ( transport_ && std::string( transport_->name() ) == "p2p" )
-         transport_->check( stream_ );
+         transport_->check( stream() );
    }
    Transport* transport() const { return transport_.get(); }
    Transport& requireTransport( const char* what ) const
@@ -460,11 +626,11 @@ class PrimitiveStorage
          if ( !plan.peers.empty() )
          {
             double** bases = basesTable( arrays, plan, plan.recvBuffer );
-            if ( !T.pack( plan, level, key, bases, stream_ ) )
-               hipCheck( hyteg_hip_gather_entries( plan.sendBuffer, bases, plan.dSendBuf, plan.dSendOff, plan.totalSend(), stream_ ),
+            if ( !T.pack( plan, level, key, bases, stream() ) )
+               hipCheck( hyteg_hip_gather_entries( plan.sendBuffer, bases, plan.dSendBuf, plan.dSendOff, plan.totalSend(), stream() ),
                          "exchange: pack" );
          }
-         T.exchangeBegin( plan, level, key, stream_ );
+         T.exchangeBegin( plan, level, key, stream() );
       }
    }
    // sharedExchangeBegin for a rank with ONE macro-cell whose boundary-share kernel delivers the shares itself
@@ -501,7 +667,7 @@ class PrimitiveStorage
          return false;
       const ExchangePlan& plan = devicePlan( level, active, 0 );
       const auto&         tbl  = shareSendTable( level, active, plan );
-      if ( !transport_->packArgs( plan, level, active, out.a, stream_ ) )
+      if ( !transport_->packArgs( plan, level, active, out.a, stream() ) )
          return false;
       out.first = tbl.first, out.list = tbl.list;
       // as sharedExchangeBegin: a collective transport is entered for the class without peers as well
@@ -510,7 +676,7 @@ class PrimitiveStorage
          if ( !testFlag( boundaryTypeOf( cls == 1 ), flag ) )
             continue;
          if ( cls == active || transport_->collective() )
-            transport_->exchangeBegin( devicePlan( level, cls, 0 ), level, cls, stream_ );
+            transport_->exchangeBegin( devicePlan( level, cls, 0 ), level, cls, stream() );
       }
       return true;
    }
@@ -523,7 +689,7 @@ class PrimitiveStorage
          const ExchangePlan& host = exchangePlan( level, cls, dofKind );
          const int           key  = cls + 2 * dofKind;
          if ( nranks_ > 1 && ( !host.peers.empty() || requireTransport( "exchange" ).collective() ) )
-            transport_->exchangeEnd( devicePlan( level, cls, dofKind ), level, key, stream_ );
+            transport_->exchangeEnd( devicePlan( level, cls, dofKind ), level, key, stream() );
          if ( host.ngroups() == 0 )
             continue;
          const ExchangePlan& plan  = devicePlan( level, cls, dofKind );
@@ -532,13 +698,13 @@ class PrimitiveStorage
          ArrivalWait         w;
          if ( remote && transport_->arrivalWait( plan, level, key, w ) )
             hipCheck( hyteg_hip_reduce_shared_after_p2p( bases, plan.dGroupPtr, plan.dEntryBuf, plan.dEntryOff, plan.ngroups(), (int) arrays.size(),
-                                                         additive ? 1 : 0, w.flags, w.npeers, w.stride, w.seq, w.status, w.timeoutMs, stream_ ),
+                                                         additive ? 1 : 0, w.flags, w.npeers, w.stride, w.seq, w.status, w.timeoutMs, stream() ),
                       "exchange: wait + reduce" );
          else
             hipCheck( additive ? hyteg_hip_sum_shared( bases, plan.dGroupPtr, plan.dEntryBuf, plan.dEntryOff, plan.ngroups(),
-                                                       (int) arrays.size(), stream_ )
+                                                       (int) arrays.size(), stream() )
                                : hyteg_hip_copy_shared( bases, plan.dGroupPtr, plan.dEntryBuf, plan.dEntryOff, plan.ngroups(),
-                                                        (int) arrays.size(), stream_ ),
+                                                        (int) arrays.size(), stream() ),
                       "exchange: reduce" );
       }
    }
@@ -933,10 +1099,45 @@ class PrimitiveStorage
    std::vector< MacroPrimitive >                           faces_, edges_, vertices_;
    std::vector< int >                                      localCells_;
    DoFType                                                 boundaryType_ = DirichletBoundary;
+   // NOTE: inside an open LaneScope launches may be pending on the lanes.  Whoever launches on, waits for or replaces stream_
+   // goes through stream() / joinLanes() first (they record the lanes' events and reset the planner, which is why the lane
+   // state is mutable); a raw use of stream_ is only right where the lanes are known to be joined or are being joined.
    mutable hyteg_hip_stream_t                              stream_       = nullptr;
    mutable hyteg_hip_stream_t                              sideStream_ = nullptr, mainStream_ = nullptr;
    mutable hyteg_hip_event_t                               forked_ = nullptr, joined_ = nullptr;
    mutable int                                             sideEnabled_ = -1;
+   // lanes (LaneScope): lane 0 is stream_, the others are streams of their own, created on first use
+   hyteg_hip_stream_t useLane( int lane ) const
+   {
+      if ( lane == 0 )
+         return stream_;
+      if ( !laneStreams_[lane] )
+      {
+         hipCheck( hyteg_hip_stream_create( &laneStreams_[lane] ), "lanes: stream_create" );
+         hipCheck( hyteg_hip_event_create( &laneEvents_[lane] ), "lanes: event_create" );
+      }
+      if ( !laneEvents_[0] )
+      {
+         hipCheck( hyteg_hip_event_create( &laneEvents_[0] ), "lanes: event_create" );
+         hipCheck( hyteg_hip_event_create( &laneFork_ ), "lanes: event_create" );
+      }
+      if ( !( laneUsed_ & ( 1u << lane ) ) )
+      {
+         // fork: behind everything on the storage's stream up to the first use of a lane since the last join
+         if ( !laneUsed_ )
+            hipCheck( hyteg_hip_event_record( laneFork_, stream_ ), "lanes: fork" );
+         hipCheck( hyteg_hip_stream_wait_event( laneStreams_[lane], laneFork_ ), "lanes: fork wait" );
+         laneUsed_ |= 1u << lane;
+      }
+      return laneStreams_[lane];
+   }
+   mutable LanePlanner                                     planner_;
+   mutable hyteg_hip_stream_t                              laneStreams_[LanePlanner::kMaxLanes] = {};
+   mutable hyteg_hip_event_t                               laneEvents_[LanePlanner::kMaxLanes]  = {}, laneFork_ = nullptr;
+   mutable int                                             laneCount_ = -1, laneDepth_ = 0;
+   mutable int                                             cellLanesMin_ = -1; // -1: read HYTEG_AMD_APPLY_CELL_LANES_MIN on first use
+   mutable unsigned                                        laneUsed_  = 0, lanesSeen_ = 0;
+   mutable bool                                            lanesOn_ = false, laneManual_ = false;
    std::shared_ptr< Transport >                            transport_;
    std::shared_ptr< TimingTree >                           timingTree_;
    mutable void *                                          dotResult_ = nullptr, *dotWorkspace_ = nullptr;

@@ -109,6 +109,9 @@ typedef void* hyteg_hip_graph_t;
 HYTEG_HIP_API int hyteg_hip_graph_begin_capture( hyteg_hip_stream_t stream );
 HYTEG_HIP_API int hyteg_hip_graph_end_capture( hyteg_hip_stream_t stream, hyteg_hip_graph_t* graph );
 HYTEG_HIP_API int hyteg_hip_graph_abort_capture( hyteg_hip_stream_t stream );
+/* *capturing = 1 while `stream` is being recorded into a graph (by this library or by anybody else), else 0: what a caller
+ * asks before it forks work onto streams of its own, which a recording would otherwise pull in */
+HYTEG_HIP_API int hyteg_hip_stream_is_capturing( hyteg_hip_stream_t stream, int* capturing );
 HYTEG_HIP_API int hyteg_hip_graph_launch( hyteg_hip_graph_t graph, hyteg_hip_stream_t stream );
 HYTEG_HIP_API int hyteg_hip_graph_destroy( hyteg_hip_graph_t graph );
 

@@ -48,6 +48,27 @@ HYTEG_HOST_API int hyteg_host_storage_set_stream( hh_storage_t s, void* stream )
 /* levels <= `level` use the batched kernels (one launch for all local cells, inner and boundary points together) when the
  * rank owns more than one cell; -1 disables batching.  Default 6, or the environment variable HYTEG_AMD_BATCH_MAX_LEVEL. */
 HYTEG_HOST_API int hyteg_host_storage_set_batch_max_level( hh_storage_t s, int level );
+/* Stream lanes of the storage: independent interior launches inside one host-layer call (the loop of
+ * hyteg_host_operator_apply_cycle: applies without shell points on different (src, dst) pairs; the cell loop of a multi-cell
+ * apply when enabled) are placed on `lanes` in-order streams, lane 0 being the storage's stream, and joined before the call
+ * returns; dependent launches keep the order one stream gives them.  1 = everything on the storage's stream in the order
+ * of issue; 0 = the default: the environment variable HYTEG_AMD_APPLY_LANES, else 2.  At most 8.  Results do not depend on it.
+ * Whatever the count, lanes are not used on a storage of several ranks, on the batched levels, while the storage's stream is
+ * recorded into a graph, and while the timing tree is enabled (hyteg_host_storage_enable_timing: its ranges wait for the
+ * storage's stream only) -- a run profiled with the timing tree therefore shows one-stream times. */
+HYTEG_HOST_API int hyteg_host_storage_set_apply_lanes( hh_storage_t s, int lanes );
+/* The cell loop of a non-batched multi-cell P1 apply: from `cells` local macro-cells on, the cells' interior kernels alternate
+ * between the lanes (one fork, one join per apply).  0 = never; -1 = the default: the environment variable
+ * HYTEG_AMD_APPLY_CELL_LANES_MIN, else 24 (level 8: -2.3 % on 24 cells, +7 % on 6). */
+HYTEG_HOST_API int hyteg_host_storage_set_apply_cell_lanes_min( hh_storage_t s, int cells );
+/* bit l of *mask: lane l carried a launch in the last lane scope of the storage (the last apply_cycle, or multi-cell apply
+ * with cell lanes); 0 if the lanes were off there. */
+HYTEG_HOST_API int hyteg_host_storage_lanes_seen( hh_storage_t s, unsigned* mask );
+/* The planner behind it, without a GPU: step k reads the arrays read_ids[read_ptr[k] .. read_ptr[k+1]) and writes
+ * write_ids[write_ptr[k] .. write_ptr[k+1]) (CSR; ids stand for device base pointers).  lane_out[k] = the lane step k is
+ * issued on; bit j of waits_out[k] = before step k its lane waits for everything issued on lane j so far. */
+HYTEG_HOST_API int hyteg_host_lane_plan( int lanes, int nsteps, const int* read_ptr, const unsigned long long* read_ids, const int* write_ptr,
+                                         const unsigned long long* write_ids, int* lane_out, unsigned* waits_out );
 /* Timing tree with the reference's timer names (walberla::WcTimingTree behind PrimitiveStorage::getTimingTree():
  * "Operator P1Function to P1Function" / "Apply", "smooth_jac", "SOR"; "P1Function" / "Assign", "Dot (local)" ...;
  * "Geometric Multigrid Solver" / "Level L" / "Smoother" ...; src/hyteg/operators/Operator.hpp:148-166,
