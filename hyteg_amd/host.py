@@ -107,6 +107,7 @@ SIGNATURES = {
     "hyteg_host_operator_apply_cycle_timed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, _vp]),
     "hyteg_host_operator_smooth_jac": (_i, [_vp, _vp, _vp, _vp, _d, _i, _i]),
     "hyteg_host_operator_smooth_sor": (_i, [_vp, _vp, _vp, _d, _i, _i, _i]),
+    "hyteg_host_operator_smooth_sor_many": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _d, _i, _i, _i]),
     "hyteg_host_operator_compute_inverse_diagonal": (_i, [_vp]),
     "hyteg_host_operator_inverse_diagonal": (_i, [_vp, C.POINTER(_vp)]),
     "hyteg_host_elementwise_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
@@ -525,6 +526,12 @@ class P1ConstantOperator:
 
     def smooth_sor(self, dst, rhs, relax, level, flag, backwards=False):
         _ck(lib().hyteg_host_operator_smooth_sor(self.h, dst.h, rhs.h, float(relax), level, flag, int(backwards)), "smooth_sor")
+
+    def smooth_sor_many(self, dsts, rhss, relax, level, flag, backwards=False):
+        """one sweep of several functions by shared launches (the velocity components of the Stokes smoother)"""
+        n = len(dsts)
+        hd, hr = (_vp * n)(*[f.h for f in dsts]), (_vp * n)(*[f.h for f in rhss])
+        _ck(lib().hyteg_host_operator_smooth_sor_many(self.h, n, hd, hr, float(relax), level, flag, int(backwards)), "smooth_sor_many")
 
     def smooth_gs(self, dst, rhs, level, flag):
         self.smooth_sor(dst, rhs, 1.0, level, flag)

@@ -66,11 +66,8 @@ class P1toP1LinearProlongation
       auto                 storage = function.getStorage();
       // no shell point selected (a macro-cell whose boundary values are fixed): nothing is shared, the kernel adds in place
       {
-         const DoFType flag     = function.effectiveFlag( flagIn );
-         bool          anyShell = storage->numRanks() > 1 || storage->useBatch( sourceLevel + 1 );
-         for ( uint_t c = 0; c < storage->getNumberOfLocalCells() && !anyShell; ++c )
-            anyShell = ( storage->maskFor( storage->getLocalCell( c ), flag ) & HYTEG_HIP_MASK_SHELL ) != 0;
-         if ( !anyShell )
+         const DoFType flag = function.effectiveFlag( flagIn );
+         if ( storage->numRanks() == 1 && !storage->useBatch( sourceLevel + 1 ) && !storage->anyShellSelected( flag ) )
          {
             ScopedTimer timerProlongate( storage->getTimingTree(), "P1toP1LinearProlongation" );
             for ( uint_t c = 0; c < storage->getNumberOfLocalCells(); ++c )

@@ -494,6 +494,19 @@ HYTEG_HOST_API int hyteg_host_operator_smooth_sor( hh_operator_t op, hh_function
 {
    return guarded( [&] { WITH_OP( op, A.smooth_sor( F( dst ), F( rhs ), relax, (uint_t) level, DoFType( flag ), backwards != 0 ) ); } );
 }
+HYTEG_HOST_API int hyteg_host_operator_smooth_sor_many( hh_operator_t op, int n, const hh_function_t* dsts, const hh_function_t* rhss, double relax,
+                                                        int level, int flag, int backwards )
+{
+   return guarded( [&] {
+      std::vector< std::reference_wrapper< const P1Function< double > > > xs, bs;
+      for ( int k = 0; k < n; ++k )
+      {
+         xs.push_back( std::cref( F( dsts[k] ) ) );
+         bs.push_back( std::cref( F( rhss[k] ) ) );
+      }
+      WITH_OP( op, A.smooth_sor_many( xs, bs, relax, (uint_t) level, DoFType( flag ), backwards != 0 ) );
+   } );
+}
 HYTEG_HOST_API int hyteg_host_operator_compute_inverse_diagonal( hh_operator_t op )
 {
    return guarded( [&] { WITH_OP( op, A.computeInverseDiagonalOperatorValues() ); } );

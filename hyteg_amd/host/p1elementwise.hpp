@@ -43,17 +43,11 @@ class P1ElementwiseDiffusion
       if ( &src == &dst )
          throw std::runtime_error( "P1ElementwiseDiffusion::apply: src and dst must differ" );
       const int64_t n = int64_t( 1 ) << level;
-      bool          anyShell = false;
-      forCells( [&]( uint_t, const MacroCell& cell ) { anyShell = anyShell || ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL ); } );
-      const P1Function< double >*             shellDst = &dst;
+      // the shares of a shared DoF are summed over the cells before the sum is added to dst
       std::unique_ptr< P1Function< double > > tmp;
-      if ( updateType == Add && anyShell && ( storage_->getCells().size() > 1 ) )
-      {
-         // the shares of a shared DoF are summed over the cells before the sum is added to dst
-         tmp.reset( new P1Function< double >( "apply_tmp", storage_, level, level, true ) );
-         tmp->interpolate( 0.0, level, All );
-         shellDst = tmp.get();
-      }
+      if ( updateType == Add && storage_->anyShellSelected( flag ) && ( storage_->getCells().size() > 1 ) )
+         tmp = P1Function< double >::zeroedScratch( "apply_tmp", storage_, level );
+      const P1Function< double >& shellDst = tmp ? *tmp : dst;
       auto kernel = [&]( const P1Function< double >& out, uint_t c, const MacroCell& cell, unsigned mask, int update ) {
          if ( mask == 0 )
             return;
@@ -65,23 +59,16 @@ class P1ElementwiseDiffusion
                                                                              update, storage_->stream() ),
                    "P1ElementwiseDiffusion::apply: apply_macro_3D" );
       };
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
-         kernel( *shellDst, c, cell, storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL,
-                 ( updateType == Add && shellDst == &dst ) ? HYTEG_HIP_ADD : HYTEG_HIP_REPLACE );
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+         kernel( shellDst, c, cell, storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL, hipUpdate( tmp ? Replace : updateType ) );
       } );
-      shellDst->beginSumSharedCopies( level, flag );
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
-         kernel( dst, c, cell, storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER, updateType == Replace ? HYTEG_HIP_REPLACE : HYTEG_HIP_ADD );
+      shellDst.beginSumSharedCopies( level, flag );
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+         kernel( dst, c, cell, storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER, hipUpdate( updateType ) );
       } );
-      shellDst->endSumSharedCopies( level, flag );
-      if ( shellDst != &dst )
-         forCells( [&]( uint_t c, const MacroCell& cell ) {
-            const double* srcs[1] = { shellDst->getCellPointer( c, level ) };
-            const double  one[1]  = { 1.0 };
-            hipCheck( hyteg_hip_p1_vector_cell_masked( 1, dst.getCellPointer( c, level ), 1, srcs, one, (int) level,
-                                                       storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL, storage_->stream() ),
-                      "P1ElementwiseDiffusion::apply: add shell" );
-         } );
+      shellDst.endSumSharedCopies( level, flag );
+      if ( tmp )
+         dst.addOnShell( *tmp, level, flag );
    }
 
    // computeInverseDiagonalOperatorValues, .cpp (same file): invDiag_ = 0; per cell
@@ -92,7 +79,7 @@ class P1ElementwiseDiffusion
       for ( uint_t l = minLevel_; l <= maxLevel_; ++l )
       {
          invDiag_->interpolate( 0.0, l, All );
-         forCells( [&]( uint_t c, const MacroCell& cell ) {
+         storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
             double cc[12];
             for ( int v = 0; v < 4; ++v )
                for ( int r = 0; r < 3; ++r )
@@ -104,7 +91,7 @@ class P1ElementwiseDiffusion
          invDiag_->sumSharedCopies( l, All );
          // invertElementwise: set-up time, on the host
          std::vector< double > h( (size_t) hyteg_hip_cell_size( (int) l ) );
-         forCells( [&]( uint_t c, const MacroCell& ) {
+         storage_->forLocalCells( [&]( uint_t c, const MacroCell& ) {
             invDiag_->copyCellToHost( c, l, h.data() );
             for ( double& v : h )
                v = v != 0.0 ? 1.0 / v : 0.0;
@@ -133,12 +120,6 @@ class P1ElementwiseDiffusion
    }
 
  private:
-   template < typename F >
-   void forCells( F&& fn ) const
-   {
-      for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
-         fn( c, storage_->getLocalCell( c ) );
-   }
    std::shared_ptr< PrimitiveStorage >     storage_;
    uint_t                                  minLevel_, maxLevel_;
    std::shared_ptr< P1Function< double > > invDiag_;

@@ -171,6 +171,27 @@ class P1Function
    }
    void setToZero( uint_t level ) const { interpolate( ValueType( 0 ), level, All ); }
 
+   // ---- Operator::apply with UpdateType Add where cells share points: every cell's partial result of a shared DoF goes to a
+   // zeroed scratch function, is summed over the cells there (sumSharedCopies) and the sum is added to the destination ----
+   static std::unique_ptr< P1Function > zeroedScratch( const std::string& name, const std::shared_ptr< PrimitiveStorage >& storage, uint_t level )
+   {
+      std::unique_ptr< P1Function > f( new P1Function( name, storage, level, level, true ) );
+      f->interpolate( ValueType( 0 ), level, All );
+      return f;
+   }
+   // this += f on the macro-face, -edge and -vertex points `flag` selects, one launch per cell
+   void addOnShell( const P1Function< ValueType >& f, uint_t level, DoFType flagIn ) const
+   {
+      const DoFType flag = effectiveFlag( flagIn );
+      forCells( [&]( uint_t c, const MacroCell& cell ) {
+         const double* srcs[1] = { f.getCellPointer( c, level ) };
+         const double  one[1]  = { 1.0 };
+         hipCheck( hyteg_hip_p1_vector_cell_masked( 1, getCellPointer( c, level ), 1, srcs, one, (int) level,
+                                                    storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL, storage_->stream() ),
+                   "addOnShell" );
+      } );
+   }
+
    // ---- dot ( VertexDoFFunction.cpp:1710-1793 ) ----
    ValueType dotLocal( const P1Function< ValueType >& rhs, uint_t level, DoFType flagIn = All ) const
    {

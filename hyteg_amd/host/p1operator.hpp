@@ -17,6 +17,7 @@ class P1ConstantOperator
  public:
    using srcType = P1Function< double >;
    using dstType = P1Function< double >;
+   using FunctionList = std::vector< std::reference_wrapper< const P1Function< double > > >;
 
    P1ConstantOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
    : storage_( storage )
@@ -56,7 +57,7 @@ class P1ConstantOperator
          // other apply runs behind all lanes, as ever
          if ( pureInterior( level, flag ) )
          {
-            forCells( [&]( uint_t c, const MacroCell& cell ) {
+            storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
                if ( !( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER ) )
                   return;
                double*            d    = dst.getCellPointer( c, level );
@@ -64,8 +65,7 @@ class P1ConstantOperator
                const void*        r[1] = { u };
                const void*        w[1] = { d };
                hyteg_hip_stream_t lane = storage_->laneFor( r, 1, w, 1 );
-               hipCheck( hyteg_hip_p1_apply_cell( d, u, (int) level, getCellStencils( cell.id, level ).inner,
-                                                  updateType == Replace ? HYTEG_HIP_REPLACE : HYTEG_HIP_ADD, lane ),
+               hipCheck( hyteg_hip_p1_apply_cell( d, u, (int) level, getCellStencils( cell.id, level ).inner, hipUpdate( updateType ), lane ),
                          "apply: cell" );
             } );
             return;
@@ -77,15 +77,12 @@ class P1ConstantOperator
          applyBatched( src, dst, level, flag, updateType );
          return;
       }
-      const P1Function< double >* shellDst = &dst;
+      // partial results of shared DoFs are summed over cells before they are added to dst
       std::unique_ptr< P1Function< double > > tmp;
       if ( updateType == Add && hasSharedPoints( level, flag ) )
-      {
-         // partial results of shared DoFs are summed over cells before they are added to dst
-         tmp.reset( new P1Function< double >( "apply_tmp", storage_, level, level, true ) );
-         tmp->interpolate( 0.0, level, All );
-         shellDst = tmp.get();
-      }
+         tmp = P1Function< double >::zeroedScratch( "apply_tmp", storage_, level );
+      const P1Function< double >& shellDst    = tmp ? *tmp : dst;
+      const int                   shellUpdate = hipUpdate( tmp ? Replace : updateType );
       // 1. this cell's share of the shared macro-face/edge/vertex DoFs (tiny kernels), 2. start the halo exchange,
       // 3. the interior stencil while the exchange is in flight, 4. reduce the shares.  1, 2 and 4 only touch shared points:
       // with a stream-agnostic transport they can form a chain on a side stream next to 3 (PrimitiveStorage::SideChain;
@@ -98,53 +95,39 @@ class P1ConstantOperator
                                                             level >= HYTEG_HIP_MIN_LEVEL );
       // a rank with ONE macro-cell that exchanges peer to peer: the share kernel stores the shares into the peers' slots itself
       PrimitiveStorage::ShareSend send;
-      const bool bySharesKernel = shellDst->beginSumSharedCopiesByShares( level, flag, send );
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
+      const bool bySharesKernel = shellDst.beginSumSharedCopiesByShares( level, flag, send );
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
          const auto& S = getCellStencils( cell.id, level );
          if ( bySharesKernel )
          {
-            hipCheck( hyteg_hip_p1_apply_cell_boundary_p2p( shellDst->getCellPointer( c, level ), src.getCellPointer( c, level ), (int) level,
-                                                            &S.slots[0][0], storage_->maskFor( cell, flag ),
-                                                            ( updateType == Add && shellDst == &dst ) ? HYTEG_HIP_ADD : HYTEG_HIP_REPLACE,
-                                                            send.first, send.list, send.a.peers, send.a.npeers, send.a.seq, send.a.counter,
-                                                            storage_->stream() ),
+            hipCheck( hyteg_hip_p1_apply_cell_boundary_p2p( shellDst.getCellPointer( c, level ), src.getCellPointer( c, level ), (int) level,
+                                                            &S.slots[0][0], storage_->maskFor( cell, flag ), shellUpdate, send.first, send.list,
+                                                            send.a.peers, send.a.npeers, send.a.seq, send.a.counter, storage_->stream() ),
                       "apply: boundary + send" );
             return;
          }
-         hipCheck( hyteg_hip_p1_apply_cell_boundary( shellDst->getCellPointer( c, level ), src.getCellPointer( c, level ), (int) level,
-                                                     &S.slots[0][0], storage_->maskFor( cell, flag ),
-                                                     ( updateType == Add && shellDst == &dst ) ? HYTEG_HIP_ADD : HYTEG_HIP_REPLACE,
-                                                     storage_->stream() ),
+         hipCheck( hyteg_hip_p1_apply_cell_boundary( shellDst.getCellPointer( c, level ), src.getCellPointer( c, level ), (int) level,
+                                                     &S.slots[0][0], storage_->maskFor( cell, flag ), shellUpdate, storage_->stream() ),
                    "apply: boundary" );
       } );
       if ( !bySharesKernel )
-         shellDst->beginSumSharedCopies( level, flag );
+         shellDst.beginSumSharedCopies( level, flag );
       chain.toMain();
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
          const unsigned mask = storage_->maskFor( cell, flag );
          if ( ( mask & HYTEG_HIP_MASK_INNER ) && level >= HYTEG_HIP_MIN_LEVEL )
             hipCheck( hyteg_hip_p1_apply_cell( dst.getCellPointer( c, level ), src.getCellPointer( c, level ), (int) level,
-                                               getCellStencils( cell.id, level ).inner,
-                                               updateType == Replace ? HYTEG_HIP_REPLACE : HYTEG_HIP_ADD,
+                                               getCellStencils( cell.id, level ).inner, hipUpdate( updateType ),
                                                // the first cell on lane 1: forked before any interior is on the storage's stream
                                                cellLanes.active() ? storage_->laneStream( (int) c + 1 ) : storage_->stream() ),
                       "apply: cell" );
       } );
       cellLanes.join();
       chain.toSide();
-      shellDst->endSumSharedCopies( level, flag );
+      shellDst.endSumSharedCopies( level, flag );
       chain.join();
-      if ( shellDst != &dst )
-      {
-         // dst += tmp on the shell points selected by flag
-         forCells( [&]( uint_t c, const MacroCell& cell ) {
-            const double* srcs[1] = { shellDst->getCellPointer( c, level ) };
-            const double  one[1]  = { 1.0 };
-            hipCheck( hyteg_hip_p1_vector_cell_masked( 1, dst.getCellPointer( c, level ), 1, srcs, one, (int) level,
-                                                       storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL, storage_->stream() ),
-                      "apply: add shell" );
-         } );
-      }
+      if ( tmp )
+         dst.addOnShell( *tmp, level, flag );
    }
 
    // r = b - A x on the points `flag` selects: apply followed by assign( { 1, -1 }, { b, r } ) as the multigrid cycle writes it
@@ -152,17 +135,15 @@ class P1ConstantOperator
    // interior kernel forms the difference itself -- one launch, the same bits
    void residual( const P1Function< double >& x, const P1Function< double >& b, const P1Function< double >& r, uint_t level, DoFType flagIn ) const
    {
-      const DoFType flag     = r.effectiveFlag( flagIn );
-      bool          anyShell = storage_->numRanks() > 1 || storage_->useBatch( level ) || level < HYTEG_HIP_MIN_LEVEL || level > 10 || &x == &r;
-      forCells( [&]( uint_t, const MacroCell& cell ) { anyShell = anyShell || ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL ); } );
-      if ( anyShell )
+      const DoFType flag = r.effectiveFlag( flagIn );
+      if ( !pureInterior( level, flag ) || level > 10 || &x == &r )
       {
          apply( x, r, level, flagIn );
          r.assign( { 1.0, -1.0 }, { b, r }, level, flagIn );
          return;
       }
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerApply( storage_->getTimingTree(), "Apply" );
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
          if ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER )
             hipCheck( hyteg_hip_p1_residual_cell( r.getCellPointer( c, level ), b.getCellPointer( c, level ), x.getCellPointer( c, level ),
                                                   (int) level, getCellStencils( cell.id, level ).inner, storage_->stream() ),
@@ -198,33 +179,14 @@ class P1ConstantOperator
          }
          return;
       }
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
-         const auto&    S    = getCellStencils( cell.id, level );
-         const unsigned mask = storage_->maskFor( cell, flag );
-         if ( ( mask & HYTEG_HIP_MASK_INNER ) && level >= HYTEG_HIP_MIN_LEVEL )
+      interiorsAndShares( dst, src, level, flag, [&]( uint_t c, const double* inner ) {
+         if ( level >= HYTEG_HIP_MIN_LEVEL )
             hipCheck( hyteg_hip_p1_jacobi_cell( dst.getCellPointer( c, level ), rhs.getCellPointer( c, level ), src.getCellPointer( c, level ),
-                                                nullptr, (int) level, S.inner, relax, storage_->stream() ),
+                                                nullptr, (int) level, inner, relax, storage_->stream() ),
                       "smooth_jac: cell" );
-         hipCheck( hyteg_hip_p1_apply_cell_boundary( dst.getCellPointer( c, level ), src.getCellPointer( c, level ), (int) level,
-                                                     &S.slots[0][0], mask, HYTEG_HIP_REPLACE, storage_->stream() ),
-                   "smooth_jac: boundary" );
       } );
-      dst.sumSharedCopies( level, flag );
       // on the shell: dst = rhs - dst ; dst = invDiag .* dst ; dst = src + relax * dst  (the reference's three passes)
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
-         const unsigned shell = storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL;
-         if ( !shell )
-            return;
-         double*       d = dst.getCellPointer( c, level );
-         const double* a[2] = { rhs.getCellPointer( c, level ), d };
-         const double  s1[2] = { 1.0, -1.0 };
-         hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, a, s1, (int) level, shell, storage_->stream() ), "smooth_jac: residual" );
-         const double* m[2] = { invDiag.getCellPointer( c, level ), d };
-         hipCheck( hyteg_hip_p1_vector_cell_masked( 2, d, 2, m, nullptr, (int) level, shell, storage_->stream() ), "smooth_jac: scale" );
-         const double* u[2] = { src.getCellPointer( c, level ), d };
-         const double  s2[2] = { 1.0, relax };
-         hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, u, s2, (int) level, shell, storage_->stream() ), "smooth_jac: update" );
-      } );
+      shellPasses( dst, &rhs, invDiag, src, relax, dst, level, flag );
    }
 
    // ---- the steps of ChebyshevSmoother::solve (ChebyshevSmoother.hpp:165-212), fused like smooth_jac: one launch per step on
@@ -242,19 +204,13 @@ class P1ConstantOperator
       const DoFType flag = x.effectiveFlag( flagIn );
       if ( &t == &x || &t == &b )
          throw std::runtime_error( "chebyshevStart: t must differ from x and b" );
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
-         const auto&    S    = getCellStencils( cell.id, level );
-         const unsigned mask = storage_->maskFor( cell, flag );
-         if ( mask & HYTEG_HIP_MASK_INNER )
-            hipCheck( hyteg_hip_p1_chebyshev_start_cell( t.getCellPointer( c, level ), b.getCellPointer( c, level ), x.getCellPointer( c, level ),
-                                                         nullptr, (int) level, S.inner, storage_->stream() ),
-                      "chebyshevStart: cell" );
-         hipCheck( hyteg_hip_p1_apply_cell_boundary( t.getCellPointer( c, level ), x.getCellPointer( c, level ), (int) level, &S.slots[0][0], mask,
-                                                     HYTEG_HIP_REPLACE, storage_->stream() ),
-                   "chebyshevStart: boundary" );
+      interiorsAndShares( t, x, level, flag, [&]( uint_t c, const double* inner ) {
+         hipCheck( hyteg_hip_p1_chebyshev_start_cell( t.getCellPointer( c, level ), b.getCellPointer( c, level ), x.getCellPointer( c, level ),
+                                                      nullptr, (int) level, inner, storage_->stream() ),
+                   "chebyshevStart: cell" );
       } );
-      t.sumSharedCopies( level, flag );
-      chebyshevShell( t, &b, x, c0, level, flag );
+      // on the shell: t = b - t ; t = invDiag .* t ; x = x + c0 t
+      shellPasses( t, &b, *getInverseDiagonalValues(), x, c0, x, level, flag );
    }
    // tOut = invDiag .* ( A tIn ) on the selected points; x = ( x + cPrev tIn ) + cCur tOut on the interiors (first term only if
    // hasPrev: the update chebyshevStart left open), x += cCur tOut on the shell
@@ -265,25 +221,19 @@ class P1ConstantOperator
       const DoFType flag = x.effectiveFlag( flagIn );
       if ( &tOut == &tIn || &tOut == &x || &x == &tIn )
          throw std::runtime_error( "chebyshevStep: tOut, x and tIn must be three different functions" );
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
-         const auto&    S    = getCellStencils( cell.id, level );
-         const unsigned mask = storage_->maskFor( cell, flag );
-         if ( mask & HYTEG_HIP_MASK_INNER )
-            hipCheck( hyteg_hip_p1_chebyshev_step_cell( tOut.getCellPointer( c, level ), x.getCellPointer( c, level ), tIn.getCellPointer( c, level ),
-                                                        nullptr, (int) level, S.inner, cPrev, cCur, hasPrev ? 1 : 0, storage_->stream() ),
-                      "chebyshevStep: cell" );
-         hipCheck( hyteg_hip_p1_apply_cell_boundary( tOut.getCellPointer( c, level ), tIn.getCellPointer( c, level ), (int) level, &S.slots[0][0],
-                                                     mask, HYTEG_HIP_REPLACE, storage_->stream() ),
-                   "chebyshevStep: boundary" );
+      interiorsAndShares( tOut, tIn, level, flag, [&]( uint_t c, const double* inner ) {
+         hipCheck( hyteg_hip_p1_chebyshev_step_cell( tOut.getCellPointer( c, level ), x.getCellPointer( c, level ), tIn.getCellPointer( c, level ),
+                                                     nullptr, (int) level, inner, cPrev, cCur, hasPrev ? 1 : 0, storage_->stream() ),
+                   "chebyshevStep: cell" );
       } );
-      tOut.sumSharedCopies( level, flag );
-      chebyshevShell( tOut, nullptr, x, cCur, level, flag );
+      // on the shell: tOut = invDiag .* tOut ; x = x + cCur tOut
+      shellPasses( tOut, nullptr, *getInverseDiagonalValues(), x, cCur, x, level, flag );
    }
    // x += c t on the interiors: closes a smoother call of order 1 (no step follows the start)
    void chebyshevFinish( const P1Function< double >& x, const P1Function< double >& t, double c, uint_t level, DoFType flagIn ) const
    {
       const DoFType flag = x.effectiveFlag( flagIn );
-      forCells( [&]( uint_t ci, const MacroCell& cell ) {
+      storage_->forLocalCells( [&]( uint_t ci, const MacroCell& cell ) {
          const unsigned inner = storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER;
          if ( !inner )
             return;
@@ -302,10 +252,8 @@ class P1ConstantOperator
    void smooth_sor_steps( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flagIn,
                           uint_t steps, bool backwards = false ) const
    {
-      const DoFType flag     = dst.effectiveFlag( flagIn );
-      bool          anyShell = false;
-      forCells( [&]( uint_t, const MacroCell& cell ) { anyShell = anyShell || ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL ); } );
-      if ( steps <= 1 || anyShell || storage_->numRanks() != 1 || storage_->useBatchSor( level ) || level < 5 )
+      const DoFType flag = dst.effectiveFlag( flagIn );
+      if ( steps <= 1 || storage_->anyShellSelected( flag ) || storage_->numRanks() != 1 || storage_->useBatchSor( level ) || level < 5 )
       {
          for ( uint_t k = 0; k < steps; ++k )
             smooth_sor( dst, rhs, relax, level, flagIn, backwards );
@@ -314,7 +262,7 @@ class P1ConstantOperator
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerSor( storage_->getTimingTree(), backwards ? "SOR backwards" : "SOR" );
       if ( &dst == &rhs )
          throw std::runtime_error( "smooth_sor: dst and rhs must differ" );
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
          if ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER )
             hipCheck( hyteg_hip_p1_sor_cell_sweeps( dst.getCellPointer( c, level ), rhs.getCellPointer( c, level ), (int) level,
                                                     getCellStencils( cell.id, level ).inner, relax, backwards ? 1 : 0, (int) steps,
@@ -332,56 +280,31 @@ class P1ConstantOperator
    void smooth_sor( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flagIn,
                     bool backwards = false ) const
    {
-      ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerSor( storage_->getTimingTree(), backwards ? "SOR backwards" : "SOR" );
-      const DoFType flag = dst.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       if ( &dst == &rhs )
          throw std::runtime_error( "smooth_sor: dst and rhs must differ" );
-      bool anyShell = false;
-      forCells( [&]( uint_t, const MacroCell& cell ) { anyShell = anyShell || ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL ); } );
-      auto sweepCells = [&]() { launchSorCells( dst, rhs, relax, level, flag, backwards ); };
-      if ( !anyShell && storage_->numRanks() == 1 )
-      {
-         sweepCells();
-         return;
-      }
-      auto& restSlot = sorRest_[level];
-      if ( !restSlot )
-         restSlot.reset( new P1Function< double >( "sor_rest", storage_, level, level ) );
-      P1Function< double >& rest = *restSlot;
-      auto                 sweepShell = [&]( unsigned bits ) {
-         if ( storage_->useBatchSor( level ) )
-         {
-            const auto masks = storage_->masksFor( flag, false, bits & HYTEG_HIP_MASK_SHELL );
-            storage_->forCellChunks( [&]( int first, int count ) {
-               const auto r = rest.cellPointers( level, first, count ), u = dst.cellPointers( level, first, count );
-               hipCheck( hyteg_hip_p1_apply_cells( count, r.data(), u.data(), (int) level, restTable( level ) + (size_t) first * 225,
-                                                   masks.data() + first, HYTEG_HIP_REPLACE, storage_->stream() ),
-                         "smooth_sor: rest (batched)" );
-            } );
-         }
-         else
-         forCells( [&]( uint_t c, const MacroCell& cell ) {
-            const auto&    T    = sorTables_.at( level ).at( cell.id );
-            const unsigned mask = storage_->maskFor( cell, flag ) & bits;
-            hipCheck( hyteg_hip_p1_apply_cell_boundary( rest.getCellPointer( c, level ), dst.getCellPointer( c, level ), (int) level,
-                                                        &T.rest[0][0], mask, HYTEG_HIP_REPLACE, storage_->stream() ),
-                      "smooth_sor: rest" );
-         } );
-         rest.sumSharedCopies( level, flag );
-         launchSorShell( dst, rhs, rest, relax, level, flag, bits, backwards );
-      };
-      if ( !backwards )
-      {
-         sweepShell( HYTEG_HIP_MASK_SHELL );
-         sweepCells();
-      }
+      sorSchedule( { dst }, { rhs }, relax, level, dst.effectiveFlag( flagIn ), backwards );
+   }
+   // Several functions swept by the SAME launches (no counterpart in the reference, which sweeps one function at a time): the
+   // Gauss-Seidel phases are chains of small dependent kernels whose duration does not depend on how many cells a launch
+   // covers, and the batched kernels take any list of cell arrays -- so the three velocity components of the Stokes smoother
+   // (StokesVelocityBlockBlockDiagonalPreconditioner) share one chain instead of running three.  The batch is ordered
+   // [function][cell]; every function sees exactly the kernels, tables and order of smooth_sor: results are bit-identical.
+   // Falls back to one smooth_sor per function where the batched path does not apply (large levels, different boundary
+   // conditions).
+   void smooth_sor_many( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, DoFType flagIn, bool backwards = false ) const
+   {
+      const uint_t nf = dsts.size();
+      if ( nf == 0 || rhss.size() != nf )
+         throw std::runtime_error( "smooth_sor_many: need as many right-hand sides as functions" );
+      const DoFType flag     = dsts[0].get().effectiveFlag( flagIn );
+      bool          together = nf > 1 && storage_->useBatch( level ) && storage_->useBatchSor( level );
+      for ( uint_t k = 0; k < nf; ++k )
+         together = together && dsts[k].get().effectiveFlag( flagIn ) == flag && &dsts[k].get() != &rhss[k].get();
+      if ( together )
+         sorSchedule( dsts, rhss, relax, level, flag, backwards );
       else
-      {
-         sweepCells();
-         sweepShell( 0xFu << 6 );  // macro-faces
-         sweepShell( 0x3Fu );      // macro-edges
-         sweepShell( 0xFu << 10 ); // macro-vertices
-      }
+         for ( uint_t k = 0; k < nf; ++k )
+            smooth_sor( dsts[k].get(), rhss[k].get(), relax, level, flagIn, backwards );
    }
    // The two halves of smooth_sor for callers that provide the stencil sum over the neighbours outside a primitive's closure
    // themselves (P2 operators: the vertex-to-vertex sweeps of P2ConstantOperator::smooth_sor_macro_{vertices,edges,faces,cells}
@@ -390,176 +313,80 @@ class P1ConstantOperator
    void smooth_sor_shell_given_rest( const P1Function< double >& dst, const P1Function< double >& rhs, const P1Function< double >& rest,
                                      double relax, uint_t level, DoFType flagIn, unsigned bits, bool backwards = false ) const
    {
-      launchSorShell( dst, rhs, rest, relax, level, dst.effectiveFlag( flagIn ), bits, backwards );
+      launchSorShell( { dst }, { rhs }, { rest }, relax, level, dst.effectiveFlag( flagIn ), bits, backwards );
    }
    void smooth_sor_cells_only( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flagIn,
                                bool backwards = false ) const
    {
-      launchSorCells( dst, rhs, relax, level, dst.effectiveFlag( flagIn ), backwards );
+      launchSorCells( { dst }, { rhs }, relax, level, dst.effectiveFlag( flagIn ), backwards );
    }
 
  private:
-   // shell points of a Chebyshev step, after the shares of A t have been summed into t: t = b - t (start only), t = invDiag .* t,
-   // x = x + c t -- the reference's passes with their operands in its order
-   void chebyshevShell( const P1Function< double >& t, const P1Function< double >* b, const P1Function< double >& x, double c, uint_t level,
-                        DoFType flag ) const
+   // the skeleton of a fused smoother step on the per-cell kernels: `interior( c, inner stencil )` launches the step on the
+   // interior of every cell where the flag selects it, every cell's share of A src on the shell points goes to dst and the
+   // shares are summed over the cells
+   template < typename Interior >
+   void interiorsAndShares( const P1Function< double >& dst, const P1Function< double >& src, uint_t level, DoFType flag, Interior&& interior ) const
    {
-      const auto& invDiag = *getInverseDiagonalValues();
-      forCells( [&]( uint_t ci, const MacroCell& cell ) {
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+         const auto&    S    = getCellStencils( cell.id, level );
+         const unsigned mask = storage_->maskFor( cell, flag );
+         if ( mask & HYTEG_HIP_MASK_INNER )
+            interior( c, S.inner );
+         hipCheck( hyteg_hip_p1_apply_cell_boundary( dst.getCellPointer( c, level ), src.getCellPointer( c, level ), (int) level, &S.slots[0][0], mask,
+                                                     HYTEG_HIP_REPLACE, storage_->stream() ),
+                   "smoother step: boundary" );
+      } );
+      dst.sumSharedCopies( level, flag );
+   }
+   // the reference's passes on the shell points, after the shares of a stencil sum have been summed into t: t = rhs - t (if rhs),
+   // t = invDiag .* t, out = base + c t -- operands in the reference's order
+   void shellPasses( const P1Function< double >& t, const P1Function< double >* rhs, const P1Function< double >& invDiag,
+                     const P1Function< double >& base, double c, const P1Function< double >& out, uint_t level, DoFType flag ) const
+   {
+      storage_->forLocalCells( [&]( uint_t ci, const MacroCell& cell ) {
          const unsigned shell = storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL;
          if ( !shell )
             return;
          double* d = t.getCellPointer( ci, level );
-         if ( b )
+         if ( rhs )
          {
-            const double* a[2]  = { b->getCellPointer( ci, level ), d };
+            const double* a[2]  = { rhs->getCellPointer( ci, level ), d };
             const double  s1[2] = { 1.0, -1.0 };
-            hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, a, s1, (int) level, shell, storage_->stream() ), "chebyshev: residual" );
+            hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, a, s1, (int) level, shell, storage_->stream() ), "shell passes: residual" );
          }
          const double* m[2] = { invDiag.getCellPointer( ci, level ), d };
-         hipCheck( hyteg_hip_p1_vector_cell_masked( 2, d, 2, m, nullptr, (int) level, shell, storage_->stream() ), "chebyshev: scale" );
-         double*       xd    = x.getCellPointer( ci, level );
-         const double* u[2]  = { xd, d };
+         hipCheck( hyteg_hip_p1_vector_cell_masked( 2, d, 2, m, nullptr, (int) level, shell, storage_->stream() ), "shell passes: scale" );
+         const double* u[2]  = { base.getCellPointer( ci, level ), d };
          const double  s2[2] = { 1.0, c };
-         hipCheck( hyteg_hip_p1_vector_cell_masked( 0, xd, 2, u, s2, (int) level, shell, storage_->stream() ), "chebyshev: update" );
-      } );
-   }
-   void launchSorCells( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flag,
-                        bool backwards ) const
-   {
-      if ( storage_->useBatchSor( level ) )
-      {
-         const auto masks = storage_->masksFor( flag );
-         storage_->forCellChunks( [&]( int first, int count ) {
-            const auto u = dst.cellPointers( level, first, count ), r = rhs.cellPointers( level, first, count );
-            hipCheck( hyteg_hip_p1_sor_cells( count, u.data(), r.data(), (int) level, stencilTable( level ) + (size_t) first * 225, relax,
-                                              backwards ? 1 : 0, masks.data() + first, storage_->stream() ),
-                      "smooth_sor: cells (batched)" );
-         } );
-         return;
-      }
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
-         const unsigned mask = storage_->maskFor( cell, flag );
-         if ( ( mask & HYTEG_HIP_MASK_INNER ) && level >= HYTEG_HIP_MIN_LEVEL )
-            hipCheck( hyteg_hip_p1_sor_cell( dst.getCellPointer( c, level ), rhs.getCellPointer( c, level ), (int) level,
-                                             getCellStencils( cell.id, level ).inner, relax, backwards ? 1 : 0, storage_->stream() ),
-                      "smooth_sor: cell" );
-      } );
-   }
-   void launchSorShell( const P1Function< double >& dst, const P1Function< double >& rhs, const P1Function< double >& rest, double relax,
-                        uint_t level, DoFType flag, unsigned bits, bool backwards ) const
-   {
-      if ( storage_->useBatchSor( level ) )
-      {
-         const auto masks = storage_->masksFor( flag, false, bits & HYTEG_HIP_MASK_SHELL );
-         storage_->forCellChunks( [&]( int first, int count ) {
-            const auto u = dst.cellPointers( level, first, count ), r = rhs.cellPointers( level, first, count ),
-                       q = rest.cellPointers( level, first, count );
-            hipCheck( hyteg_hip_p1_sor_shell_cells( count, u.data(), r.data(), q.data(), (int) level, shellTable( level ) + first, relax,
-                                                    masks.data() + first, backwards ? 1 : 0, storage_->stream() ),
-                      "smooth_sor: shell (batched)" );
-         } );
-         return;
-      }
-      forCells( [&]( uint_t c, const MacroCell& cell ) {
-         const auto&    T    = sorTables_.at( level ).at( cell.id );
-         const unsigned mask = storage_->maskFor( cell, flag ) & bits;
-         hipCheck( hyteg_hip_p1_sor_shell_cell( dst.getCellPointer( c, level ), rhs.getCellPointer( c, level ),
-                                                rest.getCellPointer( c, level ), (int) level, &T.edgeVerts[0][0], &T.edgeW[0][0],
-                                                &T.faceVerts[0][0], &T.faceW[0][0], T.vertexW, relax, mask, backwards ? 1 : 0,
-                                                storage_->stream() ),
-                   "smooth_sor: shell" );
+         hipCheck( hyteg_hip_p1_vector_cell_masked( 0, out.getCellPointer( ci, level ), 2, u, s2, (int) level, shell, storage_->stream() ),
+                   "shell passes: update" );
       } );
    }
 
- public:
-   // Several functions swept by the SAME launches (no counterpart in the reference, which sweeps one function at a time): the
-   // Gauss-Seidel phases are chains of small dependent kernels whose duration does not depend on how many cells a launch
-   // covers, and the batched kernels take any list of cell arrays -- so the three velocity components of the Stokes smoother
-   // (StokesVelocityBlockBlockDiagonalPreconditioner) share one chain instead of running three.  The batch is ordered
-   // [function][cell]; every function sees exactly the kernels, tables and order of smooth_sor: results are bit-identical.
-   // Falls back to one smooth_sor per function where the batched path does not apply (large levels, different boundary
-   // conditions).
-   void smooth_sor_many( const std::vector< std::reference_wrapper< const P1Function< double > > >& dsts,
-                         const std::vector< std::reference_wrapper< const P1Function< double > > >& rhss, double relax, uint_t level,
-                         DoFType flagIn, bool backwards = false ) const
+   // ---- smooth_sor for the functions of a list at once: the order of the classes, once.  Each of the three stages below is
+   // one launch per chunk of the list [function][cell] ([cell] for one function) where the storage batches the sweeps
+   // (useBatchSor), else one launch per function and cell. ----
+   void sorSchedule( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, DoFType flag, bool backwards ) const
    {
-      const uint_t nf = dsts.size();
-      if ( nf == 0 || rhss.size() != nf )
-         throw std::runtime_error( "smooth_sor_many: need as many right-hand sides as functions" );
-      const DoFType flag = dsts[0].get().effectiveFlag( flagIn );
-      bool          together = nf > 1 && storage_->useBatch( level ) && storage_->useBatchSor( level );
-      for ( uint_t k = 0; k < nf; ++k )
-         together = together && dsts[k].get().effectiveFlag( flagIn ) == flag && &dsts[k].get() != &rhss[k].get();
-      if ( !together )
-      {
-         for ( uint_t k = 0; k < nf; ++k )
-            smooth_sor( dsts[k].get(), rhss[k].get(), relax, level, flagIn, backwards );
-         return;
-      }
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerSor( storage_->getTimingTree(), backwards ? "SOR backwards" : "SOR" );
-      const int nc    = (int) storage_->getNumberOfLocalCells();
-      const int total = nc * (int) nf;
-      // chunks of the concatenated [function][cell] list
-      auto forChunks = [&]( auto&& fn ) {
-         for ( int first = 0; first < total; first += HYTEG_HIP_MAX_BATCH )
-            fn( first, std::min( HYTEG_HIP_MAX_BATCH, total - first ) );
-      };
-      auto pointers = [&]( const std::vector< std::reference_wrapper< const P1Function< double > > >& fs, int first, int count ) {
-         std::vector< double* > p;
-         for ( int e = first; e < first + count; ++e )
-            p.push_back( fs[(uint_t) ( e / nc )].get().getCellPointer( (uint_t) ( e % nc ), level ) );
-         return p;
-      };
-      auto repeatMasks = [&]( const std::vector< unsigned >& once ) {
-         std::vector< unsigned > m;
-         for ( uint_t k = 0; k < nf; ++k )
-            m.insert( m.end(), once.begin(), once.end() );
-         return m;
-      };
-      bool anyShell = false;
-      forCells( [&]( uint_t, const MacroCell& cell ) { anyShell = anyShell || ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL ); } );
-      auto sweepCells = [&]() {
-         const auto    masks = repeatMasks( storage_->masksFor( flag ) );
-         const double* table = repeatedTable( stencilTablesRep_, stencilTableHost( level ), level, nf );
-         forChunks( [&]( int first, int count ) {
-            const auto u = pointers( dsts, first, count ), r = pointers( rhss, first, count );
-            hipCheck( hyteg_hip_p1_sor_cells( count, u.data(), r.data(), (int) level, table + (size_t) first * 225, relax, backwards ? 1 : 0,
-                                              masks.data() + first, storage_->stream() ),
-                      "smooth_sor_many: cells" );
-         } );
-      };
-      if ( !anyShell && storage_->numRanks() == 1 )
+      auto sweepCells = [&]() { launchSorCells( dsts, rhss, relax, level, flag, backwards ); };
+      if ( !storage_->anyShellSelected( flag ) && storage_->numRanks() == 1 )
       {
          sweepCells();
          return;
       }
-      std::vector< std::reference_wrapper< const P1Function< double > > > rests;
-      for ( uint_t k = 0; k < nf; ++k )
+      FunctionList rests;
+      for ( uint_t k = 0; k < dsts.size(); ++k )
       {
-         auto& slot = sorRestMany_[std::make_pair( level, k )];
+         auto& slot = sorRest_[std::make_pair( level, k )];
          if ( !slot )
-            slot.reset( new P1Function< double >( "sor_rest_many", storage_, level, level ) );
+            slot.reset( new P1Function< double >( "sor_rest", storage_, level, level ) );
          rests.push_back( std::cref( *slot ) );
       }
       auto sweepShell = [&]( unsigned bits ) {
-         const auto    masks = repeatMasks( storage_->masksFor( flag, false, bits & HYTEG_HIP_MASK_SHELL ) );
-         const double* rt    = repeatedTable( restTablesRep_, restTableHost( level ), level, nf );
-         forChunks( [&]( int first, int count ) {
-            const auto r = pointers( rests, first, count ), u = pointers( dsts, first, count );
-            hipCheck( hyteg_hip_p1_apply_cells( count, r.data(), u.data(), (int) level, rt + (size_t) first * 225, masks.data() + first,
-                                                HYTEG_HIP_REPLACE, storage_->stream() ),
-                      "smooth_sor_many: rest" );
-         } );
-         for ( uint_t k = 0; k < nf; ++k )
-            rests[k].get().sumSharedCopies( level, flag );
-         const hyteg_hip_sor_shell_tables* st = repeatedShellTable( level, nf );
-         forChunks( [&]( int first, int count ) {
-            const auto u = pointers( dsts, first, count ), r = pointers( rhss, first, count ), q = pointers( rests, first, count );
-            hipCheck( hyteg_hip_p1_sor_shell_cells( count, u.data(), r.data(), q.data(), (int) level, st + first, relax, masks.data() + first,
-                                                    backwards ? 1 : 0, storage_->stream() ),
-                      "smooth_sor_many: shell" );
-         } );
+         launchSorRest( rests, dsts, level, flag, bits );
+         launchSorShell( dsts, rhss, rests, relax, level, flag, bits, backwards );
       };
       if ( !backwards )
       {
@@ -574,7 +401,111 @@ class P1ConstantOperator
          sweepShell( 0xFu << 10 ); // macro-vertices
       }
    }
+   // calls fn( first, count ) for chunks of at most HYTEG_HIP_MAX_BATCH entries of the list [function][cell]
+   template < typename F >
+   void forBatchChunks( uint_t nf, F&& fn ) const
+   {
+      const int total = (int) ( nf * storage_->getNumberOfLocalCells() );
+      for ( int first = 0; first < total; first += HYTEG_HIP_MAX_BATCH )
+         fn( first, std::min( HYTEG_HIP_MAX_BATCH, total - first ) );
+   }
+   std::vector< double* > batchPointers( const FunctionList& fs, uint_t level, int first, int count ) const
+   {
+      const int              nc = (int) storage_->getNumberOfLocalCells();
+      std::vector< double* > p;
+      for ( int e = first; e < first + count; ++e )
+         p.push_back( fs[(uint_t) ( e / nc )].get().getCellPointer( (uint_t) ( e % nc ), level ) );
+      return p;
+   }
+   std::vector< unsigned > batchMasks( uint_t nf, DoFType flag, unsigned keep ) const
+   {
+      const auto              once = storage_->masksFor( flag, false, keep );
+      std::vector< unsigned > m;
+      for ( uint_t k = 0; k < nf; ++k )
+         m.insert( m.end(), once.begin(), once.end() );
+      return m;
+   }
+   // rest = stencil sum over the neighbours outside the closure of the primitives of the classes in `bits`, summed over the cells
+   void launchSorRest( const FunctionList& rests, const FunctionList& dsts, uint_t level, DoFType flag, unsigned bits ) const
+   {
+      const uint_t nf = dsts.size();
+      if ( storage_->useBatchSor( level ) )
+      {
+         const auto    masks = batchMasks( nf, flag, bits & HYTEG_HIP_MASK_SHELL );
+         const double* table = restTable( level, nf );
+         forBatchChunks( nf, [&]( int first, int count ) {
+            const auto r = batchPointers( rests, level, first, count ), u = batchPointers( dsts, level, first, count );
+            hipCheck( hyteg_hip_p1_apply_cells( count, r.data(), u.data(), (int) level, table + (size_t) first * 225, masks.data() + first,
+                                                HYTEG_HIP_REPLACE, storage_->stream() ),
+                      "smooth_sor: rest (batched)" );
+         } );
+      }
+      else
+         for ( uint_t k = 0; k < nf; ++k )
+            storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+               const auto&    T    = sorTables_.at( level ).at( cell.id );
+               const unsigned mask = storage_->maskFor( cell, flag ) & bits;
+               hipCheck( hyteg_hip_p1_apply_cell_boundary( rests[k].get().getCellPointer( c, level ), dsts[k].get().getCellPointer( c, level ),
+                                                           (int) level, &T.rest[0][0], mask, HYTEG_HIP_REPLACE, storage_->stream() ),
+                         "smooth_sor: rest" );
+            } );
+      for ( uint_t k = 0; k < nf; ++k )
+         rests[k].get().sumSharedCopies( level, flag );
+   }
+   void launchSorCells( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, DoFType flag, bool backwards ) const
+   {
+      const uint_t nf = dsts.size();
+      if ( storage_->useBatchSor( level ) )
+      {
+         const auto    masks = batchMasks( nf, flag, HYTEG_HIP_MASK_ALL );
+         const double* table = stencilTable( level, nf );
+         forBatchChunks( nf, [&]( int first, int count ) {
+            const auto u = batchPointers( dsts, level, first, count ), r = batchPointers( rhss, level, first, count );
+            hipCheck( hyteg_hip_p1_sor_cells( count, u.data(), r.data(), (int) level, table + (size_t) first * 225, relax, backwards ? 1 : 0,
+                                              masks.data() + first, storage_->stream() ),
+                      "smooth_sor: cells (batched)" );
+         } );
+         return;
+      }
+      for ( uint_t k = 0; k < nf; ++k )
+         storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+            const unsigned mask = storage_->maskFor( cell, flag );
+            if ( ( mask & HYTEG_HIP_MASK_INNER ) && level >= HYTEG_HIP_MIN_LEVEL )
+               hipCheck( hyteg_hip_p1_sor_cell( dsts[k].get().getCellPointer( c, level ), rhss[k].get().getCellPointer( c, level ), (int) level,
+                                                getCellStencils( cell.id, level ).inner, relax, backwards ? 1 : 0, storage_->stream() ),
+                         "smooth_sor: cell" );
+         } );
+   }
+   void launchSorShell( const FunctionList& dsts, const FunctionList& rhss, const FunctionList& rests, double relax, uint_t level, DoFType flag,
+                        unsigned bits, bool backwards ) const
+   {
+      const uint_t nf = dsts.size();
+      if ( storage_->useBatchSor( level ) )
+      {
+         const auto                        masks = batchMasks( nf, flag, bits & HYTEG_HIP_MASK_SHELL );
+         const hyteg_hip_sor_shell_tables* table = shellTable( level, nf );
+         forBatchChunks( nf, [&]( int first, int count ) {
+            const auto u = batchPointers( dsts, level, first, count ), r = batchPointers( rhss, level, first, count ),
+                       q = batchPointers( rests, level, first, count );
+            hipCheck( hyteg_hip_p1_sor_shell_cells( count, u.data(), r.data(), q.data(), (int) level, table + first, relax, masks.data() + first,
+                                                    backwards ? 1 : 0, storage_->stream() ),
+                      "smooth_sor: shell (batched)" );
+         } );
+         return;
+      }
+      for ( uint_t k = 0; k < nf; ++k )
+         storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+            const auto&    T    = sorTables_.at( level ).at( cell.id );
+            const unsigned mask = storage_->maskFor( cell, flag ) & bits;
+            hipCheck( hyteg_hip_p1_sor_shell_cell( dsts[k].get().getCellPointer( c, level ), rhss[k].get().getCellPointer( c, level ),
+                                                   rests[k].get().getCellPointer( c, level ), (int) level, &T.edgeVerts[0][0], &T.edgeW[0][0],
+                                                   &T.faceVerts[0][0], &T.faceW[0][0], T.vertexW, relax, mask, backwards ? 1 : 0,
+                                                   storage_->stream() ),
+                      "smooth_sor: shell" );
+         } );
+   }
 
+ public:
    void smooth_gs( const P1Function< double >& dst, const P1Function< double >& rhs, uint_t level, DoFType flag ) const
    {
       smooth_sor( dst, rhs, 1.0, level, flag, false );
@@ -648,12 +579,6 @@ class P1ConstantOperator
    }
 
  private:
-   template < typename F >
-   void forCells( F&& fn ) const
-   {
-      for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
-         fn( c, storage_->getLocalCell( c ) );
-   }
    // Operator::apply with one launch for all local cells: every selected point gets (this cell's share of) its stencil sum,
    // then the shares of the shared points are summed.  Add needs the summed shares in a temporary first.
    void applyBatched( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType ) const
@@ -670,18 +595,17 @@ class P1ConstantOperator
       };
       if ( !sharedAdd )
       {
-         run( dst, HYTEG_HIP_MASK_ALL, updateType == Add ? HYTEG_HIP_ADD : HYTEG_HIP_REPLACE );
+         run( dst, HYTEG_HIP_MASK_ALL, hipUpdate( updateType ) );
          dst.sumSharedCopies( level, flag );
          return;
       }
-      P1Function< double > tmp( "apply_tmp", storage_, level, level, true );
-      tmp.interpolate( 0.0, level, All );
+      const auto tmp = P1Function< double >::zeroedScratch( "apply_tmp", storage_, level );
       run( dst, HYTEG_HIP_MASK_INNER, HYTEG_HIP_ADD );
-      run( tmp, HYTEG_HIP_MASK_SHELL, HYTEG_HIP_REPLACE );
-      tmp.sumSharedCopies( level, flag );
+      run( *tmp, HYTEG_HIP_MASK_SHELL, HYTEG_HIP_REPLACE );
+      tmp->sumSharedCopies( level, flag );
       const auto masks = storage_->masksFor( flag, false, HYTEG_HIP_MASK_SHELL );
       storage_->forCellChunks( [&]( int first, int count ) {
-         const auto   d = dst.cellPointers( level, first, count ), t = tmp.cellPointers( level, first, count );
+         const auto   d = dst.cellPointers( level, first, count ), t = tmp->cellPointers( level, first, count );
          const double one = 1.0;
          hipCheck( hyteg_hip_p1_vector_cells( 1, count, d.data(), 1, t.data(), &one, (int) level, masks.data() + first, storage_->stream() ),
                    "apply: add shell (batched)" );
@@ -717,18 +641,34 @@ class P1ConstantOperator
    }
 
  private:
-   // the per-cell tables of the batched kernels repeated nf times (smooth_sor_many: the batch is [function][cell])
-   const double* repeatedTable( std::map< std::pair< uint_t, uint_t >, const double* >& cache, const std::vector< double >& once, uint_t level,
-                                uint_t nf ) const
+   // device tables of the batched kernels, one entry per local cell, the list repeated nf times (a batch of several functions is
+   // ordered [function][cell]); built on first use, owned by the storage
+   template < typename T, typename Build >
+   const T* deviceTable( std::map< std::pair< uint_t, uint_t >, const T* >& cache, uint_t level, uint_t nf, Build&& hostTable ) const
    {
-      auto key = std::make_pair( level, nf );
-      auto it  = cache.find( key );
+      const auto key = std::make_pair( level, nf );
+      const auto it  = cache.find( key );
       if ( it != cache.end() )
          return it->second;
-      std::vector< double > h;
+      const std::vector< T > once = hostTable();
+      std::vector< T >       h;
       for ( uint_t k = 0; k < nf; ++k )
          h.insert( h.end(), once.begin(), once.end() );
-      return cache[key] = storage_->uploadTable( h );
+      return cache[key] = static_cast< const T* >( storage_->uploadBytes( h.data(), h.size() * sizeof( T ) ) );
+   }
+   // [local cell][15 point classes][15 weights]: classes 0..13 the cell's shares, 14 inner
+   const double* stencilTable( uint_t level, uint_t nf = 1 ) const
+   {
+      return deviceTable( stencilTables_, level, nf, [&] { return stencilTableHost( level ); } );
+   }
+   // the same shape with the weights of smooth_sor's `rest` (no inner class)
+   const double* restTable( uint_t level, uint_t nf = 1 ) const
+   {
+      return deviceTable( restTables_, level, nf, [&] { return restTableHost( level ); } );
+   }
+   const hyteg_hip_sor_shell_tables* shellTable( uint_t level, uint_t nf = 1 ) const
+   {
+      return deviceTable( shellTables_, level, nf, [&] { return shellTableHost( level ); } );
    }
    std::vector< double > stencilTableHost( uint_t level ) const
    {
@@ -767,68 +707,6 @@ class P1ConstantOperator
          h.push_back( r );
       }
       return h;
-   }
-   const hyteg_hip_sor_shell_tables* repeatedShellTable( uint_t level, uint_t nf ) const
-   {
-      auto key = std::make_pair( level, nf );
-      auto it  = shellTablesRep_.find( key );
-      if ( it != shellTablesRep_.end() )
-         return it->second;
-      const auto                                once = shellTableHost( level );
-      std::vector< hyteg_hip_sor_shell_tables > h;
-      for ( uint_t k = 0; k < nf; ++k )
-         h.insert( h.end(), once.begin(), once.end() );
-      return shellTablesRep_[key] =
-                 static_cast< const hyteg_hip_sor_shell_tables* >( storage_->uploadBytes( h.data(), h.size() * sizeof( h[0] ) ) );
-   }
-   // device tables [local cell][15 point classes][15 weights] for the batched kernels: classes 0..13 the cell's shares, 14 inner
-   const double* stencilTable( uint_t level ) const
-   {
-      auto it = stencilTables_.find( level );
-      if ( it != stencilTables_.end() )
-         return it->second;
-      std::vector< double > h;
-      for ( int id : storage_->getLocalCellIDs() )
-      {
-         const auto& S = getCellStencils( id, level );
-         h.insert( h.end(), &S.slots[0][0], &S.slots[0][0] + 14 * 15 );
-         h.insert( h.end(), S.inner, S.inner + 15 );
-      }
-      return stencilTables_[level] = storage_->uploadTable( h );
-   }
-   const hyteg_hip_sor_shell_tables* shellTable( uint_t level ) const
-   {
-      auto it = shellTables_.find( level );
-      if ( it != shellTables_.end() )
-         return it->second;
-      std::vector< hyteg_hip_sor_shell_tables > h;
-      for ( int id : storage_->getLocalCellIDs() )
-      {
-         const auto&                T = sorTables_.at( level ).at( id );
-         hyteg_hip_sor_shell_tables r;
-         std::memcpy( r.edge_verts, T.edgeVerts, sizeof( r.edge_verts ) );
-         std::memcpy( r.face_verts, T.faceVerts, sizeof( r.face_verts ) );
-         std::memcpy( r.edge_w, T.edgeW, sizeof( r.edge_w ) );
-         std::memcpy( r.face_w, T.faceW, sizeof( r.face_w ) );
-         std::memcpy( r.vertex_w, T.vertexW, sizeof( r.vertex_w ) );
-         h.push_back( r );
-      }
-      return shellTables_[level] =
-                 static_cast< const hyteg_hip_sor_shell_tables* >( storage_->uploadBytes( h.data(), h.size() * sizeof( h[0] ) ) );
-   }
-   const double* restTable( uint_t level ) const
-   {
-      auto it = restTables_.find( level );
-      if ( it != restTables_.end() )
-         return it->second;
-      std::vector< double > h;
-      for ( int id : storage_->getLocalCellIDs() )
-      {
-         const auto& T = sorTables_.at( level ).at( id );
-         h.insert( h.end(), &T.rest[0][0], &T.rest[0][0] + 14 * 15 );
-         h.insert( h.end(), 15, 0.0 );
-      }
-      return restTables_[level] = storage_->uploadTable( h );
    }
    // total weights and sweep orientations of every macro-primitive, handed to each adjacent cell in its local numbering
    std::vector< stencil::CellSorTables > buildSorTables( const std::vector< stencil::CellStencils >& S ) const
@@ -892,15 +770,11 @@ class P1ConstantOperator
       }
       return T;
    }
-   // an apply without any shell point selected on any local cell (residual()'s test): its launches are the cells' interior
-   // kernels and nothing else
+   // one rank, per-cell kernels and no shell point selected on any local cell: an apply (or residual) on these arguments consists
+   // of the cells' interior launches and nothing else
    bool pureInterior( uint_t level, DoFType flag ) const
    {
-      if ( storage_->numRanks() > 1 || storage_->useBatch( level ) || level < HYTEG_HIP_MIN_LEVEL )
-         return false;
-      bool anyShell = false;
-      forCells( [&]( uint_t, const MacroCell& cell ) { anyShell = anyShell || ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL ); } );
-      return !anyShell;
+      return storage_->numRanks() == 1 && !storage_->useBatch( level ) && level >= HYTEG_HIP_MIN_LEVEL && !storage_->anyShellSelected( flag );
    }
    bool hasSharedPoints( uint_t level, DoFType flag ) const
    {
@@ -915,12 +789,9 @@ class P1ConstantOperator
    uint64_t                                                   uid_ = nextUid();
    std::map< uint_t, std::vector< stencil::CellStencils > >   stencils_;
    std::map< uint_t, std::vector< stencil::CellSorTables > >  sorTables_;
-   mutable std::map< uint_t, std::unique_ptr< P1Function< double > > > sorRest_;
-   mutable std::map< std::pair< uint_t, uint_t >, std::unique_ptr< P1Function< double > > > sorRestMany_; // (level, k)
-   mutable std::map< std::pair< uint_t, uint_t >, const double* >                         stencilTablesRep_, restTablesRep_;
-   mutable std::map< std::pair< uint_t, uint_t >, const hyteg_hip_sor_shell_tables* >     shellTablesRep_;
-   mutable std::map< uint_t, const double* >                  stencilTables_, restTables_;
-   mutable std::map< uint_t, const hyteg_hip_sor_shell_tables* > shellTables_;
+   mutable std::map< std::pair< uint_t, uint_t >, std::unique_ptr< P1Function< double > > > sorRest_; // (level, k): scratch of function k
+   mutable std::map< std::pair< uint_t, uint_t >, const double* >                         stencilTables_, restTables_; // (level, nf)
+   mutable std::map< std::pair< uint_t, uint_t >, const hyteg_hip_sor_shell_tables* >     shellTables_;
    std::shared_ptr< P1Function< double > >                    inverseDiagonalValues_;
 };
 

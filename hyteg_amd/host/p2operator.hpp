@@ -278,9 +278,6 @@ class P2ElementwiseOperator
       const P1Function< double >& sv = *sorTmpV_;
       const P1Function< double >& uv = dst.getVertexDoFFunction();
       const bool                  shared = storage_->getCells().size() > 1;
-      bool                        anyShell = false;
-      for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
-         anyShell = anyShell || ( storage_->maskFor( storage_->getLocalCell( c ), flag ) & HYTEG_HIP_MASK_SHELL );
       auto update = [&]( unsigned k, unsigned keep ) {
          t.assignKinds( { 1.0, -1.0 }, { rhs, t }, level, flag, k, keep );
          t.multElementwiseKinds( { *getInverseDiagonalValues(), t }, level, flag, k, keep );
@@ -290,7 +287,7 @@ class P2ElementwiseOperator
          applyKinds( dst, t, level, flag, 1u << type, HYTEG_HIP_MASK_INNER );
          update( 1u << type, HYTEG_HIP_MASK_INNER );
       };
-      if ( level >= 2 && ( anyShell || storage_->numRanks() > 1 ) )
+      if ( level >= 2 && ( storage_->anyShellSelected( flag ) || storage_->numRanks() > 1 ) )
       {
          smoothSorReferenceOrder( dst, rhs, relax, level, flag, backwards, cellEdgeSweep );
          return;

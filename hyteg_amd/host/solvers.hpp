@@ -115,10 +115,7 @@ class MixedPrecisionJacobiSmoother : public Solver< OperatorType >
    }
    void solveSteps( const OperatorType& A, const P1Function< double >& x, const P1Function< double >& b, uint_t level, uint_t steps ) override
    {
-      bool anyShell = storage_->numRanks() > 1;
-      for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
-         anyShell = anyShell || ( storage_->maskFor( storage_->getLocalCell( c ), x.effectiveFlag( flag_ ) ) & HYTEG_HIP_MASK_SHELL );
-      if ( anyShell || !floatLevel( level ) || steps < 2 )
+      if ( storage_->numRanks() > 1 || storage_->anyShellSelected( x.effectiveFlag( flag_ ) ) || !floatLevel( level ) || steps < 2 )
       {
          for ( uint_t i = 0; i < steps; ++i )
             solve( A, x, b, level );

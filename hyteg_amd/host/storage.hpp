@@ -165,6 +165,13 @@ class PrimitiveStorage
    const std::vector< int >&            getLocalCellIDs() const { return localCells_; }
    uint_t                               getNumberOfLocalCells() const { return localCells_.size(); }
    const MacroCell&                     getLocalCell( uint_t i ) const { return cells_[localCells_.at( i )]; }
+   // calls fn( local index, cell ) for every local cell
+   template < typename F >
+   void forLocalCells( F&& fn ) const
+   {
+      for ( uint_t c = 0; c < localCells_.size(); ++c )
+         fn( c, cells_[localCells_[c]] );
+   }
 
    // boundary type of every primitive on the domain boundary (BoundaryCondition::create0123BC maps flag 1 -> Dirichlet)
    void    setBoundaryType( DoFType t ) { boundaryType_ = t; }
@@ -188,6 +195,15 @@ class PrimitiveStorage
          if ( testFlag( boundaryTypeOf( primitiveOfSlot( c, s ).onBoundary ), flag ) )
             m |= 1u << s;
       return m;
+   }
+   // does `flag` select a macro-face, -edge or -vertex point of any local cell?  If not (every cell's shell is fixed), nothing
+   // the flag selects is shared between cells
+   bool anyShellSelected( DoFType flag ) const
+   {
+      for ( int id : localCells_ )
+         if ( maskFor( cells_[id], flag ) & HYTEG_HIP_MASK_SHELL )
+            return true;
+      return false;
    }
    // like maskFor but a shared primitive is counted by its lowest-numbered neighbour cell only (dot products)
    unsigned ownedMaskFor( const MacroCell& c, DoFType flag ) const

@@ -45,6 +45,7 @@ enum DoFType : std::size_t
    NeumannBoundary   = 4,
    FreeslipBoundary  = 8
 };
+inline int     hipUpdate( UpdateType u ) { return u == Replace ? HYTEG_HIP_REPLACE : HYTEG_HIP_ADD; } // the C-ABI's `update` argument
 inline DoFType operator|( DoFType a, DoFType b ) { return DoFType( std::size_t( a ) | std::size_t( b ) ); }
 inline DoFType operator&( DoFType a, DoFType b ) { return DoFType( std::size_t( a ) & std::size_t( b ) ); }
 inline DoFType operator^( DoFType a, DoFType b ) { return DoFType( std::size_t( a ) ^ std::size_t( b ) ); }

@@ -150,6 +150,10 @@ HYTEG_HOST_API int hyteg_host_operator_apply_cycle_timed( hh_operator_t op, int 
                                                           int level, int flag, int update, int first, int steps, void* ev_start, void* ev_stop );
 HYTEG_HOST_API int hyteg_host_operator_smooth_jac( hh_operator_t op, hh_function_t dst, hh_function_t rhs, hh_function_t src, double relax, int level, int flag );
 HYTEG_HOST_API int hyteg_host_operator_smooth_sor( hh_operator_t op, hh_function_t dst, hh_function_t rhs, double relax, int level, int flag, int backwards );
+/* one sweep of `n` functions by shared launches where the batched kernels apply (P1ConstantOperator::smooth_sor_many): the
+ * same bits as n calls of hyteg_host_operator_smooth_sor */
+HYTEG_HOST_API int hyteg_host_operator_smooth_sor_many( hh_operator_t op, int n, const hh_function_t* dsts, const hh_function_t* rhss, double relax,
+                                                        int level, int flag, int backwards );
 HYTEG_HOST_API int hyteg_host_operator_compute_inverse_diagonal( hh_operator_t op );
 HYTEG_HOST_API int hyteg_host_operator_inverse_diagonal( hh_operator_t op, hh_function_t* out /* borrowed */ );
 

@@ -124,6 +124,43 @@ def test_host_smooth_sor_matches_the_global_schedule(env, mesh, level, backwards
         o.close()
 
 
+@pytest.mark.parametrize("mesh,level", [("regular_octahedron_8el", 3), ("cube_6el", 3)])
+@pytest.mark.parametrize("backwards", [False, True])
+@pytest.mark.parametrize("batch", [6, -1])
+def test_host_smooth_sor_many_is_bit_identical_to_one_smooth_sor_per_function(env, mesh, level, backwards, batch):
+    """three functions swept by shared launches (batch 6: the [function][cell] batch; -1: smooth_sor_many's per-function
+    fallback) carry the bits of three separate smooth_sor calls on copies of the same data"""
+    torch, capi, host, po = env
+    import hostutil as hu
+
+    v, c = hu.read_msh(hu.MESHES / f"{mesh}.msh")
+    glob = hu.GlobalSweepOracle(v, c, level)
+    rng = np.random.default_rng(7 + level)
+    us = [glob.to_cells(rng.standard_normal(glob.ndof)) for _ in range(3)]
+    bs = [glob.to_cells(rng.standard_normal(glob.ndof)) for _ in range(3)]
+    st = host.Storage.from_gmsh(hu.MESHES / f"{mesh}.msh")
+    st.set_batch_max_level(batch)
+    A = host.P1ConstantOperator(st, level, level)
+    xs = [host.P1Function(st, f"x{k}", level, level) for k in range(3)]
+    rs = [host.P1Function(st, f"b{k}", level, level) for k in range(3)]
+    ys = [host.P1Function(st, f"y{k}", level, level) for k in range(3)]
+    for relax in (1.0, 1.2):
+        for k in range(3):
+            hu.upload(xs[k], us[k], level)
+            hu.upload(ys[k], us[k], level)
+            hu.upload(rs[k], bs[k], level)
+        A.smooth_sor_many(xs, rs, relax, level, host.Inner, backwards)
+        for k in range(3):
+            A.smooth_sor(ys[k], rs[k], relax, level, host.Inner, backwards)
+        for k in range(3):
+            many, single = hu.download(xs[k], level), hu.download(ys[k], level)
+            assert any(not np.array_equal(a, u0) for a, u0 in zip(single, us[k]))  # the sweep changed something
+            for a, w in zip(many, single):
+                assert np.array_equal(a, w), (k, relax)
+    for o in (*xs, *rs, *ys, A, st):
+        o.close()
+
+
 def test_host_smooth_sor_level_6_matches_the_cell_centric_oracle(env):
     """bigger level (edges longer than one wave, many face rows) against the oracle's C kernels composed the same way"""
     torch, capi, host, po = env
