@@ -140,8 +140,7 @@ HYTEG_HIP_API int hyteg_hip_event_create_timing( hyteg_hip_event_t* event )
    // hipEventDisableSystemFence: "for events that are only used to measure timing ... avoids the cost of cache writeback and
    // invalidation, and the performance impact of those actions on the execution of following work" (hip_runtime_api.h); results
    // are read after a stream / device synchronisation, never through these events.  HYTEG_HIP_TIMING_EVENT_FENCE=1 keeps the fence.
-   const char*    env   = std::getenv( "HYTEG_HIP_TIMING_EVENT_FENCE" );
-   const unsigned flags = ( env && env[0] == '1' ) ? hipEventDefault : hipEventDisableSystemFence;
+   const unsigned flags = env_flag( "HYTEG_HIP_TIMING_EVENT_FENCE", false ) ? hipEventDefault : hipEventDisableSystemFence;
    hipEvent_t     e;
    HH_CHECK_HIP( hipEventCreateWithFlags( &e, flags ) );
    *event = reinterpret_cast< hyteg_hip_event_t >( e );

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/hyteg_hip.h"
@@ -30,6 +31,18 @@ int  fail( int code, const std::string& msg );
       if ( !( cond ) )                                                  \
          return ::hyteg_hip::fail( HYTEG_HIP_EINVAL, std::string( msg ) ); \
    } while ( 0 )
+
+// environment switches: each site keeps the result in a `static const`, so a variable is read once, at first use
+inline bool env_flag( const char* name, bool default_on ) // on unless "0...", or off unless "1..."
+{
+   const char* e = std::getenv( name );
+   return default_on ? !( e && e[0] == '0' ) : ( e && e[0] == '1' );
+}
+inline int env_int( const char* name, int fallback )
+{
+   const char* e = std::getenv( name );
+   return e ? std::atoi( e ) : fallback;
+}
 
 inline bool level_ok( int level ) { return level >= HYTEG_HIP_MIN_LEVEL && level <= HYTEG_HIP_MAX_LEVEL; }
 

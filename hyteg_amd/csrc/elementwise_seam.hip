@@ -10,11 +10,9 @@
 // stencil per point class; the host part of the call sums them from the coordinates (element_matrices.hpp), the device part is
 // the z-march kernel in Add mode for the inner points plus the boundary-share kernel for the shell.  No new device code.
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <vector>
 
-#include "common.hpp"
+#include "device_table.hpp"
 #include "element_matrices.hpp"
 #include "shell.hpp"
 
@@ -243,33 +241,22 @@ HYTEG_HIP_API int hyteg_hip_p2_elementwise_diffusion_apply_macro_3d( double*    
    HH_REQUIRE( level_of( micro_edges_per_macro_edge, &level ) == HYTEG_HIP_OK && level <= HYTEG_HIP_P2_MAX_LEVEL,
                "p2_elementwise_diffusion_apply_macro_3d: micro_edges_per_macro_edge must be a power of two, at most 2^9" );
    // operator table of this (cell, level), built and uploaded on first use
-   static std::mutex                                            mtx;
-   static std::map< std::pair< int, std::vector< double > >, double* > cache;
-   int dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
    std::vector< double > key( macro_vertex_coords, macro_vertex_coords + 12 );
    key.push_back( (double) micro_edges_per_macro_edge );
    const double* table_dev = nullptr;
-   {
-      std::lock_guard< std::mutex > lock( mtx );
-      auto it = cache.find( { dev, key } );
-      if ( it == cache.end() )
-      {
-         double elm[600];
-         int    rc = hyteg_hip_p2_elementwise_diffusion_element_matrices( macro_vertex_coords, micro_edges_per_macro_edge, elm );
-         if ( rc != HYTEG_HIP_OK )
-            return rc;
-         std::vector< double > table( hyteg_hip_p2_operator_table_size() );
-         rc = hyteg_hip_p2_build_operator_table( elm, table.data() );
-         if ( rc != HYTEG_HIP_OK )
-            return rc;
-         void* p = nullptr;
-         HH_CHECK_HIP( hipMalloc( &p, table.size() * sizeof( double ) ) );
-         HH_CHECK_HIP( hipMemcpy( p, table.data(), table.size() * sizeof( double ), hipMemcpyHostToDevice ) );
-         it = cache.emplace( std::make_pair( dev, key ), static_cast< double* >( p ) ).first;
-      }
-      table_dev = it->second;
-   }
+   const int     rc        = cached_operator_table(
+       key,
+       [&]( std::vector< double >& table ) {
+          double elm[600];
+          int    rb = hyteg_hip_p2_elementwise_diffusion_element_matrices( macro_vertex_coords, micro_edges_per_macro_edge, elm );
+          if ( rb != HYTEG_HIP_OK )
+             return rb;
+          table.resize( hyteg_hip_p2_operator_table_size() );
+          return hyteg_hip_p2_build_operator_table( elm, table.data() );
+       },
+       &table_dev );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
    return hyteg_hip_p2_elementwise_apply_cell( dst_vertex, dst_edge, src_vertex, src_edge, level, table_dev, 1.0, HYTEG_HIP_ADD, HYTEG_HIP_MASK_ALL, stream );
 }
 }

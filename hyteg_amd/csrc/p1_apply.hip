@@ -73,10 +73,8 @@ int launch_zmarch_shape( void* dst, const T* src, const T* rhs, const T* invdiag
    int nblocks = ( bt.count + kZMarchWavesPerBlock - 1 ) / kZMarchWavesPerBlock;
    nblocks     = ( nblocks + 7 ) & ~7;
    A.xcd_chunk = nblocks / 8;
-   static const bool xcdSlabs = [] {
-      const char* e = getenv( "HYTEG_HIP_APPLY_XCD_SLABS" ); // measurement switch: 0 = workgroups in launch order (XCDs interleaved brick by brick)
-      return !( e && e[0] == '0' );
-   }();
+   // measurement switch: 0 = workgroups in launch order (XCDs interleaved brick by brick)
+   static const bool xcdSlabs = env_flag( "HYTEG_HIP_APPLY_XCD_SLABS", true );
    if ( !xcdSlabs )
       A.xcd_chunk = 0;
    // dst of Add is read exactly once per element and written right after: nontemporal load (18.6 -> 17.2 us).  rhs /
@@ -145,10 +143,7 @@ int launch_apply( double* dst, const double* src, const double* rhs, const doubl
 {
    // z-march register kernel whenever byte offsets fit the 32-bit buffer addressing (level <= 10);
    // the LDS-tiled kernel (pointer addressing) covers level 11
-   static const bool forceTiled = [] {
-      const char* e = getenv( "HYTEG_HIP_APPLY_LDS_TILED" ); // measurement switch: the LDS-tiled kernel of round 1 at every level
-      return e && e[0] == '1';
-   }();
+   static const bool forceTiled = env_flag( "HYTEG_HIP_APPLY_LDS_TILED", false ); // measurement switch: the LDS-tiled kernel of round 1 at every level
    if ( !forceTiled && tet64( ( 1 << level ) + 1 ) * 8 < ( (int64_t) 1 << 31 ) )
       return launch_zmarch< MODE >( dst, src, rhs, invdiag, level, w, relax, stream );
 

@@ -12,8 +12,6 @@
 // (relative differences of a few ulp; tests/test_gpu_parity.py compares at 1e-12, level 8 included).
 // The backward sweep is the same planes in decreasing t.
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <tuple>
 #include <vector>
 
@@ -21,7 +19,7 @@
 
 #include <cstdlib>
 
-#include "common.hpp"
+#include "device_table.hpp"
 #include "sor_dataflow.hpp"
 
 using namespace hyteg_hip;
@@ -305,37 +303,22 @@ static std::vector< std::vector< SorBlock > > sor_blocks_by_wavefront( int level
 
 int get_sor_blocks( int level, const SorBlockTable** out )
 {
-   static std::mutex                                   mtx;
-   static std::map< std::pair< int, int >, SorBlockTable > cache;
-   int                                                 dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   auto                          key = std::make_pair( dev, level );
-   auto                          it  = cache.find( key );
-   if ( it == cache.end() )
-   {
-      const std::vector< std::vector< SorBlock > > byT = sor_blocks_by_wavefront( level );
-      SorBlockTable           tab;
-      std::vector< SorBlock > flat;
-      tab.wavefrontStart.push_back( 0 );
-      for ( auto& v : byT )
-      {
-         if ( v.empty() )
-            continue;
-         flat.insert( flat.end(), v.begin(), v.end() );
-         tab.wavefrontStart.push_back( (int) flat.size() );
-      }
-      if ( !flat.empty() )
-      {
-         void* p = nullptr;
-         HH_CHECK_HIP( hipMalloc( &p, flat.size() * sizeof( SorBlock ) ) );
-         HH_CHECK_HIP( hipMemcpy( p, flat.data(), flat.size() * sizeof( SorBlock ), hipMemcpyHostToDevice ) );
-         tab.dev = static_cast< const SorBlock* >( p );
-      }
-      it = cache.emplace( key, std::move( tab ) ).first;
-   }
-   *out = &it->second;
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< int, SorBlockTable > cache;
+   return cache.get( level,
+                     [&]( SorBlockTable& tab ) {
+                        const std::vector< std::vector< SorBlock > > byT = sor_blocks_by_wavefront( level );
+                        std::vector< SorBlock >                      flat;
+                        tab.wavefrontStart.push_back( 0 );
+                        for ( auto& v : byT )
+                        {
+                           if ( v.empty() )
+                              continue;
+                           flat.insert( flat.end(), v.begin(), v.end() );
+                           tab.wavefrontStart.push_back( (int) flat.size() );
+                        }
+                        return upload_table( flat, &tab.dev );
+                     },
+                     out );
 }
 
 
@@ -353,44 +336,29 @@ struct SorPipelineTable
 };
 int get_sor_pipeline( int level, int nsweeps, bool backwards, const SorPipelineTable** out )
 {
-   static std::mutex                                                    mtx;
-   static std::map< std::tuple< int, int, int, bool >, SorPipelineTable > cache;
-   int                                                                  dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   auto                          key = std::make_tuple( dev, level, nsweeps, backwards );
-   auto                          it  = cache.find( key );
-   if ( it == cache.end() )
-   {
-      const std::vector< std::vector< SorBlock > > byT = sor_blocks_by_wavefront( level );
-      const int                                    nT  = (int) byT.size();
-      SorPipelineTable                             tab;
-      std::vector< SorBlock >                      flat;
-      tab.stepStart.push_back( 0 );
-      for ( int tau = 0; tau < nT + kSorSweepLag * ( nsweeps - 1 ); ++tau )
-      {
-         for ( int sw = 0; sw < nsweeps; ++sw )
-         {
-            const int k = tau - kSorSweepLag * sw; // position of sweep sw in its own order
-            if ( k < 0 || k >= nT )
-               continue;
-            const auto& v = byT[(size_t) ( backwards ? nT - 1 - k : k )];
-            flat.insert( flat.end(), v.begin(), v.end() );
-         }
-         if ( (int) flat.size() > tab.stepStart.back() )
-            tab.stepStart.push_back( (int) flat.size() );
-      }
-      if ( !flat.empty() )
-      {
-         void* p = nullptr;
-         HH_CHECK_HIP( hipMalloc( &p, flat.size() * sizeof( SorBlock ) ) );
-         HH_CHECK_HIP( hipMemcpy( p, flat.data(), flat.size() * sizeof( SorBlock ), hipMemcpyHostToDevice ) );
-         tab.dev = static_cast< const SorBlock* >( p );
-      }
-      it = cache.emplace( key, std::move( tab ) ).first;
-   }
-   *out = &it->second;
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< std::tuple< int, int, bool >, SorPipelineTable > cache;
+   return cache.get( std::make_tuple( level, nsweeps, backwards ),
+                     [&]( SorPipelineTable& tab ) {
+                        const std::vector< std::vector< SorBlock > > byT = sor_blocks_by_wavefront( level );
+                        const int                                    nT  = (int) byT.size();
+                        std::vector< SorBlock >                      flat;
+                        tab.stepStart.push_back( 0 );
+                        for ( int tau = 0; tau < nT + kSorSweepLag * ( nsweeps - 1 ); ++tau )
+                        {
+                           for ( int sw = 0; sw < nsweeps; ++sw )
+                           {
+                              const int k = tau - kSorSweepLag * sw; // position of sweep sw in its own order
+                              if ( k < 0 || k >= nT )
+                                 continue;
+                              const auto& v = byT[(size_t) ( backwards ? nT - 1 - k : k )];
+                              flat.insert( flat.end(), v.begin(), v.end() );
+                           }
+                           if ( (int) flat.size() > tab.stepStart.back() )
+                              tab.stepStart.push_back( (int) flat.size() );
+                        }
+                        return upload_table( flat, &tab.dev );
+                     },
+                     out );
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -414,42 +382,29 @@ struct SorPlaneTable
 };
 int get_sor_planes( int level, const SorPlaneTable** out )
 {
-   static std::mutex                                     mtx;
-   static std::map< std::pair< int, int >, SorPlaneTable > cache;
-   int                                                   dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   auto                          it = cache.find( { dev, level } );
-   if ( it == cache.end() )
-   {
-      const int N = ( 1 << level ) + 1, n = N - 1;
-      const int tmin = 6, tmax = 1 + 2 + 3 * ( n - 3 );
-      SorPlaneTable tab;
-      tab.nplanes = tmax >= tmin ? tmax - tmin + 1 : 0;
-      std::vector< std::vector< SorPlanePoint > > byT( (size_t) std::max( tab.nplanes, 0 ) );
-      for ( int z = 1; z <= n - 3; ++z )
-         for ( int y = 1; y <= n - 2 - z; ++y )
-            for ( int x = 1; x <= n - 1 - y - z; ++x )
-               byT[(size_t) ( x + 2 * y + 3 * z - tmin )].push_back(
-                   SorPlanePoint{ (int) ( slice_start( N, z ) + row_start( N - z, y ) + x ), (short) ( N - z ), (short) y } );
-      std::vector< SorPlanePoint > flat;
-      std::vector< int >           off( 1, 0 );
-      for ( const auto& v : byT )
-      {
-         flat.insert( flat.end(), v.begin(), v.end() );
-         off.push_back( (int) flat.size() );
-      }
-      void *pp = nullptr, *po = nullptr;
-      HH_CHECK_HIP( hipMalloc( &pp, std::max< size_t >( 1, flat.size() ) * sizeof( SorPlanePoint ) ) );
-      HH_CHECK_HIP( hipMalloc( &po, off.size() * sizeof( int ) ) );
-      if ( !flat.empty() )
-         HH_CHECK_HIP( hipMemcpy( pp, flat.data(), flat.size() * sizeof( SorPlanePoint ), hipMemcpyHostToDevice ) );
-      HH_CHECK_HIP( hipMemcpy( po, off.data(), off.size() * sizeof( int ), hipMemcpyHostToDevice ) );
-      tab.pts = static_cast< const SorPlanePoint* >( pp ), tab.off = static_cast< const int* >( po );
-      it = cache.emplace( std::make_pair( dev, level ), tab ).first;
-   }
-   *out = &it->second;
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< int, SorPlaneTable > cache;
+   return cache.get( level,
+                     [&]( SorPlaneTable& tab ) {
+                        const int N = ( 1 << level ) + 1, n = N - 1;
+                        const int tmin = 6, tmax = 1 + 2 + 3 * ( n - 3 );
+                        tab.nplanes = tmax >= tmin ? tmax - tmin + 1 : 0;
+                        std::vector< std::vector< SorPlanePoint > > byT( (size_t) std::max( tab.nplanes, 0 ) );
+                        for ( int z = 1; z <= n - 3; ++z )
+                           for ( int y = 1; y <= n - 2 - z; ++y )
+                              for ( int x = 1; x <= n - 1 - y - z; ++x )
+                                 byT[(size_t) ( x + 2 * y + 3 * z - tmin )].push_back(
+                                     SorPlanePoint{ (int) ( slice_start( N, z ) + row_start( N - z, y ) + x ), (short) ( N - z ), (short) y } );
+                        std::vector< SorPlanePoint > flat;
+                        std::vector< int >           off( 1, 0 );
+                        for ( const auto& v : byT )
+                        {
+                           flat.insert( flat.end(), v.begin(), v.end() );
+                           off.push_back( (int) flat.size() );
+                        }
+                        const int rc = upload_table( flat, &tab.pts );
+                        return rc != HYTEG_HIP_OK ? rc : upload_table( off, &tab.off );
+                     },
+                     out );
 }
 struct SorSmallArgs
 {
@@ -647,10 +602,7 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_cell_sweeps( double*            u,
    HH_REQUIRE( u != rhs, "p1_sor_cell_sweeps: u and rhs must not alias" );
    HH_REQUIRE( w[7] != 0.0, "p1_sor_cell_sweeps: zero centre weight" );
    HH_REQUIRE( nsweeps >= 0 && nsweeps <= 64, "p1_sor_cell_sweeps: nsweeps must be 0..64" );
-   static const bool pipeline = [] {
-      const char* e = std::getenv( "HYTEG_HIP_SOR_PIPELINE" ); // 0: one sweep after the other
-      return !( e && e[0] == '0' );
-   }();
+   static const bool pipeline = env_flag( "HYTEG_HIP_SOR_PIPELINE", true ); // 0: one sweep after the other
    const int algo = g_sorAlgorithm.load( std::memory_order_relaxed );
    if ( nsweeps <= 1 || !pipeline || level < 5 || use_dataflow( level ) || algo == HYTEG_HIP_SOR_PLANES )
    {
@@ -710,11 +662,9 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_cell( double*            u,
    A.invc            = 1.0 / w[7];
    for ( int k = 0; k < 15; ++k )
       A.st.w[k] = w[k];
-   static const int smallMax = [] {
-      const char* e = std::getenv( "HYTEG_HIP_SOR_SMALL_MAX_LEVEL" ); // measurement switch
-      return e ? std::atoi( e ) : 4; // level 5: 53 us here against 65 us blocked, but the pipelined sweeps (blocked) would no longer be
-                                     // bit-identical to consecutive single sweeps there: the two forms sum a row in different orders
-   }();
+   // measurement switch.  Level 5: 53 us here against 65 us blocked, but the pipelined sweeps (blocked) would no longer be
+   // bit-identical to consecutive single sweeps there: the two forms sum a row in different orders
+   static const int smallMax = env_int( "HYTEG_HIP_SOR_SMALL_MAX_LEVEL", 4 );
    if ( level <= smallMax && level <= 5 && g_sorAlgorithm.load( std::memory_order_relaxed ) == HYTEG_HIP_SOR_AUTO )
    {
       // the whole cell array fits into LDS: ONE workgroup runs all hyperplanes of the sweep in one launch (the kernel of the

@@ -41,7 +41,7 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
+#include "device_table.hpp"
 #include "sor_dataflow.hpp"
 
 #ifndef HYTEG_DF_LIGHT_FENCE
@@ -413,32 +413,30 @@ struct DfControl
    int*   hostAbortDev = nullptr;
 };
 
-std::mutex                                        g_mtx;
-std::map< std::pair< int, int >, DfColumnTable >   g_cols;    // (device, nb)
+std::mutex                                        g_mtx;     // guards g_control and the launch that uses a control block
 std::map< std::pair< int, hipStream_t >, DfControl > g_control; // (device, stream)
 
 int get_columns( int dev, int nb, DfColumnTable* out )
 {
-   auto it = g_cols.find( { dev, nb } );
-   if ( it == g_cols.end() )
-   {
-      std::vector< DfColumn > cols;
-      for ( int t = 0; t <= 2 * ( nb - 1 ); ++t )
-         for ( int R = 0; R < nb; ++R )
-         {
-            const int Q = t - R;
-            if ( Q >= R && Q < nb )
-               cols.push_back( DfColumn{ (short) Q, (short) R } );
-         }
-      void* p = nullptr;
-      HH_CHECK_HIP( hipMalloc( &p, cols.size() * sizeof( DfColumn ) ) );
-      HH_CHECK_HIP( hipMemcpy( p, cols.data(), cols.size() * sizeof( DfColumn ), hipMemcpyHostToDevice ) );
-      DfColumnTable tab;
-      tab.dev = static_cast< const DfColumn* >( p ), tab.count = (int) cols.size();
-      it = g_cols.emplace( std::make_pair( dev, nb ), tab ).first;
-   }
-   *out = it->second;
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< int, DfColumnTable > cache; // (device, nb)
+   const DfColumnTable*                          tab = nullptr;
+   const int rc = cache.get_on( dev, nb,
+                                [&]( DfColumnTable& t ) {
+                                   std::vector< DfColumn > cols;
+                                   for ( int s = 0; s <= 2 * ( nb - 1 ); ++s )
+                                      for ( int R = 0; R < nb; ++R )
+                                      {
+                                         const int Q = s - R;
+                                         if ( Q >= R && Q < nb )
+                                            cols.push_back( DfColumn{ (short) Q, (short) R } );
+                                      }
+                                   t.count = (int) cols.size();
+                                   return upload_table( cols, &t.dev );
+                                },
+                                &tab );
+   if ( rc == HYTEG_HIP_OK )
+      *out = *tab;
+   return rc;
 }
 
 int get_control( int dev, hipStream_t stream, size_t ints, DfControl** out )

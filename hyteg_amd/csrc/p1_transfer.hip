@@ -1,11 +1,9 @@
 // C-ABI entry points: P1 linear restriction / prolongation on one macro-cell (gather forms).
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <utility>
 #include <vector>
 
-#include "common.hpp"
+#include "device_table.hpp"
 
 using namespace hyteg_hip;
 
@@ -536,46 +534,35 @@ struct ProlTable
 };
 int get_prolongation_bricks( int fine_level, ProlTable* out )
 {
-   static std::mutex                                     mtx;
-   static std::map< std::pair< int, int >, ProlTable > cache;
-   int                                                   dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   auto                          key = std::make_pair( dev, fine_level );
-   auto                          it  = cache.find( key );
-   if ( it == cache.end() )
-   {
-      const int               Nf = ( 1 << fine_level ) + 1, Nc = ( Nf + 1 ) / 2;
-      std::vector< ProlTask > host;
-      for ( int z0 = 1; z0 <= Nf - 4; z0 += kPB_LZ )
-         for ( int y0 = 1; y0 <= Nf - 3 - z0; y0 += kPB_NY )
-            for ( int xb = 0; xb <= Nf - 1 - y0 - z0; xb += 64 )
-            {
-               ProlTask t{};
-               t.y0    = y0;
-               t.xb_z0 = ( xb << 16 ) | z0;
-               for ( int s = 0; s < kPB_LZ; ++s )
-                  t.fbase[s] = z0 + s <= Nf - 1 - y0 ? cell_index( Nf, xb, y0, z0 + s ) : 0;
-               for ( int q = 0; q < 6; ++q )
-               {
-                  const int Z = ( z0 >> 1 ) + q, Y = y0 >> 1;
-                  t.cbase[q]  = ( Z <= Nc - 1 && Y <= Nc - 1 - Z ) ? cell_index( Nc, 0, Y, Z ) + xb / 2 : 0;
-               }
-               host.push_back( t );
-            }
-      ProlTable tab;
-      tab.count = (int) host.size();
-      if ( !host.empty() )
-      {
-         void* p = nullptr;
-         HH_CHECK_HIP( hipMalloc( &p, host.size() * sizeof( ProlTask ) ) );
-         HH_CHECK_HIP( hipMemcpy( p, host.data(), host.size() * sizeof( ProlTask ), hipMemcpyHostToDevice ) );
-         tab.dev = static_cast< const ProlTask* >( p );
-      }
-      it = cache.emplace( key, tab ).first;
-   }
-   *out = it->second;
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< int, ProlTable > cache;
+   const ProlTable*                          tab = nullptr;
+   const int rc = cache.get( fine_level,
+                             [&]( ProlTable& t ) {
+                                const int               Nf = ( 1 << fine_level ) + 1, Nc = ( Nf + 1 ) / 2;
+                                std::vector< ProlTask > host;
+                                for ( int z0 = 1; z0 <= Nf - 4; z0 += kPB_LZ )
+                                   for ( int y0 = 1; y0 <= Nf - 3 - z0; y0 += kPB_NY )
+                                      for ( int xb = 0; xb <= Nf - 1 - y0 - z0; xb += 64 )
+                                      {
+                                         ProlTask k{};
+                                         k.y0    = y0;
+                                         k.xb_z0 = ( xb << 16 ) | z0;
+                                         for ( int s = 0; s < kPB_LZ; ++s )
+                                            k.fbase[s] = z0 + s <= Nf - 1 - y0 ? cell_index( Nf, xb, y0, z0 + s ) : 0;
+                                         for ( int q = 0; q < 6; ++q )
+                                         {
+                                            const int Z = ( z0 >> 1 ) + q, Y = y0 >> 1;
+                                            k.cbase[q]  = ( Z <= Nc - 1 && Y <= Nc - 1 - Z ) ? cell_index( Nc, 0, Y, Z ) + xb / 2 : 0;
+                                         }
+                                         host.push_back( k );
+                                      }
+                                t.count = (int) host.size();
+                                return upload_table( host, &t.dev );
+                             },
+                             &tab );
+   if ( rc == HYTEG_HIP_OK )
+      *out = *tab;
+   return rc;
 }
 
 struct FaceRowTable
@@ -585,40 +572,29 @@ struct FaceRowTable
 };
 int get_face_rows( int level, FaceRowTable* out )
 {
-   static std::mutex                                        mtx;
-   static std::map< std::pair< int, int >, FaceRowTable > cache;
-   int                                                      dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   auto                          key = std::make_pair( dev, level );
-   auto                          it  = cache.find( key );
-   if ( it == cache.end() )
-   {
-      const int              N = ( 1 << level ) + 1;
-      std::vector< FaceRow > host;
-      for ( int f = 0; f < 4; ++f )
-         for ( int j = 0; j < N; ++j )
-            for ( int k0 = 0; k0 < N - j; k0 += 64 )
-               host.push_back( FaceRow{ (short) f, (short) j, (short) k0, (short) std::min( 64, N - j - k0 ) } );
-      FaceRowTable tab;
-      tab.count = (int) host.size();
-      void* p   = nullptr;
-      HH_CHECK_HIP( hipMalloc( &p, host.size() * sizeof( FaceRow ) ) );
-      HH_CHECK_HIP( hipMemcpy( p, host.data(), host.size() * sizeof( FaceRow ), hipMemcpyHostToDevice ) );
-      tab.dev = static_cast< const FaceRow* >( p );
-      it      = cache.emplace( key, tab ).first;
-   }
-   *out = it->second;
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< int, FaceRowTable > cache;
+   const FaceRowTable*                          tab = nullptr;
+   const int rc = cache.get( level,
+                             [&]( FaceRowTable& t ) {
+                                const int              N = ( 1 << level ) + 1;
+                                std::vector< FaceRow > host;
+                                for ( int f = 0; f < 4; ++f )
+                                   for ( int j = 0; j < N; ++j )
+                                      for ( int k0 = 0; k0 < N - j; k0 += 64 )
+                                         host.push_back( FaceRow{ (short) f, (short) j, (short) k0, (short) std::min( 64, N - j - k0 ) } );
+                                t.count = (int) host.size();
+                                return upload_table( host, &t.dev );
+                             },
+                             &tab );
+   if ( rc == HYTEG_HIP_OK )
+      *out = *tab;
+   return rc;
 }
 
 // measurement switch: HYTEG_HIP_TRANSFER_TILES=1 keeps the round-1 tile kernels
 bool transfer_use_tiles()
 {
-   static const bool v = [] {
-      const char* e = std::getenv( "HYTEG_HIP_TRANSFER_TILES" );
-      return e && e[0] == '1';
-   }();
+   static const bool v = env_flag( "HYTEG_HIP_TRANSFER_TILES", false );
    return v;
 }
 

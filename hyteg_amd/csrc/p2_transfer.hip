@@ -19,10 +19,10 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
+#include <tuple>
 #include <vector>
 
-#include "common.hpp"
+#include "device_table.hpp"
 
 using namespace hyteg_hip;
 
@@ -180,28 +180,21 @@ void build_tables( TransferTables& T )
 // device copy of the tables, one per device, built on first use
 int get_tables( const TransferTables** out )
 {
-   static std::mutex                                 mtx;
-   static std::vector< std::pair< int, TransferTables* > > cache;
-   int                                               dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   for ( auto& kv : cache )
-      if ( kv.first == dev )
-      {
-         *out = kv.second;
-         return HYTEG_HIP_OK;
-      }
-   static TransferTables host;
-   build_tables( host );
-   for ( int k = 0; k < 8; ++k )
-      if ( host.nrestrict[k] >= kMaxRestrict )
-         return fail( HYTEG_HIP_EINVAL, "p2 transfer: restriction table overflow" );
-   void* d = nullptr;
-   HH_CHECK_HIP( hipMalloc( &d, sizeof( TransferTables ) ) );
-   HH_CHECK_HIP( hipMemcpy( d, &host, sizeof( TransferTables ), hipMemcpyHostToDevice ) );
-   cache.push_back( { dev, static_cast< TransferTables* >( d ) } );
-   *out = static_cast< TransferTables* >( d );
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< std::tuple<>, const TransferTables* > cache;
+   const TransferTables* const*                                    t = nullptr;
+   const int rc = cache.get( std::tuple<>{},
+                             []( const TransferTables*& dev ) {
+                                std::vector< TransferTables > host( 1 );
+                                build_tables( host[0] );
+                                for ( int k = 0; k < 8; ++k )
+                                   if ( host[0].nrestrict[k] >= kMaxRestrict )
+                                      return fail( HYTEG_HIP_EINVAL, "p2 transfer: restriction table overflow" );
+                                return upload_table( host, &dev );
+                             },
+                             &t );
+   if ( rc == HYTEG_HIP_OK )
+      *out = *t;
+   return rc;
 }
 
 // ---- layout helpers (vertex array of width N; edge array: seven tetrahedral blocks of width n = N - 1, n - 1 for XYZ) ----
@@ -525,10 +518,7 @@ __global__ __launch_bounds__( 256 ) void p2_restrict_rows_kernel( const P2Transf
 // lists known at compile time (as in the P2 apply), so that the bases become layout algebra with constant offsets.
 inline bool transfer_by_threads()
 {
-   static const bool v = [] {
-      const char* e = std::getenv( "HYTEG_HIP_P2_TRANSFER_ROWS" );
-      return !( e && e[0] == '1' );
-   }();
+   static const bool v = !env_flag( "HYTEG_HIP_P2_TRANSFER_ROWS", false );
    return v;
 }
 
@@ -539,10 +529,7 @@ inline bool transfer_by_threads()
 // instead of 56 (prolongation 48.5 instead of 44.0) -- the kinds' very different term counts no longer balance over the XCDs.  Off.
 static bool kinds_interleaved()
 {
-   static const bool v = [] {
-      const char* e = std::getenv( "HYTEG_HIP_P2_TRANSFER_INTERLEAVE" );
-      return e && e[0] == '1';
-   }();
+   static const bool v = env_flag( "HYTEG_HIP_P2_TRANSFER_INTERLEAVE", false );
    return v;
 }
 

@@ -1,10 +1,8 @@
 // Runtime part of the C-ABI: errors, device/memory/stream helpers, layout helpers, tile tables.
-#include <map>
-#include <mutex>
 #include <tuple>
 #include <vector>
 
-#include "common.hpp"
+#include "device_table.hpp"
 #include "kernels_apply_zmarch.hpp"
 
 namespace hyteg_hip {
@@ -90,31 +88,18 @@ static std::vector< Tile > build_tiles( int level, TileKind kind, int capacity )
 
 int get_tiles( int level, TileKind kind, int capacity, TileTable* out )
 {
-   static std::mutex                                                  mtx;
-   static std::map< std::tuple< int, int, int, int >, TileTable >    cache;
-   int                                                                dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   auto                          key = std::make_tuple( dev, level, (int) kind, capacity );
-   auto                          it  = cache.find( key );
-   if ( it != cache.end() )
-   {
-      *out = it->second;
-      return HYTEG_HIP_OK;
-   }
-   std::vector< Tile > host = build_tiles( level, kind, capacity );
-   TileTable           tt;
-   tt.count = (int) host.size();
-   if ( tt.count > 0 )
-   {
-      void* p = nullptr;
-      HH_CHECK_HIP( hipMalloc( &p, host.size() * sizeof( Tile ) ) );
-      HH_CHECK_HIP( hipMemcpy( p, host.data(), host.size() * sizeof( Tile ), hipMemcpyHostToDevice ) );
-      tt.dev = static_cast< const Tile* >( p );
-   }
-   cache[key] = tt;
-   *out       = tt;
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< std::tuple< int, int, int >, TileTable > cache;
+   const TileTable*                                                   tt = nullptr;
+   const int rc = cache.get( std::make_tuple( level, (int) kind, capacity ),
+                             [&]( TileTable& t ) {
+                                const std::vector< Tile > host = build_tiles( level, kind, capacity );
+                                t.count                        = (int) host.size();
+                                return upload_table( host, &t.dev );
+                             },
+                             &tt );
+   if ( rc == HYTEG_HIP_OK )
+      *out = *tt;
+   return rc;
 }
 
 int get_bricks( int level, int NY, int LZ, BrickTable* out, int XS )
@@ -130,40 +115,26 @@ int get_bricks( int level, int NY, int LZ, BrickTable* out, int XS )
       *out = lastVal;
       return HYTEG_HIP_OK;
    }
-   static std::mutex                                             mtx;
-   static std::map< std::tuple< int, int, int, int >, BrickTable > cache;
-   int                                                           dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   auto                          key = std::make_tuple( dev, level, NY, LZ );
-   auto                          it  = cache.find( key );
-   if ( it != cache.end() )
-   {
-      *out       = it->second;
-      lastKey[0] = dev, lastKey[1] = level, lastKey[2] = NY, lastKey[3] = LZ;
-      lastVal    = it->second;
-      return HYTEG_HIP_OK;
-   }
-   std::vector< BrickTask > host;
-   std::vector< int >       zs;
-   build_brick_tasks( level, NY / 1000, LZ, host, &zs, XS );
-   BrickTable bt;
-   bt.count = (int) host.size();
-   // decode mode: zs = starts of the z-chunks followed by the total
-   bt.decodable = XS == 62 && (int) zs.size() - 1 <= kZMarchMaxZChunks && ( 1 << level ) - 3 <= 62 * kZMarchMaxStairs;
-   for ( int k = 0; k < kZMarchMaxZChunks; ++k )
-      bt.zs[k] = k + 1 < (int) zs.size() ? zs[k] : bt.count;
-   if ( bt.count > 0 )
-   {
-      void* p = nullptr;
-      HH_CHECK_HIP( hipMalloc( &p, host.size() * sizeof( BrickTask ) ) );
-      HH_CHECK_HIP( hipMemcpy( p, host.data(), host.size() * sizeof( BrickTask ), hipMemcpyHostToDevice ) );
-      bt.dev = static_cast< const BrickTask* >( p );
-   }
-   cache[key] = bt;
-   *out       = bt;
-   lastKey[0] = dev, lastKey[1] = level, lastKey[2] = NY, lastKey[3] = LZ;
-   lastVal    = bt;
+   static DeviceTableCache< std::tuple< int, int, int >, BrickTable > cache;
+   const BrickTable*                                                   bt = nullptr;
+   const int rc = cache.get_on( dev0, std::make_tuple( level, NY, LZ ),
+                                [&]( BrickTable& b ) {
+                                   std::vector< BrickTask > host;
+                                   std::vector< int >       zs;
+                                   build_brick_tasks( level, NY / 1000, LZ, host, &zs, XS );
+                                   b.count = (int) host.size();
+                                   // decode mode: zs = starts of the z-chunks followed by the total
+                                   b.decodable = XS == 62 && (int) zs.size() - 1 <= kZMarchMaxZChunks && ( 1 << level ) - 3 <= 62 * kZMarchMaxStairs;
+                                   for ( int k = 0; k < kZMarchMaxZChunks; ++k )
+                                      b.zs[k] = k + 1 < (int) zs.size() ? zs[k] : b.count;
+                                   return upload_table( host, &b.dev );
+                                },
+                                &bt );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   *out       = *bt;
+   lastKey[0] = dev0, lastKey[1] = level, lastKey[2] = NY, lastKey[3] = LZ;
+   lastVal    = *bt;
    return HYTEG_HIP_OK;
 }
 
@@ -175,21 +146,28 @@ namespace hyteg_hip {
 // ticket counter of the single-launch reductions, one per (device, stream); zero between launches
 int dot_counter( hipStream_t stream, unsigned** out )
 {
-   static std::mutex                                         mtx;
-   static std::map< std::pair< int, hipStream_t >, unsigned* > counters;
-   int                                                       dev = 0;
-   HH_CHECK_HIP( hipGetDevice( &dev ) );
-   std::lock_guard< std::mutex > lock( mtx );
-   auto                          it = counters.find( { dev, stream } );
-   if ( it == counters.end() )
-   {
-      void* p = nullptr;
-      HH_CHECK_HIP( hipMalloc( &p, sizeof( unsigned ) ) );
-      HH_CHECK_HIP( hipMemset( p, 0, sizeof( unsigned ) ) );
-      it = counters.emplace( std::make_pair( dev, stream ), static_cast< unsigned* >( p ) ).first;
-   }
-   *out = it->second;
-   return HYTEG_HIP_OK;
+   static DeviceTableCache< hipStream_t, unsigned* > counters;
+   unsigned* const*                                  c = nullptr;
+   const int rc = counters.get( stream, []( unsigned*& p ) { return zeroed_table( 1, &p ); }, &c );
+   if ( rc == HYTEG_HIP_OK )
+      *out = *c;
+   return rc;
+}
+
+int cached_operator_table( const std::vector< double >& key, const std::function< int( std::vector< double >& ) >& build, const double** dev_out )
+{
+   static DeviceTableCache< std::vector< double >, const double* > cache;
+   const double* const*                                            t = nullptr;
+   const int rc = cache.get( key,
+                             [&]( const double*& dev ) {
+                                std::vector< double > host;
+                                const int             rb = build( host );
+                                return rb != HYTEG_HIP_OK ? rb : upload_table( host, &dev );
+                             },
+                             &t );
+   if ( rc == HYTEG_HIP_OK )
+      *dev_out = *t;
+   return rc;
 }
 } // namespace hyteg_hip
 
