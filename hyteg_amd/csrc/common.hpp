@@ -45,6 +45,8 @@ inline int env_int( const char* name, int fallback )
 }
 
 inline bool level_ok( int level ) { return level >= HYTEG_HIP_MIN_LEVEL && level <= HYTEG_HIP_MAX_LEVEL; }
+// levels 0 and 1 too: the shell kernels and the batched kernels have no inner-point tiling that needs level 2
+inline bool any_level_ok( int level ) { return level >= 0 && level <= HYTEG_HIP_MAX_LEVEL; }
 
 // ---- HyTeG macro-cell layout (src/hyteg/indexing/MacroCellIndexing.hpp:40-52) ----------------
 // a product / a sum rounded on its own: the compiler contracts a * b + c into an FMA wherever it sees one (-ffp-contract=fast

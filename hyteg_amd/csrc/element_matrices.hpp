@@ -11,6 +11,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "cell_geometry.hpp"
+
 namespace hyteg_hip {
 namespace elmat {
 
@@ -22,9 +24,7 @@ static const int kMicroCellVerts[6][4][3] = {
     { { 1, 0, 1 }, { 0, 1, 1 }, { 0, 0, 1 }, { 0, 1, 0 } }, { { 0, 1, 0 }, { 1, 1, 0 }, { 1, 0, 1 }, { 0, 1, 1 } } };
 
 // the 15 stencil directions in the C-ABI's weight order (std::map< indexing::Index > order: z, then y, then x)
-static const int kDirs[15][3] = { { 0, 0, -1 }, { 1, 0, -1 }, { -1, 1, -1 }, { 0, 1, -1 }, { 0, -1, 0 },
-                                  { 1, -1, 0 }, { -1, 0, 0 }, { 0, 0, 0 },   { 1, 0, 0 },  { -1, 1, 0 },
-                                  { 0, 1, 0 },  { 0, -1, 1 }, { 1, -1, 1 },  { -1, 0, 1 }, { 0, 0, 1 } };
+constexpr auto& kDirs = kStencilOffsC;
 inline int dir_index( int dx, int dy, int dz )
 {
    for ( int k = 0; k < 15; ++k )

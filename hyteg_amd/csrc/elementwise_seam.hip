@@ -55,7 +55,7 @@ __global__ __launch_bounds__( 256 ) void p1_add_class_constants_kernel( double* 
    {
       const int i = tl.a + e, j = i - s0;
       const int y = row_of( W, j ), x = j - row_start( W, y );
-      const int slot = shell::shell_slot( N, x, y, tl.z );
+      const int slot = point_slot< -1 >( N, x, y, tl.z );
       diag[i] += C.c[slot < 0 ? 14 : slot];
    }
 }

@@ -92,14 +92,14 @@ __device__ __forceinline__ void p2_classrows_kind( const P2RowsArgs& A, const do
    {
       if ( x0 != 0 || top < 0 )
          return;
-      cls = class_from_flags( f0, f1, 1, F3 && top == 0 );
+      cls = slot_from_flags< 14 >( f0, f1, 1, F3 && top == 0 );
    }
    else
    {
       xOnly = top;
       if ( xOnly < ( F2 ? 1 : 0 ) || xOnly < x0 || xOnly >= x0 + 62 * NP )
          return;
-      cls = class_from_flags( f0, f1, 0, 1 );
+      cls = slot_from_flags< 14 >( f0, f1, 0, 1 );
    }
    if ( !( ( mask >> cls ) & 1u ) ) // wave-uniform
       return;

@@ -86,7 +86,7 @@ __global__ __launch_bounds__( kThreads ) void p2_elementwise_kernel( const P2Arg
    const int64_t i = (int64_t) cell_index( W, x, y, z );
    int           cls;
    if ( c == 0 )
-      cls = class_from_flags( z == 0, y == 0, x == 0, x + y + z == N - 1 );
+      cls = slot_from_flags< 14 >( z == 0, y == 0, x == 0, x + y + z == N - 1 );
    else
    {
       int f0 = 1, f1 = 1, f2 = 1, f3 = 1;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__( kThreads ) void p2_elementwise_kernel( const P2Arg
          const int px = x + kEdgeEnds[c - 1][e][0], py = y + kEdgeEnds[c - 1][e][1], pz = z + kEdgeEnds[c - 1][e][2];
          f0 &= pz == 0, f1 &= py == 0, f2 &= px == 0, f3 &= px + py + pz == N - 1;
       }
-      cls = class_from_flags( f0, f1, f2, f3 );
+      cls = slot_from_flags< 14 >( f0, f1, f2, f3 );
    }
    if ( !( ( A.mask >> cls ) & 1u ) )
       return;

@@ -228,7 +228,7 @@ __device__ inline void p2_boundary_body( const P2ClassArgs& B, int bx )
    }
    int cls;
    if constexpr ( C == 0 )
-      cls = class_from_flags( z == 0, y == 0, x == 0, x + y + z == N - 1 );
+      cls = slot_from_flags< 14 >( z == 0, y == 0, x == 0, x + y + z == N - 1 );
    else
       cls = edge_class( N, x, y, z, C - 1 );
    if ( cls == 14 || !( ( B.mask >> cls ) & 1u ) )

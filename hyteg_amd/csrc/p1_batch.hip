@@ -7,7 +7,7 @@
 #include <map>
 #include <mutex>
 
-#include "common.hpp"
+#include "cell_geometry.hpp"
 
 using namespace hyteg_hip;
 
@@ -18,39 +18,9 @@ constexpr int kThreads = 256;
 constexpr int kPer     = kTile / kThreads;
 constexpr int kMaxB    = HYTEG_HIP_MAX_BATCH;
 
-__constant__ int kOffsB[15][3] = { { 0, 0, -1 }, { 1, 0, -1 }, { -1, 1, -1 }, { 0, 1, -1 }, { 0, -1, 0 },
-                                   { 1, -1, 0 }, { -1, 0, 0 }, { 0, 0, 0 },   { 1, 0, 0 },  { -1, 1, 0 },
-                                   { 0, 1, 0 },  { 0, -1, 1 }, { 1, -1, 1 },  { -1, 0, 1 }, { 0, 0, 1 } };
-
-// class of a point: 0..13 = slot of the macro-primitive it lies on, 14 = inner point (bit numbers of the point mask)
-__device__ inline int point_class( int N, int x, int y, int z )
-{
-   const int f0 = ( z == 0 ), f1 = ( y == 0 ), f2 = ( x == 0 ), f3 = ( x + y + z == N - 1 );
-   const int cnt = f0 + f1 + f2 + f3;
-   if ( cnt == 0 )
-      return 14;
-   if ( cnt == 1 )
-      return 6 + ( f0 ? 0 : f1 ? 1 : f2 ? 2 : 3 );
-   if ( cnt == 2 )
-   {
-      if ( f0 )
-         return f1 ? 0 : ( f2 ? 1 : 2 );
-      if ( f1 )
-         return f2 ? 3 : 4;
-      return 5;
-   }
-   if ( f0 && f1 && f2 )
-      return 10;
-   if ( f0 && f1 && f3 )
-      return 11;
-   if ( f0 && f2 && f3 )
-      return 12;
-   return 13;
-}
-
 struct Point
 {
-   int  i, x, y, z, cls;
+   int  i, x, y, z, cls; // cls: 0..13 = slot of the macro-primitive the point lies on, 14 = inner point (bit numbers of the point mask)
    bool ok;
 };
 // u-th entry of this thread in tile tl
@@ -64,7 +34,7 @@ __device__ inline Point decode( const Tile& tl, int N, int u )
    p.z         = tl.z;
    p.y         = row_of( W, j );
    p.x         = j - row_start( W, p.y );
-   p.cls       = point_class( N, p.x, p.y, p.z );
+   p.cls       = point_slot< 14 >( N, p.x, p.y, p.z );
    return p;
 }
 
@@ -172,26 +142,6 @@ __device__ inline void cg_scalars_update( double* s, int phase, double relTol, d
    }
 }
 
-__device__ inline double wave_sum_b( double v )
-{
-#pragma unroll
-   for ( int off = 32; off > 0; off >>= 1 )
-      v += __shfl_down( v, off, 64 );
-   return v;
-}
-__device__ inline double block_sum_b( double v, double* sh )
-{
-   v = wave_sum_b( v );
-   if ( ( threadIdx.x & 63 ) == 0 )
-      sh[threadIdx.x >> 6] = v;
-   __syncthreads();
-   double r = 0.0;
-   if ( threadIdx.x == 0 )
-      for ( int k = 0; k < kThreads / 64; ++k )
-         r += sh[k];
-   return r;
-}
-
 // fixed (cell, tile) -> workgroup assignment and fixed reduction trees: the result does not depend on timing
 __global__ __launch_bounds__( kThreads ) void batch_dot_kernel( const DotB A )
 {
@@ -212,7 +162,7 @@ __global__ __launch_bounds__( kThreads ) void batch_dot_kernel( const DotB A )
             acc = fma( a[p.i], b[p.i], acc );
       }
    }
-   const double r = block_sum_b( acc, sh );
+   const double r = block_sum< kThreads >( acc, sh );
    if ( A.counter == nullptr )
    {
       // many workgroups: batch_dot_final_kernel reduces the partial sums (tickets on one address would serialise)
@@ -237,7 +187,7 @@ __global__ __launch_bounds__( kThreads ) void batch_dot_kernel( const DotB A )
    for ( int k = threadIdx.x; k < (int) gridDim.x; k += kThreads )
       sum += __hip_atomic_load( A.partial + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
    __syncthreads(); // sh is reused
-   const double grand = block_sum_b( sum, sh );
+   const double grand = block_sum< kThreads >( sum, sh );
    if ( threadIdx.x == 0 )
    {
       *A.result = grand;
@@ -254,7 +204,7 @@ __global__ __launch_bounds__( kThreads ) void batch_dot_final_kernel( const doub
    double            acc = 0.0;
    for ( int k = threadIdx.x; k < n; k += kThreads )
       acc += partial[k];
-   const double r = block_sum_b( acc, sh );
+   const double r = block_sum< kThreads >( acc, sh );
    if ( threadIdx.x == 0 )
    {
       *result = r;
@@ -284,7 +234,7 @@ __device__ inline double stencil_sum( const double* __restrict__ w, const double
 #pragma unroll
    for ( int k = 0; k < 15; ++k )
    {
-      const int dx = kOffsB[k][0], dy = kOffsB[k][1], dz = kOffsB[k][2];
+      const int dx = kStencilOffs[k][0], dy = kStencilOffs[k][1], dz = kStencilOffs[k][2];
       const int nx = p.x + dx, ny = p.y + dy, nz = p.z + dz;
       ok[k]        = !( nx < 0 || ny < 0 || nz < 0 || nx + ny + nz > N - 1 );
       const int rowDelta   = dy == 0 ? 0 : ( dy > 0 ? ( W - p.y ) : -( W - p.y + 1 ) );
@@ -341,13 +291,6 @@ struct TransferB
    int           Nc, update;
 };
 
-__constant__ int kNB14B[14][3] = { { -1, 0, 0 }, { -1, 0, 1 }, { -1, 1, -1 }, { -1, 1, 0 }, { 0, -1, 0 },
-                                   { 0, -1, 1 }, { 0, 0, -1 }, { 0, 0, 1 },   { 0, 1, -1 }, { 0, 1, 0 },
-                                   { 1, -1, 0 }, { 1, -1, 1 }, { 1, 0, -1 },  { 1, 0, 0 } };
-__constant__ int kAxisB[8][3]  = { { 0, 0, 0 }, { 1, 0, 0 }, { 0, 1, 0 }, { 1, -1, 0 },
-                                  { 0, 0, 1 }, { 1, 0, -1 }, { 0, 1, -1 }, { 1, -1, 1 } };
-__constant__ int kLoFirstB[8] = { 1, 1, 1, 0, 1, 0, 0, 1 };
-
 // same terms and summation order as p1_restrict_kernel (p1_transfer.hip)
 __global__ __launch_bounds__( kThreads ) void batch_restrict_kernel( const TransferB A )
 {
@@ -371,9 +314,9 @@ __global__ __launch_bounds__( kThreads ) void batch_restrict_kernel( const Trans
 #pragma unroll
       for ( int k = 0; k < 14; ++k )
       {
-         const int fx = 2 * p.x + kNB14B[k][0], fy = 2 * p.y + kNB14B[k][1], fz = 2 * p.z + kNB14B[k][2];
+         const int fx = 2 * p.x + kNB14[k][0], fy = 2 * p.y + kNB14[k][1], fz = 2 * p.z + kNB14[k][2];
          ok[k]        = !( fx < 0 || fy < 0 || fz < 0 || fx + fy + fz > Nf - 1 );
-         const int fc = ok[k] ? point_class( Nf, fx, fy, fz ) : 14;
+         const int fc = ok[k] ? point_slot< 14 >( Nf, fx, fy, fz ) : 14;
          fv[k]        = fine[ok[k] ? cell_index( Nf, fx, fy, fz ) : centre];
          // products and sums rounded separately (no FMA contraction): the per-cell kernels of p1_transfer.hip do the same, so
          // that both give the same bits as the reference's scalar loops
@@ -388,7 +331,7 @@ __global__ __launch_bounds__( kThreads ) void batch_restrict_kernel( const Trans
          acc               = ok[k] ? ( first ? term : add_rn( acc, term ) ) : acc;
          first             = first && !ok[k];
       }
-      const int    fc   = point_class( Nf, 2 * p.x, 2 * p.y, 2 * p.z );
+      const int    fc   = point_slot< 14 >( Nf, 2 * p.x, 2 * p.y, 2 * p.z );
       const double term = mul_rn( fc == 14 ? 1.0 : inv[fc], fine[cell_index( Nf, 2 * p.x, 2 * p.y, 2 * p.z )] );
       coarse[p.i]       = first ? term : add_rn( acc, term );
    }
@@ -417,18 +360,16 @@ __global__ __launch_bounds__( kThreads ) void batch_prolongate_kernel( const Tra
          v = add_rn( old, mul_rn( sc, coarse[cell_index( Nc, p.x >> 1, p.y >> 1, p.z >> 1 )] ) );
       else
       {
-         const int    ex = kAxisB[code][0], ey = kAxisB[code][1], ez = kAxisB[code][2];
+         const int    ex = kAxis[code][0], ey = kAxis[code][1], ez = kAxis[code][2];
          const double lo = coarse[cell_index( Nc, ( p.x - ex ) >> 1, ( p.y - ey ) >> 1, ( p.z - ez ) >> 1 )];
          const double hi = coarse[cell_index( Nc, ( p.x + ex ) >> 1, ( p.y + ey ) >> 1, ( p.z + ez ) >> 1 )];
          const double h  = sc * 0.5;
          const double tl = mul_rn( h, lo ), th = mul_rn( h, hi );
-         v               = kLoFirstB[code] ? add_rn( add_rn( old, tl ), th ) : add_rn( add_rn( old, th ), tl );
+         v               = kLoFirst[code] ? add_rn( add_rn( old, tl ), th ) : add_rn( add_rn( old, th ), tl );
       }
       fine[p.i] = v;
    }
 }
-
-inline bool batch_level_ok( int level ) { return level >= 0 && level <= HYTEG_HIP_MAX_LEVEL; }
 
 // tiles that cover the whole array also exist for levels 0 and 1 (get_tiles builds them for any level)
 int full_tiles( int level, TileTable* tt ) { return get_tiles( level, TILES_FULL, kTile, tt ); }
@@ -439,7 +380,7 @@ extern "C" {
 
 #define BATCH_CHECKS( name )                                                                                   \
    HH_REQUIRE( ncells >= 1 && ncells <= kMaxB, name ": ncells must be 1..HYTEG_HIP_MAX_BATCH" );              \
-   HH_REQUIRE( batch_level_ok( level ), name ": level out of range [0,11]" );                                 \
+   HH_REQUIRE( any_level_ok( level ), name ": level out of range [0,11]" );                                   \
    HH_REQUIRE( masks != nullptr, name ": null masks" );
 
 static int launch_vector_b( int                  op,
@@ -572,20 +513,6 @@ struct CgSmallArgs
    double*         info; // [0] iterations, [1] sqrt(<r,r>) at exit
 };
 
-__device__ inline double cg_block_sum( double v, double* sh )
-{
-   v = wave_sum_b( v );
-   __syncthreads(); // sh may still be read from the previous reduction
-   if ( ( threadIdx.x & 63 ) == 0 )
-      sh[threadIdx.x >> 6] = v;
-   __syncthreads();
-   double r = 0.0;
-#pragma unroll
-   for ( int k = 0; k < kCgThreads / 64; ++k )
-      r += sh[k];
-   return r; // the same value in every thread
-}
-
 __global__ __launch_bounds__( kCgThreads ) void p1_cg_small_kernel( const CgSmallArgs A )
 {
    extern __shared__ double lds[];
@@ -620,7 +547,7 @@ __global__ __launch_bounds__( kCgThreads ) void p1_cg_small_kernel( const CgSmal
             ++y;
          }
          cell[u] = c, px[u] = j, py[u] = y, pz[u] = z;
-         cls[u] = point_class( A.N, j, y, z );
+         cls[u] = point_slot< 14 >( A.N, j, y, z );
          sel[u] = ( A.mask[c] >> cls[u] ) & 1u;
          own[u] = ( A.owned[c] >> cls[u] ) & 1u;
       }
@@ -665,7 +592,7 @@ __global__ __launch_bounds__( kCgThreads ) void p1_cg_small_kernel( const CgSmal
          if ( own[u] && sel[u] )
             rr = fma( r, r, rr );
       }
-   rr                    = cg_block_sum( rr, sh );
+   rr                    = block_sum_all< kCgThreads >( rr, sh );
    double       prsold   = rr;
    const double resStart = sqrt( rr );
    int          its      = 0;
@@ -680,7 +607,7 @@ __global__ __launch_bounds__( kCgThreads ) void p1_cg_small_kernel( const CgSmal
          for ( int u = 0; u < kCgPer; ++u )
             if ( idx[u] >= 0 && own[u] && sel[u] )
                pap = fma( P[idx[u]], AP[idx[u]], pap );
-         pap                = cg_block_sum( pap, sh );
+         pap                = block_sum_all< kCgThreads >( pap, sh );
          const double alpha = prsold / pap;
          double       rsnew = 0.0;
 #pragma unroll
@@ -694,7 +621,7 @@ __global__ __launch_bounds__( kCgThreads ) void p1_cg_small_kernel( const CgSmal
                if ( own[u] )
                   rsnew = fma( r, r, rsnew );
             }
-         rsnew  = cg_block_sum( rsnew, sh );
+         rsnew  = block_sum_all< kCgThreads >( rsnew, sh );
          its    = it + 1;
          resNow = sqrt( rsnew );
          if ( resNow / resStart < A.relTol || resNow < A.absTol )

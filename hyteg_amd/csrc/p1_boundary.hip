@@ -1,7 +1,6 @@
 // C-ABI entry points for the cell-centric multi-cell model: kernels on the boundary shell of a macro-cell
 // (points on its macro-faces/edges/vertices), masked vector kernels, masked dot, and the additive exchange of
 // shared points.  The shell has O(4^L) points, so these kernels are latency- rather than bandwidth-relevant.
-#include "common.hpp"
 #include "p2p_device.hpp"
 #include "shell.hpp"
 
@@ -183,14 +182,6 @@ __global__ __launch_bounds__( kThreads ) void p1_set_inner_kernel( double* dst, 
    }
 }
 
-__device__ inline double wave_sum( double v )
-{
-#pragma unroll
-   for ( int off = 32; off > 0; off >>= 1 )
-      v += __shfl_down( v, off, 64 );
-   return v;
-}
-
 // partial sums of a.b over the masked shell points; fixed point -> workgroup assignment (deterministic)
 __global__ __launch_bounds__( kThreads ) void p1_dot_shell_kernel( const double* __restrict__ a,
                                                                     const double* __restrict__ b,
@@ -210,17 +201,9 @@ __global__ __launch_bounds__( kThreads ) void p1_dot_shell_kernel( const double*
          acc         = fma( a[i], b[i], acc );
       }
    }
-   acc = wave_sum( acc );
-   if ( ( threadIdx.x & 63 ) == 0 )
-      sh[threadIdx.x >> 6] = acc;
-   __syncthreads();
+   const double r = block_sum< kThreads >( acc, sh );
    if ( threadIdx.x == 0 )
-   {
-      double r = 0.0;
-      for ( int k = 0; k < kThreads / 64; ++k )
-         r += sh[k];
       partial[blockIdx.x] = r;
-   }
 }
 
 __global__ __launch_bounds__( kThreads ) void zero_partials_kernel( double* p, int n )
@@ -236,17 +219,9 @@ __global__ __launch_bounds__( kThreads ) void sum_partials_kernel( const double*
    double            acc = 0.0;
    for ( int k = threadIdx.x; k < n; k += kThreads )
       acc += partial[k];
-   acc = wave_sum( acc );
-   if ( ( threadIdx.x & 63 ) == 0 )
-      sh[threadIdx.x >> 6] = acc;
-   __syncthreads();
+   const double r = block_sum< kThreads >( acc, sh );
    if ( threadIdx.x == 0 )
-   {
-      double r = 0.0;
-      for ( int k = 0; k < kThreads / 64; ++k )
-         r += sh[k];
       *result = r;
-   }
 }
 
 // what a reduce kernel waits for when the values of other ranks arrive peer to peer (comm_p2p.hip): the flag words of this
@@ -418,7 +393,7 @@ __global__ __launch_bounds__( kThreads ) void p1_apply_face3d_kernel( const Face
 #pragma unroll
       for ( int s = 0; s < 15; ++s )
       {
-         const int lx = cx + kOffs[s][0], ly = cy + kOffs[s][1], lz = cz + kOffs[s][2];
+         const int lx = cx + kStencilOffs[s][0], ly = cy + kStencilOffs[s][1], lz = cz + kStencilOffs[s][2];
          if ( lx < 0 || ly < 0 || lz < 0 || lx + ly + lz > n )
             continue;
          const int bary[4] = { n - lx - ly - lz, lx, ly, lz };
@@ -437,7 +412,6 @@ inline bool vmap_ok( int v0, int v1, int v2 )
    return v0 >= 0 && v0 < 4 && v1 >= 0 && v1 < 4 && v2 >= 0 && v2 < 4 && v0 != v1 && v0 != v2 && v1 != v2;
 }
 
-inline bool shell_level_ok( int level ) { return level >= 0 && level <= HYTEG_HIP_MAX_LEVEL; }
 inline int  shell_blocks( int N ) { return ( 4 * tri( N ) + kThreads - 1 ) / kThreads; }
 
 } // namespace
@@ -459,7 +433,7 @@ HYTEG_HIP_API int hyteg_hip_p1_apply_cell_boundary( double*            dst,
                                                     hyteg_hip_stream_t stream )
 {
    HH_REQUIRE( dst && src && w_slots, "p1_apply_cell_boundary: null pointer" );
-   HH_REQUIRE( shell_level_ok( level ), "p1_apply_cell_boundary: level out of range [0,11]" );
+   HH_REQUIRE( any_level_ok( level ), "p1_apply_cell_boundary: level out of range [0,11]" );
    HH_REQUIRE( dst != src, "p1_apply_cell_boundary: src and dst must not alias" );
    HH_REQUIRE( update == HYTEG_HIP_REPLACE || update == HYTEG_HIP_ADD, "p1_apply_cell_boundary: bad update type" );
    if ( ( mask & HYTEG_HIP_MASK_SHELL ) == 0 )
@@ -486,7 +460,7 @@ HYTEG_HIP_API int hyteg_hip_p1_apply_cell_boundary_f32( float*             dst,
                                                         hyteg_hip_stream_t stream )
 {
    HH_REQUIRE( dst && src && w_slots, "p1_apply_cell_boundary_f32: null pointer" );
-   HH_REQUIRE( shell_level_ok( level ), "p1_apply_cell_boundary_f32: level out of range [0,11]" );
+   HH_REQUIRE( any_level_ok( level ), "p1_apply_cell_boundary_f32: level out of range [0,11]" );
    HH_REQUIRE( dst != src, "p1_apply_cell_boundary_f32: src and dst must not alias" );
    HH_REQUIRE( update == HYTEG_HIP_REPLACE || update == HYTEG_HIP_ADD, "p1_apply_cell_boundary_f32: bad update type" );
    if ( ( mask & HYTEG_HIP_MASK_SHELL ) == 0 )
@@ -517,7 +491,7 @@ HYTEG_HIP_API int hyteg_hip_p1_apply_cell_boundary_p2p( double*                 
                                                         hyteg_hip_stream_t          stream )
 {
    HH_REQUIRE( dst && src && w_slots, "p1_apply_cell_boundary_p2p: null pointer" );
-   HH_REQUIRE( shell_level_ok( level ), "p1_apply_cell_boundary_p2p: level out of range [0,11]" );
+   HH_REQUIRE( any_level_ok( level ), "p1_apply_cell_boundary_p2p: level out of range [0,11]" );
    HH_REQUIRE( dst != src, "p1_apply_cell_boundary_p2p: src and dst must not alias" );
    HH_REQUIRE( update == HYTEG_HIP_REPLACE || update == HYTEG_HIP_ADD, "p1_apply_cell_boundary_p2p: bad update type" );
    HH_REQUIRE( send_first && send_list && peers && npeers > 0 && counter && seq > 0, "p1_apply_cell_boundary_p2p: bad exchange arguments" );
@@ -544,7 +518,7 @@ HYTEG_HIP_API int hyteg_hip_p1_vector_cell_masked( int                  op,
 {
    HH_REQUIRE( dst && srcs, "p1_vector_cell_masked: null pointer" );
    HH_REQUIRE( op >= 0 && op <= 2, "p1_vector_cell_masked: op must be 0 (assign), 1 (add) or 2 (mult)" );
-   HH_REQUIRE( shell_level_ok( level ), "p1_vector_cell_masked: level out of range [0,11]" );
+   HH_REQUIRE( any_level_ok( level ), "p1_vector_cell_masked: level out of range [0,11]" );
    HH_REQUIRE( nsrc >= 1 && nsrc <= HYTEG_HIP_MAX_SRCS, "p1_vector_cell_masked: nsrc must be 1..HYTEG_HIP_MAX_SRCS" );
    HH_REQUIRE( op == 2 || scalars != nullptr, "p1_vector_cell_masked: null scalars" );
    for ( int k = 0; k < nsrc; ++k )
@@ -592,7 +566,7 @@ HYTEG_HIP_API int
     hyteg_hip_p1_set_cell_masked( double* dst, double value, int level, unsigned mask, hyteg_hip_stream_t stream )
 {
    HH_REQUIRE( dst, "p1_set_cell_masked: null pointer" );
-   HH_REQUIRE( shell_level_ok( level ), "p1_set_cell_masked: level out of range [0,11]" );
+   HH_REQUIRE( any_level_ok( level ), "p1_set_cell_masked: level out of range [0,11]" );
    const int N = ( 1 << level ) + 1;
    if ( ( mask & HYTEG_HIP_MASK_ALL ) == HYTEG_HIP_MASK_ALL && level <= 10 )
    {
@@ -636,7 +610,7 @@ HYTEG_HIP_API int hyteg_hip_p1_dot_cell_masked( const double*      a,
                                                 hyteg_hip_stream_t stream )
 {
    HH_REQUIRE( a && b && result_dev && workspace_dev, "p1_dot_cell_masked: null pointer" );
-   HH_REQUIRE( shell_level_ok( level ), "p1_dot_cell_masked: level out of range [0,11]" );
+   HH_REQUIRE( any_level_ok( level ), "p1_dot_cell_masked: level out of range [0,11]" );
    double*   partial = static_cast< double* >( workspace_dev ); // [0,1024): interior, [1024,1024+256): shell
    const int N       = ( 1 << level ) + 1;
    int       n_inner = 0;
@@ -765,7 +739,7 @@ HYTEG_HIP_API int hyteg_hip_gather_entries( double*            out,
 HYTEG_HIP_API int hyteg_hip_p1_copy_face_to_cell( double* cell, const double* face, int level, int v0, int v1, int v2, hyteg_hip_stream_t stream )
 {
    HH_REQUIRE( cell && face, "p1_copy_face_to_cell: null pointer" );
-   HH_REQUIRE( shell_level_ok( level ), "p1_copy_face_to_cell: level out of range [0,11]" );
+   HH_REQUIRE( any_level_ok( level ), "p1_copy_face_to_cell: level out of range [0,11]" );
    HH_REQUIRE( vmap_ok( v0, v1, v2 ), "p1_copy_face_to_cell: v0,v1,v2 must be distinct cell-local vertex ids" );
    const int N = ( 1 << level ) + 1;
    FaceMap   m{ { v0, v1, v2 }, 6 - v0 - v1 - v2 };

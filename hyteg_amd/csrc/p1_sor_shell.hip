@@ -12,7 +12,7 @@
 //   faces    : lexicographic 2-D sweep as hyperplane wavefront; one workgroup per face, one thread per row, the three
 //              already-updated neighbours travel through LDS / a register, everything else is folded into `a` by a
 //              fully parallel preparation kernel
-#include "common.hpp"
+#include "cell_geometry.hpp"
 
 using namespace hyteg_hip;
 
@@ -528,8 +528,7 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_face3d( double*            dst_face,
    HH_REQUIRE( level >= 1 && level <= HYTEG_HIP_MAX_LEVEL, "p1_sor_face3d: level out of range [1,11]" );
    HH_REQUIRE( ncells == 1 || ncells == 2, "p1_sor_face3d: a macro-face has 1 or 2 neighbour cells" );
    HH_REQUIRE( dst_face != rhs_face, "p1_sor_face3d: dst and rhs must not alias" );
-   static const int offs[15][3] = { { 0, 0, -1 }, { 1, 0, -1 }, { -1, 1, -1 }, { 0, 1, -1 }, { 0, -1, 0 }, { 1, -1, 0 }, { -1, 0, 0 }, { 0, 0, 0 },
-                                    { 1, 0, 0 },  { -1, 1, 0 }, { 0, 1, 0 },   { 0, -1, 1 }, { 1, -1, 1 }, { -1, 0, 1 }, { 0, 0, 1 } };
+   constexpr auto&  offs         = kStencilOffsC;
    static const int dirs[6][2]   = { { -1, 0 }, { 1, 0 }, { 0, -1 }, { 0, 1 }, { 1, -1 }, { -1, 1 } }; // = kFaceDirs
    FaceSorArgs A{};
    A.dst = dst_face, A.rhs = rhs_face, A.work = work, A.N = ( 1 << level ) + 1, A.backwards = backwards ? 1 : 0, A.relax = relax;

@@ -3,43 +3,17 @@
 #include <utility>
 #include <vector>
 
+#include "cell_geometry.hpp"
 #include "device_table.hpp"
 
 using namespace hyteg_hip;
 
 namespace {
 
-
-// slot in nnc[14] = { edge0..5, face0..3, vertex0..3 } of the macro-primitive the point lies on, or -1
-// (src/hyteg/indexing/MacroCellIndexing.cpp:36-91)
-__device__ inline int prim_slot( int N, int x, int y, int z )
-{
-   const int f0 = ( z == 0 ), f1 = ( y == 0 ), f2 = ( x == 0 ), f3 = ( x + y + z == N - 1 );
-   const int cnt = f0 + f1 + f2 + f3;
-   if ( cnt == 0 )
-      return -1;
-   if ( cnt == 1 )
-      return 6 + ( f0 ? 0 : f1 ? 1 : f2 ? 2 : 3 );
-   if ( cnt == 2 )
-   {
-      if ( f0 )
-         return f1 ? 0 : ( f2 ? 1 : 2 );
-      if ( f1 )
-         return f2 ? 3 : 4;
-      return 5;
-   }
-   if ( f0 && f1 && f2 )
-      return 10;
-   if ( f0 && f1 && f3 )
-      return 11;
-   if ( f0 && f2 && f3 )
-      return 12;
-   return 13;
-}
-
+// 1 / numNeighborCells of the macro-primitive a point lies on (nnc[14] = { edge0..5, face0..3, vertex0..3 }), 1 inside the cell
 __device__ inline double prim_scale( const Nnc14& s, int N, int x, int y, int z )
 {
-   const int slot = prim_slot( N, x, y, z );
+   const int slot = point_slot< -1 >( N, x, y, z );
    return slot < 0 ? 1.0 : s.inv[slot];
 }
 
@@ -63,19 +37,12 @@ __device__ inline void face_point( int N, int f, int j, int k, int& x, int& y, i
 }
 __device__ inline int lowest_face( int x, int y, int z ) { return ( z == 0 ) ? 0 : ( y == 0 ) ? 1 : ( x == 0 ) ? 2 : 3; }
 
-constexpr int kNB14c[14][3] = { { -1, 0, 0 }, { -1, 0, 1 }, { -1, 1, -1 }, { -1, 1, 0 }, { 0, -1, 0 },
-                                { 0, -1, 1 }, { 0, 0, -1 }, { 0, 0, 1 },   { 0, 1, -1 }, { 0, 1, 0 },
-                                { 1, -1, 0 }, { 1, -1, 1 }, { 1, 0, -1 },  { 1, 0, 0 } }; // = kNB14, for compile-time use
-__constant__ int kNB14[14][3] = { { -1, 0, 0 }, { -1, 0, 1 }, { -1, 1, -1 }, { -1, 1, 0 }, { 0, -1, 0 },
-                                  { 0, -1, 1 }, { 0, 0, -1 }, { 0, 0, 1 },   { 0, 1, -1 }, { 0, 1, 0 },
-                                  { 1, -1, 0 }, { 1, -1, 1 }, { 1, 0, -1 },  { 1, 0, 0 } };
-
 // restriction: one WAVE per run of 64 consecutive coarse entries of one row (TILES_ROWS of the coarse level), four waves per
 // workgroup.  Row and slice are wave-uniform (no per-thread index decoding), and for an inner coarse point (the bulk: only
 // inner fine neighbours, no scaling, no range checks) the 15 fine values come from 7 fine rows as 7 16-byte loads + one
 // 8-byte load per lane -- rows that contribute the offsets (-1, 0) are loaded at 2x - 1, rows that contribute (0, +1) at
 // 2x -- which a wave issues as contiguous 1 KiB requests (the first version issued 15 8-byte loads with stride 16 per
-// thread and decoded (x, y, z) per point: 15.8 us for level 8 -> 7).  Summation order = the 14 neighbours in kNB14 order,
+// thread and decoded (x, y, z) per point: 15.8 us for level 8 -> 7).  Summation order = the 14 neighbours in kNB14C order,
 // then the centre, as before.  Coarse points on the cell boundary (scaled, range-checked sums: ~500 instructions) are NOT
 // handled by the row waves -- two lanes of every wave would take that path and the other 62 would wait for them, which made
 // the first row-mapped version slower than the tile-mapped one (22.7 vs 15.8 us) -- but by extra workgroups at the FRONT of
@@ -109,7 +76,7 @@ __device__ inline double restrict_inner( const double* __restrict__ fine, int Nf
    const tr_d2  a00 = load2( r_00 - 1 ), a0p = load2( r_0p - 1 ), apm = load2( r_pm - 1 ), ap0 = load2( r_p0 - 1 );
    const tr_d2  am0 = load2( r_m0 ), amp = load2( r_mp ), a0m = load2( r_0m );
    const double e00 = r_00[1];
-   // kNB14 order: (-1,0,0) (-1,0,1) (-1,1,-1) (-1,1,0) (0,-1,0) (0,-1,1) (0,0,-1) (0,0,1) (0,1,-1) (0,1,0) (1,-1,0) (1,-1,1) (1,0,-1) (1,0,0)
+   // kNB14C order: (-1,0,0) (-1,0,1) (-1,1,-1) (-1,1,0) (0,-1,0) (0,-1,1) (0,0,-1) (0,0,1) (0,1,-1) (0,1,0) (1,-1,0) (1,-1,1) (1,0,-1) (1,0,0)
    double acc = 0.5 * a00.x;
    acc        = acc + 0.5 * a0p.x;
    acc        = acc + 0.5 * apm.x;
@@ -136,7 +103,7 @@ __device__ inline double restrict_shell( const double* __restrict__ fine, int Nf
 #pragma unroll
    for ( int k = 0; k < 14; ++k )
    {
-      const int  fx = 2 * x + kNB14c[k][0], fy = 2 * y + kNB14c[k][1], fz = 2 * z + kNB14c[k][2];
+      const int  fx = 2 * x + kNB14C[k][0], fy = 2 * y + kNB14C[k][1], fz = 2 * z + kNB14C[k][2];
       const bool in = fx >= 0 && fy >= 0 && fz >= 0 && fx + fy + fz <= Nf - 1;
       sc[k]         = in ? prim_scale( s, Nf, fx, fy, fz ) * 0.5 : 0.0;
       v[k]          = fine[in ? cell_index( Nf, fx, fy, fz ) : 0];
@@ -163,13 +130,13 @@ __device__ inline double restrict_face( const double* __restrict__ fine, int Nf,
    for ( int k = 0; k < 14; ++k )
    {
       constexpr auto inward = []( int kk ) {
-         const int dx = kNB14c[kk][0], dy = kNB14c[kk][1], dz = kNB14c[kk][2];
+         const int dx = kNB14C[kk][0], dy = kNB14C[kk][1], dz = kNB14C[kk][2];
          return F == 0 ? dz : F == 1 ? dy : F == 2 ? dx : -( dx + dy + dz );
       };
       const int c = inward( k );
       if ( c < 0 )
          continue;
-      const double v    = fine[cell_index( Nf, 2 * x + kNB14c[k][0], 2 * y + kNB14c[k][1], 2 * z + kNB14c[k][2] )];
+      const double v    = fine[cell_index( Nf, 2 * x + kNB14C[k][0], 2 * y + kNB14C[k][1], 2 * z + kNB14C[k][2] )];
       const double term = mul_rn( ( c == 0 ? inv_f : 1.0 ) * 0.5, v );
       acc               = add_rn( acc, term );
    }
@@ -215,7 +182,7 @@ __global__ __launch_bounds__( 64 * kRestrictWaves ) void p1_restrict_kernel( dou
          return;
       int x, y, z;
       edge_point( Nc, q / Nc, q % Nc, x, y, z );
-      const int slot = prim_slot( Nc, x, y, z );
+      const int slot = point_slot< -1 >( Nc, x, y, z );
       if ( ( mask >> slot ) & 1u )
          coarse[cell_index( Nc, x, y, z )] = restrict_shell( fine, Nf, x, y, z, s );
       return;
@@ -229,7 +196,7 @@ __global__ __launch_bounds__( 64 * kRestrictWaves ) void p1_restrict_kernel( dou
       const int     lane = threadIdx.x & 63;
       int           x, y, z;
       face_point( Nc, fr.f, fr.j, fr.k0 + lane, x, y, z );
-      if ( lane >= fr.cnt || prim_slot( Nc, x, y, z ) != 6 + fr.f || !( ( mask >> ( 6 + fr.f ) ) & 1u ) )
+      if ( lane >= fr.cnt || point_slot< -1 >( Nc, x, y, z ) != 6 + fr.f || !( ( mask >> ( 6 + fr.f ) ) & 1u ) )
          return; // edge / vertex points: the threads in front
       const double inv_f = s.inv[6 + fr.f];
       double       v;
@@ -253,20 +220,14 @@ __global__ __launch_bounds__( 64 * kRestrictWaves ) void p1_restrict_kernel( dou
    const Tile tl   = tiles[t];
    const int  lane = threadIdx.x & 63;
    const int  x    = tl.yb + lane;
-   if ( lane >= tl.cnt || prim_slot( Nc, x, tl.ya, tl.z ) >= 0 )
+   if ( lane >= tl.cnt || point_slot< -1 >( Nc, x, tl.ya, tl.z ) >= 0 )
       return; // boundary points: the workgroups in front
    coarse[tl.a + lane] = restrict_inner( fine, Nf, x, tl.ya, tl.z );
 }
 
 // prolongation: one thread per fine entry (FULL tiles of the fine level).  A fine point with all-even
 // coordinates copies its coarse twin; any other fine point is the midpoint of exactly one of the 7
-// stencil axes, selected by its parity pattern, and receives half of each of the two end points.
-// `lo_first` tells which end point the reference's scatter loop (lexicographic over coarse points)
-// would have added first.
-__constant__ int kAxis[8][3]  = { { 0, 0, 0 }, { 1, 0, 0 }, { 0, 1, 0 }, { 1, -1, 0 },
-                                 { 0, 0, 1 }, { 1, 0, -1 }, { 0, 1, -1 }, { 1, -1, 1 } };
-__constant__ int kLoFirst[8] = { 1, 1, 1, 0, 1, 0, 0, 1 };
-constexpr bool   kLoFirstC[8] = { 1, 1, 1, 0, 1, 0, 0, 1 }; // the same, for compile-time parities
+// stencil axes, selected by its parity pattern (kAxis, kLoFirst of cell_geometry.hpp).
 __device__ inline double zm_ld( __amdgpu_buffer_rsrc_t r, int voff, int soff )
 {
    typedef int v2i __attribute__( ( ext_vector_type( 2 ) ) );
@@ -309,7 +270,7 @@ __global__ __launch_bounds__( kThreads ) void p1_prolongate_kernel( const double
       const int j    = i - s0;
       const int y    = row_of( Wf, j );
       const int x    = j - row_start( Wf, y );
-      const int slot = prim_slot( Nf, x, y, z );
+      const int slot = point_slot< -1 >( Nf, x, y, z );
       on[u]          = e < tl.cnt && ( ( mask >> ( slot < 0 ? 14 : slot ) ) & 1u );
       sc[u]          = slot < 0 ? 1.0 : s.inv[slot];
       code[u]        = ( x & 1 ) | ( ( y & 1 ) << 1 ) | ( ( z & 1 ) << 2 );
@@ -347,7 +308,7 @@ __global__ __launch_bounds__( kThreads ) void p1_prolongate_kernel( const double
 //                                                (y even, z odd )  Ra = row( Y, Z ),     Rb = row( Y, Z + 1 )
 //                                                (y odd,  z odd )  Ra = row( Y, Z + 1 ), Rb = row( Y + 1, Z )
 //     even x: lo = Ra[x/2], hi = Rb[x/2];      odd x: lo = Rb[(x-1)/2], hi = Ra[(x+1)/2]
-// (kAxis / kLoFirst above, resolved per parity).  A lane loads Ra[x/2], Ra[x/2 + 1] as one 16-byte buffer load and Rb[x/2] as
+// (kAxis / kLoFirst of cell_geometry.hpp, resolved per parity).  A lane loads Ra[x/2], Ra[x/2 + 1] as one 16-byte buffer load and Rb[x/2] as
 // an 8-byte one, row bases in the scalar offset; stores are nontemporal.  The task carries the index of the brick's first
 // entry in each of its 8 fine slices and of its first coarse row in the 6 coarse slices it touches (64 bytes, one
 // s_load_dwordx16); row bases inside a slice are running sums of row lengths.  Lanes outside a row's inner range get an
@@ -420,7 +381,7 @@ __global__ __launch_bounds__( 64 * kPB_Waves ) void p1_prolongate_brick_kernel( 
          return;
       if ( fr.f >= 2 && y >= 1 && z >= 1 && y + z <= Nf - 3 )
          return; // first / last point of a brick row
-      const int slot = prim_slot( Nf, x, y, z );
+      const int slot = point_slot< -1 >( Nf, x, y, z );
       if ( ( mask >> slot ) & 1u )
          prolongate_point< UPDATE >( coarse, fine, Nf, x, y, z, slot, sN );
       return;
@@ -621,11 +582,8 @@ HYTEG_HIP_API int hyteg_hip_p1_restrict_cell_masked( double*            coarse,
    HH_REQUIRE( coarse && fine && nnc, "p1_restrict_cell: null pointer" );
    HH_REQUIRE( coarse_level >= 0 && coarse_level + 1 <= HYTEG_HIP_MAX_LEVEL, "p1_restrict_cell: level out of range" );
    Nnc14 s;
-   for ( int k = 0; k < 14; ++k )
-   {
-      HH_REQUIRE( nnc[k] >= 1.0, "p1_restrict_cell: neighbour-cell counts must be >= 1" );
-      s.inv[k] = 1.0 / nnc[k];
-   }
+   if ( const int rcn = to_nnc14( nnc, &s, "p1_restrict_cell" ); rcn != HYTEG_HIP_OK )
+      return rcn;
    TileTable tt;
    int       rc = get_tiles( coarse_level, TILES_ROWS, kRestrictRow, &tt );
    if ( rc != HYTEG_HIP_OK )
@@ -701,11 +659,8 @@ static int prolongate_impl( const double* coarse, double* fine, int coarse_level
    HH_REQUIRE( coarse_level >= 0 && coarse_level + 1 <= HYTEG_HIP_MAX_LEVEL, "p1_prolongate_cell: level out of range" );
    HH_REQUIRE( update == HYTEG_HIP_REPLACE || update == HYTEG_HIP_ADD, "p1_prolongate_cell: bad update type" );
    Nnc14 s;
-   for ( int k = 0; k < 14; ++k )
-   {
-      HH_REQUIRE( nnc[k] >= 1.0, "p1_prolongate_cell: neighbour-cell counts must be >= 1" );
-      s.inv[k] = 1.0 / nnc[k];
-   }
+   if ( const int rcn = to_nnc14( nnc, &s, "p1_prolongate_cell" ); rcn != HYTEG_HIP_OK )
+      return rcn;
    const int Nf = ( 1 << ( coarse_level + 1 ) ) + 1;
    // level 11: an 11.5 GB array is beyond 32-bit buffer offsets and int indices -> the tile kernel (64-bit pointers)
    if ( coarse_level + 1 >= 4 && coarse_level + 1 <= 10 && !transfer_use_tiles() )

@@ -3,7 +3,7 @@
 // work being the row decode that masks the two boundary entries of every row.
 #include <algorithm>
 
-#include "common.hpp"
+#include "cell_geometry.hpp"
 #include "kernels_apply_zmarch.hpp" // BrickTask
 
 using namespace hyteg_hip;
@@ -132,30 +132,6 @@ int launch_vec( double* dst, int nsrc, const double* const* srcs, const double* 
 constexpr int kDotBlocks = 1024; // partial sums; also the workspace size in doubles
 constexpr int kDotSingleLaunchBlocks = 64;
 
-__device__ inline double wave_sum( double v )
-{
-#pragma unroll
-   for ( int off = 32; off > 0; off >>= 1 )
-      v += __shfl_down( v, off, 64 );
-   return v;
-}
-
-__device__ inline double block_sum( double v, double* sh /* >= kThreads/64 */ )
-{
-   v = wave_sum( v );
-   if ( ( threadIdx.x & 63 ) == 0 )
-      sh[threadIdx.x >> 6] = v;
-   __syncthreads();
-   double r = 0.0;
-   if ( threadIdx.x == 0 )
-   {
-#pragma unroll
-      for ( int k = 0; k < kThreads / 64; ++k )
-         r += sh[k];
-   }
-   return r; // valid in thread 0
-}
-
 // One launch: every workgroup writes its partial sum through to memory (agent-scope store: the 8 XCDs do not share an L2),
 // waits until the store is acknowledged and takes a ticket; the workgroup that draws the last ticket reduces the partial sums,
 // in the same fixed order whichever it is (the order of p1_dot_final_kernel).  No release fence: on this architecture a
@@ -178,7 +154,7 @@ __device__ inline void dot_finish( double r, double* partial, unsigned* counter,
    for ( int k = threadIdx.x; k < (int) gridDim.x; k += kThreads )
       sum += __hip_atomic_load( partial + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
    __syncthreads(); // sh is reused
-   const double grand = block_sum( sum, sh );
+   const double grand = block_sum< kThreads >( sum, sh );
    if ( threadIdx.x == 0 )
    {
       *result = grand;
@@ -217,7 +193,7 @@ __global__ __launch_bounds__( kThreads ) void p1_dot_partial_kernel( const doubl
       for ( int u = 0; u < kPerThread; ++u )
          acc = in[u] ? fma( va[u], vb[u], acc ) : acc;
    }
-   const double r = block_sum( acc, sh );
+   const double r = block_sum< kThreads >( acc, sh );
    if ( result == nullptr )
    {
       // the caller reduces the partial sums together with others (masked dot)
@@ -272,7 +248,7 @@ __global__ __launch_bounds__( kThreads ) void p1_dot_brick_kernel( const double*
             acc = ok[j] ? fma( va[j], vb[j], acc ) : acc;
       }
    }
-   const double r = block_sum( acc, sh );
+   const double r = block_sum< kThreads >( acc, sh );
    if ( result == nullptr )
    {
       if ( threadIdx.x == 0 )
@@ -288,7 +264,7 @@ __global__ __launch_bounds__( kThreads ) void p1_dot_final_kernel( const double*
    double            acc = 0.0;
    for ( int k = threadIdx.x; k < n; k += kThreads )
       acc += partial[k];
-   const double r = block_sum( acc, sh );
+   const double r = block_sum< kThreads >( acc, sh );
    if ( threadIdx.x == 0 )
       *result = r;
 }

@@ -1,4 +1,4 @@
-// What the P2 translation units share (p2_elementwise.hip, p2_edge_vector.hip, p2_constant_seam.hip, p2_sor_face.hip and the
+// What the P2 translation units share (p2_elementwise.hip, p2_edge_vector.hip, p2_constant_seam.hip, p2_sor_face.hip, p2_transfer.hip and the
 // kernels_p2_*.hpp headers): index helpers of the P2 macro-cell arrays, the compile-time constant stencils of an affine macro-cell
 // with the layout of the operator table, and the argument blocks of the apply kernels.
 // Reference: celldof::macrocell::getMicroVerticesFromMicroCell (volumedofspace/CellDoFIndexing.hpp:155-198), edgedof::calcEdgeDoFIndex /
@@ -9,37 +9,13 @@
 
 #include <utility>
 
-#include "common.hpp"
+#include "cell_geometry.hpp"
 
 using namespace hyteg_hip;
 
 namespace {
 
 constexpr int kThreads = 256;
-
-__host__ __device__ inline int class_from_flags( int f0, int f1, int f2, int f3 )
-{
-   const int cnt = f0 + f1 + f2 + f3;
-   if ( cnt == 0 )
-      return 14;
-   if ( cnt == 1 )
-      return 6 + ( f0 ? 0 : f1 ? 1 : f2 ? 2 : 3 );
-   if ( cnt == 2 )
-   {
-      if ( f0 )
-         return f1 ? 0 : ( f2 ? 1 : 2 );
-      if ( f1 )
-         return f2 ? 3 : 4;
-      return 5;
-   }
-   if ( f0 && f1 && f2 )
-      return 10;
-   if ( f0 && f1 && f3 )
-      return 11;
-   if ( f0 && f2 && f3 )
-      return 12;
-   return 13;
-}
 
 // slice z of entry i of a tetrahedral array of width W (largest z with slice_start(W,z) <= i): cube-root estimate + fix-up
 // (a binary search with 64-bit products was a quarter of the instructions of the inner kernels)
@@ -51,6 +27,19 @@ __device__ inline int slice_of( int W, int64_t i )
    while ( m > 1 && tet64( m - 1 ) >= rest )
       --m;
    while ( tet64( m ) < rest )
+      ++m;
+   return W - m;
+}
+
+// the same in 32-bit arithmetic, for arrays below 2^31 entries (the P2 grid transfer: 64-bit products were a large part of its index decoding)
+__device__ inline int slice_of( int W, int i )
+{
+   const unsigned rest = tet32( (unsigned) W ) - (unsigned) i;
+   int            m    = (int) cbrtf( 6.0f * (float) rest );
+   m                   = m < 1 ? 1 : ( m > W ? W : m );
+   while ( m > 1 && tet32( (unsigned) ( m - 1 ) ) >= rest )
+      --m;
+   while ( tet32( (unsigned) m ) < rest )
       ++m;
    return W - m;
 }
@@ -76,7 +65,7 @@ __device__ inline int edge_class( int N, int x, int y, int z, int o )
       const int px = x + kEdgeEnds[o][e][0], py = y + kEdgeEnds[o][e][1], pz = z + kEdgeEnds[o][e][2];
       f0 &= pz == 0, f1 &= py == 0, f2 &= px == 0, f3 &= px + py + pz == N - 1;
    }
-   return class_from_flags( f0, f1, f2, f3 );
+   return slot_from_flags< 14 >( f0, f1, f2, f3 );
 }
 
 // =====================================================================================================================

@@ -123,7 +123,7 @@ int host_class_of( int c, int x, int y, int z, int N )
                 pz = z + ( c == 0 ? 0 : kEdgeEndsHost[c - 1][e][2] );
       f[0] &= pz == 0, f[1] &= py == 0, f[2] &= px == 0, f[3] &= px + py + pz == N - 1;
    }
-   return class_from_flags( f[0], f[1], f[2], f[3] );
+   return slot_from_flags< 14 >( f[0], f[1], f[2], f[3] );
 }
 
 // faces of the cell (bit g; 0: z = 0, 1: y = 0, 2: x = 0, 3: x + y + z = n) that contain the macro-primitive of point class cls

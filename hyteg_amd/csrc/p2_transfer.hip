@@ -23,12 +23,9 @@
 #include <vector>
 
 #include "device_table.hpp"
-
-using namespace hyteg_hip;
+#include "p2_common.hpp"
 
 namespace {
-
-constexpr int kThreads = 256;
 
 struct TEntry
 {
@@ -48,24 +45,13 @@ struct TransferTables
    int         nrestrict[8];
 };
 
-// micro-vertices of the six micro-cell types (celldof::macrocell::getMicroVerticesFromMicroCell, CellDoFIndexing.hpp:155-198)
-const int kMicroVerts[6][4][3] = { { { 0, 0, 0 }, { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 } }, { { 1, 0, 0 }, { 1, 1, 0 }, { 0, 1, 0 }, { 1, 0, 1 } },
-                                   { { 1, 0, 0 }, { 0, 1, 0 }, { 1, 0, 1 }, { 0, 0, 1 } }, { { 1, 1, 0 }, { 1, 1, 1 }, { 0, 1, 1 }, { 1, 0, 1 } },
-                                   { { 1, 0, 1 }, { 0, 1, 1 }, { 0, 0, 1 }, { 0, 1, 0 } }, { { 0, 1, 0 }, { 1, 1, 0 }, { 1, 0, 1 }, { 0, 1, 1 } } };
-// end points of an edge DoF relative to its logical index, by orientation X, Y, Z, XY, XZ, YZ, XYZ (EdgeDoFIndexing.hpp)
-const int            kEnds[7][2][3] = { { { 0, 0, 0 }, { 1, 0, 0 } }, { { 0, 0, 0 }, { 0, 1, 0 } }, { { 0, 0, 0 }, { 0, 0, 1 } },
-                                        { { 1, 0, 0 }, { 0, 1, 0 } }, { { 1, 0, 0 }, { 0, 0, 1 } }, { { 0, 1, 0 }, { 0, 0, 1 } },
-                                        { { 0, 1, 0 }, { 1, 0, 1 } } };
-__constant__ int kEndsDev[7][2][3] = { { { 0, 0, 0 }, { 1, 0, 0 } }, { { 0, 0, 0 }, { 0, 1, 0 } }, { { 0, 0, 0 }, { 0, 0, 1 } },
-                                        { { 1, 0, 0 }, { 0, 1, 0 } }, { { 1, 0, 0 }, { 0, 0, 1 } }, { { 0, 1, 0 }, { 0, 0, 1 } },
-                                        { { 0, 1, 0 }, { 1, 0, 1 } } };
-
 // the edge DoF between the micro-vertices a and b: orientation (1..7) and logical index
 bool edge_between( const int* a, const int* b, int& kind, int* idx )
 {
    for ( int o = 0; o < 7; ++o )
    {
-      const int d[3] = { kEnds[o][1][0] - kEnds[o][0][0], kEnds[o][1][1] - kEnds[o][0][1], kEnds[o][1][2] - kEnds[o][0][2] };
+      const auto& e    = kEdgeEndsHost[o];
+      const int   d[3] = { e[1][0] - e[0][0], e[1][1] - e[0][1], e[1][2] - e[0][2] };
       for ( int s = 0; s < 2; ++s )
       {
          const int* p = s ? b : a;
@@ -74,7 +60,7 @@ bool edge_between( const int* a, const int* b, int& kind, int* idx )
          {
             kind = o + 1;
             for ( int r = 0; r < 3; ++r )
-               idx[r] = p[r] - kEnds[o][0][r];
+               idx[r] = p[r] - e[0][r];
             return true;
          }
       }
@@ -92,7 +78,7 @@ void build_tables( TransferTables& T )
          // position of the fine DoF relative to the coarse index ( x>>1, y>>1, z>>1 ), in quarters of a coarse cell
          int Q[3];
          for ( int r = 0; r < 3; ++r )
-            Q[r] = 2 * p[r] + ( kf == 0 ? 0 : kEnds[kf - 1][0][r] + kEnds[kf - 1][1][r] );
+            Q[r] = 2 * p[r] + ( kf == 0 ? 0 : kEdgeEndsHost[kf - 1][0][r] + kEdgeEndsHost[kf - 1][1][r] );
          // a coarse micro-cell that contains it (any: the interpolant is continuous, and the terms with non-zero weight are
          // those of the smallest sub-simplex containing the point)
          bool found = false;
@@ -104,9 +90,9 @@ void build_tables( TransferTables& T )
                      int V[4][3];
                      for ( int k = 0; k < 4; ++k )
                      {
-                        V[k][0] = dx + kMicroVerts[t][k][0];
-                        V[k][1] = dy + kMicroVerts[t][k][1];
-                        V[k][2] = dz + kMicroVerts[t][k][2];
+                        V[k][0] = dx + cMicroVerts[t][k][0];
+                        V[k][1] = dy + cMicroVerts[t][k][1];
+                        V[k][2] = dz + cMicroVerts[t][k][2];
                      }
                      // barycentric coordinates of Q / 4 in the micro-cell V: solve with Cramer's rule (small integers: exact)
                      double M[3][3], rhs[3];
@@ -211,18 +197,6 @@ __device__ inline int dof_offset( int N, int kind, int x, int y, int z )
    const int W = width_of_kind( N, kind );
    return ( kind == 0 ? 0 : ( kind - 1 ) * (int) tet32( (unsigned) ( N - 1 ) ) ) + cell_index( W, x, y, z );
 }
-// slice z of entry i of a tetrahedral array of width W
-__device__ inline int slice_of( int W, int i )
-{
-   const unsigned rest = tet32( (unsigned) W ) - (unsigned) i;
-   int            m    = (int) cbrtf( 6.0f * (float) rest );
-   m                   = m < 1 ? 1 : ( m > W ? W : m );
-   while ( m > 1 && tet32( (unsigned) ( m - 1 ) ) >= rest )
-      --m;
-   while ( tet32( (unsigned) m ) < rest )
-      ++m;
-   return W - m;
-}
 __device__ inline void decode( int W, int i, int& x, int& y, int& z )
 {
    z           = slice_of( W, i );
@@ -230,42 +204,21 @@ __device__ inline void decode( int W, int i, int& x, int& y, int& z )
    y           = row_of( W - z, j );
    x           = j - row_start( W - z, y );
 }
-// point class 0..13 (slot of the macro-primitive: edge0..5, face0..3, vertex0..3) or 14 (inside the cell)
-__device__ inline int class_from_flags( int f0, int f1, int f2, int f3 )
-{
-   const int cnt = f0 + f1 + f2 + f3;
-   if ( cnt == 0 )
-      return 14;
-   if ( cnt == 1 )
-      return 6 + ( f0 ? 0 : f1 ? 1 : f2 ? 2 : 3 );
-   if ( cnt == 2 )
-   {
-      if ( f0 )
-         return f1 ? 0 : ( f2 ? 1 : 2 );
-      if ( f1 )
-         return f2 ? 3 : 4;
-      return 5;
-   }
-   if ( f0 && f1 && f2 )
-      return 10;
-   if ( f0 && f1 && f3 )
-      return 11;
-   if ( f0 && f2 && f3 )
-      return 12;
-   return 13;
-}
+// point class 0..13 (slot of the macro-primitive: edge0..5, face0..3, vertex0..3) or 14 (inside the cell) of a DoF of any kind.
+// For kind >= 1 this is edge_class( N, x, y, z, kind - 1 ) of p2_common.hpp, written out: the call changes the instructions of
+// all four transfer kernels (profiles/cell_geometry_checks.txt).
 __device__ inline int dof_class( int N, int kind, int x, int y, int z )
 {
    if ( kind == 0 )
-      return class_from_flags( z == 0, y == 0, x == 0, x + y + z == N - 1 );
+      return slot_from_flags< 14 >( z == 0, y == 0, x == 0, x + y + z == N - 1 );
    int f0 = 1, f1 = 1, f2 = 1, f3 = 1;
 #pragma unroll
    for ( int e = 0; e < 2; ++e )
    {
-      const int px = x + kEndsDev[kind - 1][e][0], py = y + kEndsDev[kind - 1][e][1], pz = z + kEndsDev[kind - 1][e][2];
+      const int px = x + kEdgeEnds[kind - 1][e][0], py = y + kEdgeEnds[kind - 1][e][1], pz = z + kEdgeEnds[kind - 1][e][2];
       f0 &= pz == 0, f1 &= py == 0, f2 &= px == 0, f3 &= px + py + pz == N - 1;
    }
-   return class_from_flags( f0, f1, f2, f3 );
+   return slot_from_flags< 14 >( f0, f1, f2, f3 );
 }
 
 struct P2TransferArgs
@@ -445,7 +398,7 @@ __global__ __launch_bounds__( 256 ) void p2_prolongate_rows_kernel( const P2Tran
 // "on the face x + y + z = N - 1": four wave-uniform scales per term, selected per lane.
 __device__ inline double class_scale( const Nnc14& inv, int f0, int f1, int f2, int f3 )
 {
-   const int cls = class_from_flags( f0, f1, f2, f3 );
+   const int cls = slot_from_flags< 14 >( f0, f1, f2, f3 );
    return cls == 14 ? 1.0 : inv.inv[cls];
 }
 __global__ __launch_bounds__( 256 ) void p2_restrict_rows_kernel( const P2TransferArgs A, const Tile* __restrict__ tiles, int ntiles )
@@ -486,7 +439,7 @@ __global__ __launch_bounds__( 256 ) void p2_restrict_rows_kernel( const P2Transf
       }
       else
       {
-         const int( *E )[3] = kEndsDev[kf - 1];
+         const int( *E )[3] = kEdgeEnds[kf - 1];
          f0  = ( fz + E[0][2] == 0 ) && ( fz + E[1][2] == 0 );
          f1  = ( fy + E[0][1] == 0 ) && ( fy + E[1][1] == 0 );
          ex0 = E[0][0], ex1 = E[1][0];

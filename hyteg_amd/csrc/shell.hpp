@@ -3,7 +3,7 @@
 // p1_apply_rank.hip (shares, pack and interior of a rank's cell in one launch).
 #pragma once
 
-#include "common.hpp"
+#include "cell_geometry.hpp"
 
 namespace hyteg_hip {
 namespace shell {
@@ -12,36 +12,6 @@ struct Slots14x15
 {
    double w[14][15];
 };
-
-static __constant__ int kOffs[15][3] = { { 0, 0, -1 }, { 1, 0, -1 }, { -1, 1, -1 }, { 0, 1, -1 }, { 0, -1, 0 },
-                                  { 1, -1, 0 }, { -1, 0, 0 }, { 0, 0, 0 },   { 1, 0, 0 },  { -1, 1, 0 },
-                                  { 0, 1, 0 },  { 0, -1, 1 }, { 1, -1, 1 },  { -1, 0, 1 }, { 0, 0, 1 } };
-
-// slot of the macro-primitive a point lies on (see p1_transfer.hip / MacroCellIndexing.cpp:36-91), -1 interior
-__device__ inline int shell_slot( int N, int x, int y, int z )
-{
-   const int f0 = ( z == 0 ), f1 = ( y == 0 ), f2 = ( x == 0 ), f3 = ( x + y + z == N - 1 );
-   const int cnt = f0 + f1 + f2 + f3;
-   if ( cnt == 0 )
-      return -1;
-   if ( cnt == 1 )
-      return 6 + ( f0 ? 0 : f1 ? 1 : f2 ? 2 : 3 );
-   if ( cnt == 2 )
-   {
-      if ( f0 )
-         return f1 ? 0 : ( f2 ? 1 : 2 );
-      if ( f1 )
-         return f2 ? 3 : 4;
-      return 5;
-   }
-   if ( f0 && f1 && f2 )
-      return 10;
-   if ( f0 && f1 && f3 )
-      return 11;
-   if ( f0 && f2 && f3 )
-      return 12;
-   return 13;
-}
 
 // Enumerates every shell point exactly once: q in [0, 4 tri(N)) -> (x,y,z,slot); returns false for the
 // duplicates (a point on an edge/vertex is visited through its lowest-numbered face only) and padding.
@@ -71,7 +41,7 @@ __device__ inline bool shell_point( int N, int q, int& x, int& y, int& z, int& s
    const int lowest = ( z == 0 ) ? 0 : ( y == 0 ) ? 1 : ( x == 0 ) ? 2 : 3;
    if ( lowest != f )
       return false;
-   slot = shell_slot( N, x, y, z );
+   slot = point_slot< -1 >( N, x, y, z );
    return true;
 }
 
@@ -92,7 +62,7 @@ __device__ inline T share( const Slots14x15& S, const T* __restrict__ src, int N
 #pragma unroll
    for ( int k = 0; k < 15; ++k )
    {
-      const int dx = kOffs[k][0], dy = kOffs[k][1], dz = kOffs[k][2];
+      const int dx = kStencilOffs[k][0], dy = kStencilOffs[k][1], dz = kStencilOffs[k][2];
       const int nx = x + dx, ny = y + dy, nz = z + dz;
       ok[k]        = !( nx < 0 || ny < 0 || nz < 0 || nx + ny + nz > N - 1 );
       const int rowDelta   = dy == 0 ? 0 : ( dy > 0 ? ( w - y ) : -( w - y + 1 ) );
