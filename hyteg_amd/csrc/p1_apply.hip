@@ -137,14 +137,22 @@ int launch_zmarch( void* dst, const T* src, const T* rhs, const T* invdiag, int 
    return fail( HYTEG_HIP_EINVAL, "apply: brick shape not compiled in" );
 }
 
+// Does this level run the z-march register kernel?  Yes whenever the byte offsets of the array fit its 32-bit buffer addressing
+// (level <= 10); level 11 takes the LDS-tiled kernel (pointer addressing) and the composed Chebyshev steps.
+// HYTEG_HIP_APPLY_LDS_TILED=1 (read once) sends every level down the level-11 paths, so that they can be tested entry by entry at small
+// levels.  The one predicate of launch_apply, the two Chebyshev entry points and hyteg_hip_p1_apply_kernel_name; the entry points
+// without a tiled form (_f32, p1_residual_cell, the mixed-precision steps) do not ask it and keep the z-march.
+inline bool level_runs_zmarch( int level )
+{
+   static const bool forceTiled = env_flag( "HYTEG_HIP_APPLY_LDS_TILED", false );
+   return !forceTiled && tet64( ( 1 << level ) + 1 ) * 8 < ( (int64_t) 1 << 31 );
+}
+
 template < int MODE >
 int launch_apply( double* dst, const double* src, const double* rhs, const double* invdiag, int level, const double* w,
                   double relax, hipStream_t stream )
 {
-   // z-march register kernel whenever byte offsets fit the 32-bit buffer addressing (level <= 10);
-   // the LDS-tiled kernel (pointer addressing) covers level 11
-   static const bool forceTiled = env_flag( "HYTEG_HIP_APPLY_LDS_TILED", false ); // measurement switch: the LDS-tiled kernel of round 1 at every level
-   if ( !forceTiled && tet64( ( 1 << level ) + 1 ) * 8 < ( (int64_t) 1 << 31 ) )
+   if ( level_runs_zmarch( level ) )
       return launch_zmarch< MODE >( dst, src, rhs, invdiag, level, w, relax, stream );
 
    TileTable tt;
@@ -275,7 +283,8 @@ HYTEG_HIP_API int hyteg_hip_p1_jacobi_accumulate_f32( double*            x,
 }
 
 // ---- the two fused steps of the Chebyshev smoother (host/chebyshev.hpp ChebyshevSmoother::solve) ----
-// Level 11 (byte offsets beyond the 32-bit buffer addressing of the z-march kernel) composes the step from the entry points it fuses.
+// A level that does not run the z-march (level_runs_zmarch: level 11, or every level under HYTEG_HIP_APPLY_LDS_TILED=1) composes the step
+// from the entry points it fuses.
 HYTEG_HIP_API int hyteg_hip_p1_chebyshev_start_cell( double*            t_out,
                                                      const double*      rhs,
                                                      const double*      x,
@@ -288,7 +297,7 @@ HYTEG_HIP_API int hyteg_hip_p1_chebyshev_start_cell( double*            t_out,
    HH_REQUIRE( level_ok( level ), "p1_chebyshev_start_cell: level out of range [2,11]" );
    HH_REQUIRE( t_out != x && t_out != rhs && t_out != invdiag, "p1_chebyshev_start_cell: t_out must not alias x, rhs or invdiag" );
    HH_REQUIRE( w[7] != 0.0, "p1_chebyshev_start_cell: zero centre weight" );
-   if ( tet64( ( 1 << level ) + 1 ) * 8 < ( (int64_t) 1 << 31 ) )
+   if ( level_runs_zmarch( level ) )
       return launch_zmarch< APPLY_CHEB_START >( t_out, x, rhs, invdiag, level, w, 0.0, as_stream( stream ) );
    int rc = hyteg_hip_p1_apply_cell( t_out, x, level, w, HYTEG_HIP_REPLACE, stream );
    if ( rc != HYTEG_HIP_OK )
@@ -324,7 +333,7 @@ HYTEG_HIP_API int hyteg_hip_p1_chebyshev_step_cell( double*            t_out,
    HH_REQUIRE( t_out != t_in && t_out != x && x != t_in, "p1_chebyshev_step_cell: t_out, x and t_in must be three different arrays" );
    HH_REQUIRE( invdiag != t_out && invdiag != x, "p1_chebyshev_step_cell: invdiag must not alias an output" );
    HH_REQUIRE( w[7] != 0.0, "p1_chebyshev_step_cell: zero centre weight" );
-   if ( tet64( ( 1 << level ) + 1 ) * 8 < ( (int64_t) 1 << 31 ) )
+   if ( level_runs_zmarch( level ) )
       return launch_zmarch< APPLY_CHEB_STEP >( t_out, t_in, (const double*) nullptr, invdiag, level, w, c_cur, as_stream( stream ), x, c_prev,
                                                has_prev ? 1 : 0 );
    int rc = hyteg_hip_p1_apply_cell( t_out, t_in, level, w, HYTEG_HIP_REPLACE, stream );
@@ -360,7 +369,7 @@ HYTEG_HIP_API int hyteg_hip_p1_apply_kernel_name( int level, int update, char* b
    HH_REQUIRE( level_ok( level ), "p1_apply_kernel_name: level out of range [2,11]" );
    HH_REQUIRE( update == HYTEG_HIP_REPLACE || update == HYTEG_HIP_ADD, "p1_apply_kernel_name: bad update type" );
    const int mode = update == HYTEG_HIP_REPLACE ? APPLY_REPLACE : APPLY_ADD;
-   if ( tet64( ( 1 << level ) + 1 ) * 8 >= ( (int64_t) 1 << 31 ) )
+   if ( !level_runs_zmarch( level ) )
    {
       snprintf( buf, buflen, "p1_apply_tiled_kernel<MODE=%d>", mode );
       return HYTEG_HIP_OK;

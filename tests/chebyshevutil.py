@@ -1,6 +1,7 @@
 """numpy restatements for the Chebyshev smoother tests, written from the smoother's definition: the coefficients from numpy's
 Chebyshev class (not from the code under test), the smoother call, a power iteration and a V-cycle on one macro-cell built from
-the single-cell CPU oracle."""
+the single-cell CPU oracle; and kernel_case, the two C-ABI steps against the oracle's composition (test_gpu_chebyshev.py runs it on
+the fused kernels, test_gpu_level11_paths.py on the composed fallbacks)."""
 import numpy as np
 from numpy.polynomial import chebyshev as npcheb
 
@@ -127,3 +128,66 @@ def multi_cell_smooth(orc, st, x, b, inv, c, level, flag, point_mask):
         t1 = [np.where(m, iv * tt, 0.0) for m, iv, tt in zip(masks, inv, t2)]
         x = [np.where(m, xx + c[k] * tt, xx) for m, xx, tt in zip(masks, x, t1)]
     return x
+
+
+C_PREV, C_CUR = 0.8317, -0.2113
+
+
+def _rel(a, b):
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+def kernel_inputs(tet, level, function_inverse, seed):
+    """(w, x0, rhs, t_in, junk, inv): the seeded arrays of one kernel_case"""
+    w = po.assemble_cell_stencil(tet, level)
+    n = po.cell_size(level)
+    rng = np.random.default_rng(seed)
+    x0, rhs, t_in, junk = (rng.standard_normal(n) for _ in range(4))
+    inv = (1.0 / w[7]) * (0.5 + rng.random(n)) if function_inverse else np.full(n, 1.0 / w[7])
+    return w, x0, rhs, t_in, junk, inv
+
+
+def kernel_case(torch, capi, tet, level, function_inverse, has_prev, seed, keep=None):
+    """hyteg_hip_p1_chebyshev_start_cell / _step_cell through the C-ABI against the composition apply_cell / assign / mult_elementwise
+    of the oracle: returns the relative L2 errors over the cell interior; everything else is asserted bit for bit here.  `keep`, a
+    dict, receives the three arrays the kernels computed."""
+    w, x0, rhs, t_in, junk, inv = kernel_inputs(tet, level, function_inverse, seed)
+    inner = po.inner_mask(level).astype(bool)
+    dev = lambda a: torch.from_numpy(a.copy()).cuda()
+    inv_d = dev(inv)
+    invp = inv_d.data_ptr() if function_inverse else None
+    c_prev, c_cur = C_PREV, C_CUR
+    out = {}
+    # start: t_out = inv .* ( rhs - A x ), x untouched
+    x_d, rhs_d, t_d = dev(x0), dev(rhs), dev(junk)
+    capi.p1_chebyshev_start_cell(t_d.data_ptr(), rhs_d.data_ptr(), x_d.data_ptr(), level, w, invdiag=invp)
+    torch.cuda.synchronize()
+    ref = junk.copy()
+    po.apply_cell(ref, x0, level, w)
+    po.assign(ref, [1.0, -1.0], [rhs, ref], level)
+    po.mult_elementwise(ref, [inv, ref], level)
+    got = t_d.cpu().numpy()
+    out["start t_out"] = _rel(got[inner], ref[inner])
+    assert np.array_equal(got[~inner], junk[~inner]), "start: t_out changed outside the cell interior"
+    assert np.array_equal(x_d.cpu().numpy(), x0), "start: x must not be updated by this launch"
+    if keep is not None:
+        keep["start t_out"] = got
+    # step: t_out = inv .* ( A t_in ); x = ( x + c_prev t_in ) + c_cur t_out
+    x_d, tin_d, t_d = dev(x0), dev(t_in), dev(junk)
+    capi.p1_chebyshev_step_cell(t_d.data_ptr(), x_d.data_ptr(), tin_d.data_ptr(), level, w, c_prev, c_cur, has_prev=has_prev, invdiag=invp)
+    torch.cuda.synchronize()
+    ref_t, ref_x = junk.copy(), x0.copy()
+    po.apply_cell(ref_t, t_in, level, w)
+    po.mult_elementwise(ref_t, [inv, ref_t], level)
+    if has_prev:
+        po.assign(ref_x, [1.0, c_prev], [ref_x, t_in], level)
+    po.assign(ref_x, [1.0, c_cur], [ref_x, ref_t], level)
+    got_t, got_x = t_d.cpu().numpy(), x_d.cpu().numpy()
+    out["step t_out"] = _rel(got_t[inner], ref_t[inner])
+    out["step x"] = _rel(got_x[inner], ref_x[inner])
+    assert np.array_equal(got_t[~inner], junk[~inner]), "step: t_out changed outside the cell interior"
+    assert np.array_equal(got_x[~inner], x0[~inner]), "step: x changed outside the cell interior"
+    assert np.array_equal(tin_d.cpu().numpy(), t_in), "step: t_in is read-only"
+    if keep is not None:
+        keep["step t_out"], keep["step x"] = got_t, got_x
+    return out

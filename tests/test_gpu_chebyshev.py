@@ -40,48 +40,8 @@ def _rel(a, b):
 
 # ---------------------------------------------------------------------------------------------------------------
 # 3. the kernels through the C-ABI against the composition apply_cell / assign / mult_elementwise of the oracle
+#    (chebyshevutil.kernel_case)
 # ---------------------------------------------------------------------------------------------------------------
-def _kernel_case(torch, capi, po, tet, level, function_inverse, has_prev, seed):
-    w = po.assemble_cell_stencil(tet, level)
-    n = po.cell_size(level)
-    rng = np.random.default_rng(seed)
-    x0, rhs, t_in, junk = (rng.standard_normal(n) for _ in range(4))
-    inv = (1.0 / w[7]) * (0.5 + rng.random(n)) if function_inverse else np.full(n, 1.0 / w[7])
-    inner = po.inner_mask(level).astype(bool)
-    dev = lambda a: torch.from_numpy(a.copy()).cuda()
-    inv_d = dev(inv)
-    invp = inv_d.data_ptr() if function_inverse else None
-    c_prev, c_cur = 0.8317, -0.2113
-    out = {}
-    # start: t_out = inv .* ( rhs - A x ), x untouched
-    x_d, rhs_d, t_d = dev(x0), dev(rhs), dev(junk)
-    capi.p1_chebyshev_start_cell(t_d.data_ptr(), rhs_d.data_ptr(), x_d.data_ptr(), level, w, invdiag=invp)
-    torch.cuda.synchronize()
-    ref = junk.copy()
-    po.apply_cell(ref, x0, level, w)
-    po.assign(ref, [1.0, -1.0], [rhs, ref], level)
-    po.mult_elementwise(ref, [inv, ref], level)
-    got = t_d.cpu().numpy()
-    out["start t_out"] = _rel(got[inner], ref[inner])
-    assert np.array_equal(got[~inner], junk[~inner]), "start: t_out changed outside the cell interior"
-    assert np.array_equal(x_d.cpu().numpy(), x0), "start: x must not be updated by this launch"
-    # step: t_out = inv .* ( A t_in ); x = ( x + c_prev t_in ) + c_cur t_out
-    x_d, tin_d, t_d = dev(x0), dev(t_in), dev(junk)
-    capi.p1_chebyshev_step_cell(t_d.data_ptr(), x_d.data_ptr(), tin_d.data_ptr(), level, w, c_prev, c_cur, has_prev=has_prev, invdiag=invp)
-    torch.cuda.synchronize()
-    ref_t, ref_x = junk.copy(), x0.copy()
-    po.apply_cell(ref_t, t_in, level, w)
-    po.mult_elementwise(ref_t, [inv, ref_t], level)
-    if has_prev:
-        po.assign(ref_x, [1.0, c_prev], [ref_x, t_in], level)
-    po.assign(ref_x, [1.0, c_cur], [ref_x, ref_t], level)
-    got_t, got_x = t_d.cpu().numpy(), x_d.cpu().numpy()
-    out["step t_out"] = _rel(got_t[inner], ref_t[inner])
-    out["step x"] = _rel(got_x[inner], ref_x[inner])
-    assert np.array_equal(got_t[~inner], junk[~inner]), "step: t_out changed outside the cell interior"
-    assert np.array_equal(got_x[~inner], x0[~inner]), "step: x changed outside the cell interior"
-    assert np.array_equal(tin_d.cpu().numpy(), t_in), "step: t_in is read-only"
-    return out
 
 
 @pytest.mark.parametrize("tet", list(TETS))
@@ -90,7 +50,7 @@ def test_kernels_match_the_composition(env, tet, level):
     torch, capi, host, po, hu, cu = env
     for function_inverse in (False, True):
         for has_prev in (False, True):
-            errs = _kernel_case(torch, capi, po, TETS[tet], level, function_inverse, has_prev, seed=level)
+            errs = cu.kernel_case(torch, capi, TETS[tet], level, function_inverse, has_prev, seed=level)
             print(f"{tet} level {level} function_inverse={function_inverse} has_prev={has_prev}: {errs}")
             for what, e in errs.items():
                 assert e <= 1e-12, (what, e)
@@ -102,7 +62,7 @@ def test_kernels_match_the_composition_in_every_compiled_brick_shape(env, shape)
     capi.set_apply_shape(*shape)
     try:
         for function_inverse in (False, True):
-            errs = _kernel_case(torch, capi, po, SKEW_TET, 6, function_inverse, True, seed=sum(shape))
+            errs = cu.kernel_case(torch, capi, SKEW_TET, 6, function_inverse, True, seed=sum(shape))
             print(f"shape {shape} function_inverse={function_inverse}: {errs}")
             for what, e in errs.items():
                 assert e <= 1e-12, (what, e)

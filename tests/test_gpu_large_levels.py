@@ -92,37 +92,92 @@ def test_level9_every_kernel_against_the_oracle(env):
     assert _rel(u.cpu().numpy(), ref) < 1e-12
 
 
-def _sampled_apply_check(torch, capi, po, level, nsamples=3000):
-    """apply on device arrays that never leave the GPU; the stencil is re-evaluated with torch at random interior points"""
-    n = capi.cell_size(level)
+ROW_SLICES = (1, 2, 511, 1023)  # whole rows y = 1, 2 of these slices: at level 11 each is longer than a 1024-entry tile of the LDS-tiled kernel
+
+
+def _sample_indices(torch, capi, level, nsamples, seed):
+    """(centre, neighbours): int64 device tensors with the array index of the sampled interior points and of their 15 stencil
+    neighbours (order of OFFS).  The sample: `nsamples` random interior points, the corners of the interior (first / last inner point
+    of the array, longest row, tip), and every interior x of rows y = 1, 2 of the slices ROW_SLICES that the level has -- at level
+    11 such a row crosses at least one tile seam wherever the tile table puts it, and only there a tile lies strictly inside one row"""
     N = (1 << level) + 1
-    w = po.assemble_cell_stencil(OCT_TET, level)
-    g = torch.Generator(device="cuda")
-    g.manual_seed(level)
-    src = torch.rand(n, dtype=torch.float64, device="cuda", generator=g)
-    dst = torch.full((n,), 7.0, dtype=torch.float64, device="cuda")
-    capi.p1_apply_cell(dst.data_ptr(), src.data_ptr(), level, w, capi.REPLACE)
-    torch.cuda.synchronize()
-    rng = np.random.default_rng(level)
+    rng = np.random.default_rng(seed)
     pts = []
     while len(pts) < nsamples:
         x, y, z = (int(v) for v in rng.integers(1, N - 2, 3))
         if x + y + z <= N - 2:
             pts.append((x, y, z))
-    # corners of the interior too: first / last inner point of the array, longest row, tip
     pts += [(1, 1, 1), (N - 4, 1, 1), (1, N - 4, 1), (1, 1, N - 4), (N - 5, 2, 1)]
-    centre = torch.tensor([capi.cell_index(level, *p) for p in pts], dtype=torch.int64, device="cuda")
-    want = torch.zeros(len(pts), dtype=torch.float64, device="cuda")
-    for k, (dx, dy, dz) in enumerate(OFFS):
-        idx = torch.tensor([capi.cell_index(level, x + dx, y + dy, z + dz) for x, y, z in pts], dtype=torch.int64, device="cuda")
-        want += w[k] * src[idx]
+    centre = [torch.tensor([capi.cell_index(level, *p) for p in pts], dtype=torch.int64, device="cuda")]
+    nb = [[torch.tensor([capi.cell_index(level, x + dx, y + dy, z + dz) for x, y, z in pts], dtype=torch.int64, device="cuda")]
+          for dx, dy, dz in OFFS]
+    for z in ROW_SLICES:
+        for y in (1, 2):
+            if N - 2 - y - z < 1:
+                continue
+            x = torch.arange(1, N - 1 - y - z, dtype=torch.int64, device="cuda")  # interior x: 1 .. N - 2 - y - z
+            centre.append(capi.cell_index(level, 0, y, z) + x)
+            for k, (dx, dy, dz) in enumerate(OFFS):
+                nb[k].append(capi.cell_index(level, 0, y + dy, z + dz) + x + dx)
+    return torch.cat(centre), [torch.cat(t) for t in nb]
+
+
+def _stencil_at(w, src, nb):
+    """sum_k w[k] src[neighbour k] at the sampled points, with torch on the device"""
+    au = w[0] * src[nb[0]]
+    for k in range(1, 15):
+        au += w[k] * src[nb[k]]
+    return au
+
+
+def _boundary_probes(capi, level):
+    """entries no interior kernel writes: first and last array entries, the tip, two face points"""
+    N = (1 << level) + 1
+    return [capi.cell_index(level, *p) for p in ((0, 0, 0), (N - 1, 0, 0), (0, 0, N - 1), (3, 0, 5), (0, 4, 4))]
+
+
+def _sampled_apply_check(torch, capi, po, level, nsamples=3000, mode="replace", unaligned=False):
+    """apply / fused Jacobi on device arrays that never leave the GPU; the stencil is re-evaluated with torch at the points of
+    _sample_indices.  mode: "replace", "add" (dst pre-filled with a second random array) or "jacobi_invdiag" (inverse-diagonal array);
+    unaligned: the source starts one entry into its buffer (8-byte aligned: the scalar staging of the LDS-tiled kernel at level 11)"""
+    n = capi.cell_size(level)
+    N = (1 << level) + 1
+    w = po.assemble_cell_stencil(OCT_TET, level)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(level)
+    buf = torch.rand(n + int(unaligned), dtype=torch.float64, device="cuda", generator=g)
+    src = buf[1:] if unaligned else buf
+    assert src.data_ptr() % 16 == (8 if unaligned else 0)
+    centre, nb = _sample_indices(torch, capi, level, nsamples, seed=level)
+    probes = _boundary_probes(capi, level)
+    want = _stencil_at(w, src, nb)
+    if mode == "replace":
+        dst = torch.full((n,), 7.0, dtype=torch.float64, device="cuda")
+        capi.p1_apply_cell(dst.data_ptr(), src.data_ptr(), level, w, capi.REPLACE)
+        before, bound = [7.0] * len(probes), 1e-13
+    elif mode == "add":
+        dst = torch.rand(n, dtype=torch.float64, device="cuda", generator=g)
+        want += dst[centre]
+        before = [float(dst[i]) for i in probes]
+        capi.p1_apply_cell(dst.data_ptr(), src.data_ptr(), level, w, capi.ADD)
+        bound = 1e-13
+    else:
+        assert mode == "jacobi_invdiag"
+        rhs = torch.rand(n, dtype=torch.float64, device="cuda", generator=g)
+        inv = (0.5 + torch.rand(n, dtype=torch.float64, device="cuda", generator=g)) / w[7]
+        want = src[centre] + 0.6 * (inv[centre] * (rhs[centre] - want))
+        dst = torch.full((n,), 7.0, dtype=torch.float64, device="cuda")
+        capi.p1_jacobi_cell(dst.data_ptr(), rhs.data_ptr(), src.data_ptr(), level, w, 0.6, inv.data_ptr())
+        before, bound = [7.0] * len(probes), 1e-12
+    torch.cuda.synchronize()
     got = dst[centre]
     scale = float(want.abs().max())
-    assert float((got - want).abs().max()) <= 1e-13 * scale
-    # boundary entries are not written: first and last array entries, a face point
-    for p in ((0, 0, 0), (N - 1, 0, 0), (0, 0, N - 1), (3, 0, 5), (0, 4, 4)):
-        assert float(dst[capi.cell_index(level, *p)]) == 7.0
-    # the stencil annihilates linear functions: rows are contiguous in x, so a linear field is built row by row on the device
+    err = float((got - want).abs().max())
+    print(f"level {level} {mode}{' unaligned' if unaligned else ''}: {centre.numel()} points, largest error {err:.3e}, largest |want| {scale:.3e}")
+    assert err <= bound * scale
+    # boundary entries are not written
+    for i, v in zip(probes, before):
+        assert float(dst[i]) == v
     del dst
     return n, N, w, src
 
@@ -242,6 +297,103 @@ def test_vector_kernels_jacobi_and_transfer_at_level_11(env):
     assert float(b.min()) == 1.0 and float(b.max()) == 1.0
 
 
+@pytest.mark.parametrize("mode,unaligned", [("add", False), ("jacobi_invdiag", False), ("replace", True)])
+def test_apply_modes_and_scalar_staging_at_level_11(env, mode, unaligned):
+    """what test_apply_at_the_largest_levels leaves out of the LDS-tiled kernel at 11.5 GB: Add, Jacobi with an inverse-diagonal
+    array, and the scalar staging of an 8-byte aligned source (their arithmetic is compared entry by entry at levels 2..7 in
+    test_gpu_level11_paths.py; here the addressing)"""
+    torch, capi, po = env
+    level = 11
+    free, _ = torch.cuda.mem_get_info()
+    n = capi.cell_size(level)
+    arrays = {"add": 2, "jacobi_invdiag": 4, "replace": 2}[mode]
+    if free < (arrays + 1.2) * n * 8:
+        pytest.skip(f"needs {(arrays + 1.2) * n * 8 / 2**30:.0f} GiB of device memory")
+    _sampled_apply_check(torch, capi, po, level, mode=mode, unaligned=unaligned)
+
+
+def test_chebyshev_steps_at_level_11(env):
+    """hyteg_hip_p1_chebyshev_start_cell / _step_cell at 11.5 GB per array (the steps composed from apply, assign, mult and add),
+    inverse-diagonal array, has_prev = 1: against the stencil re-evaluated with torch at the points of _sample_indices"""
+    torch, capi, po = env
+    level = 11
+    n = capi.cell_size(level)
+    free, _ = torch.cuda.mem_get_info()
+    if free < 6.5 * n * 8:
+        pytest.skip(f"needs {6.5 * n * 8 / 2**30:.0f} GiB of device memory")
+    w = po.assemble_cell_stencil(OCT_TET, level)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(211)
+    x, rhs = (torch.rand(n, dtype=torch.float64, device="cuda", generator=g) for _ in range(2))
+    inv = (0.5 + torch.rand(n, dtype=torch.float64, device="cuda", generator=g)) / w[7]
+    t_out = torch.full((n,), -3.0, dtype=torch.float64, device="cuda")
+    centre, nb = _sample_indices(torch, capi, level, 2000, seed=5)
+    probes = _boundary_probes(capi, level)
+    x_probes = [float(x[i]) for i in probes]
+    # start: t_out = inv .* ( rhs - A x ), x untouched
+    want = inv[centre] * (rhs[centre] - _stencil_at(w, x, nb))
+    x_before = x[centre].clone()
+    capi.p1_chebyshev_start_cell(t_out.data_ptr(), rhs.data_ptr(), x.data_ptr(), level, w, invdiag=inv.data_ptr())
+    torch.cuda.synchronize()
+    err, scale = float((t_out[centre] - want).abs().max()), float(want.abs().max())
+    print(f"start t_out: {centre.numel()} points, largest error {err:.3e}, largest |want| {scale:.3e}")
+    assert err <= 1e-12 * scale
+    assert bool(torch.equal(x[centre], x_before))
+    assert all(float(t_out[i]) == -3.0 for i in probes) and [float(x[i]) for i in probes] == x_probes
+    # step: t_out = inv .* ( A t_in ); x = ( x + c_prev t_in ) + c_cur t_out, with rhs as t_in
+    c_prev, c_cur = 0.8317, -0.2113
+    t_in = rhs
+    t_out.fill_(-3.0)
+    want_t = inv[centre] * _stencil_at(w, t_in, nb)
+    want_x = (x_before + c_prev * t_in[centre]) + c_cur * want_t
+    capi.p1_chebyshev_step_cell(t_out.data_ptr(), x.data_ptr(), t_in.data_ptr(), level, w, c_prev, c_cur, has_prev=True, invdiag=inv.data_ptr())
+    torch.cuda.synchronize()
+    for what, got, wanted in (("step t_out", t_out[centre], want_t), ("step x", x[centre], want_x)):
+        err, scale = float((got - wanted).abs().max()), float(wanted.abs().max())
+        print(f"{what}: largest error {err:.3e}, largest |want| {scale:.3e}")
+        assert err <= 1e-12 * scale
+    assert all(float(t_out[i]) == -3.0 for i in probes) and [float(x[i]) for i in probes] == x_probes
+
+
+def test_grid_transfer_level_10_to_11_on_a_linear_and_adjointness(env):
+    """fine level 11 is the tile prolongation with 64-bit pointers: prolongation of a linear function in the index coordinates
+    reproduces it at every fine point, and <R f, c> = <f, P c> for random f and c (all neighbour counts 1: P writes every fine
+    entry, R every coarse one) -- an index error beyond 32 bits moves either by O(1)"""
+    torch, capi, po = env
+    lc, lf = 10, 11
+    nc, nf = capi.cell_size(lc), capi.cell_size(lf)
+    free, _ = torch.cuda.mem_get_info()
+    if free < 4.5 * nf * 8:
+        pytest.skip(f"needs {4.5 * nf * 8 / 2**30:.0f} GiB of device memory")
+    ones = [1.0] * 14
+    coarse = _linear(torch, lc)
+    assert coarse.numel() == nc
+    fine = torch.full((nf,), -1.0, dtype=torch.float64, device="cuda")
+    capi.p1_prolongate_cell(coarse.data_ptr(), fine.data_ptr(), lc, ones, capi.REPLACE)
+    torch.cuda.synchronize()
+    want = _linear(torch, lf)
+    assert want.numel() == nf
+    scale = float(want.abs().max())
+    want -= fine
+    err = float(want.abs().max())
+    del want
+    print(f"prolongation of a linear function onto level {lf}: largest error {err:.3e}, largest |want| {scale:.3e}")
+    assert err <= 1e-13 * scale
+    g = torch.Generator(device="cuda")
+    g.manual_seed(1011)
+    f = torch.rand(nf, dtype=torch.float64, device="cuda", generator=g)
+    c = torch.rand(nc, dtype=torch.float64, device="cuda", generator=g)
+    Rf = torch.zeros(nc, dtype=torch.float64, device="cuda")
+    capi.p1_restrict_cell(Rf.data_ptr(), f.data_ptr(), lc, ones)
+    capi.p1_prolongate_cell(c.data_ptr(), fine.data_ptr(), lc, ones, capi.REPLACE)
+    torch.cuda.synchronize()
+    lhs = float((Rf * c).sum())
+    f *= fine
+    rhs = float(f.sum())
+    print(f"<R f, c> = {lhs!r}, <f, P c> = {rhs!r}, relative difference {abs(lhs - rhs) / abs(rhs):.3e}")
+    assert abs(lhs - rhs) <= 1e-11 * abs(rhs)
+
+
 def test_gauss_seidel_level_10_against_the_oracle(env):
     """180 M points, 64^3 / 6 blocks of 16^3 in 190 block wavefronts: block tables, row-base table and staging at 1.4 GB"""
     torch, capi, po = env
@@ -288,6 +440,20 @@ def test_gauss_seidel_level_11_leaves_a_linear_function_alone(env):
     assert float((u - u0).abs().max()) < 1e-8  # values up to 1e4, 2 x 15-term sums per point
 
 
+def _linear(torch, level):
+    """3x - 2y + 5z in units of the level's mesh width, + 1: built slice by slice, row by row on the device"""
+    N = (1 << level) + 1
+    h = 1.0 / (N - 1)
+    parts = []
+    for z in range(N):
+        W = N - z
+        ys = torch.repeat_interleave(torch.arange(W, device="cuda"), torch.arange(W, 0, -1, device="cuda"))
+        starts = torch.cumsum(torch.arange(W, 0, -1, device="cuda"), 0) - torch.arange(W, 0, -1, device="cuda")
+        xs = torch.arange(ys.numel(), device="cuda") - starts[ys]
+        parts.append((3.0 * xs - 2.0 * ys + 5.0 * z).to(torch.float64) * h + 1.0)
+    return torch.cat(parts)
+
+
 def test_grid_transfer_level_9_to_10_on_constants_and_a_linear(env):
     """fine level 10 (1.44 GB per array) is the largest level of the brick prolongation and of 32-bit buffer offsets: prolongation
     of 1 is 1 everywhere; prolongation of a linear function in the index coordinates reproduces it (P1 interpolation is exact
@@ -300,19 +466,7 @@ def test_grid_transfer_level_9_to_10_on_constants_and_a_linear(env):
     if free < 4.5 * nf * 8:
         pytest.skip(f"needs {4.5 * nf * 8 / 2**30:.0f} GiB of device memory")
 
-    def linear(level):
-        # value 3x - 2y + 5z + 1 in units of the level's mesh width: built slice by slice, row by row on the device
-        N = (1 << level) + 1
-        h = 1.0 / (N - 1)
-        parts = []
-        for z in range(N):
-            W = N - z
-            ys = torch.repeat_interleave(torch.arange(W, device="cuda"), torch.arange(W, 0, -1, device="cuda"))
-            starts = torch.cumsum(torch.arange(W, 0, -1, device="cuda"), 0) - torch.arange(W, 0, -1, device="cuda")
-            xs = torch.arange(ys.numel(), device="cuda") - starts[ys]
-            parts.append((3.0 * xs - 2.0 * ys + 5.0 * z).to(torch.float64) * h + 1.0)
-        return torch.cat(parts)
-
+    linear = lambda level: _linear(torch, level)  # noqa: E731
     ones = [1.0] * 14
     coarse = torch.ones(nc, dtype=torch.float64, device="cuda")
     fine = torch.full((nf,), -1.0, dtype=torch.float64, device="cuda")

@@ -104,8 +104,9 @@ def test_every_compiled_brick_shape_gives_the_same_bits(env, level):
 
 
 def test_apply_random_weights_and_unaligned_source(env):
-    """Non-symmetric random weights catch swapped stencil slots; a source pointer that is only 8-byte
-    aligned exercises the scalar staging path."""
+    """Non-symmetric random weights catch swapped stencil slots; the source pointer is only 8-byte aligned: the base of the
+    z-march kernel's buffer addressing at these levels.  (The scalar staging path of the LDS-tiled kernel, which an 8-byte aligned
+    source selects at level 11, is tested in test_gpu_level11_paths.py.)"""
     torch, capi, po = env
     rng = np.random.default_rng(5)
     for level in (3, 5, 6):
