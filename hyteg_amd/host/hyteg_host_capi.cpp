@@ -1,6 +1,8 @@
 // C facade of the C++ host layer (include/hyteg_host.h).  Exceptions become return codes.
 #include "hyteg_host.hpp"
 
+#include <variant>
+
 #include "../../include/hyteg_host.h"
 
 using namespace hyteg;
@@ -16,37 +18,31 @@ struct FunctionH
 {
    std::shared_ptr< P1Function< double > > p;
 };
-// form ids of hyteg_host_operator_create (include/hyteg_host.h): 0 Laplace, 1 mass, 2-4 div x/y/z, 5-7 divT x/y/z, 8 PSPG
+// the alternative's index is the form id of hyteg_host_operator_create (include/hyteg_host.h): 0 Laplace, 1 mass, 2-4 div x/y/z,
+// 5-7 divT x/y/z, 8 PSPG
 struct OperatorH
 {
-   int                                          form;
-   std::shared_ptr< P1ConstantLaplaceOperator > laplace;
-   std::shared_ptr< P1ConstantMassOperator >    mass;
-   std::shared_ptr< P1DivxOperator >            divx;
-   std::shared_ptr< P1DivyOperator >            divy;
-   std::shared_ptr< P1DivzOperator >            divz;
-   std::shared_ptr< P1DivTxOperator >           divtx;
-   std::shared_ptr< P1DivTyOperator >           divty;
-   std::shared_ptr< P1DivTzOperator >           divtz;
-   std::shared_ptr< P1PSPGOperator >            pspg;
-   FunctionH                                    invDiag; // borrowed view
-};
-struct StokesFunctionH
-{
-   std::shared_ptr< P1StokesFunction< double > > p;
-   FunctionH                                     comp[4]; // borrowed views of u, v, w, p
-};
-struct StokesOperatorH
-{
-   std::shared_ptr< P1P1StokesOperator > p;
-};
-struct StokesSolverH
-{
-   std::shared_ptr< Solver< P1P1StokesOperator > > p;
+   std::variant< std::shared_ptr< P1ConstantLaplaceOperator >, std::shared_ptr< P1ConstantMassOperator >, std::shared_ptr< P1DivxOperator >,
+                 std::shared_ptr< P1DivyOperator >, std::shared_ptr< P1DivzOperator >, std::shared_ptr< P1DivTxOperator >,
+                 std::shared_ptr< P1DivTyOperator >, std::shared_ptr< P1DivTzOperator >, std::shared_ptr< P1PSPGOperator > >
+             op;
+   FunctionH invDiag; // borrowed view
 };
 struct SolverH
 {
    std::shared_ptr< Solver< P1ConstantLaplaceOperator > > p;
+};
+struct P2FunctionH
+{
+   std::shared_ptr< P2Function< double > > p;
+};
+struct P2OperatorH
+{
+   std::shared_ptr< P2ElementwiseLaplaceOperator > p;
+};
+struct P2SolverH
+{
+   std::shared_ptr< Solver< P2ElementwiseLaplaceOperator > > p;
 };
 
 template < typename F >
@@ -69,6 +65,7 @@ int guarded( F&& fn )
    }
 }
 PrimitiveStorage&      S( hh_storage_t s ) { return *static_cast< StorageH* >( s )->p; }
+std::shared_ptr< PrimitiveStorage > SP( hh_storage_t s ) { return static_cast< StorageH* >( s )->p; }
 P1Function< double >&  F( hh_function_t f ) { return *static_cast< FunctionH* >( f )->p; }
 std::vector< std::reference_wrapper< const P1Function< double > > > refs( int n, const hh_function_t* fs )
 {
@@ -77,6 +74,159 @@ std::vector< std::reference_wrapper< const P1Function< double > > > refs( int n,
       r.push_back( std::cref( F( fs[i] ) ) );
    return r;
 }
+P2Function< double >& F2( hh_p2function_t f ) { return *static_cast< P2FunctionH* >( f )->p; }
+std::vector< std::reference_wrapper< const P2Function< double > > > refs2( int n, const hh_p2function_t* fs )
+{
+   std::vector< std::reference_wrapper< const P2Function< double > > > r;
+   for ( int i = 0; i < n; ++i )
+      r.push_back( std::cref( F2( fs[i] ) ) );
+   return r;
+}
+// fn( A ) with the operator the handle holds
+template < typename Fn >
+void withOp( hh_operator_t op, Fn&& fn )
+{
+   std::visit( [&]( auto& p ) { fn( *p ); }, static_cast< OperatorH* >( op )->op );
+}
+// the loop of hyteg_host_operator_apply_cycle and _apply_cycle_timed: consecutive applies on different pairs are independent, they
+// overlap on the storage's lanes (PrimitiveStorage::LaneScope)
+void applyCycle( hh_operator_t op, int npairs, const hh_function_t* srcs, const hh_function_t* dsts, int level, int flag, int update, int first, int steps )
+{
+   PrimitiveStorage::LaneScope lanes( *F( srcs[0] ).getStorage() );
+   withOp( op, [&]( auto& A ) {
+      for ( int k = 0; k < steps; ++k )
+      {
+         const int j = ( first + k ) % npairs;
+         A.apply( F( srcs[j] ), F( dsts[j] ), (uint_t) level, DoFType( flag ), update ? Add : Replace );
+      }
+   } );
+   lanes.join();
+}
+// scalar smoother of an integer code: 0 weighted Jacobi, 1 Gauss-Seidel, 2 SOR, 3 mixed-precision Jacobi (P1 only: BASELINE config 5's
+// "fp32 smoother"); null for any other code, which each caller maps in its own way
+template < class Op >
+std::shared_ptr< Solver< Op > > scalarSmoother( int code, const std::shared_ptr< PrimitiveStorage >& storage, int minL, int maxL, double relax )
+{
+   if ( code == 0 )
+      return std::make_shared< WeightedJacobiSmoother< Op > >( storage, (uint_t) minL, (uint_t) maxL, relax );
+   if ( code == 1 )
+      return std::make_shared< GaussSeidelSmoother< Op > >();
+   if ( code == 2 )
+      return std::make_shared< SORSmoother< Op > >( relax );
+   if constexpr ( std::is_same< Op, P1ConstantLaplaceOperator >::value )
+      if ( code == 3 )
+         return std::make_shared< MixedPrecisionJacobiSmoother< Op > >( storage, (uint_t) minL, (uint_t) maxL, relax );
+   return nullptr;
+}
+// CG on the coarsest level of a multigrid solver
+template < class Op >
+std::shared_ptr< Solver< Op > > cgCoarse( const std::shared_ptr< PrimitiveStorage >& storage, int minL, int cgMaxIter, double cgTol )
+{
+   return std::make_shared< CGSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) cgMaxIter, cgTol, cgTol );
+}
+template < class Op, class Restriction = P1toP1LinearRestriction, class Prolongation = P1toP1LinearProlongation, class... RestrictionArgs >
+std::shared_ptr< Solver< Op > > makeGmg( const std::shared_ptr< PrimitiveStorage >& storage, std::shared_ptr< Solver< Op > > smoother,
+                                         std::shared_ptr< Solver< Op > > coarse, int minL, int maxL, int pre, int post, int increment, CycleType cycle,
+                                         RestrictionArgs... restrictionArgs )
+{
+   return std::make_shared< GeometricMultigridSolver< Op, Restriction, Prolongation > >(
+       storage, smoother, coarse, std::make_shared< Restriction >( restrictionArgs... ), std::make_shared< Prolongation >(), (uint_t) minL, (uint_t) maxL,
+       (uint_t) pre, (uint_t) post, (uint_t) increment, cycle );
+}
+CycleType cycleOf( int wcycle ) { return wcycle ? CycleType::WCYCLE : CycleType::VCYCLE; }
+// borrowed view of a component: an aliasing pointer that shares ownership with the composite and points at the component
+template < class T, class Owner >
+std::shared_ptr< T > viewOf( const std::shared_ptr< Owner >& owner, const T& component )
+{
+   return std::shared_ptr< T >( owner, const_cast< T* >( &component ) );
+}
+
+// The two Stokes groups of the facade -- hyteg_host_stokes_* (P1-P1) and hyteg_host_th_* (P2-P1 Taylor-Hood) -- written once over the
+// operator and the handle of a velocity component; the extern "C" functions forward to these.
+template < class Operator, class VelocityH >
+struct StokesFacade
+{
+   using Op = Operator;
+   using Fn = typename Operator::srcType;
+   struct FunctionHandle
+   {
+      std::shared_ptr< Fn > p;
+      VelocityH             velocity[3]; // borrowed views of u, v, w
+      FunctionH             pressure;    // and of p
+   };
+   struct OperatorHandle
+   {
+      std::shared_ptr< Op > p;
+   };
+   struct SolverHandle
+   {
+      std::shared_ptr< Solver< Op > > p;
+   };
+   static Fn&           fn( void* f ) { return *static_cast< FunctionHandle* >( f )->p; }
+   static Op&           op( void* o ) { return *static_cast< OperatorHandle* >( o )->p; }
+   static Solver< Op >& solver( void* s ) { return *static_cast< SolverHandle* >( s )->p; }
+
+   static int functionCreate( hh_storage_t s, const char* name, int minL, int maxL, void** out )
+   {
+      return guarded( [&] {
+         auto* h = new FunctionHandle{};
+         h->p    = std::make_shared< Fn >( name, SP( s ), (uint_t) minL, (uint_t) maxL );
+         *out    = h;
+      } );
+   }
+   static void* velocityView( void* f, int k )
+   {
+      auto* h          = static_cast< FunctionHandle* >( f );
+      h->velocity[k].p = viewOf( h->p, h->p->uvw()[(uint_t) k] );
+      return &h->velocity[k];
+   }
+   static void* pressureView( void* f )
+   {
+      auto* h       = static_cast< FunctionHandle* >( f );
+      h->pressure.p = viewOf( h->p, h->p->p() );
+      return &h->pressure;
+   }
+   static int functionAssign( void* dst, int n, const double* scalars, void* const* fs, int level, int flag )
+   {
+      return guarded( [&] {
+         typename Fn::Refs r;
+         for ( int i = 0; i < n; ++i )
+            r.push_back( std::cref( fn( fs[i] ) ) );
+         fn( dst ).assign( std::vector< double >( scalars, scalars + n ), r, (uint_t) level, DoFType( flag ) );
+      } );
+   }
+   static int functionDot( void* a, void* b, int level, int flag, double* out )
+   {
+      return guarded( [&] { *out = fn( a ).dotGlobal( fn( b ), (uint_t) level, DoFType( flag ) ); } );
+   }
+   static int operatorCreate( hh_storage_t s, int minL, int maxL, void** out )
+   {
+      return guarded( [&] { *out = new OperatorHandle{ std::make_shared< Op >( SP( s ), (uint_t) minL, (uint_t) maxL ) }; } );
+   }
+   static int operatorApply( void* o, void* src, void* dst, int level, int flag )
+   {
+      return guarded( [&] { op( o ).apply( fn( src ), fn( dst ), (uint_t) level, DoFType( flag ) ); } );
+   }
+   static int solverSolve( void* s, void* o, void* x, void* b, int level )
+   {
+      return guarded( [&] { solver( s ).solve( op( o ), fn( x ), fn( b ), (uint_t) level ); } );
+   }
+   template < class Handle >
+   static int destroy( void* h )
+   {
+      return guarded( [&] { delete static_cast< Handle* >( h ); } );
+   }
+   // MinResSolver preconditioned with StokesPressureBlockPreconditioner< ., P1LumpedInvMassOperator >, as
+   // apps/stokesSphere/StokesSphere.cpp:227-237 composes it
+   static std::shared_ptr< Solver< Op > > pressureMinres( const std::shared_ptr< PrimitiveStorage >& storage, int minL, int maxL, int maxIter, double relTol )
+   {
+      auto prec = std::make_shared< StokesPressureBlockPreconditioner< Op, P1LumpedInvMassOperator > >( storage, (uint_t) minL, (uint_t) maxL );
+      return std::make_shared< MinResSolver< Op > >( storage, (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, relTol, 1e-16, prec );
+   }
+};
+using P1P1 = StokesFacade< P1P1StokesOperator, FunctionH >;
+using TH   = StokesFacade< P2P1TaylorHoodStokesOperator, P2FunctionH >;
+
 // ChebyshevSmoother with its coefficients set up (one spectral radius for all levels, or one per level)
 template < class Op >
 std::shared_ptr< ChebyshevSmoother< Op > > makeChebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
@@ -84,7 +234,7 @@ std::shared_ptr< ChebyshevSmoother< Op > > makeChebyshev( hh_storage_t s, int mi
 {
    if ( !radii || ( nRadii != 1 && nRadii != maxL - minL + 1 ) )
       throw std::runtime_error( "chebyshev: pass one spectral radius, or one per level" );
-   auto sm = std::make_shared< ChebyshevSmoother< Op > >( static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL );
+   auto sm = std::make_shared< ChebyshevSmoother< Op > >( SP( s ), (uint_t) minL, (uint_t) maxL );
    if ( nRadii == 1 )
       sm->setupCoefficients( (uint_t) order, radii[0], upper, lower );
    else
@@ -326,7 +476,7 @@ HYTEG_HOST_API int hyteg_host_plan_register_buffers( hh_storage_t s, int level, 
 HYTEG_HOST_API int hyteg_host_function_create( hh_storage_t s, const char* name, int minL, int maxL, hh_function_t* out )
 {
    return guarded( [&] {
-      *out = new FunctionH{ std::make_shared< P1Function< double > >( name, static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL ) };
+      *out = new FunctionH{ std::make_shared< P1Function< double > >( name, SP( s ), (uint_t) minL, (uint_t) maxL ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_function_destroy( hh_function_t f )
@@ -385,56 +535,32 @@ HYTEG_HOST_API int hyteg_host_operator_create( hh_storage_t s, int minL, int max
    return guarded( [&] {
       if ( form < 0 || form > 8 )
          throw std::runtime_error( "operator_create: unknown form id" );
-      auto* h      = new OperatorH{};
-      h->form      = form;
-      auto storage = static_cast< StorageH* >( s )->p;
+      auto         h       = std::make_unique< OperatorH >();
+      auto         storage = SP( s );
       const uint_t a = (uint_t) minL, b = (uint_t) maxL;
       switch ( form )
       {
-      case 0: h->laplace = std::make_shared< P1ConstantLaplaceOperator >( storage, a, b ); break;
-      case 1: h->mass = std::make_shared< P1ConstantMassOperator >( storage, a, b ); break;
-      case 2: h->divx = std::make_shared< P1DivxOperator >( storage, a, b ); break;
-      case 3: h->divy = std::make_shared< P1DivyOperator >( storage, a, b ); break;
-      case 4: h->divz = std::make_shared< P1DivzOperator >( storage, a, b ); break;
-      case 5: h->divtx = std::make_shared< P1DivTxOperator >( storage, a, b ); break;
-      case 6: h->divty = std::make_shared< P1DivTyOperator >( storage, a, b ); break;
-      case 7: h->divtz = std::make_shared< P1DivTzOperator >( storage, a, b ); break;
-      default: h->pspg = std::make_shared< P1PSPGOperator >( storage, a, b ); break;
+      case 0: h->op = std::make_shared< P1ConstantLaplaceOperator >( storage, a, b ); break;
+      case 1: h->op = std::make_shared< P1ConstantMassOperator >( storage, a, b ); break;
+      case 2: h->op = std::make_shared< P1DivxOperator >( storage, a, b ); break;
+      case 3: h->op = std::make_shared< P1DivyOperator >( storage, a, b ); break;
+      case 4: h->op = std::make_shared< P1DivzOperator >( storage, a, b ); break;
+      case 5: h->op = std::make_shared< P1DivTxOperator >( storage, a, b ); break;
+      case 6: h->op = std::make_shared< P1DivTyOperator >( storage, a, b ); break;
+      case 7: h->op = std::make_shared< P1DivTzOperator >( storage, a, b ); break;
+      default: h->op = std::make_shared< P1PSPGOperator >( storage, a, b ); break;
       }
-      *out = h;
+      *out = h.release();
    } );
 }
 HYTEG_HOST_API int hyteg_host_operator_destroy( hh_operator_t op )
 {
    return guarded( [&] { delete static_cast< OperatorH* >( op ); } );
 }
-#define WITH_OP_CASE( member ) \
-   {                           \
-      auto& A = *_h->member;   \
-      expr;                    \
-   }                           \
-   break
-#define WITH_OP( op, expr )                       \
-   do                                             \
-   {                                              \
-      auto* _h = static_cast< OperatorH* >( op ); \
-      switch ( _h->form )                         \
-      {                                           \
-      case 0: { auto& A = *_h->laplace; expr; } break; \
-      case 1: { auto& A = *_h->mass; expr; } break;    \
-      case 2: { auto& A = *_h->divx; expr; } break;    \
-      case 3: { auto& A = *_h->divy; expr; } break;    \
-      case 4: { auto& A = *_h->divz; expr; } break;    \
-      case 5: { auto& A = *_h->divtx; expr; } break;   \
-      case 6: { auto& A = *_h->divty; expr; } break;   \
-      case 7: { auto& A = *_h->divtz; expr; } break;   \
-      default: { auto& A = *_h->pspg; expr; } break;   \
-      }                                           \
-   } while ( 0 )
 HYTEG_HOST_API int hyteg_host_operator_stencils( hh_operator_t op, int gc, int level, double* inner15, double* slots210 )
 {
    return guarded( [&] {
-      WITH_OP( op, {
+      withOp( op, [&]( auto& A ) {
          const auto& st = A.getCellStencils( gc, (uint_t) level );
          std::copy( st.inner, st.inner + 15, inner15 );
          std::copy( &st.slots[0][0], &st.slots[0][0] + 210, slots210 );
@@ -443,22 +569,14 @@ HYTEG_HOST_API int hyteg_host_operator_stencils( hh_operator_t op, int gc, int l
 }
 HYTEG_HOST_API int hyteg_host_operator_apply( hh_operator_t op, hh_function_t src, hh_function_t dst, int level, int flag, int update )
 {
-   return guarded( [&] { WITH_OP( op, A.apply( F( src ), F( dst ), (uint_t) level, DoFType( flag ), update ? Add : Replace ) ); } );
+   return guarded( [&] { withOp( op, [&]( auto& A ) { A.apply( F( src ), F( dst ), (uint_t) level, DoFType( flag ), update ? Add : Replace ); } ); } );
 }
 HYTEG_HOST_API int hyteg_host_operator_apply_cycle( hh_operator_t op, int npairs, const hh_function_t* srcs, const hh_function_t* dsts, int level,
                                                     int flag, int update, int first, int steps )
 {
    return guarded( [&] {
-      if ( steps <= 0 || npairs <= 0 )
-         return;
-      // consecutive applies on different pairs are independent: they overlap on the storage's lanes (PrimitiveStorage::LaneScope)
-      PrimitiveStorage::LaneScope lanes( *F( srcs[0] ).getStorage() );
-      for ( int k = 0; k < steps; ++k )
-      {
-         const int j = ( first + k ) % npairs;
-         WITH_OP( op, A.apply( F( srcs[j] ), F( dsts[j] ), (uint_t) level, DoFType( flag ), update ? Add : Replace ) );
-      }
-      lanes.join();
+      if ( steps > 0 && npairs > 0 )
+         applyCycle( op, npairs, srcs, dsts, level, flag, update, first, steps );
    } );
 }
 HYTEG_HOST_API int hyteg_host_operator_apply_cycle_timed( hh_operator_t op, int npairs, const hh_function_t* srcs, const hh_function_t* dsts,
@@ -472,27 +590,19 @@ HYTEG_HOST_API int hyteg_host_operator_apply_cycle_timed( hh_operator_t op, int 
       hyteg_hip_stream_t stream = F( srcs[0] ).getStorage()->stream();
       if ( evStart )
          hipCheck( hyteg_hip_event_record( evStart, stream ), "apply_cycle_timed: record" );
-      {
-         // evStart in front of the fork, evStop behind the join: both on the storage's stream, the lanes in between
-         PrimitiveStorage::LaneScope lanes( *F( srcs[0] ).getStorage() );
-         for ( int k = 0; k < steps; ++k )
-         {
-            const int j = ( first + k ) % npairs;
-            WITH_OP( op, A.apply( F( srcs[j] ), F( dsts[j] ), (uint_t) level, DoFType( flag ), update ? Add : Replace ) );
-         }
-         lanes.join();
-      }
+      // evStart in front of the fork, evStop behind the join: both on the storage's stream, the lanes in between
+      applyCycle( op, npairs, srcs, dsts, level, flag, update, first, steps );
       if ( evStop )
          hipCheck( hyteg_hip_event_record( evStop, stream ), "apply_cycle_timed: record" );
    } );
 }
 HYTEG_HOST_API int hyteg_host_operator_smooth_jac( hh_operator_t op, hh_function_t dst, hh_function_t rhs, hh_function_t src, double relax, int level, int flag )
 {
-   return guarded( [&] { WITH_OP( op, A.smooth_jac( F( dst ), F( rhs ), F( src ), relax, (uint_t) level, DoFType( flag ) ) ); } );
+   return guarded( [&] { withOp( op, [&]( auto& A ) { A.smooth_jac( F( dst ), F( rhs ), F( src ), relax, (uint_t) level, DoFType( flag ) ); } ); } );
 }
 HYTEG_HOST_API int hyteg_host_operator_smooth_sor( hh_operator_t op, hh_function_t dst, hh_function_t rhs, double relax, int level, int flag, int backwards )
 {
-   return guarded( [&] { WITH_OP( op, A.smooth_sor( F( dst ), F( rhs ), relax, (uint_t) level, DoFType( flag ), backwards != 0 ) ); } );
+   return guarded( [&] { withOp( op, [&]( auto& A ) { A.smooth_sor( F( dst ), F( rhs ), relax, (uint_t) level, DoFType( flag ), backwards != 0 ); } ); } );
 }
 HYTEG_HOST_API int hyteg_host_operator_smooth_sor_many( hh_operator_t op, int n, const hh_function_t* dsts, const hh_function_t* rhss, double relax,
                                                         int level, int flag, int backwards )
@@ -504,18 +614,18 @@ HYTEG_HOST_API int hyteg_host_operator_smooth_sor_many( hh_operator_t op, int n,
          xs.push_back( std::cref( F( dsts[k] ) ) );
          bs.push_back( std::cref( F( rhss[k] ) ) );
       }
-      WITH_OP( op, A.smooth_sor_many( xs, bs, relax, (uint_t) level, DoFType( flag ), backwards != 0 ) );
+      withOp( op, [&]( auto& A ) { A.smooth_sor_many( xs, bs, relax, (uint_t) level, DoFType( flag ), backwards != 0 ); } );
    } );
 }
 HYTEG_HOST_API int hyteg_host_operator_compute_inverse_diagonal( hh_operator_t op )
 {
-   return guarded( [&] { WITH_OP( op, A.computeInverseDiagonalOperatorValues() ); } );
+   return guarded( [&] { withOp( op, []( auto& A ) { A.computeInverseDiagonalOperatorValues(); } ); } );
 }
 HYTEG_HOST_API int hyteg_host_operator_inverse_diagonal( hh_operator_t op, hh_function_t* out )
 {
    return guarded( [&] {
       auto* h = static_cast< OperatorH* >( op );
-      WITH_OP( op, h->invDiag.p = A.getInverseDiagonalValues() );
+      withOp( op, [&]( auto& A ) { h->invDiag.p = A.getInverseDiagonalValues(); } );
       *out = &h->invDiag;
    } );
 }
@@ -530,7 +640,7 @@ HYTEG_HOST_API int hyteg_host_elementwise_create( hh_storage_t s, int minL, int 
 {
    return guarded( [&] {
       auto* h = new ElementwiseH{};
-      h->p    = std::make_shared< operatorgeneration::P1ElementwiseDiffusion >( static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL );
+      h->p    = std::make_shared< operatorgeneration::P1ElementwiseDiffusion >( SP( s ), (uint_t) minL, (uint_t) maxL );
       *out    = h;
    } );
 }
@@ -577,21 +687,11 @@ HYTEG_HOST_API int hyteg_host_gmg_create( hh_storage_t s, int minL, int maxL, in
                                           int cgMaxIter, double cgTol, hh_solver_t* out )
 {
    return guarded( [&] {
-      using Op     = P1ConstantLaplaceOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
-      std::shared_ptr< Solver< Op > > sm;
-      if ( smoother == 0 )
-         sm = std::make_shared< WeightedJacobiSmoother< Op > >( storage, (uint_t) minL, (uint_t) maxL, relax );
-      else if ( smoother == 1 )
-         sm = std::make_shared< GaussSeidelSmoother< Op > >();
-      else if ( smoother == 3 )
-         sm = std::make_shared< MixedPrecisionJacobiSmoother< Op > >( storage, (uint_t) minL, (uint_t) maxL, relax );
-      else
+      using Op = P1ConstantLaplaceOperator;
+      auto sm  = scalarSmoother< Op >( smoother, SP( s ), minL, maxL, relax );
+      if ( !sm ) // every other code: SOR
          sm = std::make_shared< SORSmoother< Op > >( relax );
-      auto coarse = std::make_shared< CGSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) cgMaxIter, cgTol, cgTol );
-      *out        = new SolverH{ std::make_shared< GeometricMultigridSolver< Op > >(
-          storage, sm, coarse, std::make_shared< P1toP1LinearRestriction >(), std::make_shared< P1toP1LinearProlongation >(), (uint_t) minL,
-          (uint_t) maxL, (uint_t) pre, (uint_t) post, 0, wcycle ? CycleType::WCYCLE : CycleType::VCYCLE ) };
+      *out = new SolverH{ makeGmg< Op >( SP( s ), sm, cgCoarse< Op >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_gmg_set_use_graphs( hh_solver_t solver, int on )
@@ -638,8 +738,7 @@ HYTEG_HOST_API int hyteg_host_gmg_replayed_cycles( hh_solver_t solver, int* coun
 HYTEG_HOST_API int hyteg_host_cg_create( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_solver_t* out )
 {
    return guarded( [&] {
-      *out = new SolverH{ std::make_shared< CGSolver< P1ConstantLaplaceOperator > >( static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL,
-                                                                                     (uint_t) maxIter, tol, tol ) };
+      *out = new SolverH{ std::make_shared< CGSolver< P1ConstantLaplaceOperator > >( SP( s ), (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, tol, tol ) };
    } );
 }
 /* ---- ChebyshevSmoother (src/hyteg/solvers/ChebyshevSmoother.hpp) ---- */
@@ -654,7 +753,9 @@ HYTEG_HOST_API int hyteg_host_chebyshev_coefficients( int order, double lower, d
 }
 HYTEG_HOST_API int hyteg_host_chebyshev_estimate_radius( hh_operator_t op, int level, int maxIter, hh_function_t x, hh_function_t tmp, double* radius )
 {
-   return guarded( [&] { WITH_OP( op, *radius = chebyshev::estimateRadius( A, (uint_t) level, (uint_t) maxIter, A.getStorage(), F( x ), F( tmp ) ) ); } );
+   return guarded( [&] {
+      withOp( op, [&]( auto& A ) { *radius = chebyshev::estimateRadius( A, (uint_t) level, (uint_t) maxIter, A.getStorage(), F( x ), F( tmp ) ); } );
+   } );
 }
 HYTEG_HOST_API int hyteg_host_chebyshev_create( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
                                                 double lower, hh_solver_t* out )
@@ -678,22 +779,18 @@ HYTEG_HOST_API int hyteg_host_gmg_create_chebyshev( hh_storage_t s, int minL, in
                                                     double lower, int pre, int post, int wcycle, int cgMaxIter, double cgTol, hh_solver_t* out )
 {
    return guarded( [&] {
-      using Op     = P1ConstantLaplaceOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
-      auto sm      = makeChebyshev< Op >( s, minL, maxL, order, radii, nRadii, upper, lower );
-      auto coarse  = std::make_shared< CGSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) cgMaxIter, cgTol, cgTol );
-      *out         = new SolverH{ std::make_shared< GeometricMultigridSolver< Op > >(
-          storage, sm, coarse, std::make_shared< P1toP1LinearRestriction >(), std::make_shared< P1toP1LinearProlongation >(), (uint_t) minL,
-          (uint_t) maxL, (uint_t) pre, (uint_t) post, 0, wcycle ? CycleType::WCYCLE : CycleType::VCYCLE ) };
+      using Op = P1ConstantLaplaceOperator;
+      auto sm  = makeChebyshev< Op >( s, minL, maxL, order, radii, nRadii, upper, lower );
+      *out = new SolverH{ makeGmg< Op >( SP( s ), sm, cgCoarse< Op >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_solver_solve( hh_solver_t solver, hh_operator_t laplace, hh_function_t x, hh_function_t b, int level )
 {
    return guarded( [&] {
       auto* h = static_cast< OperatorH* >( laplace );
-      if ( h->form != 0 )
+      if ( h->op.index() != 0 )
          throw std::runtime_error( "solver_solve: the solvers are instantiated for the Laplace operator" );
-      static_cast< SolverH* >( solver )->p->solve( *h->laplace, F( x ), F( b ), (uint_t) level );
+      static_cast< SolverH* >( solver )->p->solve( *std::get< 0 >( h->op ), F( x ), F( b ), (uint_t) level );
    } );
 }
 HYTEG_HOST_API int hyteg_host_solver_destroy( hh_solver_t solver )
@@ -704,42 +801,24 @@ HYTEG_HOST_API int hyteg_host_solver_destroy( hh_solver_t solver )
 /* ---- P1-P1 Stokes (src/mixed_operator/P1P1StokesOperator.hpp, src/hyteg/solvers/UzawaSmoother.hpp) ---- */
 HYTEG_HOST_API int hyteg_host_stokes_function_create( hh_storage_t s, const char* name, int minL, int maxL, hh_stokes_function_t* out )
 {
-   return guarded( [&] {
-      auto* h = new StokesFunctionH{};
-      h->p    = std::make_shared< P1StokesFunction< double > >( name, static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL );
-      *out    = h;
-   } );
+   return P1P1::functionCreate( s, name, minL, maxL, out );
 }
-HYTEG_HOST_API int hyteg_host_stokes_function_destroy( hh_stokes_function_t f )
-{
-   return guarded( [&] { delete static_cast< StokesFunctionH* >( f ); } );
-}
+HYTEG_HOST_API int hyteg_host_stokes_function_destroy( hh_stokes_function_t f ) { return P1P1::destroy< P1P1::FunctionHandle >( f ); }
 HYTEG_HOST_API int hyteg_host_stokes_function_component( hh_stokes_function_t f, int k, hh_function_t* out )
 {
    return guarded( [&] {
-      auto* h = static_cast< StokesFunctionH* >( f );
       if ( k < 0 || k > 3 )
          throw std::runtime_error( "stokes_function_component: k = 0, 1, 2 (velocity) or 3 (pressure)" );
-      // aliasing pointer: shares ownership with the Stokes function, points at the component
-      const P1Function< double >& c = k < 3 ? h->p->uvw()[(uint_t) k] : h->p->p();
-      h->comp[k].p                  = std::shared_ptr< P1Function< double > >( h->p, const_cast< P1Function< double >* >( &c ) );
-      *out                          = &h->comp[k];
+      *out = k < 3 ? P1P1::velocityView( f, k ) : P1P1::pressureView( f );
    } );
 }
 HYTEG_HOST_API int hyteg_host_stokes_function_assign( hh_stokes_function_t dst, int n, const double* scalars, const hh_stokes_function_t* fs, int level, int flag )
 {
-   return guarded( [&] {
-      std::vector< std::reference_wrapper< const P1StokesFunction< double > > > r;
-      for ( int i = 0; i < n; ++i )
-         r.push_back( std::cref( *static_cast< StokesFunctionH* >( fs[i] )->p ) );
-      static_cast< StokesFunctionH* >( dst )->p->assign( std::vector< double >( scalars, scalars + n ), r, (uint_t) level, DoFType( flag ) );
-   } );
+   return P1P1::functionAssign( dst, n, scalars, fs, level, flag );
 }
 HYTEG_HOST_API int hyteg_host_stokes_function_dot( hh_stokes_function_t a, hh_stokes_function_t b, int level, int flag, double* out )
 {
-   return guarded( [&] {
-      *out = static_cast< StokesFunctionH* >( a )->p->dotGlobal( *static_cast< StokesFunctionH* >( b )->p, (uint_t) level, DoFType( flag ) );
-   } );
+   return P1P1::functionDot( a, b, level, flag, out );
 }
 HYTEG_HOST_API int hyteg_host_project_mean( hh_function_t pressure, int level )
 {
@@ -747,42 +826,26 @@ HYTEG_HOST_API int hyteg_host_project_mean( hh_function_t pressure, int level )
 }
 HYTEG_HOST_API int hyteg_host_stokes_operator_create( hh_storage_t s, int minL, int maxL, hh_stokes_operator_t* out )
 {
-   return guarded( [&] {
-      *out = new StokesOperatorH{ std::make_shared< P1P1StokesOperator >( static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL ) };
-   } );
+   return P1P1::operatorCreate( s, minL, maxL, out );
 }
-HYTEG_HOST_API int hyteg_host_stokes_operator_destroy( hh_stokes_operator_t op )
-{
-   return guarded( [&] { delete static_cast< StokesOperatorH* >( op ); } );
-}
+HYTEG_HOST_API int hyteg_host_stokes_operator_destroy( hh_stokes_operator_t op ) { return P1P1::destroy< P1P1::OperatorHandle >( op ); }
 HYTEG_HOST_API int hyteg_host_stokes_operator_apply( hh_stokes_operator_t op, hh_stokes_function_t src, hh_stokes_function_t dst, int level, int flag )
 {
-   return guarded( [&] {
-      static_cast< StokesOperatorH* >( op )->p->apply( *static_cast< StokesFunctionH* >( src )->p, *static_cast< StokesFunctionH* >( dst )->p,
-                                                       (uint_t) level, DoFType( flag ) );
-   } );
+   return P1P1::operatorApply( op, src, dst, level, flag );
 }
 HYTEG_HOST_API int hyteg_host_stokes_uzawa_create( hh_storage_t s, int minL, int maxL, double relax, int velocity_iterations, int velocity_smoother,
                                                    double velocity_relax, hh_stokes_solver_t* out )
 {
    return guarded( [&] {
       using Op     = P1P1StokesOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
-      std::shared_ptr< Solver< P1ConstantLaplaceOperator > > scalar;
-      if ( velocity_smoother == 0 )
-         scalar = std::make_shared< WeightedJacobiSmoother< P1ConstantLaplaceOperator > >( storage, (uint_t) minL, (uint_t) maxL, velocity_relax );
-      else if ( velocity_smoother == 1 )
-         scalar = std::make_shared< GaussSeidelSmoother< P1ConstantLaplaceOperator > >();
-      else if ( velocity_smoother == 2 )
-         scalar = std::make_shared< SORSmoother< P1ConstantLaplaceOperator > >( velocity_relax );
-      else if ( velocity_smoother == 3 ) // BASELINE config 5's "fp32 smoother": float Jacobi sweeps inside the Uzawa smoother
-         scalar = std::make_shared< MixedPrecisionJacobiSmoother< P1ConstantLaplaceOperator > >( storage, (uint_t) minL, (uint_t) maxL, velocity_relax );
-      else
+      auto storage = SP( s );
+      auto scalar  = scalarSmoother< P1ConstantLaplaceOperator >( velocity_smoother, storage, minL, maxL, velocity_relax );
+      if ( !scalar )
          throw std::runtime_error( "stokes_uzawa_create: unknown velocity smoother" );
       auto velocity = std::make_shared< StokesVelocityBlockBlockDiagonalPreconditioner< Op > >( storage, scalar );
-      *out          = new StokesSolverH{ std::make_shared< UzawaSmoother< Op > >( storage, velocity, (uint_t) minL, (uint_t) maxL, relax,
-                                                                                  Inner | NeumannBoundary | FreeslipBoundary,
-                                                                                  (uint_t) velocity_iterations ) };
+      *out          = new P1P1::SolverHandle{ std::make_shared< UzawaSmoother< Op > >( storage, velocity, (uint_t) minL, (uint_t) maxL, relax,
+                                                                                       Inner | NeumannBoundary | FreeslipBoundary,
+                                                                                       (uint_t) velocity_iterations ) };
    } );
 }
 // coarse: 0 = dense LU on the host (stand-in for PETScLUSolver, single rank), 1 = MinResSolver preconditioned with
@@ -794,23 +857,17 @@ HYTEG_HOST_API int hyteg_host_stokes_gmg_create_with_coarse( hh_storage_t s, hh_
 {
    return guarded( [&] {
       using Op     = P1P1StokesOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
+      auto storage = SP( s );
       std::shared_ptr< Solver< Op > > coarseSolver;
       if ( coarse == 0 )
          coarseSolver = std::make_shared< DenseCoarseGridSolver< Op > >( storage, (uint_t) minL );
       else if ( coarse == 1 )
-      {
-         auto prec    = std::make_shared< StokesPressureBlockPreconditioner< Op, P1LumpedInvMassOperator > >( storage, (uint_t) minL, (uint_t) minL );
-         coarseSolver = std::make_shared< MinResSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) coarse_max_iter, coarse_rel_tol, 1e-16, prec );
-      }
+         coarseSolver = P1P1::pressureMinres( storage, minL, minL, coarse_max_iter, coarse_rel_tol );
       else
          throw std::runtime_error( "stokes_gmg_create: unknown coarse-grid solver" );
-      *out = new StokesSolverH{
-          std::make_shared< GeometricMultigridSolver< Op, P1P1StokesToP1P1StokesRestriction, P1P1StokesToP1P1StokesProlongation > >(
-              storage, static_cast< StokesSolverH* >( smoother )->p, coarseSolver,
-              std::make_shared< P1P1StokesToP1P1StokesRestriction >( project_mean_after_restriction != 0 ),
-              std::make_shared< P1P1StokesToP1P1StokesProlongation >(), (uint_t) minL, (uint_t) maxL, (uint_t) pre, (uint_t) post,
-              (uint_t) increment ) };
+      *out = new P1P1::SolverHandle{ makeGmg< Op, P1P1StokesToP1P1StokesRestriction, P1P1StokesToP1P1StokesProlongation >(
+          storage, static_cast< P1P1::SolverHandle* >( smoother )->p, coarseSolver, minL, maxL, pre, post, increment, CycleType::VCYCLE,
+          project_mean_after_restriction != 0 ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_stokes_gmg_create( hh_storage_t s, hh_stokes_solver_t smoother, int minL, int maxL, int pre, int post, int increment,
@@ -826,7 +883,7 @@ HYTEG_HOST_API int hyteg_host_stokes_minres_create( hh_storage_t s, int minL, in
 {
    return guarded( [&] {
       using Op     = P1P1StokesOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
+      auto storage = SP( s );
       std::shared_ptr< Solver< Op > > prec;
       if ( preconditioner == 0 )
          prec = std::make_shared< IdentityPreconditioner< Op > >();
@@ -837,21 +894,20 @@ HYTEG_HOST_API int hyteg_host_stokes_minres_create( hh_storage_t s, int minL, in
          using L       = P1ConstantLaplaceOperator;
          auto smoother = std::make_shared< GaussSeidelSmoother< L > >();
          auto coarse   = std::make_shared< CGSolver< L > >( storage, (uint_t) minL, (uint_t) maxL );
-         auto gmg      = std::make_shared< GeometricMultigridSolver< L > >( storage, smoother, coarse, std::make_shared< P1toP1LinearRestriction >(),
-                                                                       std::make_shared< P1toP1LinearProlongation >(), (uint_t) minL, (uint_t) maxL, 2, 2 );
+         auto gmg      = makeGmg< L >( storage, smoother, coarse, minL, maxL, 2, 2, 0, CycleType::VCYCLE );
          prec = std::make_shared< StokesBlockDiagonalPreconditioner< Op, P1LumpedInvMassOperator > >( storage, (uint_t) minL, (uint_t) maxL,
                                                                                                        (uint_t) velocity_steps, gmg );
       }
       else
          throw std::runtime_error( "stokes_minres_create: unknown preconditioner" );
       auto solver = std::make_shared< MinResSolver< Op > >( storage, (uint_t) minL, (uint_t) maxL, (uint_t) max_iter, rel_tol, 1e-16, prec );
-      *out        = new StokesSolverH{ solver };
+      *out        = new P1P1::SolverHandle{ solver };
    } );
 }
 HYTEG_HOST_API int hyteg_host_stokes_minres_iterations( hh_stokes_solver_t solver, int* iterations )
 {
    return guarded( [&] {
-      auto* m = dynamic_cast< MinResSolver< P1P1StokesOperator >* >( static_cast< StokesSolverH* >( solver )->p.get() );
+      auto* m = dynamic_cast< MinResSolver< P1P1StokesOperator >* >( &P1P1::solver( solver ) );
       if ( !m )
          throw std::runtime_error( "stokes_minres_iterations: not a MinResSolver" );
       *iterations = (int) m->getIterations();
@@ -863,7 +919,7 @@ HYTEG_HOST_API int hyteg_host_solver_create_minres( hh_storage_t s, int minL, in
 {
    return guarded( [&] {
       using L      = P1ConstantLaplaceOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
+      auto storage = SP( s );
       std::shared_ptr< Solver< L > > prec;
       if ( jacobi_iterations > 0 )
          prec = std::make_shared< JacobiPreconditioner< L > >( storage, (uint_t) minL, (uint_t) maxL, (uint_t) jacobi_iterations );
@@ -874,40 +930,15 @@ HYTEG_HOST_API int hyteg_host_solver_create_minres( hh_storage_t s, int minL, in
 }
 HYTEG_HOST_API int hyteg_host_stokes_solver_solve( hh_stokes_solver_t solver, hh_stokes_operator_t op, hh_stokes_function_t x, hh_stokes_function_t b, int level )
 {
-   return guarded( [&] {
-      static_cast< StokesSolverH* >( solver )->p->solve( *static_cast< StokesOperatorH* >( op )->p, *static_cast< StokesFunctionH* >( x )->p,
-                                                         *static_cast< StokesFunctionH* >( b )->p, (uint_t) level );
-   } );
+   return P1P1::solverSolve( solver, op, x, b, level );
 }
-HYTEG_HOST_API int hyteg_host_stokes_solver_destroy( hh_stokes_solver_t solver )
-{
-   return guarded( [&] { delete static_cast< StokesSolverH* >( solver ); } );
-}
+HYTEG_HOST_API int hyteg_host_stokes_solver_destroy( hh_stokes_solver_t solver ) { return P1P1::destroy< P1P1::SolverHandle >( solver ); }
 
 /* ---- P2 (single macro-cell) ---- */
-namespace {
-struct P2FunctionH
-{
-   std::shared_ptr< P2Function< double > > p;
-};
-struct P2OperatorH
-{
-   std::shared_ptr< P2ElementwiseLaplaceOperator > p;
-};
-P2Function< double >& F2( hh_p2function_t f ) { return *static_cast< P2FunctionH* >( f )->p; }
-std::vector< std::reference_wrapper< const P2Function< double > > > refs2( int n, const hh_p2function_t* fs )
-{
-   std::vector< std::reference_wrapper< const P2Function< double > > > r;
-   for ( int i = 0; i < n; ++i )
-      r.push_back( std::cref( F2( fs[i] ) ) );
-   return r;
-}
-} // namespace
-
 HYTEG_HOST_API int hyteg_host_p2function_create( hh_storage_t s, const char* name, int minL, int maxL, hh_p2function_t* out )
 {
    return guarded( [&] {
-      *out = new P2FunctionH{ std::make_shared< P2Function< double > >( name, static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL ) };
+      *out = new P2FunctionH{ std::make_shared< P2Function< double > >( name, SP( s ), (uint_t) minL, (uint_t) maxL ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_p2function_destroy( hh_p2function_t f )
@@ -958,7 +989,7 @@ HYTEG_HOST_API int hyteg_host_p2function_dot( hh_p2function_t a, hh_p2function_t
 HYTEG_HOST_API int hyteg_host_p2operator_create( hh_storage_t s, int minL, int maxL, hh_p2operator_t* out )
 {
    return guarded( [&] {
-      *out = new P2OperatorH{ std::make_shared< P2ElementwiseLaplaceOperator >( static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL ) };
+      *out = new P2OperatorH{ std::make_shared< P2ElementwiseLaplaceOperator >( SP( s ), (uint_t) minL, (uint_t) maxL ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_p2_prolongate( hh_p2function_t f, int sourceLevel, int flag, int add )
@@ -978,7 +1009,7 @@ HYTEG_HOST_API int hyteg_host_p2_restrict( hh_p2function_t f, int sourceLevel, i
 HYTEG_HOST_API int hyteg_host_p2operator_create_constant( hh_storage_t s, int minL, int maxL, hh_p2operator_t* out )
 {
    return guarded( [&] {
-      *out = new P2OperatorH{ std::make_shared< P2ConstantLaplaceOperator >( static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL ) };
+      *out = new P2OperatorH{ std::make_shared< P2ConstantLaplaceOperator >( SP( s ), (uint_t) minL, (uint_t) maxL ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_p2operator_constant_stencils( hh_p2operator_t op, int local_cell, int level, double* out, int capacity, int* count )
@@ -1031,27 +1062,16 @@ HYTEG_HOST_API int hyteg_host_p2operator_smooth_sor( hh_p2operator_t op, hh_p2fu
       static_cast< P2OperatorH* >( op )->p->smooth_sor( F2( dst ), F2( rhs ), relax, (uint_t) level, DoFType( flag ), backwards != 0 );
    } );
 }
-struct P2SolverH
-{
-   std::shared_ptr< Solver< P2ElementwiseLaplaceOperator > > p;
-};
 HYTEG_HOST_API int hyteg_host_p2_gmg_create( hh_storage_t s, int minL, int maxL, int smootherKind, double relax, int pre, int post, int wcycle,
                                              int cgMaxIter, double cgTol, hh_p2solver_t* out )
 {
    return guarded( [&] {
-      using Op     = P2ElementwiseLaplaceOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
-      std::shared_ptr< Solver< Op > > smoother;
-      if ( smootherKind == 0 )
-         smoother = std::make_shared< WeightedJacobiSmoother< Op > >( storage, (uint_t) minL, (uint_t) maxL, relax );
-      else if ( smootherKind == 1 )
-         smoother = std::make_shared< GaussSeidelSmoother< Op > >();
-      else
-         smoother = std::make_shared< SORSmoother< Op > >( relax );
-      auto coarse   = std::make_shared< CGSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) cgMaxIter, cgTol, cgTol );
-      *out          = new P2SolverH{ std::make_shared< GeometricMultigridSolver< Op, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation > >(
-          storage, smoother, coarse, std::make_shared< P2toP2QuadraticRestriction >(), std::make_shared< P2toP2QuadraticProlongation >(),
-          (uint_t) minL, (uint_t) maxL, (uint_t) pre, (uint_t) post, 0, wcycle ? CycleType::WCYCLE : CycleType::VCYCLE ) };
+      using Op = P2ElementwiseLaplaceOperator;
+      auto sm  = scalarSmoother< Op >( smootherKind, SP( s ), minL, maxL, relax );
+      if ( !sm ) // every other code: SOR
+         sm = std::make_shared< SORSmoother< Op > >( relax );
+      *out = new P2SolverH{ makeGmg< Op, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation >(
+          SP( s ), sm, cgCoarse< Op >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_p2_chebyshev_estimate_radius( hh_p2operator_t op, int level, int maxIter, hh_p2function_t x, hh_p2function_t tmp,
@@ -1072,13 +1092,10 @@ HYTEG_HOST_API int hyteg_host_p2_gmg_create_chebyshev( hh_storage_t s, int minL,
                                                        double lower, int pre, int post, int wcycle, int cgMaxIter, double cgTol, hh_p2solver_t* out )
 {
    return guarded( [&] {
-      using Op     = P2ElementwiseLaplaceOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
-      auto sm      = makeChebyshev< Op >( s, minL, maxL, order, radii, nRadii, upper, lower );
-      auto coarse  = std::make_shared< CGSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) cgMaxIter, cgTol, cgTol );
-      *out         = new P2SolverH{ std::make_shared< GeometricMultigridSolver< Op, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation > >(
-          storage, sm, coarse, std::make_shared< P2toP2QuadraticRestriction >(), std::make_shared< P2toP2QuadraticProlongation >(), (uint_t) minL,
-          (uint_t) maxL, (uint_t) pre, (uint_t) post, 0, wcycle ? CycleType::WCYCLE : CycleType::VCYCLE ) };
+      using Op = P2ElementwiseLaplaceOperator;
+      auto sm  = makeChebyshev< Op >( s, minL, maxL, order, radii, nRadii, upper, lower );
+      *out = new P2SolverH{ makeGmg< Op, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation >(
+          SP( s ), sm, cgCoarse< Op >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_p2_solver_solve( hh_p2solver_t solver, hh_p2operator_t op, hh_p2function_t x, hh_p2function_t b, int level )
@@ -1093,7 +1110,7 @@ HYTEG_HOST_API int hyteg_host_p2_cg_solve( hh_storage_t s, hh_p2operator_t op, h
                                            double tol, int* iterations )
 {
    return guarded( [&] {
-      CGSolver< P2ElementwiseLaplaceOperator > cg( static_cast< StorageH* >( s )->p, (uint_t) level, (uint_t) level, (uint_t) maxIter, tol, tol );
+      CGSolver< P2ElementwiseLaplaceOperator > cg( SP( s ), (uint_t) level, (uint_t) level, (uint_t) maxIter, tol, tol );
       cg.solve( *static_cast< P2OperatorH* >( op )->p, F2( x ), F2( b ), (uint_t) level );
       if ( iterations )
          *iterations = (int) cg.getIterations();
@@ -1103,89 +1120,53 @@ HYTEG_HOST_API int hyteg_host_p2_cg_solve( hh_storage_t s, hh_p2operator_t op, h
 
 
 /* ---- P2-P1 Taylor-Hood Stokes (taylorhood.hpp) ---- */
-namespace {
-struct THFunctionH
-{
-   std::shared_ptr< P2P1TaylorHoodFunction< double > > p;
-   P2FunctionH                                         comp[3]; // aliasing views of the velocity components
-   FunctionH                                           pressure;
-};
-struct THOperatorH
-{
-   std::shared_ptr< P2P1TaylorHoodStokesOperator > p;
-};
-struct THSolverH
-{
-   std::shared_ptr< Solver< P2P1TaylorHoodStokesOperator > > p;
-};
-P2P1TaylorHoodFunction< double >& FT( hh_th_function_t f ) { return *static_cast< THFunctionH* >( f )->p; }
-} // namespace
-
 HYTEG_HOST_API int hyteg_host_th_function_create( hh_storage_t s, const char* name, int minL, int maxL, hh_th_function_t* out )
 {
-   return guarded( [&] {
-      auto* h = new THFunctionH{};
-      h->p    = std::make_shared< P2P1TaylorHoodFunction< double > >( name, static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL );
-      *out    = h;
-   } );
+   return TH::functionCreate( s, name, minL, maxL, out );
 }
-HYTEG_HOST_API int hyteg_host_th_function_destroy( hh_th_function_t f ) { return guarded( [&] { delete static_cast< THFunctionH* >( f ); } ); }
+HYTEG_HOST_API int hyteg_host_th_function_destroy( hh_th_function_t f ) { return TH::destroy< TH::FunctionHandle >( f ); }
 HYTEG_HOST_API int hyteg_host_th_function_velocity( hh_th_function_t f, int k, hh_p2function_t* out )
 {
    return guarded( [&] {
-      auto* h = static_cast< THFunctionH* >( f );
       if ( k < 0 || k > 2 )
          throw std::runtime_error( "th_function_velocity: k = 0, 1, 2" );
-      const P2Function< double >& c = h->p->uvw()[(uint_t) k];
-      h->comp[k].p                  = std::shared_ptr< P2Function< double > >( h->p, const_cast< P2Function< double >* >( &c ) );
-      *out                          = &h->comp[k];
+      *out = TH::velocityView( f, k );
    } );
 }
 HYTEG_HOST_API int hyteg_host_th_function_pressure( hh_th_function_t f, hh_function_t* out )
 {
-   return guarded( [&] {
-      auto* h       = static_cast< THFunctionH* >( f );
-      h->pressure.p = std::shared_ptr< P1Function< double > >( h->p, const_cast< P1Function< double >* >( &h->p->p() ) );
-      *out          = &h->pressure;
-   } );
+   return guarded( [&] { *out = TH::pressureView( f ); } );
 }
 HYTEG_HOST_API int hyteg_host_th_function_assign( hh_th_function_t dst, int n, const double* scalars, const hh_th_function_t* fs, int level, int flag )
 {
-   return guarded( [&] {
-      std::vector< std::reference_wrapper< const P2P1TaylorHoodFunction< double > > > r;
-      for ( int i = 0; i < n; ++i )
-         r.push_back( std::cref( FT( fs[i] ) ) );
-      FT( dst ).assign( std::vector< double >( scalars, scalars + n ), r, (uint_t) level, DoFType( flag ) );
-   } );
+   return TH::functionAssign( dst, n, scalars, fs, level, flag );
 }
 HYTEG_HOST_API int hyteg_host_th_function_interpolate_constant( hh_th_function_t f, double value, int level, int flag )
 {
-   return guarded( [&] { FT( f ).interpolate( value, (uint_t) level, DoFType( flag ) ); } );
+   return guarded( [&] { TH::fn( f ).interpolate( value, (uint_t) level, DoFType( flag ) ); } );
 }
 HYTEG_HOST_API int hyteg_host_th_function_dot( hh_th_function_t a, hh_th_function_t b, int level, int flag, double* out )
 {
-   return guarded( [&] { *out = FT( a ).dotGlobal( FT( b ), (uint_t) level, DoFType( flag ) ); } );
+   return TH::functionDot( a, b, level, flag, out );
 }
 HYTEG_HOST_API int hyteg_host_th_operator_create( hh_storage_t s, int minL, int maxL, hh_th_operator_t* out )
 {
-   return guarded( [&] {
-      *out = new THOperatorH{ std::make_shared< P2P1TaylorHoodStokesOperator >( static_cast< StorageH* >( s )->p, (uint_t) minL, (uint_t) maxL ) };
-   } );
+   return TH::operatorCreate( s, minL, maxL, out );
 }
-HYTEG_HOST_API int hyteg_host_th_operator_destroy( hh_th_operator_t op ) { return guarded( [&] { delete static_cast< THOperatorH* >( op ); } ); }
+HYTEG_HOST_API int hyteg_host_th_operator_destroy( hh_th_operator_t op ) { return TH::destroy< TH::OperatorHandle >( op ); }
 HYTEG_HOST_API int hyteg_host_th_operator_apply( hh_th_operator_t op, hh_th_function_t src, hh_th_function_t dst, int level, int flag )
 {
-   return guarded( [&] { static_cast< THOperatorH* >( op )->p->apply( FT( src ), FT( dst ), (uint_t) level, DoFType( flag ) ); } );
+   return TH::operatorApply( op, src, dst, level, flag );
 }
 // single blocks, for the parity tests: which = 0 div (velocity of src -> pressure of dst), 1 divT (pressure of src -> velocity of dst)
 HYTEG_HOST_API int hyteg_host_th_operator_apply_block( hh_th_operator_t op, int which, hh_th_function_t src, hh_th_function_t dst, int level, int flag )
 {
    return guarded( [&] {
-      auto& A = *static_cast< THOperatorH* >( op )->p;
+      auto& A = TH::op( op );
       if ( which == 0 )
-         A.div.apply( FT( src ).uvw(), FT( dst ).p(), (uint_t) level, DoFType( flag ), Replace );
+         A.div.apply( TH::fn( src ).uvw(), TH::fn( dst ).p(), (uint_t) level, DoFType( flag ), Replace );
       else if ( which == 1 )
-         A.divT.apply( FT( src ).p(), FT( dst ).uvw(), (uint_t) level, DoFType( flag ), Replace );
+         A.divT.apply( TH::fn( src ).p(), TH::fn( dst ).uvw(), (uint_t) level, DoFType( flag ), Replace );
       else
          throw std::runtime_error( "th_operator_apply_block: which = 0 (div) or 1 (divT)" );
    } );
@@ -1199,34 +1180,29 @@ HYTEG_HOST_API int hyteg_host_th_gmg_create( hh_storage_t s, int minL, int maxL,
 {
    return guarded( [&] {
       using Op     = P2P1TaylorHoodStokesOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
+      auto storage = SP( s );
       auto gs      = std::make_shared< GaussSeidelSmoother< P2ConstantLaplaceOperator > >();
-      auto vel     = std::make_shared< TaylorHoodVelocityBlockPreconditioner >( gs );
+      auto vel     = std::make_shared< StokesVelocityBlockBlockDiagonalPreconditioner< Op > >( storage, gs );
       auto uzawa   = std::make_shared< UzawaSmoother< Op > >( storage, vel, (uint_t) minL, (uint_t) maxL, uzawa_relax );
-      auto prec    = std::make_shared< StokesPressureBlockPreconditioner< Op, P1LumpedInvMassOperator > >( storage, (uint_t) minL, (uint_t) minL );
-      auto coarse  = std::make_shared< MinResSolver< Op > >( storage, (uint_t) minL, (uint_t) minL, (uint_t) coarse_max_iter, coarse_rel_tol, 1e-16, prec );
-      *out = new THSolverH{ std::make_shared< GeometricMultigridSolver< Op, P2P1StokesToP2P1StokesRestriction, P2P1StokesToP2P1StokesProlongation > >(
-          storage, uzawa, coarse, std::make_shared< P2P1StokesToP2P1StokesRestriction >( true ), std::make_shared< P2P1StokesToP2P1StokesProlongation >(),
-          (uint_t) minL, (uint_t) maxL, (uint_t) pre, (uint_t) post, (uint_t) increment ) };
+      auto coarse  = TH::pressureMinres( storage, minL, minL, coarse_max_iter, coarse_rel_tol );
+      *out         = new TH::SolverHandle{ makeGmg< Op, P2P1StokesToP2P1StokesRestriction, P2P1StokesToP2P1StokesProlongation >(
+          storage, uzawa, coarse, minL, maxL, pre, post, increment, CycleType::VCYCLE, true ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_th_minres_create( hh_storage_t s, int minL, int maxL, int max_iter, double rel_tol, hh_th_solver_t* out )
 {
    return guarded( [&] {
-      using Op     = P2P1TaylorHoodStokesOperator;
-      auto storage = static_cast< StorageH* >( s )->p;
-      auto prec    = std::make_shared< StokesPressureBlockPreconditioner< Op, P1LumpedInvMassOperator > >( storage, (uint_t) minL, (uint_t) maxL );
-      *out = new THSolverH{ std::make_shared< MinResSolver< Op > >( storage, (uint_t) minL, (uint_t) maxL, (uint_t) max_iter, rel_tol, 1e-16, prec ) };
+      *out = new TH::SolverHandle{ TH::pressureMinres( SP( s ), minL, maxL, max_iter, rel_tol ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_th_solver_solve( hh_th_solver_t solver, hh_th_operator_t op, hh_th_function_t x, hh_th_function_t b, int level )
 {
-   return guarded( [&] { static_cast< THSolverH* >( solver )->p->solve( *static_cast< THOperatorH* >( op )->p, FT( x ), FT( b ), (uint_t) level ); } );
+   return TH::solverSolve( solver, op, x, b, level );
 }
-HYTEG_HOST_API int hyteg_host_th_solver_destroy( hh_th_solver_t solver ) { return guarded( [&] { delete static_cast< THSolverH* >( solver ); } ); }
+HYTEG_HOST_API int hyteg_host_th_solver_destroy( hh_th_solver_t solver ) { return TH::destroy< TH::SolverHandle >( solver ); }
 HYTEG_HOST_API int hyteg_host_th_project_pressure_mean( hh_th_function_t f, int level )
 {
-   return guarded( [&] { projectMean( FT( f ).p(), (uint_t) level ); } );
+   return guarded( [&] { projectMean( TH::fn( f ).p(), (uint_t) level ); } );
 }
 // the 10 x 10 element matrix (FEniCS ordering) a mixed block hands to the P2 kernel: which = 0 div (edge rows zero), 1 divT (edge
 // columns zero), component k, tetrahedron coords[4][3] -- for the pins against the reference's FEniCS forms

@@ -51,6 +51,20 @@ class JacobiPreconditioner : public Solver< OperatorType >
    DoFType      flag_;
 };
 
+// dst = / += scale * src pointwise: the apply of the operators whose stencil is a centre weight only (P1LumpedInvMassOperator
+// below, P1PSPGInvDiagOperator of stokes.hpp).  Add goes through the operator's scratch function tmp.
+inline void applyPointwiseScaling( const P1Function< double >& scale, const P1Function< double >& tmp, const P1Function< double >& src,
+                                   const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType )
+{
+   if ( updateType == Replace )
+   {
+      dst.multElementwise( { scale, src }, level, flag );
+      return;
+   }
+   tmp.multElementwise( { scale, src }, level, flag );
+   dst.add( { 1.0 }, { tmp }, level, flag );
+}
+
 // P1LumpedInvMassOperator = P1ConstantOperator< mass form, Diagonal = false, Lumped = true, InvertDiagonal = true >
 // (P1ConstantOperator.hpp:197-202): the stencil's row sum on the centre, inverted (P1Operator.hpp:2128-2158; on points shared
 // between macro-cells the inverse of the SUM of the cells' row sums).  = pointwise multiplication with 1 / ( M 1 ).
@@ -80,13 +94,7 @@ class P1LumpedInvMassOperator
    }
    void apply( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
    {
-      if ( updateType == Replace )
-      {
-         dst.multElementwise( { invLumped_, src }, level, flag );
-         return;
-      }
-      tmp_.multElementwise( { invLumped_, src }, level, flag );
-      dst.add( { 1.0 }, { tmp_ }, level, flag );
+      applyPointwiseScaling( invLumped_, tmp_, src, dst, level, flag, updateType );
    }
    const P1Function< double >& getInverseLumpedMass() const { return invLumped_; }
 

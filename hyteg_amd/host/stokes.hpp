@@ -1,11 +1,13 @@
 // stokes.hpp -- part of the C++ host layer above the C-ABI (see hyteg_host.hpp for the data model).
-// The stabilised P1-P1 Stokes operator as a composition of P1 constant-stencil operators, its Uzawa smoother and
-// grid transfer: src/mixed_operator/P1P1StokesOperator.hpp, VectorLaplaceOperator.hpp, VectorToScalarOperator.hpp,
+// The Stokes composition layer, written once for both discretisations: the composite functions, the block operators, the
+// Stokes operator, its Uzawa smoother and grid transfer are templates over the velocity's scalar function / operator /
+// transfer; the pressure is always P1.  This file instantiates them for the stabilised P1-P1 operator (every block a
+// P1ConstantOperator< Form > of p1operator.hpp: the same 15-point stencil kernels as for the Laplace operator, with other
+// weights); taylorhood.hpp instantiates them for P2-P1 Taylor-Hood.
+// src/mixed_operator/P1P1StokesOperator.hpp, VectorLaplaceOperator.hpp, VectorToScalarOperator.hpp,
 // ScalarToVectorOperator.hpp, src/hyteg/composites/P1StokesFunction.hpp, src/hyteg/solvers/UzawaSmoother.hpp,
 // src/hyteg/solvers/preconditioners/stokes/StokesVelocityBlockBlockDiagonalPreconditioner.hpp,
 // src/hyteg/gridtransferoperators/P1P1StokesToP1P1Stokes{Restriction,Prolongation}.hpp.
-// Every block is a P1ConstantOperator< Form > (p1operator.hpp) with another form: the device work is the same 15-point
-// stencil kernels as for the Laplace operator, with other weights.
 #pragma once
 
 #include "minres.hpp"
@@ -23,21 +25,24 @@ using P1DivTzOperator = P1ConstantOperator< forms::P1DivTForm< 2 > >;
 using P1PSPGOperator  = P1ConstantOperator< forms::P1PSPGForm >;
 
 // =====================================================================================================
-// P1VectorFunction (src/hyteg/p1functionspace/P1VectorFunction.hpp), three components in 3D
+// Composite functions
 // =====================================================================================================
-template < typename ValueType >
-class P1VectorFunction
+// P1VectorFunction (src/hyteg/p1functionspace/P1VectorFunction.hpp) / P2VectorFunction
+// (src/hyteg/p2functionspace/P2VectorFunction.hpp): three components in 3D
+template < class ScalarFunction >
+class VectorFunction
 {
  public:
-   P1VectorFunction( const std::string& name, const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
+   using ValueType = typename ScalarFunction::valueType;
+   using Refs      = std::vector< std::reference_wrapper< const VectorFunction > >;
+   VectorFunction( const std::string& name, const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
    {
-      static const char* suffix[3] = { "_u", "_v", "_w" };
+      static const char* suffix[3] = { "_u", "_v", "_w" }; // they name timing-tree entries
       for ( int k = 0; k < 3; ++k )
-         comp_.push_back( std::make_shared< P1Function< ValueType > >( name + suffix[k], storage, minLevel, maxLevel ) );
+         comp_.push_back( std::make_shared< ScalarFunction >( name + suffix[k], storage, minLevel, maxLevel ) );
    }
-   uint_t                         getDimension() const { return 3; }
-   const P1Function< ValueType >& operator[]( uint_t k ) const { return *comp_.at( k ); }
-   const P1Function< ValueType >& component( uint_t k ) const { return *comp_.at( k ); }
+   uint_t                getDimension() const { return 3; }
+   const ScalarFunction& operator[]( uint_t k ) const { return *comp_.at( k ); }
 
    void interpolate( ValueType constant, uint_t level, DoFType flag = All ) const
    {
@@ -49,23 +54,17 @@ class P1VectorFunction
       for ( uint_t k = 0; k < 3; ++k )
          comp_[k]->interpolate( expr.at( k ), level, flag );
    }
-   void assign( const std::vector< ValueType >&                                                        scalars,
-                const std::vector< std::reference_wrapper< const P1VectorFunction< ValueType > > >& functions,
-                uint_t                                                                               level,
-                DoFType                                                                              flag = All ) const
+   void assign( const std::vector< ValueType >& scalars, const Refs& functions, uint_t level, DoFType flag = All ) const
    {
       for ( uint_t k = 0; k < 3; ++k )
          comp_[k]->assign( scalars, componentRefs( functions, k ), level, flag );
    }
-   void add( const std::vector< ValueType >&                                                        scalars,
-             const std::vector< std::reference_wrapper< const P1VectorFunction< ValueType > > >& functions,
-             uint_t                                                                               level,
-             DoFType                                                                              flag = All ) const
+   void add( const std::vector< ValueType >& scalars, const Refs& functions, uint_t level, DoFType flag = All ) const
    {
       for ( uint_t k = 0; k < 3; ++k )
          comp_[k]->add( scalars, componentRefs( functions, k ), level, flag );
    }
-   ValueType dotGlobal( const P1VectorFunction< ValueType >& rhs, uint_t level, DoFType flag = All ) const
+   ValueType dotGlobal( const VectorFunction& rhs, uint_t level, DoFType flag = All ) const
    {
       ValueType s = 0;
       for ( uint_t k = 0; k < 3; ++k )
@@ -74,80 +73,77 @@ class P1VectorFunction
    }
 
  private:
-   static std::vector< std::reference_wrapper< const P1Function< ValueType > > >
-       componentRefs( const std::vector< std::reference_wrapper< const P1VectorFunction< ValueType > > >& functions, uint_t k )
+   static std::vector< std::reference_wrapper< const ScalarFunction > > componentRefs( const Refs& functions, uint_t k )
    {
-      std::vector< std::reference_wrapper< const P1Function< ValueType > > > r;
+      std::vector< std::reference_wrapper< const ScalarFunction > > r;
       for ( const auto& f : functions )
          r.push_back( std::cref( f.get()[k] ) );
       return r;
    }
-   std::vector< std::shared_ptr< P1Function< ValueType > > > comp_;
+   std::vector< std::shared_ptr< ScalarFunction > > comp_;
 };
-
-// =====================================================================================================
-// P1StokesFunction (composites/P1StokesFunction.hpp): velocity with the storage's boundary types (create0123BC),
-// pressure with createAllInnerBC
-// =====================================================================================================
 template < typename ValueType >
-class P1StokesFunction
+using P1VectorFunction = VectorFunction< P1Function< ValueType > >;
+
+// P1StokesFunction (composites/P1StokesFunction.hpp) / P2P1TaylorHoodFunction (composites/P2P1TaylorHoodFunction.hpp):
+// velocity with the storage's boundary types (create0123BC), P1 pressure with createAllInnerBC
+template < class VelocityScalarFunction >
+class StokesFunction
 {
  public:
-   using valueType = ValueType;
-   P1StokesFunction( const std::string& name, const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
+   using valueType = typename VelocityScalarFunction::valueType;
+   using ValueType = valueType;
+   using Refs      = std::vector< std::reference_wrapper< const StokesFunction > >;
+   StokesFunction( const std::string& name, const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
    : uvw_( name + "_uvw", storage, minLevel, maxLevel )
    , p_( name + "_p", storage, minLevel, maxLevel )
    {
       p_.setBoundaryConditionAllInner();
    }
-   const P1VectorFunction< ValueType >& uvw() const { return uvw_; }
-   const P1Function< ValueType >&       p() const { return p_; }
-   uint64_t                             uid() const { return p_.uid(); }
+   const VectorFunction< VelocityScalarFunction >& uvw() const { return uvw_; }
+   const P1Function< ValueType >&                  p() const { return p_; }
+   uint64_t                                        uid() const { return p_.uid(); }
 
    void interpolate( ValueType constant, uint_t level, DoFType flag = All ) const
    {
       uvw_.interpolate( constant, level, flag );
       p_.interpolate( constant, level, flag );
    }
-   void assign( const std::vector< ValueType >&                                                        scalars,
-                const std::vector< std::reference_wrapper< const P1StokesFunction< ValueType > > >& functions,
-                uint_t                                                                               level,
-                DoFType                                                                              flag = All ) const
+   void assign( const std::vector< ValueType >& scalars, const Refs& functions, uint_t level, DoFType flag = All ) const
    {
-      std::vector< std::reference_wrapper< const P1VectorFunction< ValueType > > > v;
-      std::vector< std::reference_wrapper< const P1Function< ValueType > > >       q;
-      for ( const auto& f : functions )
-      {
-         v.push_back( std::cref( f.get().uvw() ) );
-         q.push_back( std::cref( f.get().p() ) );
-      }
-      uvw_.assign( scalars, v, level, flag );
-      p_.assign( scalars, q, level, flag );
+      const auto parts = split( functions );
+      uvw_.assign( scalars, parts.first, level, flag );
+      p_.assign( scalars, parts.second, level, flag );
    }
-   void add( const std::vector< ValueType >&                                                        scalars,
-             const std::vector< std::reference_wrapper< const P1StokesFunction< ValueType > > >& functions,
-             uint_t                                                                               level,
-             DoFType                                                                              flag = All ) const
+   void add( const std::vector< ValueType >& scalars, const Refs& functions, uint_t level, DoFType flag = All ) const
    {
-      std::vector< std::reference_wrapper< const P1VectorFunction< ValueType > > > v;
-      std::vector< std::reference_wrapper< const P1Function< ValueType > > >       q;
-      for ( const auto& f : functions )
-      {
-         v.push_back( std::cref( f.get().uvw() ) );
-         q.push_back( std::cref( f.get().p() ) );
-      }
-      uvw_.add( scalars, v, level, flag );
-      p_.add( scalars, q, level, flag );
+      const auto parts = split( functions );
+      uvw_.add( scalars, parts.first, level, flag );
+      p_.add( scalars, parts.second, level, flag );
    }
-   ValueType dotGlobal( const P1StokesFunction< ValueType >& rhs, uint_t level, DoFType flag = All ) const
+   ValueType dotGlobal( const StokesFunction& rhs, uint_t level, DoFType flag = All ) const
    {
       return uvw_.dotGlobal( rhs.uvw(), level, flag ) + p_.dotGlobal( rhs.p(), level, flag );
    }
 
  private:
-   P1VectorFunction< ValueType > uvw_;
-   P1Function< ValueType >       p_;
+   using PressureRefs = std::vector< std::reference_wrapper< const P1Function< ValueType > > >;
+   // the velocities and the pressures of a list of functions
+   static std::pair< typename VectorFunction< VelocityScalarFunction >::Refs, PressureRefs > split( const Refs& functions )
+   {
+      std::pair< typename VectorFunction< VelocityScalarFunction >::Refs, PressureRefs > parts;
+      for ( const auto& f : functions )
+      {
+         parts.first.push_back( std::cref( f.get().uvw() ) );
+         parts.second.push_back( std::cref( f.get().p() ) );
+      }
+      return parts;
+   }
+   VectorFunction< VelocityScalarFunction > uvw_;
+   P1Function< ValueType >                  p_;
 };
+template < typename ValueType >
+using P1StokesFunction = StokesFunction< P1Function< ValueType > >;
 
 // vertexdof::projectMean (VertexDoFFunction.hpp:586-592): subtract the mean over ALL DoFs (every shared DoF counted once)
 inline void projectMean( const P1Function< double >& pressure, uint_t level )
@@ -163,79 +159,79 @@ inline void projectMean( const P1Function< double >& pressure, uint_t level )
 // =====================================================================================================
 // Block operators
 // =====================================================================================================
-// VectorLaplaceOperator.hpp:122  P1ConstantVectorLaplaceOperator: block diagonal of one scalar Laplace operator
-class P1ConstantVectorLaplaceOperator
+// VectorLaplaceOperator.hpp:122  P1ConstantVectorLaplaceOperator / P2ConstantVectorLaplaceOperator: block diagonal of one
+// scalar Laplace operator
+template < class ScalarOperator >
+class VectorLaplaceOperator
 {
  public:
-   using srcType = P1VectorFunction< double >;
-   using dstType = P1VectorFunction< double >;
-   P1ConstantVectorLaplaceOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
-   : lapl_( std::make_shared< P1ConstantLaplaceOperator >( storage, minLevel, maxLevel ) )
+   using srcType = VectorFunction< typename ScalarOperator::srcType >;
+   using dstType = srcType;
+   VectorLaplaceOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
+   : lapl_( storage, minLevel, maxLevel )
    {
-      lapl_->computeInverseDiagonalOperatorValues(); // Jacobi-type velocity smoothers ask the scalar operator for it
+      lapl_.computeInverseDiagonalOperatorValues(); // Jacobi-type velocity smoothers ask the scalar operator for it
    }
    void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
    {
       for ( uint_t k = 0; k < 3; ++k )
-         lapl_->apply( src[k], dst[k], level, flag, updateType );
+         lapl_.apply( src[k], dst[k], level, flag, updateType );
    }
-   const P1ConstantLaplaceOperator&                   getSubOperator( uint_t, uint_t ) const { return *lapl_; }
-   std::shared_ptr< const P1ConstantLaplaceOperator > scalar() const { return lapl_; }
+   const ScalarOperator& getSubOperator( uint_t, uint_t ) const { return lapl_; }
 
  private:
-   std::shared_ptr< P1ConstantLaplaceOperator > lapl_;
+   ScalarOperator lapl_;
 };
+using P1ConstantVectorLaplaceOperator = VectorLaplaceOperator< P1ConstantLaplaceOperator >;
 
-// VectorToScalarOperator.hpp: P1ConstantDivOperator = ( Divx, Divy, Divz ): first component with the caller's update type,
-// the others added (:63-71)
-class P1ConstantDivOperator
+// VectorToScalarOperator.hpp: ( X, Y, Z ): first component with the caller's update type, the others added (:63-71)
+template < class X, class Y, class Z >
+class VectorToScalarOperator
 {
  public:
-   P1ConstantDivOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
+   VectorToScalarOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
    : x_( storage, minLevel, maxLevel )
    , y_( storage, minLevel, maxLevel )
    , z_( storage, minLevel, maxLevel )
    {}
-   void apply( const P1VectorFunction< double >& src, const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
+   void apply( const VectorFunction< typename X::srcType >& src, const typename X::dstType& dst, uint_t level, DoFType flag,
+               UpdateType updateType = Replace ) const
    {
       x_.apply( src[0], dst, level, flag, updateType );
       y_.apply( src[1], dst, level, flag, Add );
       z_.apply( src[2], dst, level, flag, Add );
    }
-   const P1DivxOperator& x() const { return x_; }
-   const P1DivyOperator& y() const { return y_; }
-   const P1DivzOperator& z() const { return z_; }
 
  private:
-   P1DivxOperator x_;
-   P1DivyOperator y_;
-   P1DivzOperator z_;
+   X x_;
+   Y y_;
+   Z z_;
 };
-
-// ScalarToVectorOperator.hpp: P1ConstantDivTOperator = ( DivTx, DivTy, DivTz )^T
-class P1ConstantDivTOperator
+// ScalarToVectorOperator.hpp: ( X, Y, Z )^T
+template < class X, class Y, class Z >
+class ScalarToVectorOperator
 {
  public:
-   P1ConstantDivTOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
+   ScalarToVectorOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
    : x_( storage, minLevel, maxLevel )
    , y_( storage, minLevel, maxLevel )
    , z_( storage, minLevel, maxLevel )
    {}
-   void apply( const P1Function< double >& src, const P1VectorFunction< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
+   void apply( const typename X::srcType& src, const VectorFunction< typename X::dstType >& dst, uint_t level, DoFType flag,
+               UpdateType updateType = Replace ) const
    {
       x_.apply( src, dst[0], level, flag, updateType );
       y_.apply( src, dst[1], level, flag, updateType );
       z_.apply( src, dst[2], level, flag, updateType );
    }
-   const P1DivTxOperator& x() const { return x_; }
-   const P1DivTyOperator& y() const { return y_; }
-   const P1DivTzOperator& z() const { return z_; }
 
  private:
-   P1DivTxOperator x_;
-   P1DivTyOperator y_;
-   P1DivTzOperator z_;
+   X x_;
+   Y y_;
+   Z z_;
 };
+using P1ConstantDivOperator  = VectorToScalarOperator< P1DivxOperator, P1DivyOperator, P1DivzOperator >;
+using P1ConstantDivTOperator = ScalarToVectorOperator< P1DivTxOperator, P1DivTyOperator, P1DivTzOperator >;
 
 // P1PSPGInvDiagOperator (P1ConstantOperator.hpp:206-210: Diagonal, InvertDiagonal): the stencil keeps only the centre
 // weight, inverted (P1Operator.hpp:2149-2158; on shared points the inverse of the SUM over the neighbour cells, :2110-2117)
@@ -252,14 +248,7 @@ class P1PSPGInvDiagOperator
    }
    void apply( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
    {
-      const auto& invDiag = *pspg_.getInverseDiagonalValues();
-      if ( updateType == Replace )
-      {
-         dst.multElementwise( { invDiag, src }, level, flag );
-         return;
-      }
-      tmp_.multElementwise( { invDiag, src }, level, flag );
-      dst.add( { 1.0 }, { tmp_ }, level, flag );
+      applyPointwiseScaling( *pspg_.getInverseDiagonalValues(), tmp_, src, dst, level, flag, updateType );
    }
 
  private:
@@ -267,16 +256,21 @@ class P1PSPGInvDiagOperator
    P1Function< double > tmp_;
 };
 
-// P1P1StokesOperator.hpp:32-99
-class P1P1StokesOperator
+// P1P1StokesOperator.hpp:32-99 / P2P1TaylorHoodStokesOperator.hpp:34-110: the velocity's scalar Laplace operator on every
+// component, the div and divT blocks, and the PSPG block -- applied by a stabilised operator only; its members serve the Uzawa
+// smoother of both as Schur-complement approximation
+template < class VelocityOperator, class DivOperator, class DivTOperator, bool HasPspgBlock >
+class StokesOperator
 {
  public:
-   using srcType            = P1StokesFunction< double >;
-   using dstType            = P1StokesFunction< double >;
-   using VelocityOperator_T = P1ConstantLaplaceOperator;
-   static constexpr bool hasPspgBlock = true; // has_pspg_block< P1P1StokesOperator >, P1P1StokesOperator.hpp:95
+   using srcType            = StokesFunction< typename VelocityOperator::srcType >;
+   using dstType            = srcType;
+   using VelocityOperator_T = VelocityOperator;
+   // has_pspg_block< P1P1StokesOperator > (P1P1StokesOperator.hpp:95); no specialisation for the Taylor-Hood operator
+   // (StokesOperatorTraits.hpp:25-29)
+   static constexpr bool hasPspgBlock = HasPspgBlock;
 
-   P1P1StokesOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
+   StokesOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
    : lapl( storage, minLevel, maxLevel )
    , div( storage, minLevel, maxLevel )
    , divT( storage, minLevel, maxLevel )
@@ -285,30 +279,32 @@ class P1P1StokesOperator
    , storage_( storage )
    {}
 
-   // :51-64
+   // P1P1StokesOperator.hpp:51-64, P2P1TaylorHoodStokesOperator.hpp:55-64
    void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flag, UpdateType = Replace ) const
    {
       if ( &src == &dst )
-         throw std::runtime_error( "P1P1StokesOperator::apply: src and dst must differ" );
+         throw std::runtime_error( "StokesOperator::apply: src and dst must differ" );
       lapl.apply( src.uvw(), dst.uvw(), level, flag, Replace );
       divT.apply( src.p(), dst.uvw(), level, flag, Add );
       div.apply( src.uvw(), dst.p(), level, flag, Replace );
-      pspg.apply( src.p(), dst.p(), level, flag, Add );
+      if constexpr ( hasPspgBlock )
+         pspg.apply( src.p(), dst.p(), level, flag, Add );
    }
-   const P1ConstantLaplaceOperator&    getA() const { return lapl.getSubOperator( 0, 0 ); }
+   const VelocityOperator&             getA() const { return lapl.getSubOperator( 0, 0 ); }
    std::shared_ptr< PrimitiveStorage > getStorage() const { return storage_; }
    uint64_t                            uid() const { return uid_; }
 
-   P1ConstantVectorLaplaceOperator lapl;
-   P1ConstantDivOperator           div;
-   P1ConstantDivTOperator          divT;
-   P1PSPGOperator                  pspg;
-   P1PSPGInvDiagOperator           pspg_inv_diag_;
+   VectorLaplaceOperator< VelocityOperator > lapl;
+   DivOperator                               div;
+   DivTOperator                              divT;
+   P1PSPGOperator                            pspg;
+   P1PSPGInvDiagOperator                     pspg_inv_diag_;
 
  private:
    std::shared_ptr< PrimitiveStorage > storage_;
    uint64_t                            uid_ = nextUid();
 };
+using P1P1StokesOperator = StokesOperator< P1ConstantLaplaceOperator, P1ConstantDivOperator, P1ConstantDivTOperator, true >;
 
 // =====================================================================================================
 // Smoothers and grid transfer
@@ -326,7 +322,8 @@ class StokesVelocityBlockBlockDiagonalPreconditioner : public Solver< OperatorTy
    void solve( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level ) override
    {
       // the components are independent: one solveMany instead of a loop, so that a smoother can sweep them with shared launches
-      std::vector< std::reference_wrapper< const P1Function< double > > > xs, bs;
+      // (the P1 SOR smoothers do; every other smoother's solveMany is the loop of solve() calls)
+      std::vector< std::reference_wrapper< const typename OperatorType::VelocityOperator_T::srcType > > xs, bs;
       for ( uint_t k = 0; k < x.uvw().getDimension(); ++k )
       {
          xs.push_back( std::cref( x.uvw()[k] ) );
@@ -391,45 +388,55 @@ class UzawaSmoother : public Solver< OperatorType >
    FunctionType                              r_;
 };
 
-// P1P1StokesToP1P1StokesRestriction.hpp:34-58 / ...Prolongation.hpp
-class P1P1StokesToP1P1StokesRestriction
+// P1P1StokesToP1P1StokesRestriction.hpp:34-58 / ...Prolongation.hpp, P2P1StokesToP2P1StokesRestriction.hpp / ...Prolongation.hpp:
+// the velocity's transfer on every component, the linear P1 transfer on the pressure
+template < class VelocityRestriction >
+class StokesRestriction
 {
  public:
-   explicit P1P1StokesToP1P1StokesRestriction( bool projectMeanAfterRestriction = false )
+   explicit StokesRestriction( bool projectMeanAfterRestriction = false )
    : projectMean_( projectMeanAfterRestriction )
    {}
-   void restrict( const P1StokesFunction< double >& f, uint_t sourceLevel, DoFType flag ) const
+   template < class FunctionType >
+   void restrict( const FunctionType& f, uint_t sourceLevel, DoFType flag ) const
    {
       for ( uint_t k = 0; k < 3; ++k )
-         r_.restrict( f.uvw()[k], sourceLevel, flag );
-      r_.restrict( f.p(), sourceLevel, flag );
+         rv_.restrict( f.uvw()[k], sourceLevel, flag );
+      rp_.restrict( f.p(), sourceLevel, flag );
       if ( projectMean_ )
          projectMean( f.p(), sourceLevel - 1 );
    }
 
  private:
-   P1toP1LinearRestriction r_;
+   VelocityRestriction     rv_;
+   P1toP1LinearRestriction rp_;
    bool                    projectMean_;
 };
-class P1P1StokesToP1P1StokesProlongation
+template < class VelocityProlongation >
+class StokesProlongation
 {
  public:
-   void prolongate( const P1StokesFunction< double >& f, uint_t sourceLevel, DoFType flag ) const
+   template < class FunctionType >
+   void prolongate( const FunctionType& f, uint_t sourceLevel, DoFType flag ) const
    {
       for ( uint_t k = 0; k < 3; ++k )
-         p_.prolongate( f.uvw()[k], sourceLevel, flag );
-      p_.prolongate( f.p(), sourceLevel, flag );
+         pv_.prolongate( f.uvw()[k], sourceLevel, flag );
+      pp_.prolongate( f.p(), sourceLevel, flag );
    }
-   void prolongateAndAdd( const P1StokesFunction< double >& f, uint_t sourceLevel, DoFType flag ) const
+   template < class FunctionType >
+   void prolongateAndAdd( const FunctionType& f, uint_t sourceLevel, DoFType flag ) const
    {
       for ( uint_t k = 0; k < 3; ++k )
-         p_.prolongateAndAdd( f.uvw()[k], sourceLevel, flag );
-      p_.prolongateAndAdd( f.p(), sourceLevel, flag );
+         pv_.prolongateAndAdd( f.uvw()[k], sourceLevel, flag );
+      pp_.prolongateAndAdd( f.p(), sourceLevel, flag );
    }
 
  private:
-   P1toP1LinearProlongation p_;
+   VelocityProlongation     pv_;
+   P1toP1LinearProlongation pp_;
 };
+using P1P1StokesToP1P1StokesRestriction  = StokesRestriction< P1toP1LinearRestriction >;
+using P1P1StokesToP1P1StokesProlongation = StokesProlongation< P1toP1LinearProlongation >;
 
 // Coarse-grid solver of the saddle-point system, standing in for PETScLUSolver< P1P1StokesOperator >
 // (src/hyteg/petsc/PETScLUSolver.hpp; the convergence tests use it on level 2): the level's operator is assembled into a

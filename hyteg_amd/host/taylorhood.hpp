@@ -1,7 +1,9 @@
 // taylorhood.hpp -- part of the C++ host layer above the C-ABI (see hyteg_host.hpp for the data model).
-// P2-P1 Taylor-Hood Stokes composition (BASELINE config 5's "P2-P1 Stokes block operator"):
-//   P2P1TaylorHoodFunction            src/hyteg/composites/P2P1TaylorHoodFunction.hpp
+// P2-P1 Taylor-Hood Stokes composition (BASELINE config 5's "P2-P1 Stokes block operator"): the two mixed forms and the
+// P2 -> P1 / P1 -> P2 operators are written here; everything composed of them is the templates of stokes.hpp instantiated with a
+// P2 velocity (the aliases at the end of this file).
 //   P2ToP1 / P1ToP2 mixed operators   src/mixed_operator/P2ToP1ConstantOperator.hpp:47-101, P1ToP2ConstantOperator.hpp
+//   P2P1TaylorHoodFunction            src/hyteg/composites/P2P1TaylorHoodFunction.hpp
 //   P2P1TaylorHoodStokesOperator      src/mixed_operator/P2P1TaylorHoodStokesOperator.hpp:34-110
 //   transfer                          src/hyteg/gridtransferoperators/P2P1StokesToP2P1Stokes{Restriction,Prolongation}.hpp
 // No new device code: a P2 -> P1 block is the P2 apply kernel asked for its vertex-DoF rows only, with an element matrix whose
@@ -91,12 +93,14 @@ class P2ToP1Operator : public P2ElementwiseOperator< Form >
    using Base = P2ElementwiseOperator< Form >;
 
  public:
+   using srcType = P2Function< double >;
+   using dstType = P1Function< double >;
    P2ToP1Operator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
    : Base( storage, minLevel, maxLevel )
    , tmp_( "p2_to_p1_tmp", storage, minLevel, maxLevel )
    , tmpP1_( "p2_to_p1_tmp_p1", storage, minLevel, maxLevel )
    {}
-   void apply( const P2Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flagIn, UpdateType updateType = Replace ) const
+   void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flagIn, UpdateType updateType = Replace ) const
    {
       const DoFType flag = dst.effectiveFlag( flagIn );
       tmpP1_.setBoundaryConditionAllInner( dst.hasAllInnerBoundaryCondition() );
@@ -128,12 +132,14 @@ class P1ToP2Operator : public P2ElementwiseOperator< Form >
    using Base = P2ElementwiseOperator< Form >;
 
  public:
+   using srcType = P1Function< double >;
+   using dstType = P2Function< double >;
    P1ToP2Operator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
    : Base( storage, minLevel, maxLevel )
    , tmp_( "p1_to_p2_tmp", storage, minLevel, maxLevel )
    , zero_( "p1_to_p2_zero", storage, minLevel, maxLevel )
    {}
-   void apply( const P1Function< double >& src, const P2Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
+   void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
    {
       std::vector< double* >       dv, de;
       std::vector< const double* > sv, se;
@@ -159,275 +165,26 @@ class P1ToP2Operator : public P2ElementwiseOperator< Form >
    P2Function< double > zero_; // zero edge-DoF source (the element matrix has zero edge columns; the kernel still reads the array)
 };
 
+// The composition of stokes.hpp with a P2 velocity:
 // P2VectorFunction (src/hyteg/p2functionspace/P2VectorFunction.hpp), three components
 template < typename ValueType >
-class P2VectorFunction
-{
- public:
-   P2VectorFunction( const std::string& name, const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
-   {
-      static const char* suffix[3] = { "_u", "_v", "_w" };
-      for ( int k = 0; k < 3; ++k )
-         comp_.push_back( std::make_shared< P2Function< ValueType > >( name + suffix[k], storage, minLevel, maxLevel ) );
-   }
-   uint_t                         getDimension() const { return 3; }
-   const P2Function< ValueType >& operator[]( uint_t k ) const { return *comp_.at( k ); }
-
-   void interpolate( ValueType constant, uint_t level, DoFType flag = All ) const
-   {
-      for ( auto& c : comp_ )
-         c->interpolate( constant, level, flag );
-   }
-   void interpolate( const std::vector< std::function< ValueType( const Point3D& ) > >& expr, uint_t level, DoFType flag = All ) const
-   {
-      for ( uint_t k = 0; k < 3; ++k )
-         comp_[k]->interpolate( expr.at( k ), level, flag );
-   }
-   void assign( const std::vector< ValueType >& scalars, const std::vector< std::reference_wrapper< const P2VectorFunction< ValueType > > >& functions,
-                uint_t level, DoFType flag = All ) const
-   {
-      for ( uint_t k = 0; k < 3; ++k )
-         comp_[k]->assign( scalars, componentRefs( functions, k ), level, flag );
-   }
-   void add( const std::vector< ValueType >& scalars, const std::vector< std::reference_wrapper< const P2VectorFunction< ValueType > > >& functions,
-             uint_t level, DoFType flag = All ) const
-   {
-      for ( uint_t k = 0; k < 3; ++k )
-         comp_[k]->add( scalars, componentRefs( functions, k ), level, flag );
-   }
-   ValueType dotGlobal( const P2VectorFunction< ValueType >& rhs, uint_t level, DoFType flag = All ) const
-   {
-      ValueType s = 0;
-      for ( uint_t k = 0; k < 3; ++k )
-         s += comp_[k]->dotGlobal( rhs[k], level, flag );
-      return s;
-   }
-
- private:
-   static std::vector< std::reference_wrapper< const P2Function< ValueType > > >
-       componentRefs( const std::vector< std::reference_wrapper< const P2VectorFunction< ValueType > > >& functions, uint_t k )
-   {
-      std::vector< std::reference_wrapper< const P2Function< ValueType > > > r;
-      for ( const auto& f : functions )
-         r.push_back( std::cref( f.get()[k] ) );
-      return r;
-   }
-   std::vector< std::shared_ptr< P2Function< ValueType > > > comp_;
-};
-
+using P2VectorFunction = VectorFunction< P2Function< ValueType > >;
 // P2P1TaylorHoodFunction (composites/P2P1TaylorHoodFunction.hpp): P2 velocity with the storage's boundary types, P1 pressure with
 // createAllInnerBC
 template < typename ValueType >
-class P2P1TaylorHoodFunction
-{
- public:
-   using valueType = ValueType;
-   P2P1TaylorHoodFunction( const std::string& name, const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
-   : uvw_( name + "_uvw", storage, minLevel, maxLevel )
-   , p_( name + "_p", storage, minLevel, maxLevel )
-   {
-      p_.setBoundaryConditionAllInner();
-   }
-   const P2VectorFunction< ValueType >& uvw() const { return uvw_; }
-   const P1Function< ValueType >&       p() const { return p_; }
-   uint64_t                             uid() const { return p_.uid(); }
-
-   void interpolate( ValueType constant, uint_t level, DoFType flag = All ) const
-   {
-      uvw_.interpolate( constant, level, flag );
-      p_.interpolate( constant, level, flag );
-   }
-   void assign( const std::vector< ValueType >&                                                              scalars,
-                const std::vector< std::reference_wrapper< const P2P1TaylorHoodFunction< ValueType > > >& functions, uint_t level,
-                DoFType flag = All ) const
-   {
-      std::vector< std::reference_wrapper< const P2VectorFunction< ValueType > > > v;
-      std::vector< std::reference_wrapper< const P1Function< ValueType > > >       q;
-      for ( const auto& f : functions )
-         v.push_back( std::cref( f.get().uvw() ) ), q.push_back( std::cref( f.get().p() ) );
-      uvw_.assign( scalars, v, level, flag );
-      p_.assign( scalars, q, level, flag );
-   }
-   void add( const std::vector< ValueType >&                                                              scalars,
-             const std::vector< std::reference_wrapper< const P2P1TaylorHoodFunction< ValueType > > >& functions, uint_t level,
-             DoFType flag = All ) const
-   {
-      std::vector< std::reference_wrapper< const P2VectorFunction< ValueType > > > v;
-      std::vector< std::reference_wrapper< const P1Function< ValueType > > >       q;
-      for ( const auto& f : functions )
-         v.push_back( std::cref( f.get().uvw() ) ), q.push_back( std::cref( f.get().p() ) );
-      uvw_.add( scalars, v, level, flag );
-      p_.add( scalars, q, level, flag );
-   }
-   ValueType dotGlobal( const P2P1TaylorHoodFunction< ValueType >& rhs, uint_t level, DoFType flag = All ) const
-   {
-      return uvw_.dotGlobal( rhs.uvw(), level, flag ) + p_.dotGlobal( rhs.p(), level, flag );
-   }
-
- private:
-   P2VectorFunction< ValueType > uvw_;
-   P1Function< ValueType >       p_;
-};
-
+using P2P1TaylorHoodFunction = StokesFunction< P2Function< ValueType > >;
 // the three div / divT blocks as one operator (VectorToScalarOperator / ScalarToVectorOperator, src/mixed_operator/)
-class P2ToP1DivOperator
-{
- public:
-   P2ToP1DivOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
-   : x_( storage, minLevel, maxLevel )
-   , y_( storage, minLevel, maxLevel )
-   , z_( storage, minLevel, maxLevel )
-   {}
-   void apply( const P2VectorFunction< double >& src, const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
-   {
-      x_.apply( src[0], dst, level, flag, updateType );
-      y_.apply( src[1], dst, level, flag, Add );
-      z_.apply( src[2], dst, level, flag, Add );
-   }
-
- private:
-   P2ToP1Operator< forms::P2ToP1DivForm< 0 > > x_;
-   P2ToP1Operator< forms::P2ToP1DivForm< 1 > > y_;
-   P2ToP1Operator< forms::P2ToP1DivForm< 2 > > z_;
-};
-class P1ToP2DivTOperator
-{
- public:
-   P1ToP2DivTOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
-   : x_( storage, minLevel, maxLevel )
-   , y_( storage, minLevel, maxLevel )
-   , z_( storage, minLevel, maxLevel )
-   {}
-   void apply( const P1Function< double >& src, const P2VectorFunction< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
-   {
-      x_.apply( src, dst[0], level, flag, updateType );
-      y_.apply( src, dst[1], level, flag, updateType );
-      z_.apply( src, dst[2], level, flag, updateType );
-   }
-
- private:
-   P1ToP2Operator< forms::P1ToP2DivTForm< 0 > > x_;
-   P1ToP2Operator< forms::P1ToP2DivTForm< 1 > > y_;
-   P1ToP2Operator< forms::P1ToP2DivTForm< 2 > > z_;
-};
+using P2ToP1DivOperator =
+    VectorToScalarOperator< P2ToP1Operator< forms::P2ToP1DivForm< 0 > >, P2ToP1Operator< forms::P2ToP1DivForm< 1 > >, P2ToP1Operator< forms::P2ToP1DivForm< 2 > > >;
+using P1ToP2DivTOperator =
+    ScalarToVectorOperator< P1ToP2Operator< forms::P1ToP2DivTForm< 0 > >, P1ToP2Operator< forms::P1ToP2DivTForm< 1 > >, P1ToP2Operator< forms::P1ToP2DivTForm< 2 > > >;
 // P2ConstantVectorLaplaceOperator (VectorLaplaceOperator.hpp): the scalar operator on every component
-class P2ConstantVectorLaplaceOperator
-{
- public:
-   P2ConstantVectorLaplaceOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
-   : lapl_( storage, minLevel, maxLevel )
-   {
-      lapl_.computeInverseDiagonalOperatorValues();
-   }
-   void apply( const P2VectorFunction< double >& src, const P2VectorFunction< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
-   {
-      for ( uint_t k = 0; k < 3; ++k )
-         lapl_.apply( src[k], dst[k], level, flag, updateType );
-   }
-   const P2ConstantLaplaceOperator& getSubOperator( uint_t, uint_t ) const { return lapl_; }
-
- private:
-   P2ConstantLaplaceOperator lapl_;
-};
-
-// P2P1TaylorHoodStokesOperator.hpp:34-110 (apply :55-64; the PSPG members serve the Uzawa smoother as Schur-complement approximation)
-class P2P1TaylorHoodStokesOperator
-{
- public:
-   using srcType            = P2P1TaylorHoodFunction< double >;
-   using dstType            = P2P1TaylorHoodFunction< double >;
-   using VelocityOperator_T = P2ConstantLaplaceOperator;
-   static constexpr bool hasPspgBlock = false; // no specialisation of has_pspg_block for this operator (StokesOperatorTraits.hpp:25-29)
-
-   P2P1TaylorHoodStokesOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel )
-   : lapl( storage, minLevel, maxLevel )
-   , div( storage, minLevel, maxLevel )
-   , divT( storage, minLevel, maxLevel )
-   , pspg( storage, minLevel, maxLevel )
-   , pspg_inv_diag_( storage, minLevel, maxLevel )
-   , storage_( storage )
-   {}
-   void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flag, UpdateType = Replace ) const
-   {
-      if ( &src == &dst )
-         throw std::runtime_error( "P2P1TaylorHoodStokesOperator::apply: src and dst must differ" );
-      lapl.apply( src.uvw(), dst.uvw(), level, flag, Replace );
-      divT.apply( src.p(), dst.uvw(), level, flag, Add );
-      div.apply( src.uvw(), dst.p(), level, flag, Replace );
-   }
-   const P2ConstantLaplaceOperator&    getA() const { return lapl.getSubOperator( 0, 0 ); }
-   std::shared_ptr< PrimitiveStorage > getStorage() const { return storage_; }
-   uint64_t                            uid() const { return uid_; }
-
-   P2ConstantVectorLaplaceOperator lapl;
-   P2ToP1DivOperator               div;
-   P1ToP2DivTOperator              divT;
-   P1PSPGOperator                  pspg;
-   P1PSPGInvDiagOperator           pspg_inv_diag_;
-
- private:
-   std::shared_ptr< PrimitiveStorage > storage_;
-   uint64_t                            uid_ = nextUid();
-};
-
-// StokesVelocityBlockBlockDiagonalPreconditioner for the Taylor-Hood operator: the scalar P2 smoother on every velocity component
-class TaylorHoodVelocityBlockPreconditioner : public Solver< P2P1TaylorHoodStokesOperator >
-{
- public:
-   explicit TaylorHoodVelocityBlockPreconditioner( std::shared_ptr< Solver< P2ConstantLaplaceOperator > > scalar )
-   : scalar_( std::move( scalar ) )
-   {}
-   void solve( const P2P1TaylorHoodStokesOperator& A, const P2P1TaylorHoodFunction< double >& x, const P2P1TaylorHoodFunction< double >& b,
-               uint_t level ) override
-   {
-      for ( uint_t k = 0; k < 3; ++k )
-         scalar_->solve( A.getA(), x.uvw()[k], b.uvw()[k], level );
-   }
-
- private:
-   std::shared_ptr< Solver< P2ConstantLaplaceOperator > > scalar_;
-};
-
+using P2ConstantVectorLaplaceOperator = VectorLaplaceOperator< P2ConstantLaplaceOperator >;
+// P2P1TaylorHoodStokesOperator.hpp:34-110 (apply :55-64; no PSPG block in the apply: the PSPG members serve the Uzawa smoother as
+// Schur-complement approximation)
+using P2P1TaylorHoodStokesOperator = StokesOperator< P2ConstantLaplaceOperator, P2ToP1DivOperator, P1ToP2DivTOperator, false >;
 // P2P1StokesToP2P1StokesRestriction.hpp / ...Prolongation.hpp: quadratic transfer on the velocity, linear on the pressure
-class P2P1StokesToP2P1StokesRestriction
-{
- public:
-   explicit P2P1StokesToP2P1StokesRestriction( bool projectMeanAfterRestriction = false )
-   : projectMean_( projectMeanAfterRestriction )
-   {}
-   void restrict( const P2P1TaylorHoodFunction< double >& f, uint_t sourceLevel, DoFType flag ) const
-   {
-      for ( uint_t k = 0; k < 3; ++k )
-         rv_.restrict( f.uvw()[k], sourceLevel, flag );
-      rp_.restrict( f.p(), sourceLevel, flag );
-      if ( projectMean_ )
-         projectMean( f.p(), sourceLevel - 1 );
-   }
-
- private:
-   P2toP2QuadraticRestriction rv_;
-   P1toP1LinearRestriction    rp_;
-   bool                       projectMean_;
-};
-class P2P1StokesToP2P1StokesProlongation
-{
- public:
-   void prolongate( const P2P1TaylorHoodFunction< double >& f, uint_t sourceLevel, DoFType flag ) const
-   {
-      for ( uint_t k = 0; k < 3; ++k )
-         pv_.prolongate( f.uvw()[k], sourceLevel, flag );
-      pp_.prolongate( f.p(), sourceLevel, flag );
-   }
-   void prolongateAndAdd( const P2P1TaylorHoodFunction< double >& f, uint_t sourceLevel, DoFType flag ) const
-   {
-      for ( uint_t k = 0; k < 3; ++k )
-         pv_.prolongateAndAdd( f.uvw()[k], sourceLevel, flag );
-      pp_.prolongateAndAdd( f.p(), sourceLevel, flag );
-   }
-
- private:
-   P2toP2QuadraticProlongation pv_;
-   P1toP1LinearProlongation    pp_;
-};
+using P2P1StokesToP2P1StokesRestriction  = StokesRestriction< P2toP2QuadraticRestriction >;
+using P2P1StokesToP2P1StokesProlongation = StokesProlongation< P2toP2QuadraticProlongation >;
 
 } // namespace hyteg
