@@ -69,6 +69,7 @@ SIGNATURES = {
     "hyteg_hip_cell_inner_size": (_i64, [_i]),
     "hyteg_hip_cell_index": (_i64, [_i, _i, _i, _i]),
     "hyteg_hip_p1_apply_cell": (_i, [_vp, _vp, _i, _dp, _i, _vp]),
+    "hyteg_hip_p1_apply_cell_steps": (_i, [C.POINTER(_vp), C.POINTER(_vp), _i, _i, _dp, _i, _vp]),
     "hyteg_hip_p1_apply_kernel_name": (_i, [_i, _i, C.c_char_p, _sz]),
     "hyteg_hip_p1_residual_jacobi_start_f32": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _d, _vp]),
     "hyteg_hip_p1_jacobi_accumulate_f32": (_i, [_vp, _vp, _vp, _i, _dp, _d, _vp]),
@@ -351,6 +352,14 @@ def axpy_f32_into_f64(y, x, alpha, n, stream=0):
 
 def p1_apply_cell(dst, src, level, w, update=REPLACE, stream=0):
     check(lib().hyteg_hip_p1_apply_cell(dst, src, level, _w15(w), update, stream), "p1_apply_cell")
+
+
+def p1_apply_cell_steps(dsts, srcs, level, w, update=REPLACE, stream=0):
+    """len(dsts) independent applies of one stencil in one launch (1..16 pairs; dsts[k] (=|+=) A srcs[k])"""
+    if len(srcs) != len(dsts):
+        raise ValueError("p1_apply_cell_steps: as many sources as destinations")
+    d, s = (_vp * len(dsts))(*[int(p) for p in dsts]), (_vp * len(srcs))(*[int(p) for p in srcs])
+    check(lib().hyteg_hip_p1_apply_cell_steps(d, s, len(dsts), level, _w15(w), update, stream), "p1_apply_cell_steps")
 
 
 def p1_jacobi_cell(dst, rhs, src, level, w, relax, invdiag=None, stream=0):

@@ -67,7 +67,7 @@ __global__ __launch_bounds__( kRankThreads ) void p1_apply_rank_kernel( const Br
    const int b = blockIdx.x;
    if ( b < R.brickBlocks )
    {
-      zmarch_body< MODE, kBrickNY, LZ, MODE == APPLY_ADD ? 2 : 0, false, 2, double >( A, tasks, ntasks, xcd_chunk );
+      zmarch_body< MODE, kBrickNY, LZ, MODE == APPLY_ADD ? 2 : 0, false, 2, double >( A, tasks, ntasks, xcd_chunk, A.src, A.dst );
       return;
    }
    double*       dst = static_cast< double* >( A.dst );

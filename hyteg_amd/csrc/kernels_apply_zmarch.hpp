@@ -209,8 +209,9 @@ __device__ inline BrickTask zm_decode_task( const ZMarchArgs& A, int task )
 // boundary of 8 entries of dst (doubles: 64 bytes) inside lanes 1..7 (at a boundary of 4 entries in lane 4 where it would fall
 // on lane 8) and is 56 entries long (doubles: 448 bytes), so that no 64-byte line of dst is written by two waves except the
 // first and the last line of a row (round 3: the PMC write traffic of the 62-wide form is 1.11 x the bytes of dst).
+// srcp / dstp: the source and the destination array of this launch (A.src / A.dst), or of this workgroup's step of a steps launch.
 template < int MODE, int NY, int LZ, int EX_AUX, bool DEC, int PFD, typename T, int XS = 62, int ST_AUX = 2, int SRC_AUX = 0 >
-__device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks, int ntasks, int xcd_chunk )
+__device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks, int ntasks, int xcd_chunk, const void* srcp, void* dstp )
 {
    static_assert( XS == 62 || ( XS == 56 && !DEC ), "x-stride: 62 (plain) or 56 (aligned store windows, table mode)" );
    constexpr int SZ = (int) sizeof( T );
@@ -230,25 +231,25 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
    ZM_TRACE( 1 );
 
    constexpr int kStAux = ST_AUX; // 2 = nontemporal (the default; 1 = sc0, 16 = sc1: measured variants)
-   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc( const_cast< void* >( A.src ), 0, A.bytes, 0x00020000 );
-   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc( A.dst, 0, MODE == APPLY_RESIDUAL_F32OUT ? A.bytes / 2 : A.bytes, 0x00020000 );
+   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc( const_cast< void* >( srcp ), 0, A.bytes, 0x00020000 );
+   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc( dstp, 0, MODE == APPLY_RESIDUAL_F32OUT ? A.bytes / 2 : A.bytes, 0x00020000 );
    constexpr bool kHasRhs = MODE == APPLY_JACOBI || MODE == APPLY_RESIDUAL || MODE == APPLY_RESIDUAL_F32OUT || MODE == APPLY_JACOBI_ACCUM ||
                             MODE == APPLY_CHEB_START;
    constexpr bool kHasInv = MODE == APPLY_JACOBI || MODE == APPLY_CHEB_START || MODE == APPLY_CHEB_STEP; // pointwise inverse diagonal (or 1 / centre)
    static_assert( MODE != APPLY_CHEB_STEP || SZ == 8, "the Chebyshev step updates a double iterate" );
-   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc( const_cast< void* >( kHasRhs ? A.rhs : A.src ), 0, A.bytes, 0x00020000 );
+   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc( const_cast< void* >( kHasRhs ? A.rhs : srcp ), 0, A.bytes, 0x00020000 );
    // mixed-precision modes: float outputs of a double kernel (half the bytes), the double accumulator of a float kernel (twice)
    const __amdgpu_buffer_rsrc_t rd2 =
-       __builtin_amdgcn_make_buffer_rsrc( MODE == APPLY_RESIDUAL_F32OUT ? A.dst2 : A.dst, 0, MODE == APPLY_RESIDUAL_F32OUT ? A.bytes / 2 : A.bytes, 0x00020000 );
+       __builtin_amdgcn_make_buffer_rsrc( MODE == APPLY_RESIDUAL_F32OUT ? A.dst2 : dstp, 0, MODE == APPLY_RESIDUAL_F32OUT ? A.bytes / 2 : A.bytes, 0x00020000 );
    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-       ( MODE == APPLY_JACOBI_ACCUM || MODE == APPLY_CHEB_STEP ) ? (void*) A.xacc : A.dst, 0, MODE == APPLY_JACOBI_ACCUM ? A.bytes * 2 : A.bytes, 0x00020000 );
+       ( MODE == APPLY_JACOBI_ACCUM || MODE == APPLY_CHEB_STEP ) ? (void*) A.xacc : dstp, 0, MODE == APPLY_JACOBI_ACCUM ? A.bytes * 2 : A.bytes, 0x00020000 );
    const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-       const_cast< void* >( ( kHasInv && A.invdiag ) ? A.invdiag : A.src ), 0, A.bytes, 0x00020000 );
+       const_cast< void* >( ( kHasInv && A.invdiag ) ? A.invdiag : srcp ), 0, A.bytes, 0x00020000 );
 
    const int lane_off = lane * SZ;
    const int ym       = t.y0 - 1; // first row held per slice
    // aligned windows: entry index of dst's first byte in units of the value type, modulo one 64-byte line
-   const int dst_phase = XS == 56 ? (int) ( ( reinterpret_cast< uintptr_t >( A.dst ) / SZ ) & 7 ) : 0;
+   const int dst_phase = XS == 56 ? (int) ( ( reinterpret_cast< uintptr_t >( dstp ) / SZ ) & 7 ) : 0;
 
    // S[q][r]: slice z0-1+q, row ym+r (r = 0..NY+1), x = xb + lane.  q = 0..LZ+1.
    T S[LZ + 2][NY + 2];
@@ -451,7 +452,7 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
 template < int MODE, int NY, int LZ, int EX_AUX = 0, bool DEC = false, int PFD = 1, typename T = double, int XS = 62 >
 __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void p1_apply_zmarch_kernel( const ZMarchArgs A )
 {
-   zmarch_body< MODE, NY, LZ, EX_AUX, DEC, PFD, T, XS >( A, A.tasks, A.ntasks, A.xcd_chunk );
+   zmarch_body< MODE, NY, LZ, EX_AUX, DEC, PFD, T, XS >( A, A.tasks, A.ntasks, A.xcd_chunk, A.src, A.dst );
 }
 
 // The same kernel with the three values a wave needs before it can fetch its brick -- table pointer, task count, XCD chunk --
@@ -462,7 +463,31 @@ template < int MODE, int NY, int LZ, int EX_AUX = 0, bool DEC = false, int PFD =
 __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void p1_apply_zmarch_preload_kernel( const BrickTask* tasks, int ntasks, int xcd_chunk,
                                                                                               const ZMarchArgs A )
 {
-   zmarch_body< MODE, NY, LZ, EX_AUX, DEC, PFD, T, XS, ST_AUX, SRC_AUX >( A, tasks, ntasks, xcd_chunk );
+   zmarch_body< MODE, NY, LZ, EX_AUX, DEC, PFD, T, XS, ST_AUX, SRC_AUX >( A, tasks, ntasks, xcd_chunk, A.src, A.dst );
+}
+
+// "Steps" launch: the bricks of up to kZMarchMaxSteps INDEPENDENT applies of one stencil on one macro-cell geometry in one grid,
+// grid = ( workgroups of one apply, steps ).  blockIdx.y is the step (an SGPR: no division, no table), blockIdx.x means what it
+// means in the one-apply kernel, XCD slab map included (the x-extent is a multiple of 8, so blockIdx.x & 7 stays the XCD within
+// every step as long as the dispatcher hands out workgroups x-fastest).  The (src, dst) pair of a step sits in the kernel
+// arguments and is fetched by one scalar load indexed with the step: no device-resident table, nothing to upload or to keep
+// alive.  A wave does one brick of one step and exits, as ever; the dispatcher streams the workgroups of step k+1 into the slots
+// step k's waves leave, so the steps of a launch have no boundary and no common start between them.  The caller
+// guarantees that no array written by one step is read or written by another step of the launch.  Replace and Add only.
+constexpr int kZMarchMaxSteps = 16;
+struct ZMarchStepPtrs
+{
+   const void* srcs[kZMarchMaxSteps];
+   void*       dsts[kZMarchMaxSteps];
+};
+
+template < int MODE, int NY, int LZ, int EX_AUX, int PFD, typename T >
+__global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void p1_apply_zmarch_steps_kernel( const BrickTask* tasks, int ntasks, int xcd_chunk,
+                                                                                            const ZMarchArgs A, const ZMarchStepPtrs P )
+{
+   static_assert( MODE == APPLY_REPLACE || MODE == APPLY_ADD, "a steps launch has one source and one destination per step" );
+   const unsigned step = blockIdx.y < (unsigned) kZMarchMaxSteps ? blockIdx.y : 0u; // the host never launches more
+   zmarch_body< MODE, NY, LZ, EX_AUX, false, PFD, T >( A, tasks, ntasks, xcd_chunk, P.srcs[step], P.dsts[step] );
 }
 
 // host: bricks of NY rows x XS outputs x LZ slices, ordered z-chunk, y-chunk, x-chunk (memory order); zs (optional)

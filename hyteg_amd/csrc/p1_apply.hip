@@ -42,6 +42,26 @@ inline BrickShape default_shape( int mode, int level, bool f32 )
    return BrickShape{ 4, 4, 2 };
 }
 
+// what every z-march launch of a level carries whatever its arrays: brick table, extents, stencil, XCD slab map
+template < typename T >
+int zmarch_common_args( ZMarchArgs& A, int& nblocks, const BrickTable& bt, int level, const double* w )
+{
+   A.tasks  = bt.dev;
+   A.ntasks = bt.count;
+   A.N      = ( 1 << level ) + 1;
+   A.bytes  = (unsigned) ( tet64( A.N ) * (int64_t) sizeof( T ) );
+   for ( int k = 0; k < 15; ++k )
+      A.st.w[k] = w[k];
+   nblocks     = ( bt.count + kZMarchWavesPerBlock - 1 ) / kZMarchWavesPerBlock;
+   nblocks     = ( nblocks + 7 ) & ~7;
+   A.xcd_chunk = nblocks / 8;
+   // measurement switch: 0 = workgroups in launch order (XCDs interleaved brick by brick)
+   static const bool xcdSlabs = env_flag( "HYTEG_HIP_APPLY_XCD_SLABS", true );
+   if ( !xcdSlabs )
+      A.xcd_chunk = 0;
+   return HYTEG_HIP_OK;
+}
+
 // `extra`: the second float output of APPLY_RESIDUAL_F32OUT / the double accumulator of APPLY_JACOBI_ACCUM / the iterate of APPLY_CHEB_STEP
 // (whose deferred update is relax2, applied if flag != 0)
 template < int MODE, int NY, int LZ, int PFD, typename T >
@@ -55,28 +75,17 @@ int launch_zmarch_shape( void* dst, const T* src, const T* rhs, const T* invdiag
    if ( bt.count == 0 )
       return HYTEG_HIP_OK;
    ZMarchArgs A{};
+   int        nblocks = 0;
+   zmarch_common_args< T >( A, nblocks, bt, level, w );
    A.dst     = dst;
    A.src     = src;
    A.rhs     = rhs;
    A.invdiag = invdiag;
    A.dst2    = extra;
    A.xacc    = static_cast< double* >( extra );
-   A.tasks   = bt.dev;
-   A.ntasks  = bt.count;
-   A.N       = ( 1 << level ) + 1;
-   A.bytes   = (unsigned) ( tet64( A.N ) * (int64_t) sizeof( T ) );
    A.relax   = relax;
    A.relax2  = relax2;
    A.flag    = flag;
-   for ( int k = 0; k < 15; ++k )
-      A.st.w[k] = w[k];
-   int nblocks = ( bt.count + kZMarchWavesPerBlock - 1 ) / kZMarchWavesPerBlock;
-   nblocks     = ( nblocks + 7 ) & ~7;
-   A.xcd_chunk = nblocks / 8;
-   // measurement switch: 0 = workgroups in launch order (XCDs interleaved brick by brick)
-   static const bool xcdSlabs = env_flag( "HYTEG_HIP_APPLY_XCD_SLABS", true );
-   if ( !xcdSlabs )
-      A.xcd_chunk = 0;
    // dst of Add is read exactly once per element and written right after: nontemporal load (18.6 -> 17.2 us).  rhs /
    // inverse diagonal of Jacobi are re-read by the next sweep of the smoother and stay plain (nontemporal: 12.4 -> 17.6 us
    // when they are still in the Infinity Cache, -2% when they are not).
@@ -85,6 +94,57 @@ int launch_zmarch_shape( void* dst, const T* src, const T* rhs, const T* invdiag
    // for a kernel-argument load (round 2: 9.90-10.18 -> 9.60-9.74 us)
    hipLaunchKernelGGL( ( p1_apply_zmarch_preload_kernel< MODE, NY, LZ, kExAux, false, PFD, T > ), dim3( nblocks ), dim3( 64 * kZMarchWavesPerBlock ), 0,
                        stream, A.tasks, A.ntasks, A.xcd_chunk, A );
+   HH_CHECK_HIP( hipGetLastError() );
+   return HYTEG_HIP_OK;
+}
+
+// Residency cap of the steps launch: m workgroups per CU (m waves per SIMD) by a request for dynamic LDS the kernel never touches --
+// 160 KiB / m per workgroup, rounded down to 4 KiB, so that m workgroups fit a CU's LDS and m + 1 do not (m = 1 .. 6).  Without
+// a cap up to 8 waves per SIMD are resident, i.e. the working sets of up to four steps share an L2.  Default: m = 2 at level 8
+// (HBM regime: faster than no cap in nine of nine pairs of runs, -1 to -7 %), no cap below (cache-resident: m = 2 costs +16 % at
+// level 7, +2 to +20 % at level 6); profiles/apply_steps_level8.txt.  The host layer issues no steps launch above level 8.
+// HYTEG_HIP_APPLY_STEPS_WG_PER_CU (read once) sets m for every level; 0 or out of range: no cap.
+inline unsigned steps_lds_request( int level )
+{
+   static const int fromEnv = [] {
+      const char* v = getenv( "HYTEG_HIP_APPLY_STEPS_WG_PER_CU" );
+      return v ? atoi( v ) : -1;
+   }();
+   const int m = fromEnv >= 0 ? fromEnv : ( level == 8 ? 2 : 0 );
+   return ( m >= 1 && m <= 6 ) ? (unsigned) ( ( 160 * 1024 / m ) & ~4095 ) : 0u;
+}
+
+// nsteps (2 .. kZMarchMaxSteps) independent applies of one stencil in one launch, double Replace / Add
+template < int MODE, int NY, int LZ, int PFD >
+int launch_zmarch_steps_shape( void* const* dsts, const void* const* srcs, int nsteps, int level, const double* w, hipStream_t stream )
+{
+   static_assert( MODE == APPLY_REPLACE || MODE == APPLY_ADD, "steps launch: Replace and Add" );
+   BrickTable bt;
+   int        rc = get_bricks( level, NY, LZ, &bt );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   if ( bt.count == 0 )
+      return HYTEG_HIP_OK;
+   ZMarchArgs A{};
+   int        nblocks = 0;
+   zmarch_common_args< double >( A, nblocks, bt, level, w );
+   ZMarchStepPtrs P{};
+   for ( int k = 0; k < kZMarchMaxSteps; ++k ) // the entries past nsteps repeat step 0: no wave reads them, none is null
+   {
+      P.srcs[k] = srcs[k < nsteps ? k : 0];
+      P.dsts[k] = dsts[k < nsteps ? k : 0];
+   }
+   A.src = P.srcs[0];
+   A.dst = P.dsts[0];
+   constexpr int kExAux = MODE == APPLY_ADD ? 2 : 0;
+   auto          kern   = p1_apply_zmarch_steps_kernel< MODE, NY, LZ, kExAux, PFD, double >;
+   const unsigned lds   = steps_lds_request( level );
+   if ( lds > 0 )
+   {
+      static const hipError_t attr = hipFuncSetAttribute( reinterpret_cast< const void* >( kern ), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds );
+      HH_CHECK_HIP( attr );
+   }
+   hipLaunchKernelGGL( kern, dim3( nblocks, nsteps ), dim3( 64 * kZMarchWavesPerBlock ), lds, stream, A.tasks, A.ntasks, A.xcd_chunk, A, P );
    HH_CHECK_HIP( hipGetLastError() );
    return HYTEG_HIP_OK;
 }
@@ -135,6 +195,18 @@ int launch_zmarch( void* dst, const T* src, const T* rhs, const T* invdiag, int 
    HYTEG_ZM_SHAPES( HH_X )
 #undef HH_X
    return fail( HYTEG_HIP_EINVAL, "apply: brick shape not compiled in" );
+}
+
+template < int MODE >
+int launch_zmarch_steps( void* const* dsts, const void* const* srcs, int nsteps, int level, const double* w, hipStream_t stream )
+{
+   const BrickShape s = current_shape( MODE, level, false );
+#define HH_X( NY_, LZ_, PFD_ ) \
+   if ( s == BrickShape{ NY_, LZ_, PFD_ } ) \
+      return launch_zmarch_steps_shape< MODE, NY_, LZ_, PFD_ >( dsts, srcs, nsteps, level, w, stream );
+   HYTEG_ZM_SHAPES( HH_X )
+#undef HH_X
+   return fail( HYTEG_HIP_EINVAL, "apply steps: brick shape not compiled in" );
 }
 
 // Does this level run the z-march register kernel?  Yes whenever the byte offsets of the array fit its 32-bit buffer addressing
@@ -207,6 +279,34 @@ HYTEG_HIP_API int hyteg_hip_p1_apply_cell( double*            dst,
    if ( update == HYTEG_HIP_REPLACE )
       return launch_apply< APPLY_REPLACE >( dst, src, nullptr, nullptr, level, w, 0.0, as_stream( stream ) );
    return launch_apply< APPLY_ADD >( dst, src, nullptr, nullptr, level, w, 0.0, as_stream( stream ) );
+}
+
+HYTEG_HIP_API int hyteg_hip_p1_apply_cell_steps( void* const*       dsts,
+                                                 const void* const* srcs,
+                                                 int                nsteps,
+                                                 int                level,
+                                                 const double*      w,
+                                                 int                update,
+                                                 hyteg_hip_stream_t stream )
+{
+   HH_REQUIRE( dsts && srcs && w, "p1_apply_cell_steps: null pointer" );
+   HH_REQUIRE( nsteps >= 1 && nsteps <= kZMarchMaxSteps, "p1_apply_cell_steps: nsteps out of range [1,16]" );
+   HH_REQUIRE( level_ok( level ), "p1_apply_cell_steps: level out of range [2,11]" );
+   HH_REQUIRE( update == HYTEG_HIP_REPLACE || update == HYTEG_HIP_ADD, "p1_apply_cell_steps: bad update type" );
+   for ( int i = 0; i < nsteps; ++i )
+   {
+      HH_REQUIRE( dsts[i] && srcs[i], "p1_apply_cell_steps: null array" );
+      for ( int j = 0; j < nsteps; ++j )
+         HH_REQUIRE( dsts[i] != srcs[j] && ( i == j || dsts[i] != dsts[j] ),
+                     "p1_apply_cell_steps: an array written by one step must not be read or written by another (nor be the step's own source)" );
+   }
+   if ( nsteps == 1 )
+      return hyteg_hip_p1_apply_cell( static_cast< double* >( dsts[0] ), static_cast< const double* >( srcs[0] ), level, w, update, stream );
+   if ( !level_runs_zmarch( level ) )
+      return fail( HYTEG_HIP_ENOTSUP, "p1_apply_cell_steps: this level does not run the z-march kernel" );
+   if ( update == HYTEG_HIP_REPLACE )
+      return launch_zmarch_steps< APPLY_REPLACE >( dsts, srcs, nsteps, level, w, as_stream( stream ) );
+   return launch_zmarch_steps< APPLY_ADD >( dsts, srcs, nsteps, level, w, as_stream( stream ) );
 }
 
 // ---- float instantiations (the reference instantiates its generated apply kernels for float as well:

@@ -35,6 +35,9 @@ SIGNATURES = {
     "hyteg_host_storage_set_apply_lanes": (_i, [_vp, _i]),
     "hyteg_host_storage_set_apply_cell_lanes_min": (_i, [_vp, _i]),
     "hyteg_host_storage_lanes_seen": (_i, [_vp, C.POINTER(C.c_uint)]),
+    "hyteg_host_storage_set_apply_steps": (_i, [_vp, _i]),
+    "hyteg_host_storage_steps_launches": (_i, [_vp, C.POINTER(_u)]),
+    "hyteg_host_apply_steps_plan": (_i, [_i, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _i, _i, _i, _i, _ip, _ip]),
     "hyteg_host_lane_plan": (_i, [_i, _i, _ip, C.POINTER(C.c_ulonglong), _ip, C.POINTER(C.c_ulonglong), _ip, C.POINTER(_u)]),
     "hyteg_host_storage_set_hooks": (_i, [_vp, EXCHANGE_CB, EXCHANGE_CB, ALLREDUCE_CB, _vp]),
     "hyteg_host_storage_use_rccl": (_i, [_vp, C.c_char_p]),
@@ -283,6 +286,11 @@ class Storage:
         """levels <= level run the batched kernels (one launch for all local cells); -1: per-cell kernels everywhere"""
         _ck(lib().hyteg_host_storage_set_batch_max_level(self.h, level), "set_batch_max_level")
 
+    def set_apply_steps(self, steps):
+        """steps per launch of apply_cycle on one macro-cell (independent consecutive applies share a launch); 1: one launch per
+        apply, 0: default (HYTEG_AMD_APPLY_STEPS, else 16)"""
+        _ck(lib().hyteg_host_storage_set_apply_steps(self.h, steps), "set_apply_steps")
+
     def set_apply_lanes(self, lanes):
         """stream lanes for independent interior launches inside one host-layer call (apply_cycle); 1: one stream, 0: default
         (HYTEG_AMD_APPLY_LANES, else 2)"""
@@ -297,6 +305,12 @@ class Storage:
         m = C.c_uint()
         _ck(lib().hyteg_host_storage_lanes_seen(self.h, C.byref(m)), "lanes_seen")
         return m.value
+
+    def steps_launches(self):
+        """launches of more than one step that the storage's last apply_cycle issued (0: it ran as single launches)"""
+        n = C.c_uint()
+        _ck(lib().hyteg_host_storage_steps_launches(self.h, C.byref(n)), "steps_launches")
+        return n.value
 
     def set_stream(self, stream):
         _ck(lib().hyteg_host_storage_set_stream(self.h, stream), "set_stream")

@@ -89,17 +89,19 @@ void withOp( hh_operator_t op, Fn&& fn )
    std::visit( [&]( auto& p ) { fn( *p ); }, static_cast< OperatorH* >( op )->op );
 }
 // the loop of hyteg_host_operator_apply_cycle and _apply_cycle_timed: consecutive applies on different pairs are independent, they
-// overlap on the storage's lanes (PrimitiveStorage::LaneScope)
+// share launches (P1ConstantOperator::applyRun sees all the steps before it issues the first) and overlap on the storage's lanes
+// (PrimitiveStorage::LaneScope)
 void applyCycle( hh_operator_t op, int npairs, const hh_function_t* srcs, const hh_function_t* dsts, int level, int flag, int update, int first, int steps )
 {
    PrimitiveStorage::LaneScope lanes( *F( srcs[0] ).getStorage() );
-   withOp( op, [&]( auto& A ) {
-      for ( int k = 0; k < steps; ++k )
-      {
-         const int j = ( first + k ) % npairs;
-         A.apply( F( srcs[j] ), F( dsts[j] ), (uint_t) level, DoFType( flag ), update ? Add : Replace );
-      }
-   } );
+   std::vector< const P1Function< double >* > u( (size_t) steps ), d( (size_t) steps );
+   for ( int k = 0; k < steps; ++k )
+   {
+      const int j   = ( first + k ) % npairs;
+      u[(size_t) k] = &F( srcs[j] );
+      d[(size_t) k] = &F( dsts[j] );
+   }
+   withOp( op, [&]( auto& A ) { A.applyRun( u, d, (uint_t) level, DoFType( flag ), update ? Add : Replace ); } );
    lanes.join();
 }
 // scalar smoother of an integer code: 0 weighted Jacobi, 1 Gauss-Seidel, 2 SOR, 3 mixed-precision Jacobi (P1 only: BASELINE config 5's
@@ -311,6 +313,14 @@ HYTEG_HOST_API int hyteg_host_storage_set_apply_lanes( hh_storage_t s, int lanes
 {
    return guarded( [&] { S( s ).setApplyLanes( lanes ); } );
 }
+HYTEG_HOST_API int hyteg_host_storage_set_apply_steps( hh_storage_t s, int steps )
+{
+   return guarded( [&] { S( s ).setApplySteps( steps ); } );
+}
+HYTEG_HOST_API int hyteg_host_storage_steps_launches( hh_storage_t s, unsigned* count )
+{
+   return guarded( [&] { *count = S( s ).stepsLaunchesSeen(); } );
+}
 HYTEG_HOST_API int hyteg_host_storage_set_apply_cell_lanes_min( hh_storage_t s, int cells )
 {
    return guarded( [&] { S( s ).setApplyCellLanesMin( cells ); } );
@@ -337,6 +347,24 @@ HYTEG_HOST_API int hyteg_host_lane_plan( int lanes, int nsteps, const int* read_
          const auto p = planner.place( r.data(), (int) r.size(), w.data(), (int) w.size() );
          lane_out[k] = p.lane, waits_out[k] = p.waits;
       }
+   } );
+}
+HYTEG_HOST_API int hyteg_host_apply_steps_plan( int npairs, const unsigned long long* src_ids, const unsigned long long* dst_ids, int first, int steps,
+                                                int max_group, int lanes, int* sizes_out, int* ngroups_out )
+{
+   return guarded( [&] {
+      if ( npairs < 1 || steps < 0 || first < 0 || !src_ids || !dst_ids || !ngroups_out || ( steps > 0 && !sizes_out ) )
+         throw std::runtime_error( "apply_steps_plan: bad argument" );
+      std::vector< const void* > u( (size_t) steps ), d( (size_t) steps );
+      for ( int k = 0; k < steps; ++k )
+      {
+         const int j   = (int) ( ( (long long) first + k ) % npairs );
+         u[(size_t) k] = reinterpret_cast< const void* >( (uintptr_t) src_ids[j] );
+         d[(size_t) k] = reinterpret_cast< const void* >( (uintptr_t) dst_ids[j] );
+      }
+      const std::vector< int > sizes = planApplySteps( u.data(), d.data(), steps, max_group, lanes );
+      std::copy( sizes.begin(), sizes.end(), sizes_out );
+      *ngroups_out = (int) sizes.size();
    } );
 }
 HYTEG_HOST_API int hyteg_host_storage_use_rccl( hh_storage_t s, const unsigned char* unique_id )

@@ -145,4 +145,52 @@ class LanePlanner
    std::vector< Access >                    need_;
 };
 
+// Grouping of a run of applies for the steps launch (hyteg_hip_p1_apply_cell_steps: up to 16 independent applies of one operator in
+// one grid, so that a step starts while the waves of the one before it drain).  Step k of the run reads srcs[k] and writes dsts[k]
+// (device base pointers of whole arrays).  A step conflicts with an earlier one if it writes an array that one reads or writes, or
+// reads an array that one writes.  With one lane the groups are the maximal ones: consecutive steps join the group until it has
+// maxGroup steps or the next step conflicts with one of its steps; that step starts the next group.  With several lanes a group
+// must not swallow what the lanes would have overlapped: of the r conflict-free steps that follow the start of a group (looking
+// at most maxGroup * lanes steps ahead) the group takes r / lanes and the next lanes - 1 groups as many (if they are
+// conflict-free), so that every lane gets a launch out of the same steps -- a ring of 26 pairs gives groups of
+// min( maxGroup, 13 ) on two lanes, 20 steps two groups of 10, a ring of 3 pairs single launches that alternate between the
+// lanes as they did without groups.  Returns the group sizes in order (they sum to nsteps).  A ring with one pair, or a
+// dependent chain dst[k] == src[k+1], degenerates to groups of one whatever the lanes.  Pure host code.
+inline std::vector< int > planApplySteps( const void* const* srcs, const void* const* dsts, int nsteps, int maxGroup, int lanes = 1 )
+{
+   if ( maxGroup < 1 || lanes < 1 )
+      throw std::runtime_error( "planApplySteps: group size and lane count must be at least 1" );
+   std::vector< int > sizes;
+   int                pending = 0, share = 0; // groups still owed to the other lanes by the last split, and its size
+   for ( int begin = 0; begin < nsteps; )
+   {
+      const int window = std::min( nsteps - begin, maxGroup * lanes );
+      int       r      = 1;
+      for ( ; r < window; ++r )
+      {
+         const int k        = begin + r;
+         bool      conflict = false;
+         for ( int i = begin; i < k && !conflict; ++i )
+            conflict = dsts[k] == srcs[i] || dsts[k] == dsts[i] || srcs[k] == dsts[i];
+         if ( conflict )
+            break;
+      }
+      int g;
+      if ( pending > 0 ) // one of the equal shares of the split before: as large as that one, if that many steps are conflict-free
+      {
+         g = std::min( share, r );
+         --pending;
+      }
+      else
+      {
+         g       = std::min( maxGroup, std::max( 1, r / lanes ) );
+         share   = g;
+         pending = lanes - 1;
+      }
+      sizes.push_back( g );
+      begin += g;
+   }
+   return sizes;
+}
+
 } // namespace hyteg

@@ -130,6 +130,65 @@ class P1ConstantOperator
          dst.addOnShell( *tmp, level, flag );
    }
 
+   // A run of applies the caller sees as a whole before it issues the first (the loop of apply_cycle): step k is
+   // apply( *srcs[k], *dsts[k], level, flag, updateType ), with the same results.  Where every step is one interior launch on the
+   // one local macro-cell, consecutive independent steps share a launch (hyteg_hip_p1_apply_cell_steps; groups from planApplySteps,
+   // up to PrimitiveStorage::applySteps() steps each): the grid of a group carries the bricks of all its steps, so a step starts
+   // while the waves of the one before it drain, with no kernel boundary in between.  A group is placed on the storage's lanes like
+   // a single apply that reads all its sources and writes all its destinations, and is sized so that every lane still gets one.
+   // Anything else is the plain loop.
+   void applyRun( const std::vector< const P1Function< double >* >& srcs, const std::vector< const P1Function< double >* >& dsts, uint_t level,
+                  DoFType flagIn, UpdateType updateType = Replace ) const
+   {
+      const int n       = (int) srcs.size();
+      const int G       = storage_->applySteps();
+      storage_->resetStepsLaunches();
+      // up to level 8: a level-9 launch is 70 us of several generations of waves, groups gain nothing there (measured: 70.7 -> 70.5-71.4 us)
+      bool      grouped = G > 1 && n > 1 && level <= 8 && storage_->getNumberOfLocalCells() == 1 && storage_->applyStepsUsable();
+      for ( int k = 0; k < n && grouped; ++k )
+      {
+         const DoFType flag = dsts[k]->effectiveFlag( flagIn );
+         grouped            = srcs[k] != dsts[k] && pureInterior( level, flag );
+         storage_->forLocalCells( [&]( uint_t, const MacroCell& cell ) { grouped = grouped && ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER ); } );
+      }
+      if ( !grouped )
+      {
+         for ( int k = 0; k < n; ++k )
+            apply( *srcs[k], *dsts[k], level, flagIn, updateType );
+         return;
+      }
+      std::vector< const void* > u( (size_t) n );
+      std::vector< void* >       d( (size_t) n );
+      const double*              stencil = nullptr;
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+         stencil = getCellStencils( cell.id, level ).inner;
+         for ( int k = 0; k < n; ++k )
+         {
+            u[(size_t) k] = srcs[k]->getCellPointer( c, level );
+            d[(size_t) k] = dsts[k]->getCellPointer( c, level );
+         }
+      } );
+      const int upd = hipUpdate( updateType );
+      int       k   = 0;
+      for ( const int g : planApplySteps( u.data(), d.data(), n, G, storage_->lanesOpen() ? storage_->applyLanes() : 1 ) )
+      {
+         const void* const* r = u.data() + k;
+         void* const*       w = d.data() + k;
+         hyteg_hip_stream_t s = storage_->lanesOpen() ? storage_->laneFor( r, g, w, g ) : storage_->stream();
+         int                rc = g > 1 ? hyteg_hip_p1_apply_cell_steps( w, r, g, (int) level, stencil, upd, s ) : HYTEG_HIP_ENOTSUP;
+         if ( g > 1 && rc == HYTEG_HIP_OK )
+            storage_->countStepsLaunch();
+         if ( rc == HYTEG_HIP_ENOTSUP ) // a group of one, or a level without a steps kernel: one by one on the same stream
+         {
+            rc = HYTEG_HIP_OK;
+            for ( int i = 0; i < g && rc == HYTEG_HIP_OK; ++i )
+               rc = hyteg_hip_p1_apply_cell( static_cast< double* >( w[i] ), static_cast< const double* >( r[i] ), (int) level, stencil, upd, s );
+         }
+         hipCheck( rc, "applyRun: cell" );
+         k += g;
+      }
+   }
+
    // r = b - A x on the points `flag` selects: apply followed by assign( { 1, -1 }, { b, r } ) as the multigrid cycle writes it
    // (GeometricMultigridSolver.hpp:240-246); where no shell point is selected (one macro-cell with fixed boundary values) the
    // interior kernel forms the difference itself -- one launch, the same bits

@@ -367,6 +367,46 @@ class PrimitiveStorage
       }
       return laneCount_;
    }
+   // Steps per launch of a run of independent interior applies (the loop of apply_cycle on one macro-cell: P1ConstantOperator::applyRun,
+   // planApplySteps in lanes.hpp): 1 = one launch per apply, up to 16.  setApplySteps(), else HYTEG_AMD_APPLY_STEPS, else the
+   // default kDefaultApplySteps (profiles/apply_steps_level8.txt).  A group is placed on the lanes like a single apply.  Results
+   // do not depend on it.
+   static constexpr int kMaxApplySteps = 16, kDefaultApplySteps = 16;
+   void                 setApplySteps( int steps )
+   {
+      if ( steps < 0 || steps > kMaxApplySteps )
+         throw std::runtime_error( "setApplySteps: 0 (default) to " + std::to_string( kMaxApplySteps ) + " steps per launch" );
+      applySteps_ = steps == 0 ? -1 : steps;
+   }
+   int applySteps() const
+   {
+      if ( applySteps_ < 0 )
+      {
+         static const int fromEnv = [] {
+            const char* e = std::getenv( "HYTEG_AMD_APPLY_STEPS" );
+            const int   n = e ? std::atoi( e ) : kDefaultApplySteps;
+            return std::min( std::max( n, 1 ), kMaxApplySteps );
+         }();
+         applySteps_ = fromEnv;
+      }
+      return applySteps_;
+   }
+   // launches of more than one step that the last run of applies issued (P1ConstantOperator::applyRun: the last apply_cycle); 0 if
+   // it ran as single launches.  What a test asks to know that a grouped launch was really issued.
+   unsigned stepsLaunchesSeen() const { return stepsLaunches_; }
+   void     resetStepsLaunches() const { stepsLaunches_ = 0; }
+   void     countStepsLaunch() const { ++stepsLaunches_; }
+   // may a host-layer call that sees a whole run of applies issue it as grouped launches?  Under the conditions of the lanes: one
+   // rank, no side chain open, timing tree off (its ranges count applies), stream not being recorded into a graph
+   bool applyStepsUsable() const
+   {
+      if ( nranks_ != 1 || mainStream_ || timingTree_ )
+         return false;
+      if ( lanesOpen() ) // the scope has asked the stream already
+         return true;
+      int capturing = 0;
+      return hyteg_hip_stream_is_capturing( stream_, &capturing ) == HYTEG_HIP_OK && !capturing;
+   }
    // Lanes for the cell loop of a multi-cell apply from this many local cells on; 0 = never.  Default 24: at level 8 two lanes
    // take 559.7 -> 546.7 us per apply on 24 cells (-2.3 %) but 132.0 -> 141.3 us on 6 (+7 %), three lanes are slower on both
    // (profiles/apply_lanes_level8.txt, section 4); setApplyCellLanesMin(), else HYTEG_AMD_APPLY_CELL_LANES_MIN read once.
@@ -1150,9 +1190,9 @@ class PrimitiveStorage
    mutable LanePlanner                                     planner_;
    mutable hyteg_hip_stream_t                              laneStreams_[LanePlanner::kMaxLanes] = {};
    mutable hyteg_hip_event_t                               laneEvents_[LanePlanner::kMaxLanes]  = {}, laneFork_ = nullptr;
-   mutable int                                             laneCount_ = -1, laneDepth_ = 0;
+   mutable int                                             laneCount_ = -1, laneDepth_ = 0, applySteps_ = -1;
    mutable int                                             cellLanesMin_ = -1; // -1: read HYTEG_AMD_APPLY_CELL_LANES_MIN on first use
-   mutable unsigned                                        laneUsed_  = 0, lanesSeen_ = 0;
+   mutable unsigned                                        laneUsed_  = 0, lanesSeen_ = 0, stepsLaunches_ = 0;
    mutable bool                                            lanesOn_ = false, laneManual_ = false;
    std::shared_ptr< Transport >                            transport_;
    std::shared_ptr< TimingTree >                           timingTree_;

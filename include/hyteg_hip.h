@@ -54,7 +54,8 @@ enum
    HYTEG_HIP_EINVAL  = 1, /* bad argument (null pointer, level out of range, aliasing src==dst ...) */
    HYTEG_HIP_ELAUNCH = 2, /* HIP runtime reported an error for a launch / memcpy */
    HYTEG_HIP_ENOMEM  = 3,
-   HYTEG_HIP_ENODEV  = 4 /* no usable gfx950 device */
+   HYTEG_HIP_ENODEV  = 4, /* no usable gfx950 device */
+   HYTEG_HIP_ENOTSUP = 5  /* valid arguments, but this entry point has no kernel for them: the caller takes its other path */
 };
 
 /* UpdateType, src/hyteg/types/types.hpp:29-33 */
@@ -139,6 +140,21 @@ HYTEG_HIP_API int hyteg_hip_p1_apply_cell( double*            dst,
                                            const double*      w /* host, 15 */,
                                            int                update,
                                            hyteg_hip_stream_t stream );
+/* nsteps INDEPENDENT applies of ONE stencil on one macro-cell geometry in ONE launch: dsts[k] (=|+=) A srcs[k], k = 0 .. nsteps-1,
+ * each with the bits hyteg_hip_p1_apply_cell gives for that pair (the grid carries the bricks of all steps, so a step starts while the
+ * waves of the one before it drain: no kernel boundary between them).  No reference counterpart (its kernels are host loops).
+ * Contract: 1 <= nsteps <= 16 (EINVAL otherwise, nothing is launched); dsts / srcs are HOST arrays of device pointers and are read
+ * before the call returns; the caller guarantees that no array written by one step is read or written by another step of the same
+ * call (dsts[i] == srcs[j] or dsts[i] == dsts[j] is rejected with EINVAL; overlaps of different base pointers are not detected).
+ * Levels and modes of the z-march kernel (levels 2..10, Replace and Add); any other level returns HYTEG_HIP_ENOTSUP and launches
+ * nothing, and the caller issues the applies one by one.  nsteps == 1 is hyteg_hip_p1_apply_cell. */
+HYTEG_HIP_API int hyteg_hip_p1_apply_cell_steps( void* const*       dsts /* host, nsteps device pointers */,
+                                                 const void* const* srcs /* host, nsteps device pointers */,
+                                                 int                nsteps,
+                                                 int                level,
+                                                 const double*      w /* host, 15 */,
+                                                 int                update,
+                                                 hyteg_hip_stream_t stream );
 
 /* ---- float instantiations of a2 / a4 and mixed-precision support -------------------------------------------------
  * The reference instantiates its generated apply kernels for float32 as well

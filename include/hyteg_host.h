@@ -69,6 +69,23 @@ HYTEG_HOST_API int hyteg_host_storage_lanes_seen( hh_storage_t s, unsigned* mask
  * issued on; bit j of waits_out[k] = before step k its lane waits for everything issued on lane j so far. */
 HYTEG_HOST_API int hyteg_host_lane_plan( int lanes, int nsteps, const int* read_ptr, const unsigned long long* read_ids, const int* write_ptr,
                                          const unsigned long long* write_ids, int* lane_out, unsigned* waits_out );
+/* Steps per launch of hyteg_host_operator_apply_cycle: on one rank with one local macro-cell whose shell points are all excluded,
+ * consecutive steps of the cycle that are independent of each other (no step's destination array is another step's source or
+ * destination) share one launch of up to `steps` applies (hyteg_hip_p1_apply_cell_steps): no kernel boundary between them.
+ * 1 = one launch per apply; 0 = the default: the environment variable HYTEG_AMD_APPLY_STEPS, else 16.  At most 16.  Results do not
+ * depend on it.  A group is placed on the lanes like a single apply; with several lanes a group takes at most 1 / lanes of the
+ * independent steps ahead of it, so that short rings keep alternating between the lanes.  Not used on several ranks or
+ * cells, on the batched levels, above level 8 (levels 2-8 only), while the stream is recorded into a graph and while the timing tree is enabled. */
+HYTEG_HOST_API int hyteg_host_storage_set_apply_steps( hh_storage_t s, int steps );
+/* *count: launches of more than one step that the last hyteg_host_operator_apply_cycle on this storage issued; 0 if it ran as single
+ * launches (grouping off, not applicable, or no two consecutive independent steps). */
+HYTEG_HOST_API int hyteg_host_storage_steps_launches( hh_storage_t s, unsigned* count );
+/* The grouping behind it, without a GPU: step k = 0 .. steps-1 of a cycle over a ring of npairs pairs reads src_ids[j] and writes
+ * dst_ids[j], j = ( first + k ) % npairs (ids stand for device base pointers).  sizes_out (room for `steps` entries) receives the
+ * sizes of the consecutive groups, *ngroups_out their number.  lanes = 1: maximal groups of up to max_group conflict-free steps;
+ * lanes > 1: a group takes 1 / lanes of the conflict-free steps ahead of it, so that every lane still gets a launch. */
+HYTEG_HOST_API int hyteg_host_apply_steps_plan( int npairs, const unsigned long long* src_ids, const unsigned long long* dst_ids, int first, int steps,
+                                                int max_group, int lanes, int* sizes_out, int* ngroups_out );
 /* Timing tree with the reference's timer names (walberla::WcTimingTree behind PrimitiveStorage::getTimingTree():
  * "Operator P1Function to P1Function" / "Apply", "smooth_jac", "SOR"; "P1Function" / "Assign", "Dot (local)" ...;
  * "Geometric Multigrid Solver" / "Level L" / "Smoother" ...; src/hyteg/operators/Operator.hpp:148-166,
