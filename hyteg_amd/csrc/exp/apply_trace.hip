@@ -1,8 +1,11 @@
 // Developer harness (round 2; not part of the product library): the production z-march apply kernel at level 8,
-//   * timed per variant (brick table vs decoded bricks, prefetch distance) over rotating buffer pairs, and
+//   * timed per variant (brick shape, prefetch distance) over rotating buffer pairs, and
 //   * with -DZM_DO_TRACE: per-wave timestamps (s_memrealtime, 100 MHz) at kernel entry, after the brick is known,
 //     after the prologue loads are issued, when they have arrived, and at the end, plus XCC / HW ids, to see where a
 //     launch spends its time (dispatch ramp, table load, first loads, march, tail).
+// The kernel here is this file's own wrapper of zmarch_body with every argument in the struct: the trace buffer is indexed
+// with blockIdx.x of a one-apply launch.  Commit 896fb24 is the last one with the "decode" row (bricks computed from the task
+// index instead of read from the table: profiles/r02_apply_wave_trace_table_vs_decode.txt).
 // Build: see build_trace.sh.   Run: apply_trace [level] [reps] [nbuf]
 #include <algorithm>
 #include <cmath>
@@ -38,6 +41,12 @@ __device__ unsigned long long* g_trace;
 #include "kernels_apply_zloop.hpp"
 
 using namespace hyteg_hip;
+
+template < int NY, int LZ, int PFD >
+__global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void zmarch_trace_kernel( const ZMarchArgs A )
+{
+   zmarch_body< APPLY_REPLACE, NY, LZ, PFD, double >( A, A.tasks, A.ntasks, A.xcd_chunk, A.src, A.dst );
+}
 
 #define CK( e )                                                                                \
    do                                                                                          \
@@ -130,15 +139,9 @@ int main( int argc, char** argv )
    CK( hipEventCreate( &e0 ) );
    CK( hipEventCreate( &e1 ) );
 
-   auto run = [&]( const char* name, int NY, int LZ, bool dec, auto kern ) {
+   auto run = [&]( const char* name, int NY, int LZ, auto kern ) {
       std::vector< BrickTask > tasks;
-      std::vector< int >       zs;
-      build_brick_tasks( level, NY, LZ, tasks, &zs );
-      if ( dec && ( (int) zs.size() - 1 > kZMarchMaxZChunks || N - 4 > 62 * kZMarchMaxStairs ) )
-      {
-         printf( "%-40s not decodable at this level\n", name );
-         return;
-      }
+      build_brick_tasks( level, NY, LZ, tasks );
       BrickTask* dtasks;
       CK( hipMalloc( &dtasks, tasks.size() * sizeof( BrickTask ) ) );
       CK( hipMemcpy( dtasks, tasks.data(), tasks.size() * sizeof( BrickTask ), hipMemcpyHostToDevice ) );
@@ -149,8 +152,6 @@ int main( int argc, char** argv )
       A.N      = N;
       A.st     = st;
       A.relax  = 0.66;
-      for ( int k = 0; k < kZMarchMaxZChunks; ++k )
-         A.zs[k] = k + 1 < (int) zs.size() ? zs[k] : A.ntasks;
       int nblocks = ( A.ntasks + kZMarchWavesPerBlock - 1 ) / kZMarchWavesPerBlock;
       nblocks     = ( nblocks + 7 ) & ~7;
       A.xcd_chunk = nblocks / 8;
@@ -265,13 +266,12 @@ int main( int argc, char** argv )
       CK( hipFree( dtasks ) );
    };
 
-   run( "zmarch 4x8 table PFD1", 4, 8, false, p1_apply_zmarch_kernel< APPLY_REPLACE, 4, 8, 0, false, 1 > );
-   run( "zmarch 4x8 table PFD2", 4, 8, false, p1_apply_zmarch_kernel< APPLY_REPLACE, 4, 8, 0, false, 2 > );
-   run( "zmarch 4x8 decode PFD1", 4, 8, true, p1_apply_zmarch_kernel< APPLY_REPLACE, 4, 8, 0, true, 1 > );
-   run( "zmarch 4x4 table PFD1", 4, 4, false, p1_apply_zmarch_kernel< APPLY_REPLACE, 4, 4, 0, false, 1 > );
-   run( "zmarch 4x6 table PFD1", 4, 6, false, p1_apply_zmarch_kernel< APPLY_REPLACE, 4, 6, 0, false, 1 > );
-   run( "zmarch 2x8 table PFD1", 2, 8, false, p1_apply_zmarch_kernel< APPLY_REPLACE, 2, 8, 0, false, 1 > );
-   run( "zmarch 3x8 table PFD1", 3, 8, false, p1_apply_zmarch_kernel< APPLY_REPLACE, 3, 8, 0, false, 1 > );
-   run( "zloop 4x8 renaming(4)", 4, 8, false, p1_apply_zloop_kernel< APPLY_REPLACE, 4, 4 > );
+   run( "zmarch 4x8 table PFD1", 4, 8, zmarch_trace_kernel< 4, 8, 1 > );
+   run( "zmarch 4x8 table PFD2", 4, 8, zmarch_trace_kernel< 4, 8, 2 > );
+   run( "zmarch 4x4 table PFD1", 4, 4, zmarch_trace_kernel< 4, 4, 1 > );
+   run( "zmarch 4x6 table PFD1", 4, 6, zmarch_trace_kernel< 4, 6, 1 > );
+   run( "zmarch 2x8 table PFD1", 2, 8, zmarch_trace_kernel< 2, 8, 1 > );
+   run( "zmarch 3x8 table PFD1", 3, 8, zmarch_trace_kernel< 3, 8, 1 > );
+   run( "zloop 4x8 renaming(4)", 4, 8, p1_apply_zloop_kernel< APPLY_REPLACE, 4, 4 > );
    return 0;
 }

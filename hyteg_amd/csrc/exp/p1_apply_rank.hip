@@ -67,7 +67,7 @@ __global__ __launch_bounds__( kRankThreads ) void p1_apply_rank_kernel( const Br
    const int b = blockIdx.x;
    if ( b < R.brickBlocks )
    {
-      zmarch_body< MODE, kBrickNY, LZ, MODE == APPLY_ADD ? 2 : 0, false, 2, double >( A, tasks, ntasks, xcd_chunk, A.src, A.dst );
+      zmarch_body< MODE, kBrickNY, LZ, 2, double >( A, tasks, ntasks, xcd_chunk, A.src, A.dst );
       return;
    }
    double*       dst = static_cast< double* >( A.dst );
@@ -142,8 +142,6 @@ int launch_rank( double* dst, const double* src, int level, const double* w, Ran
    A.bytes  = (unsigned) ( tet64( A.N ) * (int64_t) sizeof( double ) );
    for ( int k = 0; k < 15; ++k )
       A.st.w[k] = w[k];
-   for ( int k = 0; k < kZMarchMaxZChunks; ++k )
-      A.zs[k] = bt.zs[k];
    int nblocks   = ( bt.count + kZMarchWavesPerBlock - 1 ) / kZMarchWavesPerBlock;
    nblocks       = ( nblocks + 7 ) & ~7;
    if ( R.dbg & 16 ) // shares + pack only; the caller launches the interior kernel

@@ -16,9 +16,20 @@
 // (no exec masking).  dst is written with nontemporal stores (plain stores leave 22 MB of dirty lines for the
 // end-of-kernel L2 write-back: 14.5 -> 10.4 us at level 8).
 //
-// The superseded variants and ablation switches of round 1 (reference summation order, all-loads-first, unmasked
-// loads, per-lane addressing ...) and their harness are in the history (commit ceeab28, hyteg_amd/csrc/exp/apply_bench.hip);
-// their measurements are profiles/r01_apply_*.txt.
+// The march has ONE compiled form per ( MODE, NY, LZ, PFD, T ): the brick comes from the per-level table (get_bricks), bricks are
+// 62 outputs wide, dst is stored nontemporally, the source is loaded with the plain policy, and the policy of a mode's second
+// array follows from the mode (kExAux below).  Variants that were measured and rejected live in the history, not here:
+//   * round 1's ablation switches (reference summation order, all-loads-first, unmasked loads, per-lane addressing ...) and their
+//     harness: commit ceeab28, hyteg_amd/csrc/exp/apply_bench.hip; measurements profiles/r01_apply_*.txt.
+//   * commit 896fb24 is the last one that carries the following three as template parameters of zmarch_body:
+//       - decode mode (DEC: the brick computed from the task index and z-chunk starts in the kernel arguments, no table load):
+//         12.0 against 10.0 us, HBM regime 13.6-13.7 against 12.1-12.3 us -- ~200 scalar instructions per wave on a scalar unit
+//         that eight waves share (docs/TUNING_LOG_r01_r02.md 3.1, profiles/r03_apply_shape_sweep_hbm.txt);
+//       - aligned store windows (XS = 56: every row segment begins on a 64-byte line of dst): 11.7 against 9.5 us, write requests
+//         389 k -> 383 k -- the extra requests are the lines at row ends, not the segment boundaries;
+//       - cache-policy axes (ST_AUX, SRC_AUX, EX_AUX): nontemporal stores + plain loads 12.4-12.6 us, every other combination
+//         12.5-15.4 us (profiles/r03_apply_shape_sweep_hbm.txt);
+//     and the entry without preloaded arguments (p1_apply_zmarch_kernel; the trace harness exp/apply_trace.hip has its own).
 //
 // Index algebra: W = N-z; element (x,y,z) -> (x,y,z+1): + tri(W) - y;  (x,y,z) -> (x,y+1,z): + (W-y).
 #pragma once
@@ -47,9 +58,6 @@ struct BrickTask
 };
 static_assert( sizeof( BrickTask ) == 64, "BrickTask must be 64 bytes (one s_load_dwordx16)" );
 
-constexpr int kZMarchMaxZChunks = 32; // decode mode: number of z-chunks whose first task index fits the kernel arguments
-constexpr int kZMarchMaxStairs  = 5;  // decode mode: x-chunks of the longest row (N - 4 <= 310: up to level 8)
-
 struct ZMarchArgs
 {
    // cell arrays of the kernel's value type (double, or float: the reference instantiates its generated apply kernels for
@@ -60,14 +68,13 @@ struct ZMarchArgs
    const void*      invdiag; // JACOBI / CHEB_START / CHEB_STEP, may be null
    void*            dst2;    // RESIDUAL_F32OUT: second float output (the first Jacobi iterate of the error equation)
    double*          xacc;    // JACOBI_ACCUM: the double array the last float sweep is added to; CHEB_STEP: the iterate x
-   const BrickTask* tasks;   // table mode (DEC == false)
+   const BrickTask* tasks;   // brick table of the level and shape (get_bricks)
    int              ntasks;
    unsigned         bytes;     // size of the cell array in bytes (buffer range): entries x sizeof( value type )
    int              xcd_chunk; // workgroups per XCD group (0: identity map)
    int              N;         // 2^level + 1
    double           relax;
    Stencil15        st;
-   int              zs[kZMarchMaxZChunks]; // decode mode: first task of z-chunk k (entries past the last chunk = ntasks)
    double           relax2; // CHEB_STEP: coefficient of the deferred update x += relax2 * src ...
    int              flag;   // ... which is applied only if flag != 0
 };
@@ -141,79 +148,13 @@ __host__ __device__ inline void zm_fill_bases( BrickTask& t, int LZ )
    }
 }
 
-// Bricks are enumerated z-chunk, y-chunk, x-chunk (memory order).  z-chunk k: z0 = 1 + LZ k, M = N - 4 - LZ k (>= 1);
-// its y-chunk yc (y0 = 1 + NY yc <= M) has ( M - NY yc + 61 ) / 62 x-chunks of 62 outputs.
-template < int NY, int LZ >
-__host__ __device__ inline BrickTask zm_make_task( int N, int k, int yc, int xc )
-{
-   const int z0 = 1 + LZ * k, W = N - z0, y0 = 1 + NY * yc;
-   BrickTask t{};
-   t.xb = 62 * xc;
-   t.y0 = y0;
-   t.W0 = W + 1;
-   t.i0 = slice_start( N, z0 - 1 ) + row_start( W + 1, y0 - 1 ) + t.xb;
-   t.nz = LZ < N - 3 - z0 ? LZ : N - 3 - z0;
-   return t; // base[] is not filled: the decode mode recomputes the slice bases in the kernel
-}
-
-// Decode mode: the brick of a task index from the z-chunk starts in the kernel arguments, scalar arithmetic only —
-// no dependent table load in front of the brick's first source loads (at level 8 every wave runs ONE brick, so
-// that round trip is on the critical path of the whole launch).  Within a z-chunk the number of x-chunks per
-// y-chunk is a staircase K, K-1, ..., 1 (K <= 5 up to level 8); walk the stairs.
-template < int NY, int LZ >
-__device__ inline BrickTask zm_decode_task( const ZMarchArgs& A, int task )
-{
-   int k = 0, first = 0; // zs is non-decreasing: the last z-chunk whose first task is <= task
-#pragma unroll
-   for ( int i = 1; i < kZMarchMaxZChunks; ++i )
-   {
-      const bool ge = task >= A.zs[i];
-      k             = ge ? i : k;
-      first         = ge ? A.zs[i] : first;
-   }
-   int       t = task - first;
-   const int M = A.N - 4 - LZ * k;
-   const int K = ( M + 61 ) / 62; // x-chunks of the z-chunk's first y-chunk
-   int       yc = 0, xc = 0;
-   bool      found = false;
-#pragma unroll
-   for ( int c = kZMarchMaxStairs; c >= 1; --c )
-   {
-      if ( !found && c <= K )
-      {
-         // y-chunks with exactly c x-chunks: 62(c-1) < M - NY yc <= 62 c
-         const int lo  = M - 62 * c;
-         const int ylo = lo > 0 ? (int) ( (unsigned) ( lo + NY - 1 ) / (unsigned) NY ) : 0;
-         const int yhi = (int) ( (unsigned) ( M - 62 * ( c - 1 ) - 1 ) / (unsigned) NY );
-         const int cnt = ( yhi - ylo + 1 ) * c;
-         if ( t < cnt )
-         {
-            const int q = (int) ( (unsigned) t / (unsigned) c ); // c is a compile-time constant here
-            yc          = ylo + q;
-            xc          = t - q * c;
-            found       = true;
-         }
-         else
-            t -= cnt;
-      }
-   }
-   return zm_make_task< NY, LZ >( A.N, k, yc, xc );
-}
-
-// EX_AUX: cache policy of the second array of ADD (dst, read once: nontemporal) / JACOBI (rhs: plain, the next sweep
-// re-reads it).  gfx950 "aux" bits: 1 = sc0, 2 = nt, 16 = sc1.
 // PFD: how many slices ahead of the one being computed the loads run.
 // T: value type of the arrays and of the arithmetic (double or float; the weights travel as doubles and are converted).
-// XS: x-stride between neighbouring bricks = outputs per row segment.  62: lanes 1..62 of every row are stored (segments begin
-// at x = 1 + 62 k whatever the row's address).  56: ALIGNED store windows -- every row segment of a brick begins at the first
-// boundary of 8 entries of dst (doubles: 64 bytes) inside lanes 1..7 (at a boundary of 4 entries in lane 4 where it would fall
-// on lane 8) and is 56 entries long (doubles: 448 bytes), so that no 64-byte line of dst is written by two waves except the
-// first and the last line of a row (round 3: the PMC write traffic of the 62-wide form is 1.11 x the bytes of dst).
 // srcp / dstp: the source and the destination array of this launch (A.src / A.dst), or of this workgroup's step of a steps launch.
-template < int MODE, int NY, int LZ, int EX_AUX, bool DEC, int PFD, typename T, int XS = 62, int ST_AUX = 2, int SRC_AUX = 0 >
+template < int MODE, int NY, int LZ, int PFD, typename T >
 __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks, int ntasks, int xcd_chunk, const void* srcp, void* dstp )
 {
-   static_assert( XS == 62 || ( XS == 56 && !DEC ), "x-stride: 62 (plain) or 56 (aligned store windows, table mode)" );
+   static_assert( LZ + 2 <= kBrickMaxSlices, "the table carries the slice bases of bricks of up to kBrickMaxSlices - 2 slices" );
    constexpr int SZ = (int) sizeof( T );
    ZM_TRACE( 0 );
    int b = blockIdx.x;
@@ -222,15 +163,11 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
    const int task = __builtin_amdgcn_readfirstlane( b * kZMarchWavesPerBlock + ( threadIdx.x >> 6 ) );
    if ( task >= ntasks )
       return;
-   BrickTask t;
-   if constexpr ( DEC )
-      t = zm_decode_task< NY, LZ >( A, task );
-   else
-      t = tasks[task];
+   const BrickTask t = tasks[task];
    const int lane = threadIdx.x & 63;
    ZM_TRACE( 1 );
 
-   constexpr int kStAux = ST_AUX; // 2 = nontemporal (the default; 1 = sc0, 16 = sc1: measured variants)
+   constexpr int kStAux = 2; // gfx950 "aux" bits: 1 = sc0, 2 = nt, 16 = sc1.  dst is stored nontemporally
    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc( const_cast< void* >( srcp ), 0, A.bytes, 0x00020000 );
    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc( dstp, 0, MODE == APPLY_RESIDUAL_F32OUT ? A.bytes / 2 : A.bytes, 0x00020000 );
    constexpr bool kHasRhs = MODE == APPLY_JACOBI || MODE == APPLY_RESIDUAL || MODE == APPLY_RESIDUAL_F32OUT || MODE == APPLY_JACOBI_ACCUM ||
@@ -248,8 +185,6 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
 
    const int lane_off = lane * SZ;
    const int ym       = t.y0 - 1; // first row held per slice
-   // aligned windows: entry index of dst's first byte in units of the value type, modulo one 64-byte line
-   const int dst_phase = XS == 56 ? (int) ( ( reinterpret_cast< uintptr_t >( dstp ) / SZ ) & 7 ) : 0;
 
    // S[q][r]: slice z0-1+q, row ym+r (r = 0..NY+1), x = xb + lane.  q = 0..LZ+1.
    T S[LZ + 2][NY + 2];
@@ -268,26 +203,19 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
          if ( need )
          {
             const int last8 = ( W_q - ( ym + r ) - 1 - t.xb ) * SZ; // byte offset of the row's last entry from lane 0's
-            S[q][r]         = zm_load2< T, SRC_AUX >( rs, min( lane_off, last8 ), ix * SZ );
+            S[q][r]         = zm_load2< T >( rs, min( lane_off, last8 ), ix * SZ );
          }
          ix += W_q - ( ym + r ); // next row of the same slice
       }
    };
 
-   // wave-uniform element index of (xb, ym, z0-1+q) and row-0 length of that slice
-   // (bricks taller than the table's base array -- experimental shapes -- compute their slice bases here)
-   constexpr bool kBasesFromTable = !DEC && LZ + 2 <= kBrickMaxSlices;
+   // wave-uniform element index of (xb, ym, z0-1+q), from the table, and row-0 length of that slice
    int baseq[LZ + 2], Wqs[LZ + 2];
-   {
-      int base = t.i0, Wq = t.W0;
 #pragma unroll
-      for ( int q = 0; q < LZ + 2; ++q )
-      {
-         baseq[q] = !kBasesFromTable ? base : t.base[q < kBrickMaxSlices ? q : 0];
-         Wqs[q]   = Wq;
-         base += tri( Wq ) - ym; // (x, ym, z) -> (x, ym, z+1)
-         Wq -= 1;
-      }
+   for ( int q = 0; q < LZ + 2; ++q )
+   {
+      baseq[q] = t.base[q];
+      Wqs[q]   = t.W0 - q;
    }
    // prologue: slices 0 .. 1+PFD
    [&]< int... Is >( std::integer_sequence< int, Is... > ) {
@@ -307,6 +235,11 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
    // well, like the source slices (round 1 issued them at the top of the step that consumes them: the wave then waited a
    // whole memory round trip at its first store of every slice -- 16.9 us for the fused Jacobi against 9.7 us for the apply,
    // i.e. 7 us for 23 MB more).
+   // Cache policy of that second array: dst of Add is read exactly once per element and written right after: nontemporal load
+   // (18.6 -> 17.2 us).  rhs / inverse diagonal of Jacobi are re-read by the next sweep of the smoother and stay plain (nontemporal:
+   // 12.4 -> 17.6 us when they are still in the Infinity Cache, -2% when they are not); the right-hand side of the residual
+   // modes is re-read by the cycle: plain.
+   constexpr int kExAux = MODE == APPLY_ADD ? 2 : 0;
    T          EX0[LZ][NY], EX1[LZ][NY];
    double     EXD[LZ][NY]; // JACOBI_ACCUM: the accumulator's old values; CHEB_STEP: the iterate's
    const bool hasInv = kHasInv && A.invdiag != nullptr;
@@ -325,7 +258,7 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
             if constexpr ( MODE == APPLY_CHEB_STEP )
                EXD[s][j] = zm_load2< double, 0 >( rx, vo, ie * 8 ); // x: read and rewritten by this lane only; the next step re-reads it
             else
-               EX0[s][j] = MODE == APPLY_ADD ? zm_load2< T, EX_AUX >( rd, vo, ie * SZ ) : zm_load2< T, EX_AUX >( rr, vo, ie * SZ );
+               EX0[s][j] = MODE == APPLY_ADD ? zm_load2< T, kExAux >( rd, vo, ie * SZ ) : zm_load2< T, kExAux >( rr, vo, ie * SZ );
             if constexpr ( MODE == APPLY_JACOBI_ACCUM )
                EXD[s][j] = zm_load2< double, 2 >( rx, min( lane * 8, last8 * 2 ), ie * 8 ); // read once, rewritten right after: nontemporal
             if constexpr ( kHasInv )
@@ -398,47 +331,32 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
             out = EX1[s][j] * acc;
          else
             out = a0 + relax * ( EX1[s][j] * ( EX0[s][j] - acc ) );
-         if constexpr ( XS == 62 )
+         // outputs are lanes 1 .. min( 62, R - 2 - xb ) of slices that exist: one unsigned compare of (lane - 1)
+         const int      cnt = s < t.nz ? min( 62, R - 2 - t.xb ) : 0; // wave-uniform
+         const unsigned lm1 = (unsigned) ( lane - 1 );
+         const bool     on  = lm1 < (unsigned) max( cnt, 0 );
+         if constexpr ( MODE == APPLY_RESIDUAL_F32OUT )
          {
-            // outputs are lanes 1 .. min( 62, R - 2 - xb ) of slices that exist: one unsigned compare of (lane - 1)
-            const int      cnt = s < t.nz ? min( 62, R - 2 - t.xb ) : 0; // wave-uniform
-            const unsigned lm1 = (unsigned) ( lane - 1 );
-            const bool     on  = lm1 < (unsigned) max( cnt, 0 );
-            if constexpr ( MODE == APPLY_RESIDUAL_F32OUT )
-            {
-               // r as float, and the first Jacobi iterate of A e = r from e = 0: relax * r / centre (float arithmetic)
-               const float rf = (float) out;
-               zm_store2< float, 0 >( rd, on ? lane * 4 : -8, io * 4, rf ); // re-read by the following float sweeps: not nontemporal
-               zm_store2< float, 0 >( rd2, on ? lane * 4 : -8, io * 4, (float) relax * ( (float) invc * rf ) );
-            }
-            else if constexpr ( MODE == APPLY_JACOBI_ACCUM )
-               zm_store2< double, kStAux >( rx, on ? lane * 8 : -8, io * 8, EXD[s][j] + (double) out );
-            else if constexpr ( MODE == APPLY_CHEB_STEP )
-            {
-               // x = ( x + c_prev t_in ) + c_cur t_out: the update the previous launch deferred (x was its stencil source or t_in did
-               // not exist yet), then this step's; t_in's centre value is the register the stencil read it into
-               double xn = EXD[s][j];
-               if ( A.flag ) // wave-uniform
-                  xn = xn + (double) A.relax2 * (double) a0;
-               xn = xn + (double) relax * (double) out;
-               zm_store2< T, kStAux >( rd, on ? lane_off : -8, io * SZ, out );
-               zm_store2< double, kStAux >( rx, on ? lane * 8 : -8, io * 8, xn );
-            }
-            else
-               zm_store2< T, kStAux >( rd, on ? lane_off : -8, io * SZ, out );
+            // r as float, and the first Jacobi iterate of A e = r from e = 0: relax * r / centre (float arithmetic)
+            const float rf = (float) out;
+            zm_store2< float, 0 >( rd, on ? lane * 4 : -8, io * 4, rf ); // re-read by the following float sweeps: not nontemporal
+            zm_store2< float, 0 >( rd2, on ? lane * 4 : -8, io * 4, (float) relax * ( (float) invc * rf ) );
+         }
+         else if constexpr ( MODE == APPLY_JACOBI_ACCUM )
+            zm_store2< double, kStAux >( rx, on ? lane * 8 : -8, io * 8, EXD[s][j] + (double) out );
+         else if constexpr ( MODE == APPLY_CHEB_STEP )
+         {
+            // x = ( x + c_prev t_in ) + c_cur t_out: the update the previous launch deferred (x was its stencil source or t_in did
+            // not exist yet), then this step's; t_in's centre value is the register the stencil read it into
+            double xn = EXD[s][j];
+            if ( A.flag ) // wave-uniform
+               xn = xn + (double) A.relax2 * (double) a0;
+            xn = xn + (double) relax * (double) out;
+            zm_store2< T, kStAux >( rd, on ? lane_off : -8, io * SZ, out );
+            zm_store2< double, kStAux >( rx, on ? lane * 8 : -8, io * 8, xn );
          }
          else
-         {
-            // lanes [lo, hi): lo = the lane in 1..7 whose entry begins a 64-byte line of dst (lane 4 = a 32-byte boundary when
-            // that lane would be 8); the row's first brick starts at x = 1 instead; hi = lo + 56 clipped to the last inner x.
-            // A neighbour brick (xb + 56) computes the same lo for this row, so the windows tile the row.
-            int lo = ( ( -( io + dst_phase ) - 1 ) & 7 ) + 1; // 1 .. 8: first lane whose entry index is a multiple of 8
-            lo     = lo == 8 ? 4 : lo;
-            const int hi  = s < t.nz ? min( lo + 56, R - 1 - t.xb ) : 0;
-            const int lo1 = t.xb == 0 ? 1 : lo;
-            static_assert( MODE != APPLY_CHEB_STEP, "the Chebyshev step has no aligned-window form" );
-            zm_store2< T, kStAux >( rd, (unsigned) ( lane - lo1 ) < (unsigned) max( hi - lo1, 0 ) ? lane_off : -8, io * SZ, out );
-         }
+            zm_store2< T, kStAux >( rd, on ? lane_off : -8, io * SZ, out );
          io += R;
       }
    };
@@ -449,21 +367,15 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
    ZM_TRACE( 4 );
 }
 
-template < int MODE, int NY, int LZ, int EX_AUX = 0, bool DEC = false, int PFD = 1, typename T = double, int XS = 62 >
-__global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void p1_apply_zmarch_kernel( const ZMarchArgs A )
-{
-   zmarch_body< MODE, NY, LZ, EX_AUX, DEC, PFD, T, XS >( A, A.tasks, A.ntasks, A.xcd_chunk, A.src, A.dst );
-}
-
-// The same kernel with the three values a wave needs before it can fetch its brick -- table pointer, task count, XCD chunk --
-// as leading scalar arguments: built with -mllvm -amdgpu-kernarg-preload-count=4 the command processor places them in SGPRs
+// The one-apply kernel.  The three values a wave needs before it can fetch its brick -- table pointer, task count, XCD chunk --
+// are leading scalar arguments: built with -mllvm -amdgpu-kernarg-preload-count=4 the command processor places them in SGPRs
 // at wave launch, so the task load does not wait for a kernel-argument load first (one scalar round trip less in the start-up
 // chain of DESIGN 3.1).  The rest of the arguments stay in the struct.
-template < int MODE, int NY, int LZ, int EX_AUX = 0, bool DEC = false, int PFD = 1, typename T = double, int XS = 62, int ST_AUX = 2, int SRC_AUX = 0 >
+template < int MODE, int NY, int LZ, int PFD, typename T >
 __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void p1_apply_zmarch_preload_kernel( const BrickTask* tasks, int ntasks, int xcd_chunk,
                                                                                               const ZMarchArgs A )
 {
-   zmarch_body< MODE, NY, LZ, EX_AUX, DEC, PFD, T, XS, ST_AUX, SRC_AUX >( A, tasks, ntasks, xcd_chunk, A.src, A.dst );
+   zmarch_body< MODE, NY, LZ, PFD, T >( A, tasks, ntasks, xcd_chunk, A.src, A.dst );
 }
 
 // "Steps" launch: the bricks of up to kZMarchMaxSteps INDEPENDENT applies of one stencil on one macro-cell geometry in one grid,
@@ -481,32 +393,27 @@ struct ZMarchStepPtrs
    void*       dsts[kZMarchMaxSteps];
 };
 
-template < int MODE, int NY, int LZ, int EX_AUX, int PFD, typename T >
+template < int MODE, int NY, int LZ, int PFD, typename T >
 __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void p1_apply_zmarch_steps_kernel( const BrickTask* tasks, int ntasks, int xcd_chunk,
                                                                                             const ZMarchArgs A, const ZMarchStepPtrs P )
 {
    static_assert( MODE == APPLY_REPLACE || MODE == APPLY_ADD, "a steps launch has one source and one destination per step" );
    const unsigned step = blockIdx.y < (unsigned) kZMarchMaxSteps ? blockIdx.y : 0u; // the host never launches more
-   zmarch_body< MODE, NY, LZ, EX_AUX, false, PFD, T >( A, tasks, ntasks, xcd_chunk, P.srcs[step], P.dsts[step] );
+   zmarch_body< MODE, NY, LZ, PFD, T >( A, tasks, ntasks, xcd_chunk, P.srcs[step], P.dsts[step] );
 }
 
-// host: bricks of NY rows x XS outputs x LZ slices, ordered z-chunk, y-chunk, x-chunk (memory order); zs (optional)
-// receives the first task index of every z-chunk followed by the total
-inline void build_brick_tasks( int level, int NY, int LZ, std::vector< BrickTask >& out, std::vector< int >* zs = nullptr, int XS = 62 )
+// host: bricks of NY rows x 62 outputs x LZ slices, ordered z-chunk, y-chunk, x-chunk (memory order)
+inline void build_brick_tasks( int level, int NY, int LZ, std::vector< BrickTask >& out )
 {
    const int N = ( 1 << level ) + 1;
    out.clear();
-   if ( zs )
-      zs->clear();
    for ( int z0 = 1; z0 <= N - 4; z0 += LZ )
    {
-      if ( zs )
-         zs->push_back( (int) out.size() );
       const int W = N - z0; // row-0 length of the first output slice
       for ( int y0 = 1; y0 <= W - 3; y0 += NY )
       {
          const int xmax = W - y0 - 2; // last interior x of the brick's longest row
-         for ( int x0 = 1; x0 <= xmax; x0 += XS )
+         for ( int x0 = 1; x0 <= xmax; x0 += 62 )
          {
             BrickTask t{};
             t.xb = x0 - 1;
@@ -519,8 +426,6 @@ inline void build_brick_tasks( int level, int NY, int LZ, std::vector< BrickTask
          }
       }
    }
-   if ( zs )
-      zs->push_back( (int) out.size() );
 }
 
 } // namespace hyteg_hip

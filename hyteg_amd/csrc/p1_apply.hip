@@ -13,11 +13,8 @@ namespace {
 constexpr int kTile = 1024;
 
 // Brick shape of the z-march kernel: rows x slices per wave, and how many slices the loads run ahead of the arithmetic.
-// Level 8 has only ~64k wave-rows for 1024 SIMDs, so the shape trades reuse (taller / wider bricks re-read fewer halo rows
-// and slices) against the number of waves and against the share of a wave's loads that precede its first store (the
-// prologue: (2 + PFD) of LZ + 2 slices).  Round 3 swept the shapes with bench.py (profiles/r03_apply_shape_sweep.txt):
-// at level 8 more, shorter waves with a short prologue win -- 2 x 8, one slice ahead: 9.17-9.26 us against 9.53-9.57 us for
-// round 2's 4 x 8, two slices ahead; everything taller or wider is slower (4 x 16: 13.3, 6 x 8: 11.1, 4 x 12: 11.0 us).
+// The shape trades reuse (taller / wider bricks re-read fewer halo rows and slices) against the number of waves and against the
+// share of a wave's loads that precede its first store (the prologue: (2 + PFD) of LZ + 2 slices).
 struct BrickShape
 {
    int  ny, lz, pfd;
@@ -25,16 +22,16 @@ struct BrickShape
 };
 BrickShape g_shape_override{ 0, 0, 0 }; // hyteg_hip_set_apply_shape (tuning knob; 0 = the defaults below)
 
-// defaults read off the sweep of every compiled shape x mode x level (tools/apply_shape_sweep.py,
-// profiles/r03_apply_shape_sweep.txt): levels <= 7 (few hundred bricks, cache-resident) want many short waves; level 8
-// (one generation of waves, HBM-bound) wants 8 slices and a short prologue, two rows for the two-stream kernels and four for
-// the three-stream ones; from level 9 on (several generations) 4 x 4, two slices ahead
+// Defaults read off the sweep of every compiled shape x mode x level (tools/apply_shape_sweep.py) with every operand class 2.2 x
+// larger than the Infinity Cache (HBM regime, profiles/r03_apply_shape_sweep_hbm.txt).  Levels <= 7 (a few hundred bricks, arrays
+// of a few MB: cache-resident in any cycle) want many short waves.  Level 8 (one generation of waves, HBM-bound) wants 4 x 8, two
+// slices ahead, and one slice ahead for the modes that read a second array and store one (Add, residual: 16.6 against 17.2 /
+// 17.3 us); everything taller or wider is slower (6 x 8: 15.3, 4 x 16: 17.3 us against 12.2-12.55).  From level 9 on (several
+// generations, HBM either way) 4 x 4, two ahead.  The first sweep of round 3 (profiles/r03_apply_shape_sweep.txt) ran on rings
+// whose SOURCE arrays fitted into the Infinity Cache and preferred 2 x 8, one slice ahead, for level-8 Replace (9.15 against
+// 9.50 us); read from HBM that shape is the slower one (13.3 against 12.5 us).
 inline BrickShape default_shape( int mode, int level, bool f32 )
 {
-   // Chosen from tools/apply_shape_sweep.py with every operand class 2.2 x larger than the Infinity Cache (HBM regime,
-   // profiles/r03_apply_shape_sweep_hbm.txt).  The first sweep of round 3 ran on rings whose SOURCE arrays fitted into that cache
-   // and preferred 2 x 8, one slice ahead, for level-8 Replace (9.15 against 9.50 us); read from HBM that shape is the slower
-   // one (13.3 against 12.5 us).  Levels <= 7: arrays of a few MB, cache-resident in any cycle; levels >= 9: HBM either way.
    if ( level <= 7 )
       return ( mode == APPLY_REPLACE || f32 ) ? BrickShape{ 2, 4, 1 } : BrickShape{ 4, 4, 1 };
    if ( level == 8 )
@@ -42,10 +39,55 @@ inline BrickShape default_shape( int mode, int level, bool f32 )
    return BrickShape{ 4, 4, 2 };
 }
 
-// what every z-march launch of a level carries whatever its arrays: brick table, extents, stencil, XCD slab map
-template < typename T >
-int zmarch_common_args( ZMarchArgs& A, int& nblocks, const BrickTable& bt, int level, const double* w )
+// the shapes compiled in: the defaults and the runners-up of the sweep (so that the sweep can be repeated on another box)
+#define HYTEG_ZM_SHAPES( X ) X( 2, 8, 1 ) X( 4, 8, 2 ) X( 4, 8, 1 ) X( 4, 4, 2 ) X( 4, 4, 1 ) X( 2, 4, 1 ) X( 8, 4, 2 )
+
+// run-time shape -> compile-time ( NY, LZ, PFD ): calls f with the three as std::integral_constant arguments if s is compiled
+// in and says whether it is.  The one expansion of HYTEG_ZM_SHAPES.
+template < typename F >
+bool with_compiled_shape( const BrickShape& s, F&& f )
 {
+#define HH_X( NY_, LZ_, PFD_ ) \
+   if ( s == BrickShape{ NY_, LZ_, PFD_ } ) \
+      return f( std::integral_constant< int, NY_ >{}, std::integral_constant< int, LZ_ >{}, std::integral_constant< int, PFD_ >{} ), true;
+   HYTEG_ZM_SHAPES( HH_X )
+#undef HH_X
+   return false;
+}
+
+inline bool shape_compiled( const BrickShape& s )
+{
+   return with_compiled_shape( s, []( auto, auto, auto ) {} );
+}
+
+// the shape of a launch: hyteg_hip_set_apply_shape, else HYTEG_HIP_APPLY_SHAPE=NYxLZxPFD from the environment (read once;
+// lets tools/gpu/r03_shapes.sh A/B whole bench.py runs), else the default of the mode and level
+inline BrickShape current_shape( int mode, int level, bool f32 )
+{
+   static const BrickShape env = [] {
+      BrickShape  e{ 0, 0, 0 };
+      const char* v = getenv( "HYTEG_HIP_APPLY_SHAPE" );
+      if ( v && sscanf( v, "%dx%dx%d", &e.ny, &e.lz, &e.pfd ) != 3 )
+         e = BrickShape{ -1, -1, -1 }; // unparsable: every launch fails with "not compiled in"
+      return e;
+   }();
+   if ( g_shape_override.ny )
+      return g_shape_override;
+   if ( env.ny )
+      return env;
+   return default_shape( mode, level, f32 );
+}
+
+// what every z-march launch of a level and shape carries whatever its arrays: brick table, extents, stencil, XCD slab map.
+// nblocks = 0 on return: no bricks, nothing to launch
+template < typename T >
+int zmarch_common_args( ZMarchArgs& A, int& nblocks, int NY, int LZ, int level, const double* w )
+{
+   nblocks = 0;
+   BrickTable bt;
+   int        rc = get_bricks( level, NY, LZ, &bt );
+   if ( rc != HYTEG_HIP_OK || bt.count == 0 )
+      return rc;
    A.tasks  = bt.dev;
    A.ntasks = bt.count;
    A.N      = ( 1 << level ) + 1;
@@ -66,17 +108,13 @@ int zmarch_common_args( ZMarchArgs& A, int& nblocks, const BrickTable& bt, int l
 // (whose deferred update is relax2, applied if flag != 0)
 template < int MODE, int NY, int LZ, int PFD, typename T >
 int launch_zmarch_shape( void* dst, const T* src, const T* rhs, const T* invdiag, int level, const double* w, double relax, hipStream_t stream,
-                         void* extra = nullptr, double relax2 = 0.0, int flag = 0 )
+                         void* extra, double relax2, int flag )
 {
-   BrickTable bt;
-   int        rc = get_bricks( level, NY, LZ, &bt );
-   if ( rc != HYTEG_HIP_OK )
-      return rc;
-   if ( bt.count == 0 )
-      return HYTEG_HIP_OK;
    ZMarchArgs A{};
    int        nblocks = 0;
-   zmarch_common_args< T >( A, nblocks, bt, level, w );
+   const int  rc      = zmarch_common_args< T >( A, nblocks, NY, LZ, level, w );
+   if ( rc != HYTEG_HIP_OK || nblocks == 0 )
+      return rc;
    A.dst     = dst;
    A.src     = src;
    A.rhs     = rhs;
@@ -86,14 +124,10 @@ int launch_zmarch_shape( void* dst, const T* src, const T* rhs, const T* invdiag
    A.relax   = relax;
    A.relax2  = relax2;
    A.flag    = flag;
-   // dst of Add is read exactly once per element and written right after: nontemporal load (18.6 -> 17.2 us).  rhs /
-   // inverse diagonal of Jacobi are re-read by the next sweep of the smoother and stay plain (nontemporal: 12.4 -> 17.6 us
-   // when they are still in the Infinity Cache, -2% when they are not).
-   constexpr int kExAux = MODE == APPLY_ADD ? 2 : 0; // (the right-hand side of the residual mode is re-read by the cycle: plain)
    // the first three arguments are preloaded into SGPRs (-mllvm -amdgpu-kernarg-preload-count=4): the task load does not wait
    // for a kernel-argument load (round 2: 9.90-10.18 -> 9.60-9.74 us)
-   hipLaunchKernelGGL( ( p1_apply_zmarch_preload_kernel< MODE, NY, LZ, kExAux, false, PFD, T > ), dim3( nblocks ), dim3( 64 * kZMarchWavesPerBlock ), 0,
-                       stream, A.tasks, A.ntasks, A.xcd_chunk, A );
+   hipLaunchKernelGGL( ( p1_apply_zmarch_preload_kernel< MODE, NY, LZ, PFD, T > ), dim3( nblocks ), dim3( 64 * kZMarchWavesPerBlock ), 0, stream, A.tasks,
+                       A.ntasks, A.xcd_chunk, A );
    HH_CHECK_HIP( hipGetLastError() );
    return HYTEG_HIP_OK;
 }
@@ -119,15 +153,11 @@ template < int MODE, int NY, int LZ, int PFD >
 int launch_zmarch_steps_shape( void* const* dsts, const void* const* srcs, int nsteps, int level, const double* w, hipStream_t stream )
 {
    static_assert( MODE == APPLY_REPLACE || MODE == APPLY_ADD, "steps launch: Replace and Add" );
-   BrickTable bt;
-   int        rc = get_bricks( level, NY, LZ, &bt );
-   if ( rc != HYTEG_HIP_OK )
-      return rc;
-   if ( bt.count == 0 )
-      return HYTEG_HIP_OK;
    ZMarchArgs A{};
    int        nblocks = 0;
-   zmarch_common_args< double >( A, nblocks, bt, level, w );
+   const int  rc      = zmarch_common_args< double >( A, nblocks, NY, LZ, level, w );
+   if ( rc != HYTEG_HIP_OK || nblocks == 0 )
+      return rc;
    ZMarchStepPtrs P{};
    for ( int k = 0; k < kZMarchMaxSteps; ++k ) // the entries past nsteps repeat step 0: no wave reads them, none is null
    {
@@ -136,9 +166,8 @@ int launch_zmarch_steps_shape( void* const* dsts, const void* const* srcs, int n
    }
    A.src = P.srcs[0];
    A.dst = P.dsts[0];
-   constexpr int kExAux = MODE == APPLY_ADD ? 2 : 0;
-   auto          kern   = p1_apply_zmarch_steps_kernel< MODE, NY, LZ, kExAux, PFD, double >;
-   const unsigned lds   = steps_lds_request( level );
+   auto           kern = p1_apply_zmarch_steps_kernel< MODE, NY, LZ, PFD, double >;
+   const unsigned lds  = steps_lds_request( level );
    if ( lds > 0 )
    {
       static const hipError_t attr = hipFuncSetAttribute( reinterpret_cast< const void* >( kern ), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds );
@@ -149,37 +178,6 @@ int launch_zmarch_steps_shape( void* const* dsts, const void* const* srcs, int n
    return HYTEG_HIP_OK;
 }
 
-// the shapes compiled in: the defaults and the runners-up of the sweep (so that the sweep can be repeated on another box)
-#define HYTEG_ZM_SHAPES( X ) X( 2, 8, 1 ) X( 4, 8, 2 ) X( 4, 8, 1 ) X( 4, 4, 2 ) X( 4, 4, 1 ) X( 2, 4, 1 ) X( 8, 4, 2 )
-
-inline bool shape_compiled( const BrickShape& s )
-{
-#define HH_X( NY_, LZ_, PFD_ ) \
-   if ( s == BrickShape{ NY_, LZ_, PFD_ } ) \
-      return true;
-   HYTEG_ZM_SHAPES( HH_X )
-#undef HH_X
-   return false;
-}
-
-// the shape of a launch: hyteg_hip_set_apply_shape, else HYTEG_HIP_APPLY_SHAPE=NYxLZxPFD from the environment (read once;
-// lets tools/gpu/r03_shapes.sh A/B whole bench.py runs), else the default of the mode and level
-inline BrickShape current_shape( int mode, int level, bool f32 )
-{
-   static const BrickShape env = [] {
-      BrickShape  e{ 0, 0, 0 };
-      const char* v = getenv( "HYTEG_HIP_APPLY_SHAPE" );
-      if ( v && sscanf( v, "%dx%dx%d", &e.ny, &e.lz, &e.pfd ) != 3 )
-         e = BrickShape{ -1, -1, -1 }; // unparsable: every launch fails with "not compiled in"
-      return e;
-   }();
-   if ( g_shape_override.ny )
-      return g_shape_override;
-   if ( env.ny )
-      return env;
-   return default_shape( mode, level, f32 );
-}
-
 template < int MODE, typename T = double >
 int launch_zmarch( void* dst, const T* src, const T* rhs, const T* invdiag, int level, const double* w, double relax, hipStream_t stream,
                    void* extra = nullptr, double relax2 = 0.0, int flag = 0 )
@@ -188,25 +186,22 @@ int launch_zmarch( void* dst, const T* src, const T* rhs, const T* invdiag, int 
    // stream three / four arrays like the Jacobi sweep and take its shapes
    const int shapeMode = MODE == APPLY_RESIDUAL_F32OUT ? APPLY_RESIDUAL :
                                                          ( ( MODE == APPLY_JACOBI_ACCUM || MODE == APPLY_CHEB_START || MODE == APPLY_CHEB_STEP ) ? APPLY_JACOBI : MODE );
-   const BrickShape s         = current_shape( shapeMode, level, !std::is_same< T, double >::value );
-#define HH_X( NY_, LZ_, PFD_ ) \
-   if ( s == BrickShape{ NY_, LZ_, PFD_ } ) \
-      return launch_zmarch_shape< MODE, NY_, LZ_, PFD_, T >( dst, src, rhs, invdiag, level, w, relax, stream, extra, relax2, flag );
-   HYTEG_ZM_SHAPES( HH_X )
-#undef HH_X
-   return fail( HYTEG_HIP_EINVAL, "apply: brick shape not compiled in" );
+   int        rc       = HYTEG_HIP_OK;
+   const bool compiled = with_compiled_shape( current_shape( shapeMode, level, !std::is_same< T, double >::value ), [&]( auto ny, auto lz, auto pfd ) {
+      rc = launch_zmarch_shape< MODE, decltype( ny )::value, decltype( lz )::value, decltype( pfd )::value, T >( dst, src, rhs, invdiag, level, w, relax, stream,
+                                                                                                                 extra, relax2, flag );
+   } );
+   return compiled ? rc : fail( HYTEG_HIP_EINVAL, "apply: brick shape not compiled in" );
 }
 
 template < int MODE >
 int launch_zmarch_steps( void* const* dsts, const void* const* srcs, int nsteps, int level, const double* w, hipStream_t stream )
 {
-   const BrickShape s = current_shape( MODE, level, false );
-#define HH_X( NY_, LZ_, PFD_ ) \
-   if ( s == BrickShape{ NY_, LZ_, PFD_ } ) \
-      return launch_zmarch_steps_shape< MODE, NY_, LZ_, PFD_ >( dsts, srcs, nsteps, level, w, stream );
-   HYTEG_ZM_SHAPES( HH_X )
-#undef HH_X
-   return fail( HYTEG_HIP_EINVAL, "apply steps: brick shape not compiled in" );
+   int        rc       = HYTEG_HIP_OK;
+   const bool compiled = with_compiled_shape( current_shape( MODE, level, false ), [&]( auto ny, auto lz, auto pfd ) {
+      rc = launch_zmarch_steps_shape< MODE, decltype( ny )::value, decltype( lz )::value, decltype( pfd )::value >( dsts, srcs, nsteps, level, w, stream );
+   } );
+   return compiled ? rc : fail( HYTEG_HIP_EINVAL, "apply steps: brick shape not compiled in" );
 }
 
 // Does this level run the z-march register kernel?  Yes whenever the byte offsets of the array fit its 32-bit buffer addressing

@@ -102,14 +102,13 @@ int get_tiles( int level, TileKind kind, int capacity, TileTable* out )
    return rc;
 }
 
-int get_bricks( int level, int NY, int LZ, BrickTable* out, int XS )
+int get_bricks( int level, int NY, int LZ, BrickTable* out )
 {
    // hot path: the same (level, shape) is asked for on every launch
    thread_local int        lastKey[4] = { -1, -1, -1, -1 };
    thread_local BrickTable lastVal;
    int                     dev0 = 0;
    HH_CHECK_HIP( hipGetDevice( &dev0 ) );
-   NY = NY * 1000 + XS; // the key's shape entry carries the x-stride
    if ( lastKey[0] == dev0 && lastKey[1] == level && lastKey[2] == NY && lastKey[3] == LZ )
    {
       *out = lastVal;
@@ -120,13 +119,8 @@ int get_bricks( int level, int NY, int LZ, BrickTable* out, int XS )
    const int rc = cache.get_on( dev0, std::make_tuple( level, NY, LZ ),
                                 [&]( BrickTable& b ) {
                                    std::vector< BrickTask > host;
-                                   std::vector< int >       zs;
-                                   build_brick_tasks( level, NY / 1000, LZ, host, &zs, XS );
+                                   build_brick_tasks( level, NY, LZ, host );
                                    b.count = (int) host.size();
-                                   // decode mode: zs = starts of the z-chunks followed by the total
-                                   b.decodable = XS == 62 && (int) zs.size() - 1 <= kZMarchMaxZChunks && ( 1 << level ) - 3 <= 62 * kZMarchMaxStairs;
-                                   for ( int k = 0; k < kZMarchMaxZChunks; ++k )
-                                      b.zs[k] = k + 1 < (int) zs.size() ? zs[k] : b.count;
                                    return upload_table( host, &b.dev );
                                 },
                                 &bt );

@@ -191,8 +191,10 @@ HYTEG_HIP_API int hyteg_hip_p1_jacobi_accumulate_f32( double* x, const float* rh
                                                       hyteg_hip_stream_t stream );
 
 /* Name of the kernel instantiation hyteg_hip_p1_apply_cell( ..., level, ..., update, ... ) launches on the current device,
- * with its template arguments, e.g. "p1_apply_zmarch_preload_kernel<MODE=0,NY=2,LZ=8,EX_AUX=0,DEC=0,PFD=1>" — what profiler
- * output and recorded counter files are matched against (no reference counterpart: measurement support). */
+ * with its template arguments, e.g. "p1_apply_zmarch_preload_kernel<MODE=0,NY=4,LZ=8,EX_AUX=0,DEC=0,PFD=2>" — what profiler
+ * output and recorded counter files are matched against (no reference counterpart: measurement support).  EX_AUX (2 for Add,
+ * 0 otherwise) and DEC (always 0) are no template arguments of the kernel any more: they are constants kept for continuity of
+ * the recorded names. */
 HYTEG_HIP_API int hyteg_hip_p1_apply_kernel_name( int level, int update, char* buf, size_t buflen );
 /* Tuning knob (measurement support, like hyteg_hip_set_sor_algorithm): brick shape of the z-march apply / Jacobi / residual
  * kernels for all later launches of this process -- ny rows x lz slices per wave, loads pfd slices ahead of the arithmetic.

@@ -34,7 +34,7 @@ def mean_counter(prefix, kernel_substr, counter):
     return (sum(vals) / len(vals), len(vals)) if vals else (None, 0)
 
 
-KERNEL = "p1_apply_zmarch_"  # p1_apply_zmarch_kernel or p1_apply_zmarch_preload_kernel (first arguments preloaded into SGPRs)
+KERNEL = "p1_apply_zmarch_"  # p1_apply_zmarch_preload_kernel (first arguments preloaded into SGPRs)
 fetch, nf = mean_counter("bench", KERNEL, "FETCH_SIZE")
 write, nw = mean_counter("bench", KERNEL, "WRITE_SIZE")
 cfetch, _ = mean_counter("bench", "calib_copy_kernel<true>", "FETCH_SIZE")
@@ -52,17 +52,18 @@ if None in (fetch, write, cfetch, cwrite):
 
 
 def capi_kernel_name(rocprof_name):
-    """'void hyteg_hip::p1_apply_zmarch_kernel<0, 4, 8, 0, false, 2, double>' -> the form hyteg_hip_p1_apply_kernel_name
-    (and bench.py's roofline.kernel) uses: 'p1_apply_zmarch_kernel<MODE=0,NY=4,LZ=8,EX_AUX=0,DEC=0,PFD=2>'"""
+    """'void hyteg_hip::p1_apply_zmarch_preload_kernel<0, 4, 8, 2, double>' (template arguments MODE, NY, LZ, PFD, T) -> the form
+    hyteg_hip_p1_apply_kernel_name (and bench.py's roofline.kernel) uses:
+    'p1_apply_zmarch_preload_kernel<MODE=0,NY=4,LZ=8,EX_AUX=0,DEC=0,PFD=2>'.  EX_AUX (2 for MODE 1 = Add, else 0) and DEC=0 are
+    constants of that form, kept for continuity of the recorded names."""
     import re
 
     m = re.search(r"(p1_apply_zmarch_(?:preload_)?kernel)<([^>]*)>", rocprof_name)
     if not m:
         return None
-    a = [x.strip() for x in m.group(2).split(",")]
-    dec = {"false": "0", "true": "1"}.get(a[4], a[4])
-    name = f"{m.group(1)}<MODE={a[0]},NY={a[1]},LZ={a[2]},EX_AUX={a[3]},DEC={dec},PFD={a[5]}>"
-    return name if len(a) < 7 or a[6] == "double" else name[:-1] + f",T={a[6]}>"
+    mode, ny, lz, pfd, t = [x.strip() for x in m.group(2).split(",")]
+    name = f"{m.group(1)}<MODE={mode},NY={ny},LZ={lz},EX_AUX={2 if mode == '1' else 0},DEC=0,PFD={pfd}>"
+    return name if t == "double" else name[:-1] + f",T={t}>"
 
 
 import subprocess
