@@ -116,6 +116,8 @@ SIGNATURES = {
     "hyteg_hip_p2_build_operator_table": (_i, [_dp, _dp]),
     "hyteg_hip_p2_prolongate_cell": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_uint, _vp]),
     "hyteg_hip_p2_restrict_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, C.c_uint, _vp]),
+    "hyteg_hip_p2_restrict_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _vp, C.POINTER(C.c_uint), _vp]),
+    "hyteg_hip_p2_prolongate_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, C.POINTER(C.c_uint), _vp]),
     "hyteg_hip_p2_edge_vector_cell_masked": (_i, [_i, _vp, _i, C.POINTER(_vp), _dp, _i, C.c_uint, _vp]),
     "hyteg_hip_p2_edge_vector_cell_kinds": (_i, [_i, _vp, _i, C.POINTER(_vp), _dp, _i, C.c_uint, C.c_uint, _vp]),
     "hyteg_hip_p2_elementwise_apply_cells_kinds": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_vp), _d, _i,
@@ -512,6 +514,18 @@ def p1_restrict_cells(coarse, fine, coarse_level, nnc_inv_dev, masks, stream=0):
 def p1_prolongate_cells(coarse, fine, coarse_level, nnc_inv_dev, masks, update=REPLACE, stream=0):
     check(lib().hyteg_hip_p1_prolongate_cells(len(coarse), _ptrs(coarse), _ptrs(fine), coarse_level, nnc_inv_dev, _masks(masks), update, stream),
           "p1_prolongate_cells")
+
+
+def p2_restrict_cells(coarse_v, coarse_e, fine_v, fine_e, coarse_level, nnc_inv_dev, masks, stream=0):
+    """P2 restriction of a batch of macro-cells in one launch; every array argument is a list of device pointers (one per cell),
+    nnc_inv_dev a device table [ncells][14] of 1 / numNeighborCells"""
+    check(lib().hyteg_hip_p2_restrict_cells(len(coarse_v), _ptrs(coarse_v), _ptrs(coarse_e), _ptrs(fine_v), _ptrs(fine_e), coarse_level,
+                                            nnc_inv_dev, _masks(masks), stream), "p2_restrict_cells")
+
+
+def p2_prolongate_cells(fine_v, fine_e, coarse_v, coarse_e, coarse_level, masks, update=REPLACE, stream=0):
+    check(lib().hyteg_hip_p2_prolongate_cells(len(fine_v), _ptrs(fine_v), _ptrs(fine_e), _ptrs(coarse_v), _ptrs(coarse_e), coarse_level,
+                                              update, _masks(masks), stream), "p2_prolongate_cells")
 
 
 def p2_edge_array_size(level):

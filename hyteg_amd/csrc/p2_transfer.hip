@@ -250,11 +250,14 @@ __device__ inline void kind_and_block( int& kind, int& block )
    block = ( q >> 3 ) * 8 + ( g & 7 );
 }
 
+// The prolongation's per-DoF body is written once, for the argument block of the per-cell kernel (P2TransferArgs) and for the view of
+// one cell of a batch (P2TransferCell, below): same table, same term order, same fma chain, hence the same bits.  `Args` only says
+// where the pointers, widths, mask and scales are read from, and the per-cell kernel compiles to the instructions it had with the
+// body written into it (profiles/p2_transfer_cells.txt).
 // one thread per fine DoF of a kind
-__global__ __launch_bounds__( kThreads ) void p2_prolongate_kernel( const P2TransferArgs A )
+template < typename Args >
+__device__ __forceinline__ void p2_prolongate_dof( const Args& A, int kind, int block )
 {
-   int kind, block;
-   kind_and_block( kind, block );
    const int     W    = width_of_kind( A.Nf, kind );
    const int i    = (int) ( block * kThreads + threadIdx.x );
    if ( W <= 0 || i >= (int) tet32( (unsigned) W ) )
@@ -281,8 +284,16 @@ __global__ __launch_bounds__( kThreads ) void p2_prolongate_kernel( const P2Tran
       acc += *out;
    *out = acc;
 }
+__global__ __launch_bounds__( kThreads ) void p2_prolongate_kernel( const P2TransferArgs A )
+{
+   int kind, block;
+   kind_and_block( kind, block );
+   p2_prolongate_dof( A, kind, block );
+}
 
-// one thread per coarse DoF of a kind
+// one thread per coarse DoF of a kind.  This kernel keeps the body in its own text: called through p2_restrict_dof (below, the same
+// statements) it compiles to other instructions -- 4 % faster at level 7 -> 6, but the kernel is in the measured table and is left
+// as measured (profiles/p2_transfer_cells.txt).  A change of the statements here is a change there.
 __global__ __launch_bounds__( kThreads ) void p2_restrict_kernel( const P2TransferArgs A )
 {
    int kind, block;
@@ -325,6 +336,112 @@ __global__ __launch_bounds__( kThreads ) void p2_restrict_kernel( const P2Transf
    }
    double* out = kind == 0 ? A.dstV + i : A.dstE + ( kind - 1 ) * (int) tet32( (unsigned) ( A.Nc - 1 ) ) + i;
    *out        = acc;
+}
+
+// ---- the same for up to HYTEG_HIP_MAX_BATCH macro-cells of one level in one launch: grid ( blocks, 8 kinds, cells ) ----------------
+// On the small levels of a cycle a per-cell launch is bound by the serial chain of ONE thread (up to 125 table terms with index
+// decoding and point classes: ~52 us at every level, profiles/r03_final_th_cycle_kernel_stats.csv) while the GPU is nearly empty;
+// the batch pays that chain once for all cells of a chunk.  The cells' arrays and point masks travel by value in the kernel
+// arguments, as for the other batched P2 kernels (P2BatchPtrs, p2_common.hpp); the restriction reads the 14 scales of a cell from
+// the storage's device table.  No rows / interleaved variant: those are measurement switches of the per-cell path.
+struct P2TransferBatchPtrs
+{
+   double*       dstV[HYTEG_HIP_MAX_BATCH];
+   double*       dstE[HYTEG_HIP_MAX_BATCH];
+   const double* srcV[HYTEG_HIP_MAX_BATCH];
+   const double* srcE[HYTEG_HIP_MAX_BATCH];
+   unsigned      mask[HYTEG_HIP_MAX_BATCH];
+};
+static_assert( sizeof( P2TransferBatchPtrs ) == HYTEG_HIP_MAX_BATCH * ( 4 * sizeof( void* ) + sizeof( unsigned ) ), "P2TransferBatchPtrs" );
+struct P2TransferBatchArgs
+{
+   P2TransferBatchPtrs   P;
+   const TransferTables* T;
+   const double*         nncInv; // device: [cell][14], restriction only
+   int                   Nc, Nf;
+   int                   update;
+};
+static_assert( sizeof( P2TransferBatchArgs ) <= 4096, "the batched P2 transfer's arguments must fit the 4 KB kernel-argument segment" );
+// one cell of a batch, with the member names the per-DoF bodies read
+struct P2TransferCell
+{
+   double*               dstV;
+   double*               dstE;
+   const double*         srcV;
+   const double*         srcE;
+   const TransferTables* T;
+   int                   Nc, Nf;
+   int                   update;
+   unsigned              mask;
+   struct
+   {
+      const double* inv;
+   } nncInv;
+};
+__device__ inline P2TransferCell p2_transfer_cell( const P2TransferBatchArgs& B, int cell )
+{
+   P2TransferCell A;
+   A.dstV = B.P.dstV[cell], A.dstE = B.P.dstE[cell], A.srcV = B.P.srcV[cell], A.srcE = B.P.srcE[cell];
+   A.T = B.T, A.Nc = B.Nc, A.Nf = B.Nf, A.update = B.update, A.mask = B.P.mask[cell];
+   A.nncInv.inv = B.nncInv + 14 * cell;
+   return A;
+}
+// the restriction's per-DoF body for the batch: statement by statement that of p2_restrict_kernel above
+template < typename Args >
+__device__ __forceinline__ void p2_restrict_dof( const Args& A, int kind, int block )
+{
+   const int     W    = width_of_kind( A.Nc, kind );
+   const int i    = (int) ( block * kThreads + threadIdx.x );
+   if ( W <= 0 || i >= (int) tet32( (unsigned) W ) )
+      return;
+   int x, y, z;
+   decode( W, i, x, y, z );
+   if ( !( ( A.mask >> dof_class( A.Nc, kind, x, y, z ) ) & 1u ) )
+      return;
+   const TEntry* e   = A.T->restrict_[kind];
+   const int     n   = A.T->nrestrict[kind];
+   double        acc = 0.0;
+   // chunks of kChunk terms with all their loads in flight together (round 3; the table is padded with zero entries -- weight 0,
+   // the fine vertex ( 2x, 2y, 2z ) -- up to kMaxRestrict, a multiple of kChunk).  A fine DoF outside the macro-cell contributes
+   // weight 0 times entry 0 of the array: an exact 0, the bits of the loop that skipped it.
+   constexpr int kChunk = 16;
+   static_assert( kMaxRestrict % kChunk == 0, "restriction table padding" );
+   for ( int k0 = 0; k0 < n; k0 += kChunk )
+   {
+      double v[kChunk], ws[kChunk];
+#pragma unroll
+      for ( int j = 0; j < kChunk; ++j )
+      {
+         const TEntry t  = e[k0 + j];
+         const int    kf = t.kind;
+         const int    fx = 2 * x + t.dx, fy = 2 * y + t.dy, fz = 2 * z + t.dz;
+         const bool   ex = dof_exists( A.Nf, kf, fx, fy, fz );
+         const int    cls   = dof_class( A.Nf, kf, fx, fy, fz );
+         const double scale = cls == 14 ? 1.0 : A.nncInv.inv[cls];
+         const int    off   = ex ? dof_offset( A.Nf, kf, fx, fy, fz ) : 0;
+         v[j]               = kf == 0 ? A.srcV[off] : A.srcE[off];
+         ws[j]              = ex ? t.w * scale : 0.0;
+      }
+#pragma unroll
+      for ( int j = 0; j < kChunk; ++j )
+         acc = fma( ws[j], v[j], acc );
+   }
+   double* out = kind == 0 ? A.dstV + i : A.dstE + ( kind - 1 ) * (int) tet32( (unsigned) ( A.Nc - 1 ) ) + i;
+   *out        = acc;
+}
+__global__ __launch_bounds__( kThreads ) void p2_prolongate_batch_kernel( const P2TransferBatchArgs B )
+{
+   const int cell = blockIdx.z;
+   if ( B.P.mask[cell] == 0u )
+      return; // nothing selected: the cell's arrays are not touched
+   p2_prolongate_dof( p2_transfer_cell( B, cell ), (int) blockIdx.y, (int) blockIdx.x );
+}
+__global__ __launch_bounds__( kThreads ) void p2_restrict_batch_kernel( const P2TransferBatchArgs B )
+{
+   const int cell = blockIdx.z;
+   if ( B.P.mask[cell] == 0u )
+      return;
+   p2_restrict_dof( p2_transfer_cell( B, cell ), (int) blockIdx.y, (int) blockIdx.x );
 }
 
 // ---- round 3: both transfers by ROWS ----------------------------------------------------------------------------------------
@@ -572,5 +689,80 @@ HYTEG_HIP_API int hyteg_hip_p2_restrict_cell( double*            coarse_vertex,
    }
    HH_CHECK_HIP( hipGetLastError() );
    return HYTEG_HIP_OK;
+}
+
+// both batched transfers: every argument is checked before anything touches the GPU (the device tables included)
+static int launch_transfer_cells( bool                 restrict_,
+                                  const char*          what,
+                                  int                  ncells,
+                                  double* const*       dstV,
+                                  double* const*       dstE,
+                                  const double* const* srcV,
+                                  const double* const* srcE,
+                                  int                  coarse_level,
+                                  int                  update,
+                                  const double*        nnc_inv_dev,
+                                  const unsigned*      masks,
+                                  hyteg_hip_stream_t   stream )
+{
+   const std::string name( what );
+   HH_REQUIRE( ncells >= 1 && ncells <= HYTEG_HIP_MAX_BATCH, name + ": ncells must be 1..HYTEG_HIP_MAX_BATCH" );
+   HH_REQUIRE( dstV && dstE && srcV && srcE && masks && ( !restrict_ || nnc_inv_dev ), name + ": null pointer" );
+   HH_REQUIRE( coarse_level >= 0 && coarse_level + 1 <= 10, name + ": coarse level out of range [0,9]" );
+   HH_REQUIRE( update == HYTEG_HIP_REPLACE || update == HYTEG_HIP_ADD, name + ": bad update type" );
+   P2TransferBatchArgs B{};
+   bool                any = false;
+   for ( int c = 0; c < ncells; ++c )
+   {
+      HH_REQUIRE( dstV[c] && dstE[c] && srcV[c] && srcE[c], name + ": null array of a cell" );
+      B.P.dstV[c] = dstV[c], B.P.dstE[c] = dstE[c], B.P.srcV[c] = srcV[c], B.P.srcE[c] = srcE[c];
+      B.P.mask[c] = masks[c] & HYTEG_HIP_MASK_ALL;
+      any         = any || B.P.mask[c];
+   }
+   if ( !any )
+      return HYTEG_HIP_OK;
+   const int rc = get_tables( &B.T );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   B.nncInv = nnc_inv_dev;
+   B.Nc = ( 1 << coarse_level ) + 1, B.Nf = ( 1 << ( coarse_level + 1 ) ) + 1;
+   B.update = update;
+   // the vertex kind is the widest: its block count serves all eight kinds, as in the per-cell launches
+   const unsigned blocks = (unsigned) ( ( tet64( restrict_ ? B.Nc : B.Nf ) + kThreads - 1 ) / kThreads );
+   const dim3     grid( blocks, 8, (unsigned) ncells );
+   if ( restrict_ )
+      hipLaunchKernelGGL( p2_restrict_batch_kernel, grid, dim3( kThreads ), 0, as_stream( stream ), B );
+   else
+      hipLaunchKernelGGL( p2_prolongate_batch_kernel, grid, dim3( kThreads ), 0, as_stream( stream ), B );
+   HH_CHECK_HIP( hipGetLastError() );
+   return HYTEG_HIP_OK;
+}
+
+HYTEG_HIP_API int hyteg_hip_p2_restrict_cells( int                  ncells,
+                                               double* const*       coarse_vertex,
+                                               double* const*       coarse_edge,
+                                               const double* const* fine_vertex,
+                                               const double* const* fine_edge,
+                                               int                  coarse_level,
+                                               const double*        nnc_inv_dev,
+                                               const unsigned*      masks,
+                                               hyteg_hip_stream_t   stream )
+{
+   return launch_transfer_cells( true, "p2_restrict_cells", ncells, coarse_vertex, coarse_edge, fine_vertex, fine_edge, coarse_level,
+                                 HYTEG_HIP_REPLACE, nnc_inv_dev, masks, stream );
+}
+
+HYTEG_HIP_API int hyteg_hip_p2_prolongate_cells( int                  ncells,
+                                                 double* const*       fine_vertex,
+                                                 double* const*       fine_edge,
+                                                 const double* const* coarse_vertex,
+                                                 const double* const* coarse_edge,
+                                                 int                  coarse_level,
+                                                 int                  update,
+                                                 const unsigned*      masks,
+                                                 hyteg_hip_stream_t   stream )
+{
+   return launch_transfer_cells( false, "p2_prolongate_cells", ncells, fine_vertex, fine_edge, coarse_vertex, coarse_edge, coarse_level,
+                                 update, nullptr, masks, stream );
 }
 }

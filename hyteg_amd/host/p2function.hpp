@@ -54,6 +54,14 @@ class P2Function
          throw std::runtime_error( "P2Function '" + name_ + "': bad cell or level" );
       return edge_[c][level - minLevel_];
    }
+   // device pointers of the edge-DoF arrays of local cells [first, first + count) at `level`
+   std::vector< double* > edgeCellPointers( uint_t level, int first, int count ) const
+   {
+      std::vector< double* > p;
+      for ( int c = first; c < first + count; ++c )
+         p.push_back( getEdgeCellPointer( (uint_t) c, level ) );
+      return p;
+   }
    uint_t getNumberOfEdgeDoFs( uint_t level ) const { return hyteg_hip_p2_edge_array_size( (int) level ); }
 
    void interpolate( ValueType constant, uint_t level, DoFType flag = All ) const

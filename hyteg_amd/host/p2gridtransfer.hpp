@@ -36,15 +36,32 @@ class P2toP2QuadraticProlongation
    {
       auto        storage = src.getStorage();
       ScopedTimer timer( storage->getTimingTree(), "P2toP2QuadraticProlongation" );
-      for ( uint_t c = 0; c < storage->getNumberOfLocalCells(); ++c )
+      if ( storage->useBatch( sourceLevel + 1 ) )
       {
-         const MacroCell& cell = storage->getLocalCell( c );
-         hipCheck( hyteg_hip_p2_prolongate_cell( dst.getVertexDoFFunction().getCellPointer( c, sourceLevel + 1 ),
-                                                 dst.getEdgeCellPointer( c, sourceLevel + 1 ),
-                                                 src.getVertexDoFFunction().getCellPointer( c, sourceLevel ),
-                                                 src.getEdgeCellPointer( c, sourceLevel ), (int) sourceLevel, HYTEG_HIP_REPLACE,
-                                                 storage->maskFor( cell, flag ), storage->stream() ),
-                   "P2toP2QuadraticProlongation" );
+         // one launch per chunk of cells instead of one per cell: the same per-DoF chain, hence the same bits
+         const auto masks = storage->masksFor( flag );
+         storage->forCellChunks( [&]( int first, int count ) {
+            const auto fv = dst.getVertexDoFFunction().cellPointers( sourceLevel + 1, first, count ),
+                       fe = dst.edgeCellPointers( sourceLevel + 1, first, count ),
+                       cv = src.getVertexDoFFunction().cellPointers( sourceLevel, first, count ),
+                       ce = src.edgeCellPointers( sourceLevel, first, count );
+            hipCheck( hyteg_hip_p2_prolongate_cells( count, fv.data(), fe.data(), cv.data(), ce.data(), (int) sourceLevel, HYTEG_HIP_REPLACE,
+                                                     masks.data() + first, storage->stream() ),
+                      "P2toP2QuadraticProlongation (batched)" );
+         } );
+      }
+      else
+      {
+         for ( uint_t c = 0; c < storage->getNumberOfLocalCells(); ++c )
+         {
+            const MacroCell& cell = storage->getLocalCell( c );
+            hipCheck( hyteg_hip_p2_prolongate_cell( dst.getVertexDoFFunction().getCellPointer( c, sourceLevel + 1 ),
+                                                    dst.getEdgeCellPointer( c, sourceLevel + 1 ),
+                                                    src.getVertexDoFFunction().getCellPointer( c, sourceLevel ),
+                                                    src.getEdgeCellPointer( c, sourceLevel ), (int) sourceLevel, HYTEG_HIP_REPLACE,
+                                                    storage->maskFor( cell, flag ), storage->stream() ),
+                      "P2toP2QuadraticProlongation" );
+         }
       }
       // every cell has computed the complete value of the DoFs on its boundary from its own coarse DoFs; the values of the
       // neighbour cells agree up to rounding (different containing micro-cells): one copy wins, so that all copies of a
@@ -63,16 +80,32 @@ class P2toP2QuadraticRestriction
       auto         storage  = function.getStorage();
       ScopedTimer  timer( storage->getTimingTree(), "P2toP2QuadraticRestriction" );
       const uint_t dstLevel = sourceLevel - 1;
-      for ( uint_t c = 0; c < storage->getNumberOfLocalCells(); ++c )
+      if ( storage->useBatch( sourceLevel ) )
       {
-         const MacroCell& cell = storage->getLocalCell( c );
-         const auto       nnc  = storage->numNeighborCells( cell );
-         hipCheck( hyteg_hip_p2_restrict_cell( function.getVertexDoFFunction().getCellPointer( c, dstLevel ),
-                                               function.getEdgeCellPointer( c, dstLevel ),
-                                               function.getVertexDoFFunction().getCellPointer( c, sourceLevel ),
-                                               function.getEdgeCellPointer( c, sourceLevel ), (int) dstLevel, nnc.data(),
-                                               storage->maskFor( cell, flag ), storage->stream() ),
-                   "P2toP2QuadraticRestriction" );
+         const auto masks = storage->masksFor( flag );
+         storage->forCellChunks( [&]( int first, int count ) {
+            const auto cv = function.getVertexDoFFunction().cellPointers( dstLevel, first, count ),
+                       ce = function.edgeCellPointers( dstLevel, first, count ),
+                       fv = function.getVertexDoFFunction().cellPointers( sourceLevel, first, count ),
+                       fe = function.edgeCellPointers( sourceLevel, first, count );
+            hipCheck( hyteg_hip_p2_restrict_cells( count, cv.data(), ce.data(), fv.data(), fe.data(), (int) dstLevel,
+                                                   storage->nncInvDevice() + (size_t) first * 14, masks.data() + first, storage->stream() ),
+                      "P2toP2QuadraticRestriction (batched)" );
+         } );
+      }
+      else
+      {
+         for ( uint_t c = 0; c < storage->getNumberOfLocalCells(); ++c )
+         {
+            const MacroCell& cell = storage->getLocalCell( c );
+            const auto       nnc  = storage->numNeighborCells( cell );
+            hipCheck( hyteg_hip_p2_restrict_cell( function.getVertexDoFFunction().getCellPointer( c, dstLevel ),
+                                                  function.getEdgeCellPointer( c, dstLevel ),
+                                                  function.getVertexDoFFunction().getCellPointer( c, sourceLevel ),
+                                                  function.getEdgeCellPointer( c, sourceLevel ), (int) dstLevel, nnc.data(),
+                                                  storage->maskFor( cell, flag ), storage->stream() ),
+                      "P2toP2QuadraticRestriction" );
+         }
       }
       // communicateAdditively< Cell, {Face, Edge, Vertex} > of both DoF kinds (P2toP2QuadraticRestriction.cpp:276-285)
       function.getVertexDoFFunction().sumSharedCopies( dstLevel, flag );

@@ -882,6 +882,30 @@ HYTEG_HIP_API int hyteg_hip_p2_restrict_cell( double*            coarse_vertex,
                                               const double*      nnc /* host, 14 */,
                                               unsigned           mask,
                                               hyteg_hip_stream_t stream );
+/* hyteg_hip_p2_restrict_cell for up to HYTEG_HIP_MAX_BATCH macro-cells of one level in ONE launch
+ * (the loop over the macro-cells of P2toP2QuadraticRestriction::restrictAdditively3D, P2toP2QuadraticRestriction.cpp:131-286).
+ * Pointer arrays and masks are HOST arrays of length ncells; nnc_inv_dev: device table [ncells][14] = 1 / numNeighborCells
+ * in the slot order of hyteg_hip_p2_restrict_cell.  Bit-identical to the per-cell calls (same table, term order and fma
+ * chain); a cell whose mask is 0 is skipped, its arrays are not touched.  Every argument is checked before any GPU work. */
+HYTEG_HIP_API int hyteg_hip_p2_restrict_cells( int                  ncells,
+                                               double* const*       coarse_vertex,
+                                               double* const*       coarse_edge,
+                                               const double* const* fine_vertex,
+                                               const double* const* fine_edge,
+                                               int                  coarse_level,
+                                               const double*        nnc_inv_dev,
+                                               const unsigned*      masks,
+                                               hyteg_hip_stream_t   stream );
+/* hyteg_hip_p2_prolongate_cell for a batch (P2toP2QuadraticProlongation.cpp:217-424) */
+HYTEG_HIP_API int hyteg_hip_p2_prolongate_cells( int                  ncells,
+                                                 double* const*       fine_vertex,
+                                                 double* const*       fine_edge,
+                                                 const double* const* coarse_vertex,
+                                                 const double* const* coarse_edge,
+                                                 int                  coarse_level,
+                                                 int                  update,
+                                                 const unsigned*      masks,
+                                                 hyteg_hip_stream_t   stream );
 
 /* ---- events and the neighbour exchange over RCCL (xGMI) --------------------------------------------------------
  * One process per GPU.  Replaces, on this path, what the reference does through waLBerla's BufferSystem over MPI:

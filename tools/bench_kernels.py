@@ -194,6 +194,31 @@ def main():
     timeit(f"P2 restrict level {L2} -> {L2 - 1}",
            lambda k: capi.p2_restrict_cell(CV[k % nb2].data_ptr(), CE[k % nb2].data_ptr(), SV[k % nb2].data_ptr(), SE[k % nb2].data_ptr(),
                                            L2 - 1, ones, 0x7FFF, sh), 8 * (nv2 + ne2 + nvc + nec), nvc + nec, r=max(3, reps // 10))
+    # the same transfer on the small levels of a cycle, for the 24 macro-cells of cube_24el: the per-cell loop (24 launches) against one
+    # batched launch; time, bytes and DoFs are those of all 24 cells
+    ncell = 24
+    inv24 = torch.ones(14 * ncell, dtype=torch.float64, device="cuda")
+    for fine in (3, 6):
+        nvf, nef, nvk, nek = capi.cell_size(fine), capi.p2_edge_array_size(fine), capi.cell_size(fine - 1), capi.p2_edge_array_size(fine - 1)
+        FV, FE, KV, KE = ([torch.rand(m, dtype=torch.float64, device="cuda") for _ in range(ncell)] for m in (nvf, nef, nvk, nek))
+        fv, fe, kv, ke = ([t.data_ptr() for t in ts] for ts in (FV, FE, KV, KE))
+        masks24, nbytes = [0x7FFF] * ncell, 8 * ncell * (nvf + nef + nvk + nek)
+
+        def restrict_loop(k):
+            for c in range(ncell):
+                capi.p2_restrict_cell(kv[c], ke[c], fv[c], fe[c], fine - 1, ones, 0x7FFF, sh)
+
+        def prolongate_loop(k):
+            for c in range(ncell):
+                capi.p2_prolongate_cell(fv[c], fe[c], kv[c], ke[c], fine - 1, 0, 0x7FFF, sh)
+
+        r24 = max(3, reps // 10)
+        timeit(f"P2 restrict level {fine} -> {fine - 1}, 24 cells, per-cell loop", restrict_loop, nbytes, ncell * (nvk + nek), r=r24)
+        timeit(f"P2 restrict level {fine} -> {fine - 1}, 24 cells, one batched launch",
+               lambda k: capi.p2_restrict_cells(kv, ke, fv, fe, fine - 1, inv24.data_ptr(), masks24, sh), nbytes, ncell * (nvk + nek), r=r24)
+        timeit(f"P2 prolongate level {fine - 1} -> {fine}, 24 cells, per-cell loop", prolongate_loop, nbytes, ncell * (nvf + nef), r=r24)
+        timeit(f"P2 prolongate level {fine - 1} -> {fine}, 24 cells, one batched launch",
+               lambda k: capi.p2_prolongate_cells(fv, fe, kv, ke, fine - 1, masks24, 0, sh), nbytes, ncell * (nvf + nef), r=r24)
     if args.only:
         print(json.dumps({"level": L, "kernels": rows}))
         return
