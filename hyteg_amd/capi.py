@@ -459,6 +459,12 @@ def p1_prolongate_cell_masked(coarse, fine, coarse_level, nnc, mask, stream=0):
           "p1_prolongate_cell_masked")
 
 
+def p1_prolongate_cell_masked_update(coarse, fine, coarse_level, nnc, mask, update=REPLACE, stream=0):
+    """ADD adds the interpolant to the selected inner points and overwrites the selected shell points"""
+    check(lib().hyteg_hip_p1_prolongate_cell_masked_update(coarse, fine, coarse_level, _f14(nnc), mask, update, stream),
+          "p1_prolongate_cell_masked_update")
+
+
 def sum_shared(bases, group_ptr, entry_buf, entry_off, ngroups, n_writable, stream=0):
     check(lib().hyteg_hip_sum_shared(bases, group_ptr, entry_buf, entry_off, ngroups, n_writable, stream), "sum_shared")
 
@@ -495,6 +501,44 @@ def p1_vector_cells(op, dst, srcs, scalars, level, masks, stream=0):
 
 def p1_dot_cells(a, b, level, masks, result_dev, workspace_dev, stream=0):
     check(lib().hyteg_hip_p1_dot_cells(len(a), _ptrs(a), _ptrs(b), level, _masks(masks), result_dev, workspace_dev, stream), "p1_dot_cells")
+
+
+# slots of the conjugate gradient scalars (enum hyteg_hip_cg_slot)
+(HYTEG_HIP_CG_PRSOLD, HYTEG_HIP_CG_PAP, HYTEG_HIP_CG_RR, HYTEG_HIP_CG_ALPHA, HYTEG_HIP_CG_NEG_ALPHA, HYTEG_HIP_CG_BETA, HYTEG_HIP_CG_RES_START,
+ HYTEG_HIP_CG_DONE, HYTEG_HIP_CG_ITERATIONS, HYTEG_HIP_CG_ONE) = range(10)
+HYTEG_HIP_CG_SLOTS = 16
+HYTEG_HIP_MAX_BATCH = 80
+
+
+def p1_vector_cells_dev(op, dst, srcs, scalar_ptrs, level, masks, stream=0):
+    """p1_vector_cells (op 0 assign, 1 add) with one device pointer per coefficient, read when the kernel runs"""
+    flat = [p for f in srcs for p in f]
+    sp = (_vp * len(scalar_ptrs))(*[None if p is None else int(p) for p in scalar_ptrs]) if scalar_ptrs is not None else None
+    check(lib().hyteg_hip_p1_vector_cells_dev(op, len(dst), _ptrs(dst), len(srcs), _ptrs(flat) if flat else None, sp, level, _masks(masks), stream),
+          "p1_vector_cells_dev")
+
+
+def p1_dot_cells_cg(a, b, level, masks, s_dev, slot, phase, rel_tol, abs_tol, workspace_dev, stream=0):
+    """p1_dot_cells into s_dev[slot] followed by cg_scalars(phase) in the same launch"""
+    check(lib().hyteg_hip_p1_dot_cells_cg(len(a), _ptrs(a), _ptrs(b), level, _masks(masks), s_dev, slot, phase, float(rel_tol), float(abs_tol),
+                                          workspace_dev, stream), "p1_dot_cells_cg")
+
+
+def cg_scalars(s_dev, phase, rel_tol, abs_tol, stream=0):
+    check(lib().hyteg_hip_cg_scalars(s_dev, phase, float(rel_tol), float(abs_tol), stream), "cg_scalars")
+
+
+def p1_cg_small_max_entries(): return int(lib().hyteg_hip_p1_cg_small_max_entries())
+
+
+def p1_cg_small_cells(x, b, level, stencils_dev, masks, owned_masks, max_iter, rel_tol, abs_tol, info_dev=None, groups=None, stream=0):
+    """the whole CG solve in one launch; groups: up to two (group_ptr_dev, entry_cell_dev, entry_off_dev, ngroups), one per exchange class"""
+    groups = list(groups or [])
+    groups += [(None, None, None, 0)] * (2 - len(groups))
+    gp, ec, eo = ((_vp * 2)(*[g[k] for g in groups]) for k in range(3))
+    ng = (C.c_int * 2)(*[int(g[3]) for g in groups])
+    check(lib().hyteg_hip_p1_cg_small_cells(len(x), _ptrs(x), _ptrs(b), level, stencils_dev, _masks(masks), _masks(owned_masks), gp, ec, eo, ng,
+                                            int(max_iter), float(rel_tol), float(abs_tol), info_dev, stream), "p1_cg_small_cells")
 
 
 def p1_apply_cells(dst, src, level, stencils_dev, masks, update=REPLACE, stream=0):
@@ -547,6 +591,29 @@ def p2_edge_vector_cell_masked(op, dst, srcs, scalars, level, mask, stream=0):
     sc = (C.c_double * max(1, len(scalars or [])))(*[float(v) for v in (scalars or [0.0])])
     check(lib().hyteg_hip_p2_edge_vector_cell_masked(op, dst, n, _ptrs(srcs) if n else None, sc if scalars is not None else None, level, mask,
                                                      stream), "p2_edge_vector_cell_masked")
+
+
+def p2_edge_vector_cell_kinds(op, dst, srcs, scalars, level, mask, kind_mask, stream=0):
+    """kind_mask: edge-DoF orientations that take part (bit 1..7 = X, Y, Z, XY, XZ, YZ, XYZ)"""
+    n = len(srcs)
+    sc = (C.c_double * max(1, len(scalars or [])))(*[float(v) for v in (scalars or [0.0])])
+    check(lib().hyteg_hip_p2_edge_vector_cell_kinds(op, dst, n, _ptrs(srcs) if n else None, sc if scalars is not None else None, level, mask,
+                                                    kind_mask, stream), "p2_edge_vector_cell_kinds")
+
+
+def p2_edge_vector_cells_kinds(op, dst, srcs, scalars, level, masks, kind_mask=0xFE, stream=0):
+    """dst: list of device pointers (one per cell); srcs: list (per function) of lists (per cell)"""
+    flat = [p for f in srcs for p in f]
+    sc = (C.c_double * max(1, len(scalars or [])))(*[float(v) for v in (scalars or [0.0])])
+    check(lib().hyteg_hip_p2_edge_vector_cells_kinds(op, len(dst), _ptrs(dst), len(srcs), _ptrs(flat) if flat else None,
+                                                     sc if scalars is not None else None, level, _masks(masks), kind_mask, stream),
+          "p2_edge_vector_cells_kinds")
+
+
+def p2_edge_dot_cells_masked(a, b, level, masks, results_dev, stream=0):
+    """results_dev[c] = the masked dot product of cell c"""
+    check(lib().hyteg_hip_p2_edge_dot_cells_masked(len(a), _ptrs(a), _ptrs(b), level, _masks(masks), results_dev, stream),
+          "p2_edge_dot_cells_masked")
 
 
 def p2_edge_dot_cell_masked(a, b, level, mask, result_dev, workspace_dev, stream=0):

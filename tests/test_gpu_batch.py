@@ -237,3 +237,199 @@ def test_sor_shell_cells_match_the_per_cell_kernel(env, level, backwards):
                                t["face_w"], t["vertex_w"], 1.1, masks[k], backwards)
         torch.cuda.synchronize()
         assert np.array_equal(du[k].cpu().numpy(), ref.cpu().numpy())
+
+
+# ---- the batched entry points one by one, against the oracle and numpy ---------------------------------------------------
+def _oracle_share(po, src, level, tab):
+    """(A src on the inner points, the cell's share of A src on the shell points) in one array, zero where neither writes"""
+    out = np.zeros_like(src)
+    if level >= 2:
+        po.apply_cell(out, src, level, tab[14], po.REPLACE)
+    po.apply_cell_boundary(out, src, level, tab[:14].reshape(-1), po.MASK_SHELL, po.REPLACE)
+    return out
+
+
+@pytest.mark.parametrize("level", [0, 1, 2, 3, 5])
+@pytest.mark.parametrize("phase", [0, 1])
+def test_jacobi_cells_phases_match_the_oracle(env, level, phase):
+    """phase 0: the complete update on selected inner points, the cell's share of A src on selected shell points;
+    phase 1: dst = src + relax * invdiag * (rhs - dst) on selected shell points, inner points untouched (bit 14 or not);
+    every mask of MASKS and a zero mask visits every cell"""
+    torch, capi, host, po = env
+    import hostutil as hu
+
+    tabs = _cells(po, level)
+    n = po.cell_size(level)
+    rng = np.random.default_rng(50 + level)
+    src, rhs, dst0 = ([rng.standard_normal(n) for _ in range(3)] for _ in range(3))
+    invd = [rng.uniform(0.5, 1.5, n) for _ in range(3)]
+    relax = 0.7
+    assert all(np.abs(r).min() > 0 for r in rhs)
+    dsrc, drhs, dinv = ([_dev(torch, a) for a in arrs] for arrs in (src, rhs, invd))
+    dtab = _dev(torch, tabs.reshape(-1))
+    inner = po.slot_of_points(level) == 14
+    assert inner.any() == (level >= 2)
+    all_masks = MASKS + [0]
+    checked = 0
+    for rot in range(len(all_masks)):
+        masks = [all_masks[(rot + c) % len(all_masks)] for c in range(3)]
+        ddst = [_dev(torch, a) for a in dst0]
+        capi.p1_jacobi_cells([t.data_ptr() for t in ddst], [t.data_ptr() for t in drhs], [t.data_ptr() for t in dsrc], [t.data_ptr() for t in dinv],
+                             level, dtab.data_ptr(), relax, masks, phase)
+        for c in range(3):
+            got = ddst[c].cpu().numpy()
+            sel = hu.point_mask(level, masks[c])
+            assert np.array_equal(got[~sel], dst0[c][~sel])
+            if phase == 0:
+                asrc = _oracle_share(po, src[c], level, tabs[c])
+                want = np.where(inner, src[c] + relax * invd[c] * (rhs[c] - asrc), asrc)
+                cmp = sel
+            else:
+                want = src[c] + relax * (invd[c] * (rhs[c] - dst0[c]))
+                cmp = sel & ~inner
+                assert np.array_equal(got[inner], dst0[c][inner])
+            if masks[c] == 0:
+                assert np.array_equal(got, dst0[c])
+            if cmp.any():
+                assert np.abs(got[cmp] - want[cmp]).max() <= 1e-13 * max(1.0, np.abs(want).max()), (hex(masks[c]), c)
+                checked += int(cmp.sum())
+    assert checked > 0
+
+
+@pytest.mark.parametrize("level", [0, 2, 4])
+@pytest.mark.parametrize("nsrc", [1, 3, 4])
+def test_vector_cells_with_one_three_and_four_sources(env, level, nsrc):
+    """batch_vector_kernel<1>, <3> and <4> against numpy (the two-source instantiation is test_vector_and_dot_cells)"""
+    torch, capi, host, po = env
+    import hostutil as hu
+
+    n = po.cell_size(level)
+    rng = np.random.default_rng(60 + 10 * level + nsrc)
+    srcs = [[rng.standard_normal(n) for _ in range(3)] for _ in range(nsrc)]
+    d0 = [rng.standard_normal(n) for _ in range(3)]
+    scalars = [2.0, -0.5, 0.25, 3.0][:nsrc]
+    dsrc = [[_dev(torch, a) for a in f] for f in srcs]
+    checked = 0
+    for op in (0, 1, 2):
+        dd = [_dev(torch, x) for x in d0]
+        capi.p1_vector_cells(op, [t.data_ptr() for t in dd], [[t.data_ptr() for t in f] for f in dsrc], None if op == 2 else scalars, level, MASKS)
+        for c in range(3):
+            sel = hu.point_mask(level, MASKS[c])
+            if op == 2:
+                want = srcs[0][c].copy()
+                for k in range(1, nsrc):
+                    want = want * srcs[k][c]
+            else:
+                want = scalars[0] * srcs[0][c]
+                for k in range(1, nsrc):
+                    want = want + scalars[k] * srcs[k][c]
+                if op == 1:
+                    want = d0[c] + want
+            got = dd[c].cpu().numpy()
+            assert np.array_equal(got[~sel], d0[c][~sel])
+            if sel.any():
+                assert np.abs(got[sel] - want[sel]).max() <= 1e-14 * max(1.0, np.abs(want).max())
+                checked += 1
+            else:  # level 0 is four macro-vertices, and the mask of cell 1 has no vertex slot
+                assert level == 0 and c == 1 and not MASKS[c] & 0x3C00
+    assert checked == (6 if level == 0 else 9)
+
+
+def _full_tiles_per_cell(level, capacity=256):
+    """workgroups per cell of the batched kernels: every z-slice of the array in balanced tiles of at most `capacity` entries"""
+    N = (1 << level) + 1
+    return sum(((N - z) * (N - z + 1) // 2 + capacity - 1) // capacity for z in range(N))
+
+
+@pytest.mark.parametrize("ncells,level,regime", [(3, 2, "one launch"), (3, 5, "two launches"), (5, 6, "grid stride")])
+def test_dot_cells_in_its_three_launch_regimes(env, ncells, level, regime):
+    """up to 64 workgroups: the last one to finish reduces; 65..1023: a second launch reduces; from 1024 tiles on, 1024 workgroups
+    walk several tiles each.  Twice on the same workspace: the ticket counter of the first regime has to be back at zero for
+    the second call to write a result at all, and the fixed summation order makes the two results bit-identical."""
+    import math
+
+    torch, capi, host, po = env
+    import hostutil as hu
+
+    total = ncells * _full_tiles_per_cell(level)
+    assert {"one launch": total <= 64, "two launches": 64 < total < 1024, "grid stride": total > 1024}[regime], total
+    n = po.cell_size(level)
+    rng = np.random.default_rng(70 + level)
+    a, b = rng.standard_normal((ncells, n)), rng.standard_normal((ncells, n))
+    masks = [(MASKS + [1 << 14, 0x4000 | 0x03C0])[c % 5] for c in range(ncells)]
+    ta, tb = _dev(torch, a), _dev(torch, b)
+    prods = np.concatenate([(a[c] * b[c])[hu.point_mask(level, masks[c])] for c in range(ncells)])
+    ref, scale = math.fsum(prods), float(np.abs(prods).sum())
+    ws = torch.full((capi.dot_workspace_bytes() // 8,), 1e300, dtype=torch.float64, device="cuda")
+    got = []
+    for _ in range(2):
+        res = torch.full((1,), 1e300, dtype=torch.float64, device="cuda")
+        capi.p1_dot_cells([ta[c].data_ptr() for c in range(ncells)], [tb[c].data_ptr() for c in range(ncells)], level, masks, res.data_ptr(),
+                          ws.data_ptr())
+        got.append(float(res.cpu()[0]))
+        assert abs(got[-1] - ref) <= 1e-13 * scale, (got, ref, scale)
+    assert got[0] == got[1] and len(prods) > 0
+
+
+@pytest.mark.parametrize("coarse_level", [0, 2, 3, 4])
+@pytest.mark.parametrize("update", [0, 1])
+def test_prolongate_cell_masked_update(env, coarse_level, update):
+    """fine level 1 and 3: the tile kernel, 4 and 5: the brick kernel.  ADD adds the interpolant to the selected inner points
+    and overwrites the selected shell points; REPLACE overwrites the selected points; everything else keeps its bits."""
+    torch, capi, host, po = env
+    import hostutil as hu
+
+    nnc = [3, 4, 5, 6, 7, 8, 2, 1, 2, 2, 9, 10, 11, 12]  # _NNC_MIXED of test_gpu_parity.py
+    fl = coarse_level + 1
+    rng = np.random.default_rng(80 + coarse_level)
+    coarse_h, fine0 = rng.standard_normal(po.cell_size(coarse_level)), rng.standard_normal(po.cell_size(fl))
+    full = po.prolongate_cell(coarse_h, np.zeros_like(fine0), coarse_level, np.array(nnc, dtype=np.float64))
+    inner = po.slot_of_points(fl) == 14
+    coarse = _dev(torch, coarse_h)
+    checked = 0
+    for mask in (0x7FFF, 1 << 14, 0x4000 | 0x03C0, 0x3FFF):
+        fine = _dev(torch, fine0)
+        capi.p1_prolongate_cell_masked_update(coarse.data_ptr(), fine.data_ptr(), coarse_level, nnc, mask, update)
+        got = fine.cpu().numpy()
+        sel = hu.point_mask(fl, mask)
+        want = np.where(sel, np.where(inner & (update == capi.ADD), fine0 + full, full), fine0)
+        assert np.array_equal(got[~sel], fine0[~sel]), hex(mask)
+        nw = np.linalg.norm(want)
+        assert np.linalg.norm(got - want) / (nw if nw > 0 else 1.0) < 1e-13, hex(mask)  # TOL and _rel of test_gpu_host.py
+        if sel.any():
+            assert np.abs(got[sel] - want[sel]).max() <= 1e-13 * np.abs(want).max(), hex(mask)
+        checked += int(sel.sum())
+    assert checked > 0
+
+
+@pytest.mark.parametrize("level", [0, 1, 3, 5])
+@pytest.mark.parametrize("tet", ["REF_TET", "SKEW_TET"])
+def test_apply_cell_boundary_f32_matches_the_oracle_in_double(env, level, tet):
+    """the float instantiation on its own: REPLACE and ADD, against the double oracle on float32-representable inputs"""
+    torch, capi, host, po = env
+    import conftest
+    import hostutil as hu
+
+    ws = po.assemble_cell_slot_stencils(getattr(conftest, tet), level)
+    n = po.cell_size(level)
+    rng = np.random.default_rng(90 + level)
+    src32, d32 = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    src64, d64 = src32.astype(np.float64), d32.astype(np.float64)
+    dsrc = _dev(torch, src32)
+    checked = 0
+    for mask in (0x3FFF, 0x2A5, 0):
+        sel = hu.point_mask(level, mask)
+        for update in (capi.REPLACE, capi.ADD):
+            dst = _dev(torch, d32)
+            capi.p1_apply_cell_boundary_f32(dst.data_ptr(), dsrc.data_ptr(), level, ws, mask, update)
+            got = dst.cpu().numpy()
+            assert got.dtype == np.float32
+            assert np.array_equal(got[~sel], d32[~sel])
+            want = po.apply_cell_boundary(d64.copy(), src64, level, ws, mask, update)
+            if sel.any():
+                assert np.linalg.norm(got[sel] - want[sel]) / np.linalg.norm(want[sel]) < 2e-6  # F32_TOL of test_gpu_fp32.py
+                checked += int(sel.sum())
+            else:  # the zero mask, and at level 0 (four vertices) the mask without a vertex slot
+                assert mask == 0 or (level == 0 and not mask & 0x3C00)
+                assert np.array_equal(got, d32)
+    assert checked > 0
