@@ -106,6 +106,9 @@ SIGNATURES = {
     "hyteg_hip_p1_copy_cell_to_face": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "hyteg_hip_p1_vector_cells": (_i, [_i, _i, C.POINTER(_vp), _i, C.POINTER(_vp), _dp, _i, C.POINTER(C.c_uint), _vp]),
     "hyteg_hip_p1_dot_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp, _vp, _vp]),
+    "hyteg_hip_reduce_workspace_bytes": (_sz, []),
+    "hyteg_hip_p1_reduce_cells": (_i, [_i, C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp, _vp, _vp]),
+    "hyteg_hip_p2_edge_reduce_cells": (_i, [_i, C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp, _vp, _vp]),
     "hyteg_hip_p1_apply_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), _i, _vp, C.POINTER(C.c_uint), _i, _vp]),
     "hyteg_hip_p1_jacobi_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _vp, _d,
                                         C.POINTER(C.c_uint), _i, _vp]),
@@ -501,6 +504,28 @@ def p1_vector_cells(op, dst, srcs, scalars, level, masks, stream=0):
 
 def p1_dot_cells(a, b, level, masks, result_dev, workspace_dev, stream=0):
     check(lib().hyteg_hip_p1_dot_cells(len(a), _ptrs(a), _ptrs(b), level, _masks(masks), result_dev, workspace_dev, stream), "p1_dot_cells")
+
+
+# statistics of the reduction, in the order of a cell's results (HYTEG_HIP_REDUCE_*)
+REDUCE_SUM, REDUCE_SUM_ABS, REDUCE_MIN, REDUCE_MAX, REDUCE_MAX_ABS = range(5)
+REDUCE_COUNT = 5
+
+
+def reduce_workspace_bytes(): return int(lib().hyteg_hip_reduce_workspace_bytes())
+
+
+def p1_reduce_cells(a, level, masks, results_dev, workspace_dev, stream=0):
+    """results_dev[c * REDUCE_COUNT + q] = statistic q (sum, sum of magnitudes, min, max, max magnitude) of the points of the
+    vertex-DoF array a[c] that masks[c] selects; a: list of device pointers, one per cell"""
+    check(lib().hyteg_hip_p1_reduce_cells(len(a) if a is not None else 1, _ptrs(a) if a is not None else None, level,
+                                          _masks(masks) if masks is not None else None, results_dev, workspace_dev, stream), "p1_reduce_cells")
+
+
+def p2_edge_reduce_cells(a, level, masks, results_dev, workspace_dev, stream=0):
+    """p1_reduce_cells for edge-DoF arrays"""
+    check(lib().hyteg_hip_p2_edge_reduce_cells(len(a) if a is not None else 1, _ptrs(a) if a is not None else None, level,
+                                               _masks(masks) if masks is not None else None, results_dev, workspace_dev, stream),
+          "p2_edge_reduce_cells")
 
 
 # slots of the conjugate gradient scalars (enum hyteg_hip_cg_slot)

@@ -2,6 +2,8 @@
 // neighbour and axis tables of the linear grid transfer -- and the workgroup reductions of the dot products, one definition each.
 #pragma once
 
+#include <cfloat>
+
 #include "common.hpp"
 
 namespace hyteg_hip {
@@ -122,6 +124,106 @@ __device__ inline double block_sum_all( double v, double* sh )
       r += sh[k];
    return r;
 }
+
+// the min / max siblings of wave_sum and block_sum (exact, so their order is free; NaN is outside the contract)
+__device__ inline double wave_min( double v )
+{
+#pragma unroll
+   for ( int off = 32; off > 0; off >>= 1 )
+      v = fmin( v, __shfl_down( v, off, 64 ) );
+   return v;
+}
+__device__ inline double wave_max( double v )
+{
+#pragma unroll
+   for ( int off = 32; off > 0; off >>= 1 )
+      v = fmax( v, __shfl_down( v, off, 64 ) );
+   return v;
+}
+template < int THREADS >
+__device__ inline double block_min( double v, double* sh )
+{
+   v = wave_min( v );
+   if ( ( threadIdx.x & 63 ) == 0 )
+      sh[threadIdx.x >> 6] = v;
+   __syncthreads();
+   double r = v;
+   if ( threadIdx.x == 0 )
+   {
+#pragma unroll
+      for ( int k = 1; k < THREADS / 64; ++k )
+         r = fmin( r, sh[k] );
+   }
+   return r;
+}
+template < int THREADS >
+__device__ inline double block_max( double v, double* sh )
+{
+   v = wave_max( v );
+   if ( ( threadIdx.x & 63 ) == 0 )
+      sh[threadIdx.x >> 6] = v;
+   __syncthreads();
+   double r = v;
+   if ( threadIdx.x == 0 )
+   {
+#pragma unroll
+      for ( int k = 1; k < THREADS / 64; ++k )
+         r = fmax( r, sh[k] );
+   }
+   return r;
+}
+
+// ---- the statistics reduction (hyteg_hip_p1_reduce_cells, hyteg_hip_p2_edge_reduce_cells) ------------------------------------
+// five accumulators per lane, in the order of HYTEG_HIP_REDUCE_*; the starting values are the reference's
+// (VertexDoFFunction.cpp:1809, 1912, 1962, 2012) and what an empty selection returns
+struct Stats
+{
+   double v[HYTEG_HIP_REDUCE_COUNT] = { 0.0, 0.0, DBL_MAX, -DBL_MAX, 0.0 };
+};
+// an entry that is not selected is replaced by the neutral element of each accumulator, never used in arithmetic
+__device__ inline void stats_take( Stats& s, double x, bool selected )
+{
+   const double ax = fabs( x );
+   s.v[HYTEG_HIP_REDUCE_SUM] += selected ? x : 0.0;
+   s.v[HYTEG_HIP_REDUCE_SUM_ABS] += selected ? ax : 0.0;
+   s.v[HYTEG_HIP_REDUCE_MIN]     = fmin( s.v[HYTEG_HIP_REDUCE_MIN], selected ? x : DBL_MAX );
+   s.v[HYTEG_HIP_REDUCE_MAX]     = fmax( s.v[HYTEG_HIP_REDUCE_MAX], selected ? x : -DBL_MAX );
+   s.v[HYTEG_HIP_REDUCE_MAX_ABS] = fmax( s.v[HYTEG_HIP_REDUCE_MAX_ABS], selected ? ax : 0.0 );
+}
+// partial statistics b (an array in the order of HYTEG_HIP_REDUCE_*, `stride` doubles apart) folded into a
+__device__ inline void stats_merge( Stats& s, const double* b, int stride )
+{
+   s.v[HYTEG_HIP_REDUCE_SUM] += b[HYTEG_HIP_REDUCE_SUM * stride];
+   s.v[HYTEG_HIP_REDUCE_SUM_ABS] += b[HYTEG_HIP_REDUCE_SUM_ABS * stride];
+   s.v[HYTEG_HIP_REDUCE_MIN]     = fmin( s.v[HYTEG_HIP_REDUCE_MIN], b[HYTEG_HIP_REDUCE_MIN * stride] );
+   s.v[HYTEG_HIP_REDUCE_MAX]     = fmax( s.v[HYTEG_HIP_REDUCE_MAX], b[HYTEG_HIP_REDUCE_MAX * stride] );
+   s.v[HYTEG_HIP_REDUCE_MAX_ABS] = fmax( s.v[HYTEG_HIP_REDUCE_MAX_ABS], b[HYTEG_HIP_REDUCE_MAX_ABS * stride] );
+}
+// the statistics of a workgroup, valid in thread 0; sh: HYTEG_HIP_REDUCE_COUNT * THREADS / 64 doubles of LDS (fixed trees)
+template < int THREADS >
+__device__ inline Stats block_stats( const Stats& s, double* sh )
+{
+   constexpr int W = THREADS / 64;
+   Stats         r;
+   r.v[HYTEG_HIP_REDUCE_SUM]     = block_sum< THREADS >( s.v[HYTEG_HIP_REDUCE_SUM], sh + HYTEG_HIP_REDUCE_SUM * W );
+   r.v[HYTEG_HIP_REDUCE_SUM_ABS] = block_sum< THREADS >( s.v[HYTEG_HIP_REDUCE_SUM_ABS], sh + HYTEG_HIP_REDUCE_SUM_ABS * W );
+   r.v[HYTEG_HIP_REDUCE_MIN]     = block_min< THREADS >( s.v[HYTEG_HIP_REDUCE_MIN], sh + HYTEG_HIP_REDUCE_MIN * W );
+   r.v[HYTEG_HIP_REDUCE_MAX]     = block_max< THREADS >( s.v[HYTEG_HIP_REDUCE_MAX], sh + HYTEG_HIP_REDUCE_MAX * W );
+   r.v[HYTEG_HIP_REDUCE_MAX_ABS] = block_max< THREADS >( s.v[HYTEG_HIP_REDUCE_MAX_ABS], sh + HYTEG_HIP_REDUCE_MAX_ABS * W );
+   return r;
+}
+
+// Workgroups per cell of the statistics reduction, from the number of 256-entry tiles of a cell's array alone (never from the
+// number of cells in the launch: a cell's partial results and their order are then the same in every batch).  Up to
+// kReduceSoloTiles tiles one workgroup walks the whole cell and writes the result, one launch; above that the tiles are dealt
+// round robin to min( tiles, kReduceMaxGroups ) workgroups and reduce_finish folds each cell's partial results in a second launch.
+constexpr int kReduceSoloTiles = 32, kReduceMaxGroups = 1024;
+inline int    reduce_groups( int64_t tiles )
+{
+   return tiles <= kReduceSoloTiles ? 1 : (int) ( tiles < kReduceMaxGroups ? tiles : kReduceMaxGroups );
+}
+// results[c][q] = partial results [c][q][0 .. groups) of cell c folded in ascending order by one workgroup per cell (p1_batch.hip)
+int reduce_finish( hipStream_t stream, const double* partial, int ncells, int groups, double* results );
 
 // 1 / numNeighborCells from the counts of the C-ABI, which must be >= 1
 inline int to_nnc14( const double* nnc, Nnc14* out, const char* who )

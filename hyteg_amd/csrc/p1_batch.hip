@@ -213,6 +213,71 @@ __global__ __launch_bounds__( kThreads ) void batch_dot_final_kernel( const doub
    }
 }
 
+// ---- statistics: sum, sum of magnitudes, min, max, max magnitude of every cell in one pass -------------------------
+struct ReduceB
+{
+   const double* a[kMaxB];
+   unsigned      mask[kMaxB];
+   const Tile*   tiles;
+   int           N, ntiles;
+   double*       partial; // [cell][statistic][workgroup of the cell]
+   double*       results; // [cell][statistic]
+};
+
+// workgroup g of gridDim.x takes the tiles g, g + gridDim.x, .. of cell blockIdx.y: what a cell's workgroups read, and in which
+// order, depends on the level alone (reduce_groups), so a cell's numbers are the same in every batch and at every position
+__global__ __launch_bounds__( kThreads ) void batch_reduce_kernel( const ReduceB A )
+{
+   __shared__ double sh[HYTEG_HIP_REDUCE_COUNT * kThreads / 64];
+   const int         cell = blockIdx.y;
+   const unsigned    mask = A.mask[cell];
+   const double*     a    = A.a[cell];
+   Stats             s;
+   if ( mask != 0 )
+      for ( int t = blockIdx.x; t < A.ntiles; t += gridDim.x )
+      {
+         const Tile tl = A.tiles[t];
+#pragma unroll
+         for ( int u = 0; u < kPer; ++u )
+         {
+            // a lane beyond the tile decodes (and loads) the tile's last entry: the load does not wait for the selection
+            const Point p = decode( tl, A.N, u );
+            stats_take( s, a[p.i], p.ok && ( ( mask >> p.cls ) & 1u ) );
+         }
+      }
+   const Stats r = block_stats< kThreads >( s, sh );
+   if ( threadIdx.x != 0 )
+      return;
+   if ( gridDim.x == 1 )
+   {
+#pragma unroll
+      for ( int q = 0; q < HYTEG_HIP_REDUCE_COUNT; ++q )
+         A.results[cell * HYTEG_HIP_REDUCE_COUNT + q] = r.v[q];
+      return;
+   }
+#pragma unroll
+   for ( int q = 0; q < HYTEG_HIP_REDUCE_COUNT; ++q )
+      A.partial[( cell * HYTEG_HIP_REDUCE_COUNT + q ) * gridDim.x + blockIdx.x] = r.v[q];
+}
+
+// one workgroup per cell: thread t folds the partial results t, t + kThreads, .. in ascending order, then the fixed trees
+__global__ __launch_bounds__( kThreads ) void reduce_finish_kernel( const double* partial, int groups, double* results )
+{
+   __shared__ double sh[HYTEG_HIP_REDUCE_COUNT * kThreads / 64];
+   const int         cell = blockIdx.x;
+   const double*     base = partial + (size_t) cell * HYTEG_HIP_REDUCE_COUNT * groups;
+   Stats             s;
+   for ( int g = threadIdx.x; g < groups; g += kThreads )
+      stats_merge( s, base + g, groups );
+   const Stats r = block_stats< kThreads >( s, sh );
+   if ( threadIdx.x == 0 )
+   {
+#pragma unroll
+      for ( int q = 0; q < HYTEG_HIP_REDUCE_COUNT; ++q )
+         results[cell * HYTEG_HIP_REDUCE_COUNT + q] = r.v[q];
+   }
+}
+
 // ---- apply / Jacobi ------------------------------------------------------------------------------------------
 struct ApplyB
 {
@@ -783,6 +848,53 @@ HYTEG_HIP_API int hyteg_hip_p1_dot_cells_cg( int                  ncells,
    HH_REQUIRE( s_dev && ( slot == HYTEG_HIP_CG_PAP || slot == HYTEG_HIP_CG_RR ) && phase >= 0 && phase <= 2,
                "p1_dot_cells_cg: slot must be PAP or RR, phase 0..2" );
    return launch_dot_b( ncells, a, b, level, masks, s_dev + slot, workspace_dev, s_dev, phase, rel_tol, abs_tol, stream );
+}
+
+} // extern "C"
+
+namespace hyteg_hip {
+int reduce_finish( hipStream_t stream, const double* partial, int ncells, int groups, double* results )
+{
+   hipLaunchKernelGGL( reduce_finish_kernel, dim3( (unsigned) ncells ), dim3( kThreads ), 0, stream, partial, groups, results );
+   HH_CHECK_HIP( hipGetLastError() );
+   return HYTEG_HIP_OK;
+}
+} // namespace hyteg_hip
+
+extern "C" {
+
+HYTEG_HIP_API size_t hyteg_hip_reduce_workspace_bytes( void )
+{
+   return (size_t) kMaxB * kReduceMaxGroups * HYTEG_HIP_REDUCE_COUNT * sizeof( double );
+}
+
+HYTEG_HIP_API int hyteg_hip_p1_reduce_cells( int                  ncells,
+                                             const double* const* a,
+                                             int                  level,
+                                             const unsigned*      masks,
+                                             double*              results_dev,
+                                             void*                workspace_dev,
+                                             hyteg_hip_stream_t   stream )
+{
+   BATCH_CHECKS( "p1_reduce_cells" );
+   HH_REQUIRE( a && results_dev && workspace_dev, "p1_reduce_cells: null pointer" );
+   ReduceB A{};
+   for ( int c = 0; c < ncells; ++c )
+   {
+      HH_REQUIRE( a[c], "p1_reduce_cells: null array" );
+      A.a[c]    = a[c];
+      A.mask[c] = masks[c] & HYTEG_HIP_MASK_ALL;
+   }
+   TileTable tt;
+   int       rc = full_tiles( level, &tt );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   A.tiles = tt.dev, A.N = ( 1 << level ) + 1, A.ntiles = tt.count;
+   A.partial = static_cast< double* >( workspace_dev ), A.results = results_dev;
+   const int groups = reduce_groups( tt.count );
+   hipLaunchKernelGGL( batch_reduce_kernel, dim3( (unsigned) groups, (unsigned) ncells ), dim3( kThreads ), 0, as_stream( stream ), A );
+   HH_CHECK_HIP( hipGetLastError() );
+   return groups == 1 ? HYTEG_HIP_OK : reduce_finish( as_stream( stream ), A.partial, ncells, groups, results_dev );
 }
 
 static int launch_apply_b( int                  mode,

@@ -191,9 +191,70 @@ __global__ __launch_bounds__( kThreads ) void p2_sum_partials_kernel( const doub
    }
 }
 
+// the statistics (sum, sum of magnitudes, min, max, max magnitude) of the edge-DoF arrays of up to HYTEG_HIP_MAX_BATCH macro-cells in one
+// pass: blockIdx.y = cell, workgroup g of gridDim.x takes the 256-entry tiles g, g + gridDim.x, .. of the cell's array.  gridDim.x comes
+// from the level alone (reduce_groups), so a cell's numbers do not depend on the batch it is in (batch_reduce_kernel, p1_batch.hip)
+struct EdgeReduceArgs
+{
+   const double* a[HYTEG_HIP_MAX_BATCH];
+   unsigned      mask[HYTEG_HIP_MAX_BATCH];
+   int64_t       size;
+   int           N;
+   double*       partial; // [cell][statistic][workgroup of the cell]
+   double*       results; // [cell][statistic]
+};
+__global__ __launch_bounds__( kThreads ) void p2_edge_reduce_batch_kernel( const EdgeReduceArgs A )
+{
+   __shared__ double sh[HYTEG_HIP_REDUCE_COUNT * kThreads / 64];
+   const int         cell = blockIdx.y;
+   const unsigned    mask = A.mask[cell];
+   const double*     a    = A.a[cell];
+   Stats             s;
+   if ( mask != 0 )
+      for ( int64_t i = (int64_t) blockIdx.x * kThreads + threadIdx.x; i < A.size; i += (int64_t) gridDim.x * kThreads )
+      {
+         int        x, y, z, o;
+         const bool selected = edge_entry( A.N - 1, i, x, y, z, o ) && ( ( mask >> edge_class( A.N, x, y, z, o ) ) & 1u );
+         stats_take( s, a[i], selected );
+      }
+   const Stats r = block_stats< kThreads >( s, sh );
+   if ( threadIdx.x != 0 )
+      return;
+   if ( gridDim.x == 1 )
+   {
+#pragma unroll
+      for ( int q = 0; q < HYTEG_HIP_REDUCE_COUNT; ++q )
+         A.results[cell * HYTEG_HIP_REDUCE_COUNT + q] = r.v[q];
+      return;
+   }
+#pragma unroll
+   for ( int q = 0; q < HYTEG_HIP_REDUCE_COUNT; ++q )
+      A.partial[( cell * HYTEG_HIP_REDUCE_COUNT + q ) * gridDim.x + blockIdx.x] = r.v[q];
+}
+
 } // namespace
 
 extern "C" {
+
+HYTEG_HIP_API int hyteg_hip_p2_edge_reduce_cells( int ncells, const double* const* a, int level, const unsigned* masks, double* results_dev,
+                                                  void* workspace_dev, hyteg_hip_stream_t stream )
+{
+   HH_REQUIRE( a && masks && results_dev && workspace_dev, "p2_edge_reduce_cells: null pointer" );
+   HH_REQUIRE( ncells >= 1 && ncells <= HYTEG_HIP_MAX_BATCH, "p2_edge_reduce_cells: 1 <= ncells <= HYTEG_HIP_MAX_BATCH" );
+   HH_REQUIRE( level >= 0 && level <= HYTEG_HIP_P2_MAX_LEVEL, "p2_edge_reduce_cells: level out of range [0,9]" );
+   EdgeReduceArgs A{};
+   A.size = (int64_t) hyteg_hip_p2_edge_array_size( level ), A.N = ( 1 << level ) + 1;
+   A.partial = static_cast< double* >( workspace_dev ), A.results = results_dev;
+   for ( int c = 0; c < ncells; ++c )
+   {
+      HH_REQUIRE( a[c], "p2_edge_reduce_cells: null array" );
+      A.a[c] = a[c], A.mask[c] = masks[c] & HYTEG_HIP_MASK_ALL;
+   }
+   const int groups = reduce_groups( ( A.size + kThreads - 1 ) / kThreads );
+   hipLaunchKernelGGL( p2_edge_reduce_batch_kernel, dim3( (unsigned) groups, (unsigned) ncells ), dim3( kThreads ), 0, as_stream( stream ), A );
+   HH_CHECK_HIP( hipGetLastError() );
+   return groups == 1 ? HYTEG_HIP_OK : reduce_finish( as_stream( stream ), A.partial, ncells, groups, results_dev );
+}
 
 HYTEG_HIP_API int hyteg_hip_p2_edge_vector_cell_masked( int                  op,
                                                         double*              dst,

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -49,6 +50,11 @@ SIGNATURES = {
     "hyteg_host_storage_check_transport": (_i, [_vp]),
     "hyteg_host_storage_transport_name": (_i, [_vp, C.c_char_p, _i]),
     "hyteg_host_storage_allreduce_sum": (_i, [_vp, _dp, _i]),
+    "hyteg_host_storage_allreduce_max": (_i, [_vp, _dp, _i]),
+    "hyteg_host_storage_p1_number_of_dofs": (_i, [_vp, _i, _i, C.POINTER(C.c_ulonglong)]),
+    "hyteg_host_storage_p2_number_of_dofs": (_i, [_vp, _i, _i, C.POINTER(C.c_ulonglong)]),
+    "hyteg_host_p1_reduce": (_i, [_vp, _i, _i, _i, _dp]),
+    "hyteg_host_p2_reduce": (_i, [_vp, _i, _i, _i, _dp]),
     "hyteg_host_storage_enable_timing": (_i, [_vp, _i, _i]),
     "hyteg_host_storage_timing_json": (_i, [_vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hyteg_host_storage_timing_reset": (_i, [_vp]),
@@ -236,6 +242,41 @@ def cell_size(level: int) -> int:
     return n * (n + 1) * (n + 2) // 6
 
 
+class Reduction(NamedTuple):
+    """the statistics of a function from one pass over its arrays (P1Function::reduceLocal)"""
+    sum: float
+    sum_abs: float
+    min: float
+    max: float
+    max_magnitude: float
+
+
+class _Reductions:
+    """sumGlobal / getMaxDoFValue / getMinDoFValue / getMaxDoFMagnitude of the function classes (VertexDoFFunction.cpp:1796-2057,
+    P2Function.cpp:351-365, 566-605).  The sums count every DoF once and the cell interiors only if `flag` contains Inner; the
+    extrema always include the cell interiors, whatever the flag -- the reference's rule."""
+
+    _reduce_fn = None  # name of the facade function
+
+    def reduce(self, level, flag=All, mpi_reduce=True) -> Reduction:
+        out = (C.c_double * 5)()
+        _ck(getattr(lib(), self._reduce_fn)(self.h, int(level), int(flag), int(bool(mpi_reduce)), out), self._reduce_fn)
+        return Reduction(*out)
+
+    def sum(self, level, flag=All, absolute=False):
+        r = self.reduce(level, flag)
+        return r.sum_abs if absolute else r.sum
+
+    def max_value(self, level, flag=All, mpi_reduce=True):
+        return self.reduce(level, flag, mpi_reduce).max
+
+    def min_value(self, level, flag=All, mpi_reduce=True):
+        return self.reduce(level, flag, mpi_reduce).min
+
+    def max_magnitude(self, level, flag=All, mpi_reduce=True):
+        return self.reduce(level, flag, mpi_reduce).max_magnitude
+
+
 class Storage:
     """hyteg::PrimitiveStorage"""
 
@@ -378,6 +419,19 @@ class Storage:
         _ck(lib().hyteg_host_storage_allreduce_sum(self.h, a.ctypes.data_as(_dp), len(a)), "storage_allreduce_sum")
         return a
 
+    def allreduce_max(self, values):
+        """maximum over all ranks of each of a sequence of floats (exact; built on the transport's sum); min = -allreduce_max(-x)"""
+        a = np.ascontiguousarray(values, dtype=np.float64).copy()
+        _ck(lib().hyteg_host_storage_allreduce_max(self.h, a.ctypes.data_as(_dp), len(a)), "storage_allreduce_max")
+        return a
+
+    def number_of_dofs(self, level, p2=False, global_=True):
+        """numberOfGlobalDoFs / numberOfLocalDoFs of a P1 (p2: a P2) function: what the sum of a function of ones gives"""
+        n = C.c_ulonglong()
+        fn = lib().hyteg_host_storage_p2_number_of_dofs if p2 else lib().hyteg_host_storage_p1_number_of_dofs
+        _ck(fn(self.h, int(level), int(bool(global_)), C.byref(n)), "number_of_dofs")
+        return n.value
+
     def enable_timing(self, on=True, synchronize=False):
         """walberla-style timing tree with the reference's timer names; synchronize: ranges measure device execution"""
         _ck(lib().hyteg_host_storage_enable_timing(self.h, int(on), int(synchronize)), "storage_enable_timing")
@@ -423,8 +477,9 @@ class Storage:
             self.h = None
 
 
-class P1Function:
+class P1Function(_Reductions):
     """hyteg::P1Function<double>"""
+    _reduce_fn = "hyteg_host_p1_reduce"
 
     def __init__(self, storage: Storage, name: str, min_level: int, max_level: int, _borrowed=None):
         self.storage, self.min_level, self.max_level = storage, min_level, max_level
@@ -793,8 +848,9 @@ class StokesSolver:
         self.h = None
 
 
-class P2Function:
+class P2Function(_Reductions):
     """hyteg::P2Function<double>: vertex DoFs (the P1 cell array) + edge DoFs (EdgeDoFIndexing.hpp layout)"""
+    _reduce_fn = "hyteg_host_p2_reduce"
 
     def __init__(self, storage: Storage, name: str, min_level: int, max_level: int, _borrowed=None):
         self.storage = storage

@@ -194,6 +194,7 @@ class RcclTransport : public Transport
    bool        collective() const override { return false; }
    bool        anyStream( int, int ) const override { return true; }
    const char* name() const override { return "rccl"; }
+   static constexpr int kScalars = 16; // values per allreduceSum (PrimitiveStorage::allreduceMax sizes its rounds by it)
 
  private:
    struct Events
@@ -212,7 +213,6 @@ class RcclTransport : public Transport
       }
       return it->second;
    }
-   static constexpr int                         kScalars = 16;
    hyteg_hip_comm_t                             comm_       = nullptr;
    hyteg_hip_stream_t                           commStream_ = nullptr;
    double*                                      scalars_    = nullptr;

@@ -82,6 +82,24 @@ std::vector< std::reference_wrapper< const P2Function< double > > > refs2( int n
       r.push_back( std::cref( F2( fs[i] ) ) );
    return r;
 }
+// one device pass for the five numbers; over the ranks: one sum of two values, three maxima (min = -max( -x ), VertexDoFFunction.cpp:2053)
+template < typename Function >
+void reduceInto( const Function& f, int level, int flag, int mpiReduce, double* out )
+{
+   const auto r                  = f.reduceLocal( (uint_t) level, DoFType( flag ) );
+   out[HYTEG_HIP_REDUCE_SUM]     = r.sum;
+   out[HYTEG_HIP_REDUCE_SUM_ABS] = r.sumAbs;
+   out[HYTEG_HIP_REDUCE_MIN]     = r.min;
+   out[HYTEG_HIP_REDUCE_MAX]     = r.max;
+   out[HYTEG_HIP_REDUCE_MAX_ABS] = r.maxMagnitude;
+   const PrimitiveStorage& st    = *f.getStorage();
+   if ( !mpiReduce || st.numRanks() == 1 )
+      return;
+   st.requireTransport( "reduce" ).allreduceSum( out + HYTEG_HIP_REDUCE_SUM, 2 );
+   out[HYTEG_HIP_REDUCE_MIN]     = -st.allreduceMax( -out[HYTEG_HIP_REDUCE_MIN], "reduce" );
+   out[HYTEG_HIP_REDUCE_MAX]     = st.allreduceMax( out[HYTEG_HIP_REDUCE_MAX], "reduce" );
+   out[HYTEG_HIP_REDUCE_MAX_ABS] = st.allreduceMax( out[HYTEG_HIP_REDUCE_MAX_ABS], "reduce" );
+}
 // fn( A ) with the operator the handle holds
 template < typename Fn >
 void withOp( hh_operator_t op, Fn&& fn )
@@ -428,6 +446,21 @@ HYTEG_HOST_API int hyteg_host_storage_allreduce_sum( hh_storage_t s, double* val
          S( s ).requireTransport( "allreduce_sum" ).allreduceSum( values, n );
    } );
 }
+HYTEG_HOST_API int hyteg_host_storage_allreduce_max( hh_storage_t s, double* values, int n )
+{
+   return guarded( [&] {
+      for ( int k = 0; k < n; ++k )
+         values[k] = S( s ).allreduceMax( values[k], "allreduce_max" );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_storage_p1_number_of_dofs( hh_storage_t s, int level, int global, unsigned long long* count )
+{
+   return guarded( [&] { *count = S( s ).numberOfDoFs( (uint_t) level, 0, global != 0 ); } );
+}
+HYTEG_HOST_API int hyteg_host_storage_p2_number_of_dofs( hh_storage_t s, int level, int global, unsigned long long* count )
+{
+   return guarded( [&] { *count = S( s ).numberOfDoFs( (uint_t) level, 0, global != 0 ) + S( s ).numberOfDoFs( (uint_t) level, 1, global != 0 ); } );
+}
 HYTEG_HOST_API int hyteg_host_storage_enable_timing( hh_storage_t s, int on, int synchronize )
 {
    return guarded( [&] { S( s ).enableTiming( on != 0, synchronize != 0 ); } );
@@ -544,6 +577,10 @@ HYTEG_HOST_API int hyteg_host_function_dot( hh_function_t a, hh_function_t b, in
    return guarded( [&] {
       *result = global ? F( a ).dotGlobal( F( b ), (uint_t) level, DoFType( flag ) ) : F( a ).dotLocal( F( b ), (uint_t) level, DoFType( flag ) );
    } );
+}
+HYTEG_HOST_API int hyteg_host_p1_reduce( hh_function_t f, int level, int flag, int mpi_reduce, double* out )
+{
+   return guarded( [&] { reduceInto( F( f ), level, flag, mpi_reduce, out ); } );
 }
 HYTEG_HOST_API int hyteg_host_function_sum_shared( hh_function_t f, int level, int flag )
 {
@@ -1013,6 +1050,10 @@ HYTEG_HOST_API int hyteg_host_p2function_mult_elementwise( hh_p2function_t dst, 
 HYTEG_HOST_API int hyteg_host_p2function_dot( hh_p2function_t a, hh_p2function_t b, int level, int flag, double* result )
 {
    return guarded( [&] { *result = F2( a ).dotGlobal( F2( b ), (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2_reduce( hh_p2function_t f, int level, int flag, int mpi_reduce, double* out )
+{
+   return guarded( [&] { reduceInto( F2( f ), level, flag, mpi_reduce, out ); } );
 }
 HYTEG_HOST_API int hyteg_host_p2operator_create( hh_storage_t s, int minL, int maxL, hh_p2operator_t* out )
 {

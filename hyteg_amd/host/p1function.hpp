@@ -242,6 +242,97 @@ class P1Function
       return storage_->allreduceSum( local, "dotGlobal" );
    }
 
+   // ---- sum / max / min / max magnitude ( VertexDoFFunction.cpp:1796-1851, :1909-2057 ) ----
+   // The statistics of this rank's DoFs, all from one pass over the arrays (hyteg_hip_p1_reduce_cells): one launch per chunk of
+   // cells, one download, cells combined in ascending order.
+   // Masks, as in the reference: the sums count every DoF once (owned masks) and the cell interiors only if `flag` contains Inner
+   // (:1841-1847).  getMaxDoFValue, getMinDoFValue and getMaxDoFMagnitude do NOT flag-test the macro-cells (:1914-1918, :1964-1968,
+   // :2014-2018): a cell's interior always takes part, whatever the flag, and only the faces, edges and vertices are selected by it.
+   // That is the reference's behaviour and is kept.  With Inner in the flag the two sets of masks are the same and one pass serves
+   // all five numbers; without it the extrema take a second pass under their own masks (still one download).
+   struct Reduction
+   {
+      ValueType sum = 0, sumAbs = 0, min = std::numeric_limits< ValueType >::max(), max = -std::numeric_limits< ValueType >::max(),
+                maxMagnitude = 0;
+      // the other part of a composite function, or another cell, folded in
+      void merge( const Reduction& o )
+      {
+         sum += o.sum, sumAbs += o.sumAbs;
+         min = std::min( min, o.min ), max = std::max( max, o.max ), maxMagnitude = std::max( maxMagnitude, o.maxMagnitude );
+      }
+   };
+   Reduction reduceLocal( uint_t level, DoFType flagIn = All ) const
+   {
+      ScopedTimer timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Sum (local)" );
+      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      return reduceArrays( *storage_, flag, [&]( int first, int count, const unsigned* masks, double* results ) {
+         const auto a = cellPointers( level, first, count );
+         hipCheck( hyteg_hip_p1_reduce_cells( count, a.data(), (int) level, masks, results, storage_->reduceWorkspace(), storage_->stream() ),
+                   "reduceLocal" );
+      } );
+   }
+   // shared with the edge-DoF part of P2Function: launch( first, count, masks, results_dev ) reduces a chunk of cells
+   template < typename Launch >
+   static Reduction reduceArrays( const PrimitiveStorage& storage, DoFType flag, Launch&& launch )
+   {
+      const uint_t nLocal = storage.getNumberOfLocalCells();
+      Reduction    r;
+      if ( nLocal == 0 )
+         return r;
+      const auto              sumMasks = storage.masksFor( flag, true );
+      std::vector< unsigned > extMasks = sumMasks;
+      for ( unsigned& m : extMasks )
+         m |= HYTEG_HIP_MASK_INNER;
+      const uint_t sets = extMasks == sumMasks ? 1 : 2;
+      double*      dev  = storage.reduceResult();
+      storage.forCellChunks( [&]( int first, int count ) {
+         launch( first, count, sumMasks.data() + first, dev + (size_t) first * HYTEG_HIP_REDUCE_COUNT );
+         if ( sets == 2 )
+            launch( first, count, extMasks.data() + first, dev + ( nLocal + (size_t) first ) * HYTEG_HIP_REDUCE_COUNT );
+      } );
+      std::vector< double > host( sets * nLocal * HYTEG_HIP_REDUCE_COUNT );
+      hipCheck( hyteg_hip_download( host.data(), dev, host.size() * sizeof( double ), storage.stream() ), "reduceLocal: download" );
+      for ( uint_t c = 0; c < nLocal; ++c ) // cells in ascending order: deterministic
+      {
+         const double* s = host.data() + c * HYTEG_HIP_REDUCE_COUNT;
+         const double* e = host.data() + ( ( sets - 1 ) * nLocal + c ) * HYTEG_HIP_REDUCE_COUNT;
+         r.sum += s[HYTEG_HIP_REDUCE_SUM], r.sumAbs += s[HYTEG_HIP_REDUCE_SUM_ABS];
+         r.min          = std::min( r.min, e[HYTEG_HIP_REDUCE_MIN] );
+         r.max          = std::max( r.max, e[HYTEG_HIP_REDUCE_MAX] );
+         r.maxMagnitude = std::max( r.maxMagnitude, e[HYTEG_HIP_REDUCE_MAX_ABS] );
+      }
+      return r;
+   }
+   ValueType sumLocal( uint_t level, DoFType flag = All, bool absolute = false ) const
+   {
+      const Reduction r = reduceLocal( level, flag );
+      return absolute ? r.sumAbs : r.sum;
+   }
+   ValueType sumGlobal( uint_t level, DoFType flag = All, bool absolute = false ) const
+   {
+      const double local = sumLocal( level, flag, absolute );
+      ScopedTimer  timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Sum (reduce)" );
+      return storage_->allreduceSum( local, "sumGlobal" );
+   }
+   ValueType getMaxDoFValue( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   {
+      const double local = reduceLocal( level, flag ).max;
+      return mpiReduce ? storage_->allreduceMax( local, "getMaxDoFValue" ) : local;
+   }
+   ValueType getMinDoFValue( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   {
+      const double local = reduceLocal( level, flag ).min;
+      return mpiReduce ? -storage_->allreduceMax( -local, "getMinDoFValue" ) : local; // as at VertexDoFFunction.cpp:2053
+   }
+   ValueType getMaxDoFMagnitude( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   {
+      const double local = reduceLocal( level, flag ).maxMagnitude;
+      return mpiReduce ? storage_->allreduceMax( local, "getMaxDoFMagnitude" ) : local;
+   }
+   // numberOfLocalDoFs / numberOfGlobalDoFs< P1FunctionTag > (src/hyteg/functions/FunctionTools.hpp): what the sum of ones gives
+   uint64_t numberOfLocalDoFs( uint_t level ) const { return storage_->numberOfDoFs( level, 0, false ); }
+   uint64_t numberOfGlobalDoFs( uint_t level ) const { return storage_->numberOfDoFs( level, 0, true ); }
+
    // ---- shared-point exchange (the cell-centric replacement of communicate<> / communicateAdditively<>) ----
    // additive: every copy of a shared DoF := sum of all copies (VertexDoFAdditivePackInfo.hpp:676-745 + copy back)
    void sumSharedCopies( uint_t level, DoFType flag = All ) const

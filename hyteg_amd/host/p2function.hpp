@@ -211,6 +211,52 @@ class P2Function
       return storage_->allreduceSum( dotLocal( rhs, level, flag ), "P2Function::dotGlobal" );
    }
 
+   // ---- sum / max / min / max magnitude ( P2Function.cpp:351-365, :566-605: the vertex-DoF part, then the edge-DoF part;
+   // EdgeDoFFunction.cpp:1284-1490 ) ----
+   // one pass over the vertex-DoF arrays and one over the edge-DoF arrays (hyteg_hip_p2_edge_reduce_cells); masks as in
+   // P1Function::reduceLocal -- the extrema of the reference's EdgeDoFFunction do not flag-test the macro-cells either (:1409)
+   using Reduction = typename P1Function< ValueType >::Reduction;
+   Reduction reduceLocal( uint_t level, DoFType flag = All ) const
+   {
+      Reduction   r = vertexDoFFunction_.reduceLocal( level, flag );
+      ScopedTimer timerFn( storage_->getTimingTree(), "P2Function" ), timerOp( storage_->getTimingTree(), "Sum (local)" );
+      r.merge( P1Function< ValueType >::reduceArrays( *storage_, flag, [&]( int first, int count, const unsigned* masks, double* results ) {
+         const auto a = edgeCellPointers( level, first, count );
+         hipCheck( hyteg_hip_p2_edge_reduce_cells( count, a.data(), (int) level, masks, results, storage_->reduceWorkspace(), storage_->stream() ),
+                   "P2Function::reduceLocal" );
+      } ) );
+      return r;
+   }
+   ValueType sumLocal( uint_t level, DoFType flag = All, bool absolute = false ) const
+   {
+      const Reduction r = reduceLocal( level, flag );
+      return absolute ? r.sumAbs : r.sum;
+   }
+   ValueType sumGlobal( uint_t level, DoFType flag = All, bool absolute = false ) const
+   {
+      const double local = sumLocal( level, flag, absolute );
+      ScopedTimer  timerFn( storage_->getTimingTree(), "P2Function" ), timerOp( storage_->getTimingTree(), "Sum (reduce)" );
+      return storage_->allreduceSum( local, "P2Function::sumGlobal" );
+   }
+   ValueType getMaxDoFValue( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   {
+      const double local = reduceLocal( level, flag ).max;
+      return mpiReduce ? storage_->allreduceMax( local, "P2Function::getMaxDoFValue" ) : local;
+   }
+   ValueType getMinDoFValue( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   {
+      const double local = reduceLocal( level, flag ).min;
+      return mpiReduce ? -storage_->allreduceMax( -local, "P2Function::getMinDoFValue" ) : local;
+   }
+   ValueType getMaxDoFMagnitude( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   {
+      const double local = reduceLocal( level, flag ).maxMagnitude;
+      return mpiReduce ? storage_->allreduceMax( local, "P2Function::getMaxDoFMagnitude" ) : local;
+   }
+   // numberOfLocalDoFs / numberOfGlobalDoFs< P2FunctionTag >: vertex DoFs + edge DoFs
+   uint64_t numberOfLocalDoFs( uint_t level ) const { return storage_->numberOfDoFs( level, 0, false ) + storage_->numberOfDoFs( level, 1, false ); }
+   uint64_t numberOfGlobalDoFs( uint_t level ) const { return storage_->numberOfDoFs( level, 0, true ) + storage_->numberOfDoFs( level, 1, true ); }
+
    // every copy of a shared edge DoF := sum of all copies (communicateAdditively< Cell, Face / Edge > of the EdgeDoFFunction)
    void sumSharedEdgeCopies( uint_t level, DoFType flag = All ) const
    {

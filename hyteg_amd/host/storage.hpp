@@ -129,6 +129,10 @@ class PrimitiveStorage
          hyteg_hip_free( dotResult_ );
       if ( dotWorkspace_ )
          hyteg_hip_free( dotWorkspace_ );
+      if ( reduceResult_ )
+         hyteg_hip_free( reduceResult_ );
+      if ( reduceWorkspace_ )
+         hyteg_hip_free( reduceWorkspace_ );
       for ( void* p : scratchAll_ )
          hyteg_hip_free( p );
       for ( int l = 1; l < LanePlanner::kMaxLanes; ++l )
@@ -659,6 +663,54 @@ class PrimitiveStorage
          requireTransport( what ).allreduceSum( &v, 1 );
       return v;
    }
+   // walberla::mpi::allReduce( v, MAX ) on the transport's sum, so that no transport needs a second operation: every rank writes
+   // its value into its own slot of a vector of zeros, the vector is summed over the ranks (exact: x + 0 == x) and the host
+   // takes the largest slot.  In rounds of kAllreduceSlots ranks, the number of scalars the RCCL transport carries per call.
+   static constexpr int kAllreduceSlots = RcclTransport::kScalars;
+   double               allreduceMax( double v, const char* what ) const
+   {
+      if ( nranks_ == 1 )
+         return v;
+      Transport& T      = requireTransport( what );
+      double     result = v;
+      for ( int first = 0; first < nranks_; first += kAllreduceSlots )
+      {
+         const int n                   = std::min( kAllreduceSlots, nranks_ - first );
+         double    slot[kAllreduceSlots] = {};
+         if ( rank_ >= first && rank_ < first + n )
+            slot[rank_ - first] = v;
+         T.allreduceSum( slot, n );
+         for ( int k = 0; k < n; ++k )
+            result = std::max( result, slot[k] );
+      }
+      return result;
+   }
+
+   // ---- DoF counts (numberOfLocalDoFs / numberOfGlobalDoFs, src/hyteg/functions/FunctionTools.hpp): pure topology.  A DoF on a
+   // macro-vertex, -edge or -face belongs to the rank of the lowest-numbered neighbour cell, as in ownedMaskFor -- what the sum of a
+   // function of ones over this rank gives.  dofKind 0: vertex DoFs (P1), 1: edge DoFs; a P2 function has both.
+   uint64_t numberOfDoFs( uint_t level, int dofKind, bool global ) const
+   {
+      const uint64_t n = uint64_t( 1 ) << level;
+      const auto     tet = []( uint64_t w ) { return w * ( w + 1 ) * ( w + 2 ) / 6; };
+      // per macro-edge, macro-face, macro-vertex and macro-cell interior
+      uint64_t per[4];
+      if ( dofKind == 0 )
+         per[0] = n - 1, per[1] = ( n - 1 ) * ( n >= 2 ? n - 2 : 0 ) / 2, per[2] = 1, per[3] = n >= 4 ? tet( n - 3 ) : 0;
+      else
+         per[0] = n, per[1] = 3 * n * ( n - 1 ) / 2, per[2] = 0, per[3] = 6 * tet( n ) + tet( n - 1 ) - 6 * n * n;
+      uint64_t count = 0;
+      for ( const MacroCell& c : cells_ )
+      {
+         if ( !global && c.rank != rank_ )
+            continue;
+         count += per[3];
+         for ( int s = 0; s < 14; ++s )
+            if ( primitiveOfSlot( c, s ).cells.front() == c.id )
+               count += per[s < 6 ? 0 : ( s < 10 ? 1 : 2 )];
+      }
+      return count;
+   }
 
    // Shared-point exchange of the arrays `arrays` (one device array per local cell: the vertex-DoF or the edge-DoF arrays
    // of one function at `level`): pack the partial values other ranks need + start the transfer / wait + reduce local and
@@ -876,6 +928,23 @@ class PrimitiveStorage
    {
       dotResult();
       return dotWorkspace_;
+   }
+   // results of the statistics reduction (reduceLocal of the function classes): two sets of HYTEG_HIP_REDUCE_COUNT numbers per
+   // local cell (one under the sum's masks, one under the masks of the extrema), and the kernels' workspace
+   double* reduceResult() const
+   {
+      if ( !reduceResult_ )
+      {
+         hipCheck( hyteg_hip_malloc( &reduceResult_, sizeof( double ) * 2 * HYTEG_HIP_REDUCE_COUNT * std::max< size_t >( 1, localCells_.size() ) ),
+                   "PrimitiveStorage: malloc" );
+         hipCheck( hyteg_hip_malloc( &reduceWorkspace_, hyteg_hip_reduce_workspace_bytes() ), "PrimitiveStorage: malloc" );
+      }
+      return static_cast< double* >( reduceResult_ );
+   }
+   void* reduceWorkspace() const
+   {
+      reduceResult();
+      return reduceWorkspace_;
    }
 
    // ---------------------------------------------------------------------------------------------------
@@ -1197,6 +1266,7 @@ class PrimitiveStorage
    std::shared_ptr< Transport >                            transport_;
    std::shared_ptr< TimingTree >                           timingTree_;
    mutable void *                                          dotResult_ = nullptr, *dotWorkspace_ = nullptr;
+   mutable void *                                          reduceResult_ = nullptr, *reduceWorkspace_ = nullptr;
    mutable std::map< size_t, std::vector< double* > >      scratchFree_;
    mutable std::vector< void* >                            scratchAll_;
    mutable std::map< std::vector< double* >, double** >    pointerTables_;

@@ -573,6 +573,31 @@ HYTEG_HIP_API int hyteg_hip_p1_dot_cells( int                  ncells,
                                           double*              result_dev,
                                           void*                workspace_dev,
                                           hyteg_hip_stream_t   stream );
+/* The statistics of a function on every macro-cell of a rank in ONE pass over its arrays (8 bytes read per DoF, nothing written):
+ * results_dev[c * HYTEG_HIP_REDUCE_COUNT + q] = statistic q of the points of cell c that masks[c] selects (the 15-bit point mask of
+ * hyteg_hip_p1_dot_cells).  Replaces the per-primitive loops of VertexDoFFunction::sumLocal (VertexDoFFunction.cpp:1805-1851, with and
+ * without `absolute`), getMaxDoFValue (:1909-1957), getMaxDoFMagnitude (:1959-2007) and getMinDoFValue (:2009-2057); an empty
+ * selection gives their starting values 0, 0, +DBL_MAX, -DBL_MAX, 0 (:1809, :1912, :1962, :2012).
+ * The numbers of cell c depend on that cell's array, the level and its mask alone -- not on ncells, the cell's position in the batch
+ * or timing: the workgroups of a cell and the tiles each reads follow from the level, and the partial results of a cell are folded in
+ * a fixed order (up to 32 tiles of 256 entries: one workgroup per cell, one launch; above: up to 1024 per cell and a second launch of
+ * one workgroup per cell).  Stream-ordered, no allocation beyond the cached tile table, no synchronisation.  NaN entries are outside
+ * the contract.  Levels 0..11; a and masks: HOST arrays of ncells entries; workspace_dev: hyteg_hip_reduce_workspace_bytes() bytes,
+ * not to be shared by reductions in flight on different streams. */
+#define HYTEG_HIP_REDUCE_SUM 0     /* sum of x   */
+#define HYTEG_HIP_REDUCE_SUM_ABS 1 /* sum of |x| */
+#define HYTEG_HIP_REDUCE_MIN 2
+#define HYTEG_HIP_REDUCE_MAX 3
+#define HYTEG_HIP_REDUCE_MAX_ABS 4
+#define HYTEG_HIP_REDUCE_COUNT 5
+HYTEG_HIP_API size_t hyteg_hip_reduce_workspace_bytes( void );
+HYTEG_HIP_API int    hyteg_hip_p1_reduce_cells( int                  ncells,
+                                                const double* const* a,
+                                                int                  level,
+                                                const unsigned*      masks,
+                                                double*              results_dev,
+                                                void*                workspace_dev,
+                                                hyteg_hip_stream_t   stream );
 /* stencils_dev: [ncells][15][15]; rows 0..13 = the cell's share of the stencil at a point of macro-primitive slot s
  * (w_slots of hyteg_hip_p1_apply_cell_boundary), row 14 = the inner stencil (w of hyteg_hip_p1_apply_cell) */
 HYTEG_HIP_API int hyteg_hip_p1_apply_cells( int                  ncells,
@@ -732,6 +757,12 @@ HYTEG_HIP_API int hyteg_hip_p2_edge_vector_cells_kinds( int op, int ncells, doub
  * (a, b, masks: HOST arrays of ncells entries; one workgroup per cell, fixed summation order) */
 HYTEG_HIP_API int hyteg_hip_p2_edge_dot_cells_masked( int ncells, const double* const* a, const double* const* b, int level, const unsigned* masks,
                                                       double* results_dev, hyteg_hip_stream_t stream );
+/* hyteg_hip_p1_reduce_cells for the edge-DoF arrays (same arguments, results, workspace and guarantees; entries selected by point class
+ * as in hyteg_hip_p2_edge_dot_cells_masked): the macro-cell loops of EdgeDoFFunction::sumLocal, getMaxDoFValue, getMinDoFValue and
+ * getMaxDoFMagnitude (src/hyteg/edgedofspace/EdgeDoFFunction.cpp:1284-1490).  Levels 0..HYTEG_HIP_P2_MAX_LEVEL; up to 32 tiles of 256
+ * entries (level 4) one workgroup per cell, above that up to 1024 per cell and a second launch. */
+HYTEG_HIP_API int hyteg_hip_p2_edge_reduce_cells( int ncells, const double* const* a, int level, const unsigned* masks, double* results_dev,
+                                                  void* workspace_dev, hyteg_hip_stream_t stream );
 /* hyteg_hip_p2_elementwise_apply_cell_kinds for up to HYTEG_HIP_MAX_BATCH macro-cells of one level in two launches (inner DoFs, boundary
  * DoFs; P2ElementwiseOperator::gemv's loop over the macro-cells, P2ElementwiseOperator.cpp:131-223): all arguments per cell as HOST
  * arrays of ncells entries.  Levels 2..6 (thread-per-DoF kernels: where a launch per cell is pure launch latency). */

@@ -123,6 +123,14 @@ HYTEG_HOST_API int hyteg_host_storage_check_transport( hh_storage_t s );
 /* in-place sum over all ranks of n doubles in host memory through the storage's transport (no-op on one rank):
  * walberla::mpi::allReduceInplace( ..., SUM ) of the reference's norms and dot products */
 HYTEG_HOST_API int hyteg_host_storage_allreduce_sum( hh_storage_t s, double* values, int n );
+/* in-place maximum over all ranks of each of n doubles in host memory (no-op on one rank): walberla::mpi::allReduce( ..., MAX ) of
+ * getMaxDoFValue and its siblings (VertexDoFFunction.cpp:1953).  Built on the transport's sum -- every rank fills its own slot of a vector
+ * of zeros, in rounds of at most 16 ranks -- so it is exact and needs no further transport operation or hook.  min = -max( -x ). */
+HYTEG_HOST_API int hyteg_host_storage_allreduce_max( hh_storage_t s, double* values, int n );
+/* numberOfLocalDoFs / numberOfGlobalDoFs (src/hyteg/functions/FunctionTools.hpp) of a P1 function (vertex DoFs) and of a P2 function
+ * (vertex + edge DoFs) at `level`, from the topology alone (no GPU); a shared DoF belongs to the rank of its lowest-numbered cell */
+HYTEG_HOST_API int hyteg_host_storage_p1_number_of_dofs( hh_storage_t s, int level, int global, unsigned long long* count );
+HYTEG_HOST_API int hyteg_host_storage_p2_number_of_dofs( hh_storage_t s, int level, int global, unsigned long long* count );
 HYTEG_HOST_API int hyteg_host_storage_set_hooks( hh_storage_t s, int ( *exchange_begin )( void*, int, int ),
                                                  int ( *exchange_end )( void*, int, int ),
                                                  int ( *allreduce_sum )( void*, double*, int ), void* user );
@@ -144,6 +152,10 @@ HYTEG_HOST_API int hyteg_host_function_assign( hh_function_t dst, int n, const d
 HYTEG_HOST_API int hyteg_host_function_add( hh_function_t dst, int n, const double* scalars, const hh_function_t* srcs, int level, int flag );
 HYTEG_HOST_API int hyteg_host_function_mult_elementwise( hh_function_t dst, int n, const hh_function_t* srcs, int level, int flag );
 HYTEG_HOST_API int hyteg_host_function_dot( hh_function_t a, hh_function_t b, int level, int flag, int global, double* result );
+/* out[HYTEG_HIP_REDUCE_SUM .. HYTEG_HIP_REDUCE_MAX_ABS] = sumLocal( level, flag ), sumLocal( .., absolute ), getMinDoFValue, getMaxDoFValue,
+ * getMaxDoFMagnitude of the function (VertexDoFFunction.cpp:1796-2057) from ONE pass over its arrays; mpi_reduce != 0: reduced over the
+ * ranks (sumGlobal; mpiReduce = true).  The extrema always include the cell interiors, as in the reference (see P1Function::reduceLocal). */
+HYTEG_HOST_API int hyteg_host_p1_reduce( hh_function_t f, int level, int flag, int mpi_reduce, double* out );
 HYTEG_HOST_API int hyteg_host_function_sum_shared( hh_function_t f, int level, int flag );
 HYTEG_HOST_API int hyteg_host_function_sync_shared( hh_function_t f, int level, int flag );
 /* BoundaryCondition::createAllInnerBC() for this function (the pressure of a Stokes function): every point counts as Inner */
@@ -282,6 +294,8 @@ HYTEG_HOST_API int hyteg_host_p2function_add( hh_p2function_t dst, int n, const 
 /* P2Function::multElementwise (src/hyteg/p2functionspace/P2Function.cpp: vertex- and edge-DoF parts separately) */
 HYTEG_HOST_API int hyteg_host_p2function_mult_elementwise( hh_p2function_t dst, int n, const hh_p2function_t* srcs, int level, int flag );
 HYTEG_HOST_API int hyteg_host_p2function_dot( hh_p2function_t a, hh_p2function_t b, int level, int flag, double* result );
+/* hyteg_host_p1_reduce for a P2 function: vertex-DoF and edge-DoF parts combined as in P2Function.cpp:351-365, :566-605 */
+HYTEG_HOST_API int hyteg_host_p2_reduce( hh_p2function_t f, int level, int flag, int mpi_reduce, double* out );
 HYTEG_HOST_API int hyteg_host_p2operator_create( hh_storage_t s, int min_level, int max_level, hh_p2operator_t* out );
 /* P2toP2QuadraticProlongation::prolongate / prolongateAndAdd (add != 0) from source_level to source_level + 1 and
  * P2toP2QuadraticRestriction::restrict from source_level to source_level - 1 (src/hyteg/gridtransferoperators/) */

@@ -135,6 +135,15 @@ def main():
     timeit("add 1 source", lambda k: capi.p1_add_cell(p(B, k), [2.0], [p(A, k)], L, sh), 24 * inner, inner)
     timeit("multElementwise 2 sources", lambda k: capi.p1_mult_cell(p(B, k), [p(A, k), p(Cc, k)], L, sh), 24 * inner, inner)
     timeit("dot", lambda k: capi.p1_dot_cell(p(A, k), p(B, k), L, res.data_ptr(), ws.data_ptr(), sh), 16 * inner, inner)
+    # the statistics reduction of the function classes (sum, sum of magnitudes, min, max, max magnitude in one pass over the
+    # array, all point classes) beside the dot product of the same array with itself through the batched entry, which decodes the same
+    # point classes; a diagnostic kernel: the figures are information, no threshold is attached
+    rws = torch.zeros(capi.reduce_workspace_bytes() // 8, dtype=torch.float64, device="cuda")
+    res5 = torch.zeros(capi.REDUCE_COUNT, dtype=torch.float64, device="cuda")
+    timeit("statistics reduction (5 numbers, 1 cell, full mask)",
+           lambda k: capi.p1_reduce_cells([p(A, k)], L, [0x7FFF], res5.data_ptr(), rws.data_ptr(), sh), 8 * n, n)
+    timeit("dot a.a beside the statistics reduction (batched entry, 1 cell, full mask)",
+           lambda k: capi.p1_dot_cells([p(A, k)], [p(A, k)], L, [0x7FFF], res.data_ptr(), ws.data_ptr(), sh), 8 * n, n)
     timeit("restrict (fine L -> coarse L-1)", lambda k: capi.p1_restrict_cell(p(Co, k), p(A, k), L - 1, ones, sh), 8 * (n + nc), nc)
     timeit("prolongate Replace (coarse L-1 -> fine L)", lambda k: capi.p1_prolongate_cell(p(Co, k), p(B, k), L - 1, ones, 0, sh),
            8 * (n + nc), n)
