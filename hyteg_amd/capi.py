@@ -121,6 +121,10 @@ SIGNATURES = {
     "hyteg_hip_p2_restrict_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, C.c_uint, _vp]),
     "hyteg_hip_p2_restrict_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _vp, C.POINTER(C.c_uint), _vp]),
     "hyteg_hip_p2_prolongate_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, C.POINTER(C.c_uint), _vp]),
+    "hyteg_hip_p1_to_p2_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp]),
+    "hyteg_hip_p2_to_p1_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp]),
+    "hyteg_hip_p1_to_p2_cell": (_i, [_vp, _vp, _vp, _i, C.c_uint, _vp]),
+    "hyteg_hip_p2_to_p1_cell": (_i, [_vp, _vp, _vp, _i, C.c_uint, _vp]),
     "hyteg_hip_p2_edge_vector_cell_masked": (_i, [_i, _vp, _i, C.POINTER(_vp), _dp, _i, C.c_uint, _vp]),
     "hyteg_hip_p2_edge_vector_cell_kinds": (_i, [_i, _vp, _i, C.POINTER(_vp), _dp, _i, C.c_uint, C.c_uint, _vp]),
     "hyteg_hip_p2_elementwise_apply_cells_kinds": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(_vp), _d, _i,
@@ -595,6 +599,30 @@ def p2_restrict_cells(coarse_v, coarse_e, fine_v, fine_e, coarse_level, nnc_inv_
 def p2_prolongate_cells(fine_v, fine_e, coarse_v, coarse_e, coarse_level, masks, update=REPLACE, stream=0):
     check(lib().hyteg_hip_p2_prolongate_cells(len(fine_v), _ptrs(fine_v), _ptrs(fine_e), _ptrs(coarse_v), _ptrs(coarse_e), coarse_level,
                                               update, _masks(masks), stream), "p2_prolongate_cells")
+
+
+def _ptrs_or_null(ps):
+    return None if ps is None else _ptrs(ps)
+
+
+def p1_to_p2_cells(p2_v, p2_e, p1, p2_level, masks, stream=0):
+    """P1toP2Conversion on a batch of macro-cells: lists of device pointers (one per cell); p1 is of level p2_level + 1"""
+    check(lib().hyteg_hip_p1_to_p2_cells(len(masks), _ptrs_or_null(p2_v), _ptrs_or_null(p2_e), _ptrs_or_null(p1), p2_level,
+                                         _masks(masks), stream), "p1_to_p2_cells")
+
+
+def p2_to_p1_cells(p1, p2_v, p2_e, p2_level, masks, stream=0):
+    """P2toP1Conversion on a batch of macro-cells; the level argument is the P2 level, p1 is of level p2_level + 1"""
+    check(lib().hyteg_hip_p2_to_p1_cells(len(masks), _ptrs_or_null(p1), _ptrs_or_null(p2_v), _ptrs_or_null(p2_e), p2_level,
+                                         _masks(masks), stream), "p2_to_p1_cells")
+
+
+def p1_to_p2_cell(p2_v, p2_e, p1, p2_level, mask=0x7FFF, stream=0):
+    check(lib().hyteg_hip_p1_to_p2_cell(p2_v, p2_e, p1, p2_level, mask, stream), "p1_to_p2_cell")
+
+
+def p2_to_p1_cell(p1, p2_v, p2_e, p2_level, mask=0x7FFF, stream=0):
+    check(lib().hyteg_hip_p2_to_p1_cell(p1, p2_v, p2_e, p2_level, mask, stream), "p2_to_p1_cell")
 
 
 def p2_edge_array_size(level):

@@ -594,6 +594,8 @@ inline bool transfer_by_threads()
 
 } // namespace
 
+#include "kernels_p1p2_conversion.hpp"
+
 // HYTEG_HIP_P2_TRANSFER_INTERLEAVE=1: the kinds of one region follow each other on one XCD instead of grid ( blocks, 8 ), kind by kind.
 // Measured (profiles/r03_p2_transfer_rows.txt): the HBM reads of the restriction fall from 95 to 70 MB, but the launch takes 101 us
 // instead of 56 (prolongation 48.5 instead of 44.0) -- the kinds' very different term counts no longer balance over the XCDs.  Off.
@@ -764,5 +766,38 @@ HYTEG_HIP_API int hyteg_hip_p2_prolongate_cells( int                  ncells,
 {
    return launch_transfer_cells( false, "p2_prolongate_cells", ncells, fine_vertex, fine_edge, coarse_vertex, coarse_edge, coarse_level,
                                  update, nullptr, masks, stream );
+}
+
+HYTEG_HIP_API int hyteg_hip_p1_to_p2_cells( int                  ncells,
+                                            double* const*       p2_vertex,
+                                            double* const*       p2_edge,
+                                            const double* const* p1,
+                                            int                  p2_level,
+                                            const unsigned*      masks,
+                                            hyteg_hip_stream_t   stream )
+{
+   return launch_p1p2_conversion( true, "p1_to_p2_cells", ncells, p1, p2_vertex, p2_edge, p2_level, masks, stream );
+}
+
+HYTEG_HIP_API int hyteg_hip_p2_to_p1_cells( int                  ncells,
+                                            double* const*       p1,
+                                            const double* const* p2_vertex,
+                                            const double* const* p2_edge,
+                                            int                  p2_level,
+                                            const unsigned*      masks,
+                                            hyteg_hip_stream_t   stream )
+{
+   return launch_p1p2_conversion( false, "p2_to_p1_cells", ncells, p1, p2_vertex, p2_edge, p2_level, masks, stream );
+}
+
+// one cell: the batch of one
+HYTEG_HIP_API int hyteg_hip_p1_to_p2_cell( double* p2_vertex, double* p2_edge, const double* p1, int p2_level, unsigned mask, hyteg_hip_stream_t stream )
+{
+   return launch_p1p2_conversion( true, "p1_to_p2_cell", 1, &p1, &p2_vertex, &p2_edge, p2_level, &mask, stream );
+}
+
+HYTEG_HIP_API int hyteg_hip_p2_to_p1_cell( double* p1, const double* p2_vertex, const double* p2_edge, int p2_level, unsigned mask, hyteg_hip_stream_t stream )
+{
+   return launch_p1p2_conversion( false, "p2_to_p1_cell", 1, &p1, &p2_vertex, &p2_edge, p2_level, &mask, stream );
 }
 }

@@ -21,6 +21,7 @@ _vp, _i, _d, _u = C.c_void_p, C.c_int, C.c_double, C.c_uint
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
 EXCHANGE_CB = C.CFUNCTYPE(_i, _vp, _i, _i)
 ALLREDUCE_CB = C.CFUNCTYPE(_i, _vp, _dp, _i)
+LEVEL_CB = C.CFUNCTYPE(None, C.c_uint64, _vp)  # hh_level_callback_t: the callbacks of FullMultigridSolver
 
 SIGNATURES = {
     "hyteg_host_last_error": (C.c_char_p, []),
@@ -128,6 +129,13 @@ SIGNATURES = {
     "hyteg_host_restrict": (_i, [_vp, _i, _i]),
     "hyteg_host_prolongate": (_i, [_vp, _i, _i]),
     "hyteg_host_prolongate_and_add": (_i, [_vp, _i, _i]),
+    "hyteg_host_p1_to_p2": (_i, [_vp, _vp, _i, _i]),
+    "hyteg_host_p2_to_p1": (_i, [_vp, _vp, _i, _i]),
+    "hyteg_host_quadratic_prolongation_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "hyteg_host_quadratic_prolongation_prolongate": (_i, [_vp, _vp, _i, _i]),
+    "hyteg_host_quadratic_prolongation_destroy": (_i, [_vp]),
+    "hyteg_host_fmg_create": (_i, [_vp, _vp, _i, _i, C.POINTER(_u), _i, _i, LEVEL_CB, _vp, LEVEL_CB, _vp, C.POINTER(_vp)]),
+    "hyteg_host_p2_fmg_create": (_i, [_vp, _vp, _i, _i, C.POINTER(_u), _i, LEVEL_CB, _vp, LEVEL_CB, _vp, C.POINTER(_vp)]),
     "hyteg_host_gmg_create": (_i, [_vp, _i, _i, _i, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_chebyshev_coefficients": (_i, [_i, _d, _d, _dp]),
     "hyteg_host_chebyshev_estimate_radius": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(_d)]),
@@ -662,6 +670,78 @@ def prolongate_and_add(f: P1Function, source_level, flag):
     _ck(lib().hyteg_host_prolongate_and_add(f.h, source_level, flag), "prolongateAndAdd")
 
 
+def p1_to_p2(p1: P1Function, p2: "P2Function", p2_level, flag=All):
+    """hyteg::P1toP2Conversion: the P2 function of level p2_level := the P1 function of level p2_level + 1 (a copy, DoF by DoF)"""
+    _ck(lib().hyteg_host_p1_to_p2(p1.h, p2.h, p2_level, flag), "P1toP2Conversion")
+
+
+def p2_to_p1(p2: "P2Function", p1: P1Function, p1_level, flag=All):
+    """hyteg::P2toP1Conversion: the P1 function of level p1_level := the P2 function of level p1_level - 1"""
+    _ck(lib().hyteg_host_p2_to_p1(p2.h, p1.h, p1_level, flag), "P2toP1Conversion")
+
+
+class P1QuadraticProlongation:
+    """hyteg::P1toP1QuadraticProlongationThroughP2Injection( storage, p1_min_level, p1_max_level ): owns the P2 temporary"""
+
+    def __init__(self, storage: Storage, p1_min_level: int, p1_max_level: int):
+        self.storage = storage
+        h = _vp()
+        _ck(lib().hyteg_host_quadratic_prolongation_create(storage.h, p1_min_level, p1_max_level, C.byref(h)), "P1QuadraticProlongation")
+        self.h = h
+
+    def prolongate(self, f: P1Function, source_level, flag):
+        _ck(lib().hyteg_host_quadratic_prolongation_prolongate(self.h, f.h, source_level, flag), "prolongate_quadratic")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_quadratic_prolongation_destroy(self.h)
+            self.h = None
+
+
+def prolongate_quadratic(f: P1Function, source_level, flag):
+    """One quadratic prolongation source_level -> source_level + 1 with a temporary of its own.  The DoFs of the finer level that
+    `flag` excludes end as zero (see hyteg_host.h); a solver that prolongates repeatedly keeps a P1QuadraticProlongation instead."""
+    p = P1QuadraticProlongation(f.storage, source_level, source_level + 1)
+    try:
+        p.prolongate(f, source_level, flag)
+    finally:
+        p.close()
+
+
+def _fmg_arguments(cycles_per_level, post_cycle, post_prolongate):
+    """ctypes arguments of hyteg_host_fmg_create: the cycle counts (a number: the scalar form) and the two callbacks.  An exception
+    raised in a callback cannot cross the C frames: it is kept in `state` and raised by solve()."""
+    if np.ndim(cycles_per_level) == 0:
+        counts, n = (_u * 1)(int(cycles_per_level)), 0
+    else:
+        counts, n = (_u * max(1, len(cycles_per_level)))(*[int(v) for v in cycles_per_level]), len(cycles_per_level)
+        if n == 0:
+            raise ValueError("fmg: cycles_per_level is empty")  # 0 entries would select the scalar form
+    state = {"exception": None}
+
+    def trampoline(fn):
+        if fn is None:
+            return LEVEL_CB()  # a null function pointer
+
+        def call(level, _user):
+            try:
+                if state["exception"] is None:
+                    fn(int(level))
+            except BaseException as e:  # noqa: BLE001 -- re-raised by solve()
+                state["exception"] = e
+
+        return LEVEL_CB(call)
+
+    return counts, n, trampoline(post_cycle), trampoline(post_prolongate), state
+
+
+def _raise_callback_exception(solver):
+    state = getattr(solver, "_callbacks", (None, None, None))[2]
+    if state and state["exception"] is not None:
+        exc, state["exception"] = state["exception"], None
+        raise exc
+
+
 class Solver:
     def __init__(self, handle):
         self.h = handle
@@ -713,8 +793,23 @@ class Solver:
             "solver_create_minres")
         return cls(h)
 
+    @classmethod
+    def fmg(cls, storage, gmg_solver, min_level, max_level, cycles_per_level=1, prolongation="linear", post_cycle=None, post_prolongate=None):
+        """hyteg::FullMultigridSolver around the multigrid solver `gmg_solver`: from min_level up, cycles_per_level (a number, or one
+        per level 0..max_level) cycles, post_cycle( level ), the prolongation to the next level ("linear": P1toP1LinearProlongation,
+        "quadratic": P1toP1QuadraticProlongationThroughP2Injection), post_prolongate( level )"""
+        kind = {"linear": 0, "quadratic": 1}[prolongation]
+        counts, n, cb_cycle, cb_prolongate, state = _fmg_arguments(cycles_per_level, post_cycle, post_prolongate)
+        h = _vp()
+        _ck(lib().hyteg_host_fmg_create(storage.h, gmg_solver.h, min_level, max_level, counts, n, kind, cb_cycle, None, cb_prolongate, None,
+                                        C.byref(h)), "fmg_create")
+        self = cls(h)
+        self._callbacks = (cb_cycle, cb_prolongate, state)  # the C side keeps the function pointers
+        return self
+
     def solve(self, laplace: P1ConstantOperator, x: P1Function, b: P1Function, level: int):
         _ck(lib().hyteg_host_solver_solve(self.h, laplace.h, x.h, b.h, level), "solve")
+        _raise_callback_exception(self)
 
     def set_use_graphs(self, on: bool) -> None:
         """GeometricMultigridSolver::setUseGraphs: record the launches of a cycle once, replay them as graphs (default off)"""
@@ -996,8 +1091,21 @@ class P2Solver:
                                                      int(bool(wcycle)), cg_max_iter, float(cg_tol), C.byref(self.h)), "P2 gmg chebyshev")
         return self
 
+    @classmethod
+    def fmg(cls, storage, gmg_solver, min_level, max_level, cycles_per_level=1, post_cycle=None, post_prolongate=None):
+        """hyteg::FullMultigridSolver around the P2 multigrid solver `gmg_solver`, prolongating with P2toP2QuadraticProlongation;
+        arguments as for Solver.fmg"""
+        self = cls.__new__(cls)
+        self.storage, self.h = storage, _vp()
+        counts, n, cb_cycle, cb_prolongate, state = _fmg_arguments(cycles_per_level, post_cycle, post_prolongate)
+        _ck(lib().hyteg_host_p2_fmg_create(storage.h, gmg_solver.h, min_level, max_level, counts, n, cb_cycle, None, cb_prolongate, None,
+                                           C.byref(self.h)), "P2 fmg_create")
+        self._callbacks = (cb_cycle, cb_prolongate, state)
+        return self
+
     def solve(self, op, x: "P2Function", b: "P2Function", level):
         _ck(lib().hyteg_host_p2_solver_solve(self.h, op.h, x.h, b.h, level), "P2 solve")
+        _raise_callback_exception(self)
 
     def close(self):
         if self.h:

@@ -8,7 +8,9 @@
 //                                multElementwise, dotLocal, dotGlobal)
 //   P1ConstantOperator< Form >   src/constant_stencil_operator/P1ConstantOperator.hpp:33-168 + P1Operator.hpp:192-447
 //   P1toP1LinearRestriction / P1toP1LinearProlongation   src/hyteg/gridtransferoperators/
-//   WeightedJacobiSmoother, GaussSeidelSmoother, SORSmoother, CGSolver, GeometricMultigridSolver  src/hyteg/solvers/
+//   P1toP2Conversion / P2toP1Conversion, P1toP1QuadraticProlongationThroughP2Injection           src/hyteg/gridtransferoperators/
+//   WeightedJacobiSmoother, GaussSeidelSmoother, SORSmoother, CGSolver, GeometricMultigridSolver,
+//   FullMultigridSolver                                                                           src/hyteg/solvers/
 //   ChebyshevSmoother, chebyshev::estimateRadius, InvDiagOperatorWrapper                         src/hyteg/solvers/ChebyshevSmoother.hpp
 //
 // Data model: one device array per (macro-cell, level) in HyTeG's cell layout.  The DoFs
@@ -31,6 +33,7 @@
 #include "p2operator.hpp"
 #include "p2gridtransfer.hpp"
 #include "gridtransfer.hpp"
+#include "p1p2conversion.hpp"
 #include "solvers.hpp"
 #include "chebyshev.hpp"
 #include "stokes.hpp"

@@ -154,6 +154,26 @@ std::shared_ptr< Solver< Op > > makeGmg( const std::shared_ptr< PrimitiveStorage
        (uint_t) pre, (uint_t) post, (uint_t) increment, cycle );
 }
 CycleType cycleOf( int wcycle ) { return wcycle ? CycleType::WCYCLE : CycleType::VCYCLE; }
+struct QuadraticProlongationH
+{
+   std::shared_ptr< P1toP1QuadraticProlongationThroughP2Injection > p;
+};
+// the cycle counts of hyteg_host_fmg_create / hyteg_host_p2_fmg_create: nCycles == 0 is the scalar constructor form (one count for
+// every level), otherwise the counts are handed on as given and FullMultigridSolver checks their number
+std::vector< uint_t > fmgCycles( const char* who, int minL, int maxL, const unsigned* cyclesPerLevel, int nCycles )
+{
+   if ( minL < 0 || maxL < minL || !cyclesPerLevel || nCycles < 0 )
+      throw std::runtime_error( std::string( who ) + ": needs 0 <= min_level <= max_level and cycle counts" );
+   if ( nCycles == 0 )
+      return std::vector< uint_t >( (size_t) maxL + 1, (uint_t) cyclesPerLevel[0] );
+   return std::vector< uint_t >( cyclesPerLevel, cyclesPerLevel + nCycles );
+}
+std::function< void( uint_t ) > levelCallback( hh_level_callback_t fn, void* user )
+{
+   if ( !fn )
+      return []( uint_t ) {};
+   return [fn, user]( uint_t level ) { fn( (uint64_t) level, user ); };
+}
 // borrowed view of a component: an aliasing pointer that shares ownership with the composite and points at the component
 template < class T, class Owner >
 std::shared_ptr< T > viewOf( const std::shared_ptr< Owner >& owner, const T& component )
@@ -747,6 +767,56 @@ HYTEG_HOST_API int hyteg_host_prolongate_and_add( hh_function_t f, int sourceLev
 {
    return guarded( [&] { P1toP1LinearProlongation().prolongateAndAdd( F( f ), (uint_t) sourceLevel, DoFType( flag ) ); } );
 }
+HYTEG_HOST_API int hyteg_host_p1_to_p2( hh_function_t p1, hh_p2function_t p2, int p2Level, int flag )
+{
+   return guarded( [&] { P1toP2Conversion( F( p1 ), F2( p2 ), (uint_t) p2Level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2_to_p1( hh_p2function_t p2, hh_function_t p1, int p1Level, int flag )
+{
+   return guarded( [&] { P2toP1Conversion( F2( p2 ), F( p1 ), (uint_t) p1Level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_quadratic_prolongation_create( hh_storage_t s, int p1MinLevel, int p1MaxLevel, hh_quadratic_prolongation_t* out )
+{
+   return guarded( [&] {
+      if ( p1MinLevel < 0 || p1MaxLevel < 0 )
+         throw std::runtime_error( "quadratic_prolongation_create: negative level" );
+      *out = new QuadraticProlongationH{ std::make_shared< P1toP1QuadraticProlongationThroughP2Injection >( SP( s ), (uint_t) p1MinLevel, (uint_t) p1MaxLevel ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_quadratic_prolongation_prolongate( hh_quadratic_prolongation_t p, hh_function_t f, int sourceLevel, int flag )
+{
+   return guarded( [&] { static_cast< QuadraticProlongationH* >( p )->p->prolongate( F( f ), (uint_t) sourceLevel, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_quadratic_prolongation_destroy( hh_quadratic_prolongation_t p )
+{
+   return guarded( [&] { delete static_cast< QuadraticProlongationH* >( p ); } );
+}
+HYTEG_HOST_API int hyteg_host_fmg_create( hh_storage_t s, hh_solver_t gmg, int minL, int maxL, const unsigned* cyclesPerLevel, int nCycles, int prolongation,
+                                          hh_level_callback_t postCycle, void* postCycleUser, hh_level_callback_t postProlongate,
+                                          void* postProlongateUser, hh_solver_t* out )
+{
+   return guarded( [&] {
+      using Op  = P1ConstantLaplaceOperator;
+      auto g    = std::dynamic_pointer_cast< GeometricMultigridSolver< Op > >( static_cast< SolverH* >( gmg )->p );
+      if ( !g )
+         throw std::runtime_error( "fmg_create: not a geometric multigrid solver" );
+      const auto cycles = fmgCycles( "fmg_create", minL, maxL, cyclesPerLevel, nCycles );
+      const auto cbCycle = levelCallback( postCycle, postCycleUser ), cbProlongate = levelCallback( postProlongate, postProlongateUser );
+      if ( prolongation == 0 )
+         *out = new SolverH{ std::make_shared< FullMultigridSolver< Op > >( SP( s ), g, std::make_shared< P1toP1LinearProlongation >(), (uint_t) minL,
+                                                                             (uint_t) maxL, cycles, cbCycle, cbProlongate ) };
+      else if ( prolongation == 1 )
+      {
+         using Quadratic = P1toP1QuadraticProlongationThroughP2Injection;
+         // the prolongation is used from minL to maxL - 1: its temporary spans the P2 levels minL - 1 .. maxL - 1
+         auto p = std::make_shared< Quadratic >( SP( s ), (uint_t) minL, (uint_t) maxL );
+         *out   = new SolverH{ std::make_shared< FullMultigridSolver< Op, GeometricMultigridSolver< Op >, Quadratic > >( SP( s ), g, p, (uint_t) minL, (uint_t) maxL,
+                                                                                                                         cycles, cbCycle, cbProlongate ) };
+      }
+      else
+         throw std::runtime_error( "fmg_create: prolongation must be 0 (linear) or 1 (quadratic)" );
+   } );
+}
 
 HYTEG_HOST_API int hyteg_host_gmg_create( hh_storage_t s, int minL, int maxL, int smoother, double relax, int pre, int post, int wcycle,
                                           int cgMaxIter, double cgTol, hh_solver_t* out )
@@ -1141,6 +1211,22 @@ HYTEG_HOST_API int hyteg_host_p2_gmg_create( hh_storage_t s, int minL, int maxL,
          sm = std::make_shared< SORSmoother< Op > >( relax );
       *out = new P2SolverH{ makeGmg< Op, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation >(
           SP( s ), sm, cgCoarse< Op >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2_fmg_create( hh_storage_t s, hh_p2solver_t gmg, int minL, int maxL, const unsigned* cyclesPerLevel, int nCycles,
+                                             hh_level_callback_t postCycle, void* postCycleUser, hh_level_callback_t postProlongate,
+                                             void* postProlongateUser, hh_p2solver_t* out )
+{
+   return guarded( [&] {
+      using Op  = P2ElementwiseLaplaceOperator;
+      using Gmg = GeometricMultigridSolver< Op, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation >;
+      auto g    = std::dynamic_pointer_cast< Gmg >( static_cast< P2SolverH* >( gmg )->p );
+      if ( !g )
+         throw std::runtime_error( "p2_fmg_create: not a geometric multigrid solver" );
+      *out = new P2SolverH{ std::make_shared< FullMultigridSolver< Op, Gmg, P2toP2QuadraticProlongation > >(
+          SP( s ), g, std::make_shared< P2toP2QuadraticProlongation >(), (uint_t) minL, (uint_t) maxL,
+          fmgCycles( "p2_fmg_create", minL, maxL, cyclesPerLevel, nCycles ), levelCallback( postCycle, postCycleUser ),
+          levelCallback( postProlongate, postProlongateUser ) ) };
    } );
 }
 HYTEG_HOST_API int hyteg_host_p2_chebyshev_estimate_radius( hh_p2operator_t op, int level, int maxIter, hh_p2function_t x, hh_p2function_t tmp,

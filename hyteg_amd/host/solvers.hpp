@@ -1,11 +1,12 @@
 // solvers.hpp -- part of the C++ host layer above the C-ABI (see hyteg_host.hpp for the data model).
-// smoother wrappers, CGSolver, GeometricMultigridSolver (src/hyteg/solvers/)
+// smoother wrappers, CGSolver, GeometricMultigridSolver, FullMultigridSolver (src/hyteg/solvers/)
 #pragma once
 
 #include "p1operator.hpp"
 #include "p2operator.hpp"
 #include "gridtransfer.hpp"
 #include "p2gridtransfer.hpp"
+#include "p1p2conversion.hpp"
 
 namespace hyteg {
 
@@ -632,6 +633,93 @@ class GeometricMultigridSolver : public Solver< OperatorType >
    Recording*                                   recording_     = nullptr;
    std::map< Key, Recording >                   recordings_;
    uint_t                                       replayed_ = 0;
+};
+
+// FullMultigridSolver.hpp:33-114: from the coarsest level up, cyclesPerLevel[l] multigrid cycles on level l, then the iterate is
+// prolongated to level l + 1 as the start value there.  The FMG prolongation should be one order higher than the cycle's own:
+// P1toP1QuadraticProlongationThroughP2Injection for P1 functions (the linear one is the reference's default), the quadratic one
+// for P2 functions.  The inner solver may replay recorded cycles (setUseGraphs): a cycle invoked at another level is another recording.
+template < class OperatorType, class MultigridSolverType = GeometricMultigridSolver< OperatorType >, class ProlongationType = P1toP1LinearProlongation >
+class FullMultigridSolver : public Solver< OperatorType >
+{
+ public:
+   using FunctionType = typename OperatorType::srcType;
+   using Callback     = std::function< void( uint_t currentLevel ) >;
+   FullMultigridSolver( const std::shared_ptr< PrimitiveStorage >&    storage,
+                        const std::shared_ptr< MultigridSolverType >& gmgSolver,
+                        const std::shared_ptr< ProlongationType >&    fmgProlongation,
+                        const uint_t&                                 minLevel,
+                        const uint_t&                                 maxLevel,
+                        const uint_t&                                 cyclesPerLevel         = 1,
+                        const Callback&                               postCycleCallback      = []( uint_t ) {},
+                        const Callback&                               postProlongateCallback = []( uint_t ) {} )
+   : FullMultigridSolver( storage, gmgSolver, fmgProlongation, minLevel, maxLevel, std::vector< uint_t >( maxLevel + 1, cyclesPerLevel ), postCycleCallback,
+                          postProlongateCallback )
+   {}
+   // one count per level 0..maxLevel; those below minLevel must be given and are ignored
+   FullMultigridSolver( const std::shared_ptr< PrimitiveStorage >&    storage,
+                        const std::shared_ptr< MultigridSolverType >& gmgSolver,
+                        const std::shared_ptr< ProlongationType >&    fmgProlongation,
+                        const uint_t&                                 minLevel,
+                        const uint_t&                                 maxLevel,
+                        const std::vector< uint_t >&                  cyclesPerLevel,
+                        const Callback&                               postCycleCallback      = []( uint_t ) {},
+                        const Callback&                               postProlongateCallback = []( uint_t ) {} )
+   : gmgSolver_( gmgSolver )
+   , fmgProlongation_( fmgProlongation )
+   , minLevel_( minLevel )
+   , maxLevel_( maxLevel )
+   , cyclesPerLevel_( cyclesPerLevel )
+   , flag_( Inner | NeumannBoundary | FreeslipBoundary )
+   , postCycleCallback_( postCycleCallback )
+   , postProlongateCallback_( postProlongateCallback )
+   , storage_( storage )
+   {
+      if ( cyclesPerLevel.size() != maxLevel + 1 )
+         throw std::runtime_error( "FullMultigridSolver: specify the number of cycles for every level in {0, ..., maxLevel}; values below "
+                                   "minLevel must be given but are ignored" );
+      if ( !gmgSolver || !fmgProlongation )
+         throw std::runtime_error( "FullMultigridSolver: needs a multigrid solver and a prolongation" );
+   }
+
+   void solve( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level ) override
+   {
+      if ( level > maxLevel_ )
+         throw std::runtime_error( "FullMultigridSolver: level above maxLevel" );
+      TimingTree* tt = storage_->getTimingTree();
+      ScopedTimer timerFmg( tt, "FMG Solver" );
+      for ( uint_t currentLevel = minLevel_; currentLevel <= level; currentLevel++ )
+      {
+         {
+            ScopedTimer timer( tt, "GMG Solver" );
+            for ( uint_t cycle = 0; cycle < cyclesPerLevel_[currentLevel]; cycle++ )
+               gmgSolver_->solve( A, x, b, currentLevel );
+         }
+         {
+            ScopedTimer timer( tt, "Post-cycle callback" );
+            postCycleCallback_( currentLevel );
+         }
+         {
+            ScopedTimer timer( tt, "FMG Prolongation" );
+            if ( currentLevel < maxLevel_ )
+               fmgProlongation_->prolongate( x, currentLevel, flag_ );
+         }
+         {
+            // also on the top level, where nothing was prolongated (FullMultigridSolver.hpp:109-111)
+            ScopedTimer timer( tt, "Post-prolongate callback" );
+            postProlongateCallback_( currentLevel );
+         }
+      }
+   }
+
+ private:
+   std::shared_ptr< MultigridSolverType > gmgSolver_;
+   std::shared_ptr< ProlongationType >    fmgProlongation_;
+   uint_t                                 minLevel_, maxLevel_;
+   std::vector< uint_t >                  cyclesPerLevel_;
+   DoFType                                flag_;
+   Callback                               postCycleCallback_, postProlongateCallback_;
+   std::shared_ptr< PrimitiveStorage >    storage_;
 };
 
 } // namespace hyteg

@@ -187,4 +187,16 @@ using P2P1TaylorHoodStokesOperator = StokesOperator< P2ConstantLaplaceOperator, 
 using P2P1StokesToP2P1StokesRestriction  = StokesRestriction< P2toP2QuadraticRestriction >;
 using P2P1StokesToP2P1StokesProlongation = StokesProlongation< P2toP2QuadraticProlongation >;
 
+// P1toP2Conversion / P2toP1Conversion of vector functions (P1toP2Conversion.cpp:141-149, P2toP1Conversion.cpp:142-150): component by component
+inline void P1toP2Conversion( const P1VectorFunction< double >& src, const P2VectorFunction< double >& dst, const uint_t& P2Level, const DoFType& flag = All )
+{
+   for ( uint_t k = 0; k < src.getDimension(); ++k )
+      P1toP2Conversion( src[k], dst[k], P2Level, flag );
+}
+inline void P2toP1Conversion( const P2VectorFunction< double >& src, const P1VectorFunction< double >& dst, const uint_t& P1Level, const DoFType& flag = All )
+{
+   for ( uint_t k = 0; k < src.getDimension(); ++k )
+      P2toP1Conversion( src[k], dst[k], P1Level, flag );
+}
+
 } // namespace hyteg

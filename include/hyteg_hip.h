@@ -938,6 +938,40 @@ HYTEG_HIP_API int hyteg_hip_p2_prolongate_cells( int                  ncells,
                                                  const unsigned*      masks,
                                                  hyteg_hip_stream_t   stream );
 
+/* ---- P1 <-> P2 conversion on the macro-cells of a rank ----------------------------------------------------------------
+ * replaces the macro-cell loops of P1toP2Conversion and P2toP1Conversion
+ *   src/hyteg/gridtransferoperators/P1toP2Conversion.cpp:28-149
+ *   src/hyteg/gridtransferoperators/P2toP1Conversion.cpp:28-150
+ * A P2 function of level L has the DoFs of a P1 function of level L + 1: the point ( X, Y, Z ) of the vertex array of level
+ * L + 1 is the P2 DoF with logical index ( X / 2, Y / 2, Z / 2 ) whose kind the parities of ( X, Y, Z ) select -- (e,e,e) vertex,
+ * (o,e,e) X, (e,o,e) Y, (e,e,o) Z, (o,o,e) XY, (o,e,o) XZ, (e,o,o) YZ, (o,o,o) XYZ.  The conversion is this permutation: values
+ * are copied, never rounded.
+ * p1: hyteg_hip_cell_size( p2_level + 1 ) entries; p2_vertex: hyteg_hip_cell_size( p2_level ); p2_edge:
+ * hyteg_hip_p2_edge_array_size( p2_level ) in the seven-block order of the grid transfer above.  p2_level: 0..HYTEG_HIP_P2_MAX_LEVEL.
+ * masks: 15-bit point-class masks of the DESTINATION DoFs, as for hyteg_hip_p2_prolongate_cells (a point and the P2 DoF on it
+ * have the same class); a DoF whose class is not selected keeps its value, a cell whose mask is 0 is skipped.
+ * Pointer arrays and masks are HOST arrays of 1 <= ncells <= HYTEG_HIP_MAX_BATCH entries; one launch per call, no table, no
+ * allocation and no synchronisation, so the calls are legal while `stream` is being captured.  Every argument is checked
+ * before any GPU work: EINVAL for a level or ncells out of range, a null pointer, or a p1 array that is the p2_vertex or
+ * p2_edge array of the same cell. */
+HYTEG_HIP_API int hyteg_hip_p1_to_p2_cells( int                  ncells,
+                                            double* const*       p2_vertex,
+                                            double* const*       p2_edge,
+                                            const double* const* p1,
+                                            int                  p2_level,
+                                            const unsigned*      masks,
+                                            hyteg_hip_stream_t   stream );
+HYTEG_HIP_API int hyteg_hip_p2_to_p1_cells( int                  ncells,
+                                            double* const*       p1,
+                                            const double* const* p2_vertex,
+                                            const double* const* p2_edge,
+                                            int                  p2_level,
+                                            const unsigned*      masks,
+                                            hyteg_hip_stream_t   stream );
+/* the same for one macro-cell: the batch of one */
+HYTEG_HIP_API int hyteg_hip_p1_to_p2_cell( double* p2_vertex, double* p2_edge, const double* p1, int p2_level, unsigned mask, hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_to_p1_cell( double* p1, const double* p2_vertex, const double* p2_edge, int p2_level, unsigned mask, hyteg_hip_stream_t stream );
+
 /* ---- events and the neighbour exchange over RCCL (xGMI) --------------------------------------------------------
  * One process per GPU.  Replaces, on this path, what the reference does through waLBerla's BufferSystem over MPI:
  *   src/hyteg/communication/BufferedCommunication.cpp:181-470   start/endCommunication: pack, Isend/Irecv, wait, unpack

@@ -203,6 +203,23 @@ HYTEG_HOST_API int hyteg_host_elementwise_smooth_jac( hh_elementwise_t op, hh_fu
 HYTEG_HOST_API int hyteg_host_restrict( hh_function_t f, int source_level, int flag );
 HYTEG_HOST_API int hyteg_host_prolongate( hh_function_t f, int source_level, int flag );
 HYTEG_HOST_API int hyteg_host_prolongate_and_add( hh_function_t f, int source_level, int flag );
+/* P1toP2Conversion( p1, p2, P2Level, flag ) / P2toP1Conversion( p2, p1, P1Level, flag )
+ * (src/hyteg/gridtransferoperators/P1toP2Conversion.cpp:28-149, P2toP1Conversion.cpp:28-150): the P2 function of level L and the P1
+ * function of level L + 1 have the same DoFs; the values `flag` selects are copied, one launch per chunk of macro-cells.  The
+ * levels follow the reference: the first call takes the P2 level, the second the P1 level.  The flag is translated with the
+ * source function's boundary condition; no exchange follows. */
+HYTEG_HOST_API int hyteg_host_p1_to_p2( hh_function_t p1, hh_p2function_t p2, int p2_level, int flag );
+HYTEG_HOST_API int hyteg_host_p2_to_p1( hh_p2function_t p2, hh_function_t p1, int p1_level, int flag );
+/* P1toP1QuadraticProlongationThroughP2Injection( storage, p1MinLevel, p1MaxLevel )
+ * (src/hyteg/gridtransferoperators/P1toP1QuadraticProlongationThroughP2Injection.hpp:33-55): prolongate( f, source_level, flag ) =
+ * P1toP2Conversion( All ), P2toP2QuadraticProlongation::prolongate( flag ), P2toP1Conversion( All ) through a P2 function the
+ * object owns.  1 <= p1_min_level (the reference asks for > 2), source_level in p1_min_level .. p1_max_level - 1 and
+ * p1_max_level <= 10.  The DoFs of level source_level + 1 that `flag` excludes are overwritten with zero: restore boundary
+ * values afterwards. */
+typedef void* hh_quadratic_prolongation_t;
+HYTEG_HOST_API int hyteg_host_quadratic_prolongation_create( hh_storage_t s, int p1_min_level, int p1_max_level, hh_quadratic_prolongation_t* out );
+HYTEG_HOST_API int hyteg_host_quadratic_prolongation_prolongate( hh_quadratic_prolongation_t p, hh_function_t f, int source_level, int flag );
+HYTEG_HOST_API int hyteg_host_quadratic_prolongation_destroy( hh_quadratic_prolongation_t p );
 
 /* ---- solvers on the Laplace operator ----
  * smoother: 0 = weighted Jacobi (relax), 1 = Gauss-Seidel, 2 = SOR (relax).  Coarse grid: CG. */
@@ -234,6 +251,18 @@ HYTEG_HOST_API int hyteg_host_gmg_create_chebyshev( hh_storage_t s, int min_leve
  * replayed_cycles counts the cycles that ran from a recording */
 HYTEG_HOST_API int hyteg_host_gmg_set_use_graphs( hh_solver_t solver, int on );
 HYTEG_HOST_API int hyteg_host_gmg_replayed_cycles( hh_solver_t solver, int* count );
+/* FullMultigridSolver (src/hyteg/solvers/FullMultigridSolver.hpp:33-114) around a multigrid solver of hyteg_host_gmg_create /
+ * _gmg_create_chebyshev, which it shares (the multigrid solver's handle may be destroyed before this one).
+ * solve( level ), through hyteg_host_solver_solve: for l = min_level .. level: cycles_per_level[l] cycles on level l,
+ * post_cycle( l, user ), the prolongation of x from l to l + 1 with the flag Inner | NeumannBoundary | FreeslipBoundary if
+ * l < max_level, post_prolongate( l, user ) -- also on the top level.  cycles_per_level: n_cycles = 0: cycles_per_level[0] cycles on
+ * every level; otherwise one count per level 0 .. max_level (those below min_level are ignored), any other number is an error.
+ * prolongation: 0 = P1toP1LinearProlongation, 1 = P1toP1QuadraticProlongationThroughP2Injection (min_level >= 1, max_level <= 10).
+ * The callbacks may be null. */
+typedef void ( *hh_level_callback_t )( uint64_t level, void* user );
+HYTEG_HOST_API int hyteg_host_fmg_create( hh_storage_t s, hh_solver_t gmg, int min_level, int max_level, const unsigned* cycles_per_level, int n_cycles,
+                                          int prolongation, hh_level_callback_t post_cycle, void* post_cycle_user,
+                                          hh_level_callback_t post_prolongate, void* post_prolongate_user, hh_solver_t* out );
 /* CGSolver::setUseDeviceScalars / setUseSingleLaunch (hyteg_host.hpp); on: bit 0 = alpha, beta and the convergence test stay
  * on the device (storages of one rank up to level 5), bit 1 = problems that fit one workgroup are solved by one launch
  * (both default on); `solver` is a CG solver or a multigrid solver whose coarse solver is one */
@@ -339,6 +368,10 @@ HYTEG_HOST_API int hyteg_host_p2_chebyshev_create( hh_storage_t s, int min_level
 HYTEG_HOST_API int hyteg_host_p2_gmg_create_chebyshev( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
                                                        double upper, double lower, int pre, int post, int wcycle, int cg_max_iter, double cg_tol,
                                                        hh_p2solver_t* out );
+/* hyteg_host_fmg_create for a P2 multigrid solver of the entries above; the FMG prolongation is P2toP2QuadraticProlongation */
+HYTEG_HOST_API int hyteg_host_p2_fmg_create( hh_storage_t s, hh_p2solver_t gmg, int min_level, int max_level, const unsigned* cycles_per_level,
+                                             int n_cycles, hh_level_callback_t post_cycle, void* post_cycle_user,
+                                             hh_level_callback_t post_prolongate, void* post_prolongate_user, hh_p2solver_t* out );
 HYTEG_HOST_API int hyteg_host_p2_solver_solve( hh_p2solver_t solver, hh_p2operator_t op, hh_p2function_t x, hh_p2function_t b, int level );
 HYTEG_HOST_API int hyteg_host_p2_solver_destroy( hh_p2solver_t solver );
 /* CGSolver< P2ElementwiseLaplaceOperator > on one level, flags Inner | NeumannBoundary as in the reference's CGSolver */

@@ -228,6 +228,23 @@ def main():
         timeit(f"P2 prolongate level {fine - 1} -> {fine}, 24 cells, per-cell loop", prolongate_loop, nbytes, ncell * (nvf + nef), r=r24)
         timeit(f"P2 prolongate level {fine - 1} -> {fine}, 24 cells, one batched launch",
                lambda k: capi.p2_prolongate_cells(fv, fe, kv, ke, fine - 1, masks24, 0, sh), nbytes, ncell * (nvf + nef), r=r24)
+    # P1 <-> P2 conversion at P2 level 7 (P1 level 8), both directions, beside hyteg_hip_copy of the same number of bytes in the same
+    # run: a permutation, 8 bytes read and 8 written per DoF; information, no threshold is attached
+    Lc = 7
+    nvc7, nec7, np1 = capi.cell_size(Lc), capi.p2_edge_array_size(Lc), capi.cell_size(Lc + 1)
+    assert nvc7 + nec7 == np1
+    nbc = max(2, -(-int(2.2 * 256 * 2**20) // (np1 * 8)))
+    P1s = [torch.rand(np1, dtype=torch.float64, device="cuda") for _ in range(nbc)]
+    P2s = [torch.rand(np1, dtype=torch.float64, device="cuda") for _ in range(nbc)]  # vertex array, then the edge array, in one allocation
+    pv = lambda k: P2s[k % nbc].data_ptr()  # noqa: E731
+    pe = lambda k: P2s[k % nbc].data_ptr() + 8 * nvc7  # noqa: E731
+    timeit(f"P1 -> P2 conversion, P2 level {Lc} ({np1} DoFs)", lambda k: capi.p1_to_p2_cell(pv(k), pe(k), P1s[k % nbc].data_ptr(), Lc, 0x7FFF, sh),
+           16 * np1, np1)
+    timeit(f"P2 -> P1 conversion, P2 level {Lc} ({np1} DoFs)", lambda k: capi.p2_to_p1_cell(P1s[k % nbc].data_ptr(), pv(k), pe(k), Lc, 0x7FFF, sh),
+           16 * np1, np1)
+    timeit(f"hyteg_hip_copy of the bytes of the conversion ({8 * np1} bytes)",
+           lambda k: capi.check(capi.lib().hyteg_hip_copy(P2s[k % nbc].data_ptr(), P1s[k % nbc].data_ptr(), 8 * np1, sh), "copy"), 16 * np1, np1)
+    del P1s, P2s
     if args.only:
         print(json.dumps({"level": L, "kernels": rows}))
         return
