@@ -11,6 +11,11 @@
 // the 14 neighbour terms of an update in three partial chains: order-exact in its updates, reassociated within an update
 // (relative differences of a few ulp; tests/test_gpu_parity.py compares at 1e-12, level 8 included).
 // The backward sweep is the same planes in decreasing t.
+//
+// Four forms of the sweep: planes (one launch per hyperplane), small (the cell in LDS, one launch), blocks (one launch per block
+// wavefront; sor_block_body behind a single-cell and a batch kernel) and dataflow (p1_sor_dataflow.hip).  sor_form() is the one
+// place that says which form an entry point runs at a level; each form has one launch function that serves the single-cell and
+// the batched entry alike.
 #include <algorithm>
 #include <tuple>
 #include <vector>
@@ -459,15 +464,142 @@ __global__ __launch_bounds__( kSmallThreads ) void p1_sor_small_kernel( const So
       ug[i] = lu[i];
 }
 
-// which form of the cell sweep the entry points use: 0 = by level (default), 1 = one launch per hyperplane,
-// 2 = blocks (one launch per block wavefront; levels <= 5 of a batch: one workgroup per cell), 3 = dataflow (one launch)
-std::atomic< int > g_sorAlgorithm{ 0 };
+// ---------------------------------------------------------------------------------------------------------
+// Host side: which form an entry point runs (sor_form, sor_sweeps_pipelined), then one launch function per form.
+// ---------------------------------------------------------------------------------------------------------
+std::atomic< int > g_sorAlgorithm{ HYTEG_HIP_SOR_AUTO }; // hyteg_hip_set_sor_algorithm
 
-inline bool use_dataflow( int level )
+// dataflow: one launch for the whole sweep (opt-in only: measured slower than the blocked form at every level); small: the cell
+// in LDS, one workgroup walks all hyperplanes; blocks: one launch per block wavefront; planes: one launch per hyperplane
+enum class SorForm { Dataflow, Small, Blocks, Planes };
+enum class SorEntry { Cell, Cells }; // hyteg_hip_p1_sor_cell, hyteg_hip_p1_sor_cells
+
+inline bool sor_dataflow( int algo, int level ) { return algo == HYTEG_HIP_SOR_DATAFLOW && level >= kSorDataflowMinLevel; }
+
+// The form of one sweep; in each group the first match wins.
+SorForm sor_form( SorEntry entry, int level )
 {
-   const int a = g_sorAlgorithm.load( std::memory_order_relaxed );
-   // opt-in only: measured slower than the blocked form at every level (p1_sor_dataflow.hip)
-   return a == HYTEG_HIP_SOR_DATAFLOW && level >= kSorDataflowMinLevel;
+   const int algo = g_sorAlgorithm.load( std::memory_order_relaxed );
+   if ( sor_dataflow( algo, level ) )
+      return SorForm::Dataflow;
+   if ( entry == SorEntry::Cell )
+   {
+      // measurement switch.  Level 5: 53 us small against 65 us blocked, but the pipelined sweeps (blocked) would no longer be
+      // bit-identical to consecutive single sweeps there: the two forms sum a row in different orders
+      static const int smallMax = env_int( "HYTEG_HIP_SOR_SMALL_MAX_LEVEL", 4 );
+      if ( level <= std::min( smallMax, 5 ) && algo == HYTEG_HIP_SOR_AUTO )
+         return SorForm::Small; // 4.7 / 8.0 / 21 us at levels 2 / 3 / 4 (profiles/r03_sor_small_planes.txt)
+      if ( level >= 5 && algo != HYTEG_HIP_SOR_PLANES )
+         return SorForm::Blocks;
+      return SorForm::Planes;
+   }
+   // a batch has no plane form: SOR_PLANES means the blocked kernel at every level
+   if ( level <= 5 && algo != HYTEG_HIP_SOR_PLANES )
+      return SorForm::Small;
+   return SorForm::Blocks;
+}
+
+// hyteg_hip_p1_sor_cell_sweeps: the pipeline of blocked sweeps, or else nsweeps calls of hyteg_hip_p1_sor_cell
+bool sor_sweeps_pipelined( int level, int nsweeps )
+{
+   static const bool pipeline = env_flag( "HYTEG_HIP_SOR_PIPELINE", true ); // 0: one sweep after the other
+   const int         algo     = g_sorAlgorithm.load( std::memory_order_relaxed );
+   return nsweeps > 1 && pipeline && level >= 5 && !sor_dataflow( algo, level ) && algo != HYTEG_HIP_SOR_PLANES;
+}
+
+// f( first cell, count ) for every run of consecutive cells in sel[0..m), until one fails.  The stencil table of a batch is
+// indexed by the position in the batch, so one launch can only cover cells that are neighbours there.
+template < class F >
+int for_each_run( const int* sel, int m, F f )
+{
+   for ( int k = 0, e = 0; k < m; k = e + 1 )
+   {
+      for ( e = k; e + 1 < m && sel[e + 1] == sel[e] + 1; )
+         ++e;
+      const int rc = f( sel[k], e - k + 1 );
+      if ( rc != HYTEG_HIP_OK )
+         return rc;
+   }
+   return HYTEG_HIP_OK;
+}
+
+// small form on `count` cells, one workgroup each; weights from the device table `stencils` (indexed by workgroup), or, with
+// stencils == nullptr, the one host stencil `w`
+int launch_sor_small( int count, double* const* u, const double* const* rhs, int level, const double* stencils, const double* w, double relax,
+                      int backwards, hipStream_t s )
+{
+   const SorPlaneTable* planes = nullptr;
+   const int            rc     = get_sor_planes( level, &planes );
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
+   SorSmallArgs A{};
+   for ( int j = 0; j < count; ++j )
+      A.u[j] = u[j], A.rhs[j] = rhs[j];
+   A.stencils = stencils;
+   for ( int k = 0; w && k < 15; ++k )
+      A.w[k] = w[k];
+   A.pts = planes->pts, A.off = planes->off, A.nplanes = planes->nplanes;
+   A.N = ( 1 << level ) + 1, A.size = (int) tet64( A.N ), A.backwards = backwards ? 1 : 0;
+   A.relax = relax, A.one_minus_relax = 1.0 + ( -relax );
+   const size_t lds = (size_t) A.size * sizeof( double );
+   if ( lds > 48 * 1024 )
+      HH_CHECK_HIP( hipFuncSetAttribute( reinterpret_cast< const void* >( p1_sor_small_kernel ), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int) lds ) );
+   hipLaunchKernelGGL( p1_sor_small_kernel, dim3( count ), dim3( kSmallThreads ), lds, s, A );
+   return HYTEG_HIP_OK;
+}
+
+SorBlockArgs make_sor_block_args( double* u, const double* rhs, int level, const double* w, double relax, int backwards )
+{
+   SorBlockArgs B{ u, rhs, nullptr, ( 1 << level ) + 1, backwards ? 1 : 0, relax, 1.0 + ( -relax ), 1.0 / w[7], {} };
+   std::copy( w, w + 15, B.st.w );
+   return B;
+}
+
+// blocked form: one launch of `kernel` per group blocks[start[g]] .. blocks[start[g + 1]) (a block wavefront, or a step of the
+// pipeline), the groups in reverse if `reversed`; gridDim.y = count cells
+template < class Args >
+void launch_sor_blocks( void ( *kernel )( const Args ), Args& A, const SorBlock* blocks, const std::vector< int >& start, bool reversed, int count,
+                        hipStream_t s )
+{
+   const int ngroups = (int) start.size() - 1;
+   for ( int k = 0; k < ngroups; ++k )
+   {
+      const int g  = reversed ? ngroups - 1 - k : k;
+      const int lo = start[g], hi = start[g + 1];
+      A.blocks     = blocks + lo;
+      hipLaunchKernelGGL( kernel, dim3( hi - lo, count ), dim3( kB * kB ), 0, s, A );
+   }
+}
+
+// one blocked sweep of `count` cells: the block wavefronts of the level, last to first if backwards
+template < class Args >
+int launch_sor_wavefronts( void ( *kernel )( const Args ), Args& A, int level, int backwards, int count, hipStream_t s )
+{
+   const SorBlockTable* tab = nullptr;
+   const int            rc  = get_sor_blocks( level, &tab );
+   if ( rc == HYTEG_HIP_OK )
+      launch_sor_blocks( kernel, A, tab->dev, tab->wavefrontStart, backwards != 0, count, s );
+   return rc;
+}
+
+void launch_sor_planes( double* u, const double* rhs, int level, const double* w, double relax, int backwards, hipStream_t s )
+{
+   const int n = 1 << level;
+   SorArgs   A{ u, rhs, n + 1, 0, relax, 1.0 + ( -relax ), 1.0 / w[7], {} };
+   std::copy( w, w + 15, A.st.w );
+   // interior: x,y,z >= 1, x+y+z <= n-1  =>  t from 6 to max over the interior of x+2y+3z = 3(n-1)-3 (x=y=1, z=n-3)
+   const int tmin = 6, tmax = 1 + 2 + 3 * ( n - 3 );
+   for ( int k = 0; k <= tmax - tmin; ++k )
+   {
+      A.t = backwards ? tmax - k : tmin + k;
+      // slices that can hold a point of this plane: 3z <= t - 3
+      int nz = ( A.t - 3 ) / 3;
+      nz     = nz > n - 3 ? n - 3 : nz;
+      if ( nz < 1 )
+         continue;
+      hipLaunchKernelGGL( p1_sor_plane_kernel, dim3( nz ), dim3( kThreads ), 0, s, A );
+   }
 }
 
 } // namespace
@@ -497,7 +629,7 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_cells( int                  ncells,
    if ( level < 2 )
       return HYTEG_HIP_OK; // no inner points
    // cells whose inner points are not selected are left out of the batch
-   int           sel[HYTEG_HIP_MAX_BATCH], m = 0;
+   int sel[HYTEG_HIP_MAX_BATCH], m = 0;
    for ( int c = 0; c < ncells; ++c )
       if ( masks[c] & HYTEG_HIP_MASK_INNER )
       {
@@ -506,84 +638,31 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_cells( int                  ncells,
       }
    if ( m == 0 )
       return HYTEG_HIP_OK;
-   const int N = ( 1 << level ) + 1;
-   if ( use_dataflow( level ) )
+   const hipStream_t s  = as_stream( stream );
+   int               rc = HYTEG_HIP_OK;
+   switch ( sor_form( SorEntry::Cells, level ) )
    {
-      // one launch per run of consecutive selected cells (the stencil table is indexed by the position in the batch)
-      int k = 0;
-      while ( k < m )
-      {
-         int e = k;
-         while ( e + 1 < m && sel[e + 1] == sel[e] + 1 )
-            ++e;
-         double*       uu[HYTEG_HIP_MAX_BATCH];
-         const double* rr[HYTEG_HIP_MAX_BATCH];
-         for ( int j = k; j <= e; ++j )
-            uu[j - k] = u[sel[j]], rr[j - k] = rhs[sel[j]];
-         const int rc = launch_sor_dataflow( e - k + 1, uu, rr, level, stencils_dev + (size_t) sel[k] * 225, nullptr, relax, backwards,
-                                             as_stream( stream ) );
-         if ( rc != HYTEG_HIP_OK )
-            return rc;
-         k = e + 1;
-      }
-      return HYTEG_HIP_OK;
+   case SorForm::Dataflow:
+      return for_each_run( sel, m, [&]( int first, int count ) {
+         return launch_sor_dataflow( count, u + first, rhs + first, level, stencils_dev + (size_t) first * 225, nullptr, relax, backwards, s );
+      } );
+   case SorForm::Small:
+      rc = for_each_run( sel, m, [&]( int first, int count ) {
+         return launch_sor_small( count, u + first, rhs + first, level, stencils_dev + (size_t) first * 225, nullptr, relax, backwards, s );
+      } );
+      break;
+   default: // blocks
+      rc = for_each_run( sel, m, [&]( int first, int count ) {
+         SorBlockBatchArgs B{};
+         for ( int j = 0; j < count; ++j )
+            B.u[j] = u[first + j], B.rhs[j] = rhs[first + j];
+         B.stencils = stencils_dev + (size_t) first * 225;
+         B.N = ( 1 << level ) + 1, B.backwards = backwards ? 1 : 0, B.relax = relax, B.one_minus_relax = 1.0 + ( -relax );
+         return launch_sor_wavefronts( p1_sor_block_batch_kernel, B, level, backwards, count, s );
+      } );
    }
-   if ( level <= 5 && g_sorAlgorithm.load( std::memory_order_relaxed ) != HYTEG_HIP_SOR_PLANES )
-   {
-      // the stencil table is indexed by the position in the batch: compact batches need the original cell index,
-      // so the kernel gets one launch per run of consecutive selected cells
-      const SorPlaneTable* planes = nullptr;
-      const int            prc    = get_sor_planes( level, &planes );
-      if ( prc != HYTEG_HIP_OK )
-         return prc;
-      int k = 0;
-      while ( k < m )
-      {
-         int e = k;
-         while ( e + 1 < m && sel[e + 1] == sel[e] + 1 )
-            ++e;
-         SorSmallArgs A{};
-         for ( int j = k; j <= e; ++j )
-            A.u[j - k] = u[sel[j]], A.rhs[j - k] = rhs[sel[j]];
-         A.stencils = stencils_dev + (size_t) sel[k] * 225;
-         A.pts = planes->pts, A.off = planes->off, A.nplanes = planes->nplanes;
-         A.N = N, A.size = (int) tet64( N ), A.backwards = backwards ? 1 : 0;
-         A.relax = relax, A.one_minus_relax = 1.0 + ( -relax );
-         const size_t lds = (size_t) A.size * sizeof( double );
-         if ( lds > 48 * 1024 )
-            HH_CHECK_HIP( hipFuncSetAttribute( reinterpret_cast< const void* >( p1_sor_small_kernel ),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds ) );
-         hipLaunchKernelGGL( p1_sor_small_kernel, dim3( e - k + 1 ), dim3( kSmallThreads ), lds, as_stream( stream ), A );
-         k = e + 1;
-      }
-      HH_CHECK_HIP( hipGetLastError() );
-      return HYTEG_HIP_OK;
-   }
-   const SorBlockTable* tab = nullptr;
-   int                  rc  = get_sor_blocks( level, &tab );
    if ( rc != HYTEG_HIP_OK )
       return rc;
-   int k = 0;
-   while ( k < m )
-   {
-      int e = k;
-      while ( e + 1 < m && sel[e + 1] == sel[e] + 1 )
-         ++e;
-      SorBlockBatchArgs B{};
-      for ( int j = k; j <= e; ++j )
-         B.u[j - k] = u[sel[j]], B.rhs[j - k] = rhs[sel[j]];
-      B.stencils = stencils_dev + (size_t) sel[k] * 225;
-      B.N = N, B.backwards = backwards ? 1 : 0, B.relax = relax, B.one_minus_relax = 1.0 + ( -relax );
-      const int nw = (int) tab->wavefrontStart.size() - 1;
-      for ( int q = 0; q < nw; ++q )
-      {
-         const int wv = backwards ? nw - 1 - q : q;
-         const int lo = tab->wavefrontStart[wv], hi = tab->wavefrontStart[wv + 1];
-         B.blocks     = tab->dev + lo;
-         hipLaunchKernelGGL( p1_sor_block_batch_kernel, dim3( hi - lo, e - k + 1 ), dim3( kB * kB ), 0, as_stream( stream ), B );
-      }
-      k = e + 1;
-   }
    HH_CHECK_HIP( hipGetLastError() );
    return HYTEG_HIP_OK;
 }
@@ -602,9 +681,7 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_cell_sweeps( double*            u,
    HH_REQUIRE( u != rhs, "p1_sor_cell_sweeps: u and rhs must not alias" );
    HH_REQUIRE( w[7] != 0.0, "p1_sor_cell_sweeps: zero centre weight" );
    HH_REQUIRE( nsweeps >= 0 && nsweeps <= 64, "p1_sor_cell_sweeps: nsweeps must be 0..64" );
-   static const bool pipeline = env_flag( "HYTEG_HIP_SOR_PIPELINE", true ); // 0: one sweep after the other
-   const int algo = g_sorAlgorithm.load( std::memory_order_relaxed );
-   if ( nsweeps <= 1 || !pipeline || level < 5 || use_dataflow( level ) || algo == HYTEG_HIP_SOR_PLANES )
+   if ( !sor_sweeps_pipelined( level, nsweeps ) )
    {
       for ( int k = 0; k < nsweeps; ++k )
       {
@@ -615,26 +692,11 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_cell_sweeps( double*            u,
       return HYTEG_HIP_OK;
    }
    const SorPipelineTable* tab = nullptr;
-   int                     rc  = get_sor_pipeline( level, nsweeps, backwards != 0, &tab );
+   const int               rc  = get_sor_pipeline( level, nsweeps, backwards != 0, &tab );
    if ( rc != HYTEG_HIP_OK )
       return rc;
-   SorBlockArgs B;
-   B.u               = u;
-   B.rhs             = rhs;
-   B.N               = ( 1 << level ) + 1;
-   B.backwards       = backwards ? 1 : 0;
-   B.relax           = relax;
-   B.one_minus_relax = 1.0 + ( -relax );
-   B.invc            = 1.0 / w[7];
-   for ( int k = 0; k < 15; ++k )
-      B.st.w[k] = w[k];
-   const int nsteps = (int) tab->stepStart.size() - 1;
-   for ( int k = 0; k < nsteps; ++k )
-   {
-      const int lo = tab->stepStart[k], hi = tab->stepStart[k + 1];
-      B.blocks     = tab->dev + lo;
-      hipLaunchKernelGGL( p1_sor_block_kernel, dim3( hi - lo ), dim3( kB * kB ), 0, as_stream( stream ), B );
-   }
+   SorBlockArgs B = make_sor_block_args( u, rhs, level, w, relax, backwards );
+   launch_sor_blocks( p1_sor_block_kernel, B, tab->dev, tab->stepStart, false, 1, as_stream( stream ) ); // the table is in step order
    HH_CHECK_HIP( hipGetLastError() );
    return HYTEG_HIP_OK;
 }
@@ -651,88 +713,27 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_cell( double*            u,
    HH_REQUIRE( level_ok( level ), "p1_sor_cell: level out of range [2,11]" );
    HH_REQUIRE( u != rhs, "p1_sor_cell: u and rhs must not alias" );
    HH_REQUIRE( w[7] != 0.0, "p1_sor_cell: zero centre weight" );
-   if ( use_dataflow( level ) )
-      return launch_sor_dataflow( 1, &u, &rhs, level, nullptr, w, relax, backwards, as_stream( stream ) );
-   SorArgs A;
-   A.u               = u;
-   A.rhs             = rhs;
-   A.N               = ( 1 << level ) + 1;
-   A.relax           = relax;
-   A.one_minus_relax = 1.0 + ( -relax );
-   A.invc            = 1.0 / w[7];
-   for ( int k = 0; k < 15; ++k )
-      A.st.w[k] = w[k];
-   // measurement switch.  Level 5: 53 us here against 65 us blocked, but the pipelined sweeps (blocked) would no longer be
-   // bit-identical to consecutive single sweeps there: the two forms sum a row in different orders
-   static const int smallMax = env_int( "HYTEG_HIP_SOR_SMALL_MAX_LEVEL", 4 );
-   if ( level <= smallMax && level <= 5 && g_sorAlgorithm.load( std::memory_order_relaxed ) == HYTEG_HIP_SOR_AUTO )
+   const hipStream_t s  = as_stream( stream );
+   int               rc = HYTEG_HIP_OK;
+   switch ( sor_form( SorEntry::Cell, level ) )
    {
-      // the whole cell array fits into LDS: ONE workgroup runs all hyperplanes of the sweep in one launch (the kernel of the
-      // batched entry point with one cell; same update order and summation order as the plane kernel).  Measured against one
-      // launch per plane: 5 / 11 / 28 us instead of 5 / 33 / 125 us at levels 2 / 3 / 4 (round 1, scanning candidates; with
-      // the plane table of round 3: 4.7 / 8.0 / 21 us, profiles/r03_sor_small_planes.txt).
-      SorSmallArgs S{};
-      const SorPlaneTable* planes = nullptr;
-      const int            prc    = get_sor_planes( level, &planes );
-      if ( prc != HYTEG_HIP_OK )
-         return prc;
-      S.u[0] = u, S.rhs[0] = rhs, S.stencils = nullptr;
-      S.pts = planes->pts, S.off = planes->off, S.nplanes = planes->nplanes;
-      S.N = A.N, S.size = (int) tet64( A.N ), S.backwards = backwards ? 1 : 0;
-      S.relax = relax, S.one_minus_relax = A.one_minus_relax;
-      for ( int k = 0; k < 15; ++k )
-         S.w[k] = w[k];
-      const size_t lds = (size_t) S.size * sizeof( double );
-      if ( lds > 48 * 1024 )
-         HH_CHECK_HIP( hipFuncSetAttribute( reinterpret_cast< const void* >( p1_sor_small_kernel ), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int) lds ) );
-      hipLaunchKernelGGL( p1_sor_small_kernel, dim3( 1 ), dim3( kSmallThreads ), lds, as_stream( stream ), S );
-      HH_CHECK_HIP( hipGetLastError() );
-      return HYTEG_HIP_OK;
+   case SorForm::Dataflow:
+      return launch_sor_dataflow( 1, &u, &rhs, level, nullptr, w, relax, backwards, s );
+   case SorForm::Small:
+      rc = launch_sor_small( 1, &u, &rhs, level, nullptr, w, relax, backwards, s );
+      break;
+   case SorForm::Blocks: {
+      SorBlockArgs B = make_sor_block_args( u, rhs, level, w, relax, backwards );
+      rc             = launch_sor_wavefronts( p1_sor_block_kernel, B, level, backwards, 1, s );
+      break;
    }
-   if ( level >= 5 && g_sorAlgorithm.load( std::memory_order_relaxed ) != HYTEG_HIP_SOR_PLANES )
-   {
-      // blocked sweep: one launch per block wavefront
-      const SorBlockTable* tab = nullptr;
-      int                  rc  = get_sor_blocks( level, &tab );
-      if ( rc != HYTEG_HIP_OK )
-         return rc;
-      SorBlockArgs B;
-      B.u               = u;
-      B.rhs             = rhs;
-      B.N               = A.N;
-      B.backwards       = backwards ? 1 : 0;
-      B.relax           = relax;
-      B.one_minus_relax = A.one_minus_relax;
-      B.invc            = A.invc;
-      B.st              = A.st;
-      const int nw      = (int) tab->wavefrontStart.size() - 1;
-      for ( int k = 0; k < nw; ++k )
-      {
-         const int wv = backwards ? nw - 1 - k : k;
-         const int lo = tab->wavefrontStart[wv], hi = tab->wavefrontStart[wv + 1];
-         B.blocks     = tab->dev + lo;
-         hipLaunchKernelGGL( p1_sor_block_kernel, dim3( hi - lo ), dim3( kB * kB ), 0, as_stream( stream ), B );
-      }
-      HH_CHECK_HIP( hipGetLastError() );
-      return HYTEG_HIP_OK;
+   case SorForm::Planes:
+      launch_sor_planes( u, rhs, level, w, relax, backwards, s );
    }
-   const int n = 1 << level;
-   // interior: x,y,z >= 1, x+y+z <= n-1  =>  t from 6 to max over the interior of x+2y+3z = 3(n-1)-3 (x=y=1, z=n-3)
-   const int tmin = 6, tmax = 1 + 2 + 3 * ( n - 3 );
-   if ( tmax < tmin )
-      return HYTEG_HIP_OK;
-   for ( int k = 0; k <= tmax - tmin; ++k )
-   {
-      A.t = backwards ? tmax - k : tmin + k;
-      // slices that can hold a point of this plane: 3z <= t - 3
-      int nz = ( A.t - 3 ) / 3;
-      nz     = nz > n - 3 ? n - 3 : nz;
-      if ( nz < 1 )
-         continue;
-      hipLaunchKernelGGL( p1_sor_plane_kernel, dim3( nz ), dim3( kThreads ), 0, as_stream( stream ), A );
-   }
+   if ( rc != HYTEG_HIP_OK )
+      return rc;
    HH_CHECK_HIP( hipGetLastError() );
    return HYTEG_HIP_OK;
 }
 }
+

@@ -12,6 +12,14 @@
 //   faces    : lexicographic 2-D sweep as hyperplane wavefront; one workgroup per face, one thread per row, the three
 //              already-updated neighbours travel through LDS / a register, everything else is folded into `a` by a
 //              fully parallel preparation kernel
+// The face sweep exists once: face_prep_inplane and face_sweep_body< RPT, Face > are written against a Face (where point (i, j)
+// lives, where the prepared values are, the seven in-plane weights).  CellFace is a face of a macro-cell in the cell's array
+// (p1_sor_face_prep_kernel, p1_sor_face_sweep_kernel), ArrayFace the face array of HyTeG's own layout (p1_sor_face3d_prep_kernel,
+// p1_sor_face3d_sweep_kernel); the four kernels are wrappers that pick their face and, in the preparation, what is off the face.
+// launch_face_sweep chooses rows per thread, workgroup size and LDS for both.
+#include <algorithm>
+#include <type_traits>
+
 #include "cell_geometry.hpp"
 
 using namespace hyteg_hip;
@@ -156,54 +164,73 @@ __constant__ int kFaceDirs[6][2] = { { -1, 0 }, { 1, 0 }, { 0, -1 }, { 0, 1 }, {
 
 __device__ inline bool face_interior( int N, int i, int j ) { return i >= 1 && j >= 1 && i + j <= N - 2; }
 
+// A Face tells the preparation and the wavefront where a macro-face lives: index( i, j ) of face point (i, j) in the array that is
+// swept, the array `a` of prepared values (same index) and the seven in-plane weights w (centre, then W E S N SE NW).
+// face f of a macro-cell in the cell's own array: a in `rest`, total weights from the shell descriptor
+struct CellFace
+{
+   FaceFrame     F;
+   int           N;
+   double*       a;
+   const double* w;
+   __device__ inline CellFace( const SorShellCell& A, int f ) : F( A, f ), N( A.N ), a( A.rest ), w( A.S->faceW[f] ) {}
+   __device__ inline int index( int i, int j ) const { return F.index( N, i, j ); }
+};
+
 constexpr int kPrepThreads = 128;
 
-// rest[p] <- a_p = (1-relax) u_p + relax/c ( rhs_p - rest_p - sum_{not-yet-updated in-plane neighbours} w u
-//                                            - sum_{already-final in-plane neighbours on the face boundary} w u )
+// the in-plane part of a = (1-relax) u + relax/c t for point (i, j): t arrives holding rhs minus everything off the face and
+// loses the in-plane neighbours that are not updated before the point, and the already-final ones on the face boundary.
+// idx = F.index( i, j ) comes from the caller: a second evaluation here is not merged with the caller's (39 instructions on a CellFace)
+template < class Face >
+__device__ inline double face_prep_inplane( const Face& F, const double* u, int backwards, double relax, double sc, int i, int j, int idx, double t )
+{
+   const int N = F.N;
+#pragma unroll
+   for ( int d = 0; d < 6; ++d )
+   {
+      // forward: W, S, SE are updated before (i,j); backwards: E, N, NW
+      const bool prev = backwards ? ( d & 1 ) : !( d & 1 );
+      const int  ni = i + kFaceDirs[d][0], nj = j + kFaceDirs[d][1];
+      if ( !prev || !face_interior( N, ni, nj ) )
+         t -= F.w[1 + d] * u[F.index( ni, nj )];
+   }
+   return ( 1.0 - relax ) * u[idx] + sc * t;
+}
+
+// rest[p] <- a_p = (1-relax) u_p + relax/c ( rhs_p - rest_p - in-plane part )
 __global__ __launch_bounds__( kPrepThreads ) void p1_sor_face_prep_kernel( const SorShellArgs AA )
 {
    const SorShellCell A( AA, blockIdx.z );
    const int          f = blockIdx.y;
    if ( !( ( A.mask >> ( 6 + f ) ) & 1u ) )
       return;
-   const int       N = A.N, j = blockIdx.x + 1;
-   const FaceFrame F( A, f );
-   const double    sc = A.relax / A.S->faceW[f][0];
+   const int      N = A.N, j = blockIdx.x + 1;
+   const CellFace F( A, f );
+   const double   sc = A.relax / F.w[0];
    for ( int i = 1 + (int) threadIdx.x; i <= N - 2 - j; i += kPrepThreads )
    {
-      const int idx = F.index( N, i, j );
-      double    t   = A.rhs[idx] - A.rest[idx];
-#pragma unroll
-      for ( int d = 0; d < 6; ++d )
-      {
-         // forward: W, S, SE are updated before (i,j); backwards: E, N, NW
-         const bool prev = A.backwards ? ( d & 1 ) : !( d & 1 );
-         const int  ni = i + kFaceDirs[d][0], nj = j + kFaceDirs[d][1];
-         if ( !prev || !face_interior( N, ni, nj ) )
-            t -= A.S->faceW[f][1 + d] * A.dst[F.index( N, ni, nj )];
-      }
-      A.rest[idx] = ( 1.0 - A.relax ) * A.dst[idx] + sc * t;
+      const int idx = F.index( i, j );
+      A.rest[idx]   = face_prep_inplane( F, A.dst, A.backwards, A.relax, sc, i, j, idx, A.rhs[idx] - A.rest[idx] );
    }
 }
 
 constexpr int kSweepDepth = 8; // software prefetch distance of the a-values along a row
 
-template < int RPT >
-__global__ __launch_bounds__( 1024 ) void p1_sor_face_sweep_kernel( const SorShellArgs AA )
+// The hyperplane wavefront of one face by one workgroup: thread t owns the rows t + 1 + u * blockDim.x (u < RPT) in sweep order and
+// marches along them, row r staggered by kappa * r steps; the value of a step travels to the next row through a three-slot LDS ring,
+// the a-values arrive through a register ring of kSweepDepth steps.
+template < int RPT, class Face >
+__device__ inline void face_sweep_body( const Face& F, double* dst, int bw, double relax )
 {
-   const SorShellCell A( AA, blockIdx.y );
-   const int          f = blockIdx.x;
-   if ( !( ( A.mask >> ( 6 + f ) ) & 1u ) )
-      return;
    extern __shared__ double val[]; // [3][stride]
-   const int                N = A.N, R = N - 3, bw = A.backwards;
+   const int                N = F.N, R = N - 3;
    const int                stride = RPT * (int) blockDim.x + 2;
-   const FaceFrame          F( A, f );
-   const double             sc    = A.relax / A.S->faceW[f][0];
-   const int                kappa = bw ? 1 : 2;
+   const double             sc     = relax / F.w[0];
+   const int                kappa  = bw ? 1 : 2;
    // neighbour in the same row, neighbour of step tau-1, neighbour of step tau-2
    const int    dL = bw ? 1 : 0, d1 = bw ? 5 : 4, d2 = bw ? 3 : 2;
-   const double bL = -sc * A.S->faceW[f][1 + dL], b1 = -sc * A.S->faceW[f][1 + d1], b2 = -sc * A.S->faceW[f][1 + d2];
+   const double bL = -sc * F.w[1 + dL], b1 = -sc * F.w[1 + d1], b2 = -sc * F.w[1 + d2];
    const int    tauMin = 1 + kappa, tauMax = bw ? 2 * N - 6 : 2 * N - 5;
 
    double q[RPT][kSweepDepth];
@@ -220,7 +247,7 @@ __global__ __launch_bounds__( 1024 ) void p1_sor_face_sweep_kernel( const SorShe
       for ( int k = 0; k < kSweepDepth; ++k )
       {
          const int s = tauMin + k - kappa * rr[u];
-         q[u][k]     = ( rr[u] <= R && s >= 1 && s <= len[u] ) ? A.rest[F.index( N, bw ? len[u] + 1 - s : s, jj[u] )] : 0.0;
+         q[u][k]     = ( rr[u] <= R && s >= 1 && s <= len[u] ) ? F.a[F.index( bw ? len[u] + 1 - s : s, jj[u] )] : 0.0;
       }
    }
    int p0 = tauMin % 3; // LDS ring slot of the current step
@@ -243,17 +270,27 @@ __global__ __launch_bounds__( 1024 ) void p1_sor_face_sweep_kernel( const SorShe
                const double n1 = face_interior( N, i + kFaceDirs[d1][0], j + kFaceDirs[d1][1] ) ? val[pm1 * stride + rr[u] - 1] : 0.0;
                const double n2 = face_interior( N, i + kFaceDirs[d2][0], j + kFaceDirs[d2][1] ) ? val[pm2 * stride + rr[u] - 1] : 0.0;
                const double v  = fma( bL, left[u], fma( b1, n1, fma( b2, n2, q[u][k] ) ) );
-               left[u]                    = v;
-               val[p0 * stride + rr[u]]   = v;
-               A.dst[F.index( N, i, j )]  = v;
+               left[u]                  = v;
+               val[p0 * stride + rr[u]] = v;
+               dst[F.index( i, j )]     = v;
             }
             const int sn = s + kSweepDepth;
-            q[u][k]      = ( rr[u] <= R && sn >= 1 && sn <= len[u] ) ? A.rest[F.index( N, bw ? len[u] + 1 - sn : sn, jj[u] )] : 0.0;
+            q[u][k]      = ( rr[u] <= R && sn >= 1 && sn <= len[u] ) ? F.a[F.index( bw ? len[u] + 1 - sn : sn, jj[u] )] : 0.0;
          }
          __syncthreads();
          p0 = p0 == 2 ? 0 : p0 + 1;
       }
    }
+}
+
+template < int RPT >
+__global__ __launch_bounds__( 1024 ) void p1_sor_face_sweep_kernel( const SorShellArgs AA )
+{
+   const SorShellCell A( AA, blockIdx.y );
+   const int          f = blockIdx.x;
+   if ( !( ( A.mask >> ( 6 + f ) ) & 1u ) )
+      return;
+   face_sweep_body< RPT >( CellFace( A, f ), A.dst, A.backwards, A.relax );
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -262,8 +299,8 @@ __global__ __launch_bounds__( 1024 ) void p1_sor_face_sweep_kernel( const SorShe
 // P1Operator::smooth_sor_face3D, P1Operator.hpp:1424-1503).  Which face-array entry a stencil leaf of a neighbour cell lands on
 // is a property of the leaf and the cell's vertex map alone (the map is linear), so the host folds the 2 x 14 leaves into
 // seven in-plane weights (centre + W E S N SE NW, summed over the cells) and a list of ghost-layer leaves; the preparation
-// kernel forms  a = (1 - relax) u + relax / c ( rhs - ghost leaves - in-plane neighbours that are not updated before the
-// point ), the sweep kernel is the hyperplane wavefront above with the face array's own index function.
+// kernel forms  a = (1 - relax) u + relax / c ( rhs - ghost leaves - in-plane part ), the sweep kernel is the wavefront above
+// on an ArrayFace.
 // ---------------------------------------------------------------------------------------------------------------------
 struct FaceSorArgs
 {
@@ -277,91 +314,52 @@ struct FaceSorArgs
    int           gk[32], gdx[32], gdy[32]; // ghost-layer leaves: neighbour cell, offset in face coordinates
    double        gw[32];
 };
+// the face DoFs of a face array: a in `work`, weights folded by the host
+struct ArrayFace
+{
+   int           N;
+   double*       a;
+   const double* w;
+   __device__ inline ArrayFace( const FaceSorArgs& A ) : N( A.N ), a( A.work ), w( A.W ) {}
+   __device__ inline int index( int i, int j ) const { return row_start( N, j ) + i; }
+};
 
 __global__ __launch_bounds__( kPrepThreads ) void p1_sor_face3d_prep_kernel( const FaceSorArgs A )
 {
-   const int    N = A.N, j = blockIdx.x + 1;
-   const double sc = A.relax / A.W[0];
+   const int       N = A.N, j = blockIdx.x + 1;
+   const ArrayFace F( A );
+   const double    sc = A.relax / A.W[0];
    for ( int i = 1 + (int) threadIdx.x; i <= N - 2 - j; i += kPrepThreads )
    {
-      const int idx = row_start( N, j ) + i;
+      const int idx = F.index( i, j );
       double    t   = A.rhs[idx];
       for ( int g = 0; g < A.nghost; ++g )
          t -= A.gw[g] * A.dst[tri( N ) + A.gk[g] * tri( N - 1 ) + row_start( N - 1, j + A.gdy[g] ) + i + A.gdx[g]];
-#pragma unroll
-      for ( int d = 0; d < 6; ++d )
-      {
-         // forward: W, S, SE are updated before (i,j); backwards: E, N, NW
-         const bool prev = A.backwards ? ( d & 1 ) : !( d & 1 );
-         const int  ni = i + kFaceDirs[d][0], nj = j + kFaceDirs[d][1];
-         if ( !prev || !face_interior( N, ni, nj ) )
-            t -= A.W[1 + d] * A.dst[row_start( N, nj ) + ni];
-      }
-      A.work[idx] = ( 1.0 - A.relax ) * A.dst[idx] + sc * t;
+      A.work[idx] = face_prep_inplane( F, A.dst, A.backwards, A.relax, sc, i, j, idx, t );
    }
 }
 
 template < int RPT >
 __global__ __launch_bounds__( 1024 ) void p1_sor_face3d_sweep_kernel( const FaceSorArgs A )
 {
-   extern __shared__ double val[]; // [3][stride]
-   const int                N = A.N, R = N - 3, bw = A.backwards;
-   const int                stride = RPT * (int) blockDim.x + 2;
-   const double             sc     = A.relax / A.W[0];
-   const int                kappa  = bw ? 1 : 2;
-   // neighbour in the same row, neighbour of step tau-1, neighbour of step tau-2
-   const int    dL = bw ? 1 : 0, d1 = bw ? 5 : 4, d2 = bw ? 3 : 2;
-   const double bL = -sc * A.W[1 + dL], b1 = -sc * A.W[1 + d1], b2 = -sc * A.W[1 + d2];
-   const int    tauMin = 1 + kappa, tauMax = bw ? 2 * N - 6 : 2 * N - 5;
+   face_sweep_body< RPT >( ArrayFace( A ), A.dst, A.backwards, A.relax );
+}
 
-   double q[RPT][kSweepDepth];
-   double left[RPT];
-   int    rr[RPT], jj[RPT], len[RPT];
-#pragma unroll
-   for ( int u = 0; u < RPT; ++u )
-   {
-      rr[u]   = (int) threadIdx.x + 1 + u * (int) blockDim.x; // ordinal of the row in sweep order
-      jj[u]   = bw ? R + 1 - rr[u] : rr[u];
-      len[u]  = N - 2 - jj[u];
-      left[u] = 0.0;
-#pragma unroll
-      for ( int k = 0; k < kSweepDepth; ++k )
-      {
-         const int s = tauMin + k - kappa * rr[u];
-         q[u][k]     = ( rr[u] <= R && s >= 1 && s <= len[u] ) ? A.work[row_start( N, jj[u] ) + ( bw ? len[u] + 1 - s : s )] : 0.0;
-      }
-   }
-   int p0 = tauMin % 3; // LDS ring slot of the current step
-   for ( int tau0 = tauMin; tau0 <= tauMax; tau0 += kSweepDepth )
-   {
-#pragma unroll
-      for ( int k = 0; k < kSweepDepth; ++k )
-      {
-         const int tau = tau0 + k;
-         const int pm1 = p0 == 0 ? 2 : p0 - 1, pm2 = pm1 == 0 ? 2 : pm1 - 1;
-#pragma unroll
-         for ( int u = 0; u < RPT; ++u )
-         {
-            const int s = tau - kappa * rr[u];
-            if ( rr[u] <= R && s >= 1 && s <= len[u] )
-            {
-               const int i = bw ? len[u] + 1 - s : s, j = jj[u];
-               if ( s == 1 )
-                  left[u] = 0.0;
-               const double n1 = face_interior( N, i + kFaceDirs[d1][0], j + kFaceDirs[d1][1] ) ? val[pm1 * stride + rr[u] - 1] : 0.0;
-               const double n2 = face_interior( N, i + kFaceDirs[d2][0], j + kFaceDirs[d2][1] ) ? val[pm2 * stride + rr[u] - 1] : 0.0;
-               const double v  = fma( bL, left[u], fma( b1, n1, fma( b2, n2, q[u][k] ) ) );
-               left[u]                       = v;
-               val[p0 * stride + rr[u]]      = v;
-               A.dst[row_start( N, j ) + i]  = v;
-            }
-            const int sn = s + kSweepDepth;
-            q[u][k]      = ( rr[u] <= R && sn >= 1 && sn <= len[u] ) ? A.work[row_start( N, jj[u] ) + ( bw ? len[u] + 1 - sn : sn )] : 0.0;
-         }
-         __syncthreads();
-         p0 = p0 == 2 ? 0 : p0 + 1;
-      }
-   }
+// Launch shape of the wavefront for a face of R rows: one row per thread up to 512 rows, two up to 1024, four above, but never more
+// than MAX_RPT; whole waves; three ring slots of one value per row (+ 2) in LDS.  launch( integral_constant RPT, threads, lds )
+// launches the caller's kernel< RPT >.
+template < int MAX_RPT, class Launch >
+void launch_face_sweep( int R, Launch launch )
+{
+   const int    rpt     = std::min( R > 512 ? ( R > 1024 ? 4 : 2 ) : 1, MAX_RPT );
+   const int    threads = ( ( ( R + rpt - 1 ) / rpt + 63 ) / 64 ) * 64;
+   const size_t lds     = size_t( 3 ) * ( size_t( rpt ) * threads + 2 ) * sizeof( double );
+   if constexpr ( MAX_RPT >= 4 )
+      if ( rpt == 4 )
+         return launch( std::integral_constant< int, 4 >{}, threads, lds );
+   if ( rpt == 2 )
+      return launch( std::integral_constant< int, 2 >{}, threads, lds );
+   launch( std::integral_constant< int, 1 >{}, threads, lds );
 }
 
 bool is_perm( const int* v, int n, const int* ref )
@@ -395,13 +393,9 @@ static int launch_sor_shell( SorShellArgs& A, int ncells, unsigned any_mask, int
    auto       doFaces    = [&]() {
       const int R = N - 3;
       hipLaunchKernelGGL( p1_sor_face_prep_kernel, dim3( R, 4, ncells ), dim3( kPrepThreads ), 0, s, A );
-      const int    rpt     = R > 512 ? 2 : 1;
-      const int    threads = ( ( ( R + rpt - 1 ) / rpt + 63 ) / 64 ) * 64;
-      const size_t lds     = size_t( 3 ) * ( size_t( rpt ) * threads + 2 ) * sizeof( double );
-      if ( rpt == 2 )
-         hipLaunchKernelGGL( p1_sor_face_sweep_kernel< 2 >, dim3( 4, ncells ), dim3( threads ), lds, s, A );
-      else
-         hipLaunchKernelGGL( p1_sor_face_sweep_kernel< 1 >, dim3( 4, ncells ), dim3( threads ), lds, s, A );
+      launch_face_sweep< 2 >( R, [&]( auto rpt, int threads, size_t lds ) {
+         hipLaunchKernelGGL( p1_sor_face_sweep_kernel< decltype( rpt )::value >, dim3( 4, ncells ), dim3( threads ), lds, s, A );
+      } );
    };
    if ( !backwards )
    {
@@ -571,15 +565,9 @@ HYTEG_HIP_API int hyteg_hip_p1_sor_face3d( double*            dst_face,
       return HYTEG_HIP_OK; // no inner face DoFs below level 2
    hipStream_t st = as_stream( stream );
    hipLaunchKernelGGL( p1_sor_face3d_prep_kernel, dim3( R ), dim3( kPrepThreads ), 0, st, A );
-   const int    rpt     = R > 512 ? ( R > 1024 ? 4 : 2 ) : 1;
-   const int    threads = ( ( ( R + rpt - 1 ) / rpt + 63 ) / 64 ) * 64;
-   const size_t lds     = size_t( 3 ) * ( size_t( rpt ) * threads + 2 ) * sizeof( double );
-   if ( rpt == 4 )
-      hipLaunchKernelGGL( p1_sor_face3d_sweep_kernel< 4 >, dim3( 1 ), dim3( threads ), lds, st, A );
-   else if ( rpt == 2 )
-      hipLaunchKernelGGL( p1_sor_face3d_sweep_kernel< 2 >, dim3( 1 ), dim3( threads ), lds, st, A );
-   else
-      hipLaunchKernelGGL( p1_sor_face3d_sweep_kernel< 1 >, dim3( 1 ), dim3( threads ), lds, st, A );
+   launch_face_sweep< 4 >( R, [&]( auto rpt, int threads, size_t lds ) {
+      hipLaunchKernelGGL( p1_sor_face3d_sweep_kernel< decltype( rpt )::value >, dim3( 1 ), dim3( threads ), lds, st, A );
+   } );
    HH_CHECK_HIP( hipGetLastError() );
    return HYTEG_HIP_OK;
 }
