@@ -20,8 +20,9 @@ Two transports sit behind the shared-point exchange of the C++ host layer (hyteg
            64-byte arena handles and, per plan, where every peer expects this rank's values.  The all-reduce of dot
            products and plans of levels that were not connected stay with the transport underneath.
 
-A plan is identified by (level, key) with key = cls + 2 * dof_kind (boundary class 0 / 1; vertex DoFs / edge DoFs of P2
-functions)."""
+A plan is identified by (level, key) with key = Storage.plan_key(cls, dof_kind): cls an index into
+storage.boundary_classes (one exchange class per mesh boundary flag: 0 = interior, 1 = domain boundary unless the application
+has set other flags), dof_kind vertex DoFs / edge DoFs of P2 functions.  For the classes 0 and 1 the key is cls + 2 * dof_kind."""
 from __future__ import annotations
 
 import numpy as np
@@ -44,6 +45,9 @@ class DistributedContext:
         auto = transport == "auto"
         self.transport_note = ""
         self._levels, self._dof_kinds = tuple(levels), tuple(dof_kinds)
+        # the exchange classes: the same on every rank, since every rank flags the whole mesh
+        self.class_flags = storage.boundary_classes
+        self.n_classes = len(self.class_flags)
         if auto:
             transport = "hooks"
             if dist.get_backend() == "nccl" and self.device.type == "cuda":
@@ -85,8 +89,8 @@ class DistributedContext:
             self._stream = torch.cuda.ExternalStream(raw, device=self.device) if raw else torch.cuda.default_stream(self.device)
         for level in levels:
             for dof_kind in dof_kinds:
-                for cls in (0, 1):
-                    key = cls + 2 * dof_kind
+                for cls in range(self.n_classes):
+                    key = storage.plan_key(cls, dof_kind)
                     p = storage.plan(level, key)
                     self.plans[(level, key)] = p
                     # the exchange is a collective: either every rank takes part in it or none does
@@ -124,7 +128,7 @@ class DistributedContext:
         levels = self._levels if levels is None else tuple(levels)
         dof_kinds = self._dof_kinds if dof_kinds is None else tuple(dof_kinds)
         st = self.storage
-        keys = [(lv, cls + 2 * dk) for lv in levels for dk in dof_kinds for cls in (0, 1)]
+        keys = [(lv, st.plan_key(cls, dk)) for lv in levels for dk in dof_kinds for cls in range(self.n_classes)]
         plans = {k: st.plan(*k) for k in keys}
         align = 256
         need = 4096 + sum(2 * -(-max(8, 8 * int(p["total_recv"])) // align) * align + -(-max(1, 64 * len(p["peers"])) // align) * align

@@ -21,6 +21,8 @@ _vp, _i, _d, _u = C.c_void_p, C.c_int, C.c_double, C.c_uint
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
 EXCHANGE_CB = C.CFUNCTYPE(_i, _vp, _i, _i)
 ALLREDUCE_CB = C.CFUNCTYPE(_i, _vp, _dp, _i)
+LOCATION_CB = C.CFUNCTYPE(_i, _vp, _dp)  # the predicate of set_mesh_boundary_flags_by_*_location: (user, xyz) -> 0 / 1
+_ull = C.c_ulonglong
 LEVEL_CB = C.CFUNCTYPE(None, C.c_uint64, _vp)  # hh_level_callback_t: the callbacks of FullMultigridSolver
 
 SIGNATURES = {
@@ -32,6 +34,27 @@ SIGNATURES = {
     "hyteg_host_storage_local_cell": (_i, [_vp, _i, _ip, _dp, _dp]),
     "hyteg_host_storage_mask": (_i, [_vp, _i, _i, _i, C.POINTER(_u)]),
     "hyteg_host_storage_set_boundary_type": (_i, [_vp, _i]),
+    "hyteg_host_storage_mask_bc": (_i, [_vp, _i, _i, _i, _vp, C.POINTER(_u)]),
+    "hyteg_host_storage_set_mesh_boundary_flags_on_boundary": (_i, [_vp, _ull, _ull, _i]),
+    "hyteg_host_storage_set_mesh_boundary_flags_inner": (_i, [_vp, _ull, _i]),
+    "hyteg_host_storage_set_mesh_boundary_flags_by_vertex_location": (_i, [_vp, _ull, LOCATION_CB, _vp, _i]),
+    "hyteg_host_storage_set_mesh_boundary_flags_by_centroid_location": (_i, [_vp, _ull, LOCATION_CB, _vp]),
+    "hyteg_host_storage_set_mesh_boundary_flag": (_i, [_vp, _i, _i, _ull]),
+    "hyteg_host_storage_primitive": (_i, [_vp, _i, _i, _ip, _ip, _dp, C.POINTER(_ull), _ip]),
+    "hyteg_host_storage_boundary_classes": (_i, [_vp, _ip, C.POINTER(_ull)]),
+    "hyteg_host_storage_default_boundary_condition": (_i, [_vp, C.POINTER(_vp)]),
+    "hyteg_host_boundary_condition_create": (_i, [_i, C.POINTER(_vp)]),
+    "hyteg_host_boundary_condition_destroy": (_i, [_vp]),
+    "hyteg_host_boundary_condition_create_domain": (_i, [_vp, C.c_char_p, _i, _i, C.POINTER(_ull), _ip]),
+    "hyteg_host_boundary_condition_type": (_i, [_vp, _ull, _ip]),
+    "hyteg_host_boundary_condition_uid": (_i, [_vp, _ull, _ip, C.c_char_p, _i]),
+    "hyteg_host_boundary_condition_equal": (_i, [_vp, _vp, _ip]),
+    "hyteg_host_function_set_boundary_condition": (_i, [_vp, _vp]),
+    "hyteg_host_function_boundary_condition": (_i, [_vp, C.POINTER(_vp)]),
+    "hyteg_host_function_interpolate_constant_on_boundary": (_i, [_vp, _d, _i, _i, C.c_char_p]),
+    "hyteg_host_p2function_set_boundary_condition": (_i, [_vp, _vp]),
+    "hyteg_host_p2function_boundary_condition": (_i, [_vp, C.POINTER(_vp)]),
+    "hyteg_host_p2function_interpolate_constant_on_boundary": (_i, [_vp, _d, _i, _i, C.c_char_p]),
     "hyteg_host_storage_set_stream": (_i, [_vp, _vp]),
     "hyteg_host_storage_set_batch_max_level": (_i, [_vp, _i]),
     "hyteg_host_storage_set_apply_lanes": (_i, [_vp, _i]),
@@ -148,6 +171,8 @@ SIGNATURES = {
     "hyteg_host_gmg_replayed_cycles": (_i, [_vp, C.POINTER(_i)]),
     "hyteg_host_cg_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_solver_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_solver_solve_steps": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
+    "hyteg_host_mixed_precision_jacobi_create": (_i, [_vp, _i, _i, _d, _i, C.POINTER(_vp)]),
     "hyteg_host_solver_destroy": (_i, [_vp]),
     "hyteg_host_p2function_create": (_i, [_vp, C.c_char_p, _i, _i, C.POINTER(_vp)]),
     "hyteg_host_p2function_destroy": (_i, [_vp]),
@@ -285,6 +310,120 @@ class _Reductions:
         return self.reduce(level, flag, mpi_reduce).max_magnitude
 
 
+class BoundaryUID(NamedTuple):
+    """names one boundary of a BoundaryCondition (hyteg::BoundaryUID); id 0: the flags that were given no boundary"""
+    id: int
+    name: str
+
+
+class Primitive(NamedTuple):
+    """a macro-vertex, -edge or -face: (sorted) global vertex ids, their coordinates, mesh boundary flag, on the domain boundary"""
+    vertex_ids: tuple
+    coordinates: np.ndarray
+    flag: int
+    on_boundary: bool
+
+
+class BoundaryCondition:
+    """hyteg::BoundaryCondition: maps the mesh boundary flag of a macro-primitive to a DoFType.  A value: a function that is
+    given one keeps a copy."""
+
+    def __init__(self, _handle=None):
+        if _handle is None:
+            _handle = _vp()
+            _ck(lib().hyteg_host_boundary_condition_create(0, C.byref(_handle)), "boundary_condition_create")
+        self.h = _handle
+
+    @classmethod
+    def _preset(cls, preset):
+        h = _vp()
+        _ck(lib().hyteg_host_boundary_condition_create(preset, C.byref(h)), "boundary_condition_create")
+        return cls(h)
+
+    @classmethod
+    def create_0123(cls):
+        """1 -> Dirichlet, 2 -> Neumann, 3 -> free slip, every other flag -> Inner"""
+        return cls._preset(1)
+
+    @classmethod
+    def create_all_inner(cls):
+        return cls._preset(2)
+
+    def create_domain(self, name, dof_type, flags) -> BoundaryUID:
+        f = [int(flags)] if np.isscalar(flags) else [int(x) for x in flags]
+        arr = (_ull * max(len(f), 1))(*f)
+        uid = _i()
+        _ck(lib().hyteg_host_boundary_condition_create_domain(self.h, name.encode(), int(dof_type), len(f), arr, C.byref(uid)),
+            "boundary_condition_create_domain")
+        return BoundaryUID(uid.value, name)
+
+    def create_inner(self, name, flags):
+        return self.create_domain(name, Inner, flags)
+
+    def create_dirichlet(self, name, flags):
+        return self.create_domain(name, DirichletBoundary, flags)
+
+    def create_neumann(self, name, flags):
+        return self.create_domain(name, NeumannBoundary, flags)
+
+    def create_freeslip(self, name, flags):
+        return self.create_domain(name, FreeslipBoundary, flags)
+
+    def boundary_type(self, flag) -> int:
+        t = _i()
+        _ck(lib().hyteg_host_boundary_condition_type(self.h, int(flag), C.byref(t)), "boundary_condition_type")
+        return t.value
+
+    def boundary_uid(self, flag) -> BoundaryUID:
+        """getBoundaryUIDFromMeshFlag"""
+        uid = _i()
+        buf = C.create_string_buffer(256)
+        _ck(lib().hyteg_host_boundary_condition_uid(self.h, int(flag), C.byref(uid), buf, 256), "boundary_condition_uid")
+        return BoundaryUID(uid.value, buf.value.decode())
+
+    def __eq__(self, other):
+        if not isinstance(other, BoundaryCondition):
+            return NotImplemented
+        eq = _i()
+        _ck(lib().hyteg_host_boundary_condition_equal(self.h, other.h, C.byref(eq)), "boundary_condition_equal")
+        return bool(eq.value)
+
+    __hash__ = None
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_boundary_condition_destroy(self.h)
+        self.h = None
+
+    def __del__(self):  # a value object handed out freely (Function.boundary_condition makes a copy per access): freed with it
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown: the library may be gone
+            pass
+
+
+class _BoundaryConditioned:
+    """set_boundary_condition / boundary_condition / interpolate on one boundary, for P1Function and P2Function"""
+
+    _bc_prefix = None  # "hyteg_host_function" or "hyteg_host_p2function"
+
+    def set_boundary_condition(self, bc: BoundaryCondition):
+        """Function::setBoundaryCondition: the function keeps a copy"""
+        _ck(getattr(lib(), self._bc_prefix + "_set_boundary_condition")(self.h, bc.h), "set_boundary_condition")
+
+    @property
+    def boundary_condition(self) -> BoundaryCondition:
+        """a copy of the function's condition (the storage's default one if it was given none)"""
+        h = _vp()
+        _ck(getattr(lib(), self._bc_prefix + "_boundary_condition")(self.h, C.byref(h)), "boundary_condition")
+        return BoundaryCondition(h)
+
+    def _interpolate_on_boundary(self, value, level, boundary_uid: BoundaryUID):
+        """a BoundaryUID belongs to the condition that created it: one that is not a boundary of this function's condition fails"""
+        _ck(getattr(lib(), self._bc_prefix + "_interpolate_constant_on_boundary")(self.h, float(value), level, int(boundary_uid.id),
+                                                                                  boundary_uid.name.encode()), "interpolate (boundary)")
+
+
 class Storage:
     """hyteg::PrimitiveStorage"""
 
@@ -323,10 +462,90 @@ class Storage:
             "storage_local_cell")
         return gid.value, co.reshape(4, 3), nnc
 
-    def mask(self, i, flag, owned=False):
+    def mask(self, i, flag, owned=False, bc=None):
+        """point mask of local cell i under `flag`; bc: a BoundaryCondition (None: the storage's default one)"""
         m = _u()
-        _ck(lib().hyteg_host_storage_mask(self.h, i, flag, int(owned), C.byref(m)), "storage_mask")
+        if bc is None:
+            _ck(lib().hyteg_host_storage_mask(self.h, i, flag, int(owned), C.byref(m)), "storage_mask")
+        else:
+            _ck(lib().hyteg_host_storage_mask_bc(self.h, i, flag, int(owned), bc.h, C.byref(m)), "storage_mask")
         return m.value
+
+    # ---- mesh boundary flags (SetupPrimitiveStorage::setMeshBoundaryFlags*): before the first function, operator or plan ----
+    def set_mesh_boundary_flags_on_boundary(self, flag_on_boundary, flag_inner, highest_dimension_always_inner=True):
+        _ck(lib().hyteg_host_storage_set_mesh_boundary_flags_on_boundary(self.h, int(flag_on_boundary), int(flag_inner),
+                                                                        int(bool(highest_dimension_always_inner))),
+            "set_mesh_boundary_flags_on_boundary")
+
+    def set_mesh_boundary_flags_inner(self, flag_inner, highest_dimension_always_inner=True):
+        _ck(lib().hyteg_host_storage_set_mesh_boundary_flags_inner(self.h, int(flag_inner), int(bool(highest_dimension_always_inner))),
+            "set_mesh_boundary_flags_inner")
+
+    @staticmethod
+    def _location_callback(predicate):
+        def call(user, xyz):
+            global _hook_exception
+            try:
+                return 1 if predicate(xyz[0], xyz[1], xyz[2]) else 0
+            except BaseException as e:  # noqa: BLE001 - must not propagate into the C frames
+                if _hook_exception is None:
+                    _hook_exception = e
+                return 0
+        return LOCATION_CB(call)
+
+    @staticmethod
+    def _ck_location(rc, what):
+        global _hook_exception
+        _ck(rc, what)
+        if _hook_exception is not None:
+            exc, _hook_exception = _hook_exception, None
+            raise HytegHostError(f"{what}: the predicate raised") from exc
+
+    def set_mesh_boundary_flags_by_vertex_location(self, flag, predicate, all_vertices=True):
+        """flag on every primitive whose vertices all (all_vertices=False: at least one) satisfy predicate(x, y, z)"""
+        cb = self._location_callback(predicate)
+        self._ck_location(lib().hyteg_host_storage_set_mesh_boundary_flags_by_vertex_location(self.h, int(flag), cb, None,
+                                                                                              int(bool(all_vertices))),
+                          "set_mesh_boundary_flags_by_vertex_location")
+
+    def set_mesh_boundary_flags_by_centroid_location(self, flag, predicate):
+        """flag on every primitive whose centroid satisfies predicate(x, y, z)"""
+        cb = self._location_callback(predicate)
+        self._ck_location(lib().hyteg_host_storage_set_mesh_boundary_flags_by_centroid_location(self.h, int(flag), cb, None),
+                          "set_mesh_boundary_flags_by_centroid_location")
+
+    def set_mesh_boundary_flag(self, dim, index, flag):
+        """dim 0: macro-vertex, 1: -edge, 2: -face"""
+        _ck(lib().hyteg_host_storage_set_mesh_boundary_flag(self.h, int(dim), int(index), int(flag)), "set_mesh_boundary_flag")
+
+    def primitive(self, dim, index) -> Primitive:
+        n, ids, co, flag, onb = _i(), (C.c_int * 3)(), np.zeros(9), _ull(), _i()
+        _ck(lib().hyteg_host_storage_primitive(self.h, int(dim), int(index), C.byref(n), ids, co.ctypes.data_as(_dp), C.byref(flag),
+                                               C.byref(onb)), "storage_primitive")
+        return Primitive(tuple(ids[:n.value]), co.reshape(3, 3)[:n.value].copy(), flag.value, bool(onb.value))
+
+    def n_primitives(self, dim):
+        return (self.n_vertices, self.n_edges, self.n_faces)[dim]
+
+    @property
+    def boundary_classes(self):
+        """the mesh flags of the exchange classes, ascending: class c has the plans of key (c & 1) + 2 * dof_kind + 4 * (c >> 1).
+        Asking fixes the mesh boundary flags."""
+        n = _i()
+        _ck(lib().hyteg_host_storage_boundary_classes(self.h, C.byref(n), None), "boundary_classes")
+        f = (_ull * max(n.value, 1))()
+        _ck(lib().hyteg_host_storage_boundary_classes(self.h, C.byref(n), f), "boundary_classes")
+        return [int(x) for x in f[:n.value]]
+
+    @staticmethod
+    def plan_key(cls, dof_kind=0):
+        return (cls & 1) + 2 * dof_kind + 4 * (cls >> 1)
+
+    @property
+    def default_boundary_condition(self) -> BoundaryCondition:
+        h = _vp()
+        _ck(lib().hyteg_host_storage_default_boundary_condition(self.h, C.byref(h)), "default_boundary_condition")
+        return BoundaryCondition(h)
 
     def set_boundary_type(self, t):
         _ck(lib().hyteg_host_storage_set_boundary_type(self.h, t), "set_boundary_type")
@@ -366,7 +585,7 @@ class Storage:
         self.stream = int(stream) if stream else 0
 
     def set_hooks(self, exchange_begin, exchange_end, allreduce_sum):
-        """hooks(level, key) with key = cls + 2 * dof_kind; an exception in a hook fails the operation that called it"""
+        """hooks(level, key) with key = Storage.plan_key(cls, dof_kind); an exception in a hook fails the operation that called it"""
 
         def guard(fn):
             def call(user, *args):
@@ -462,7 +681,7 @@ class Storage:
         return buf.value.decode()
 
     def plan(self, level, key):
-        """exchange plan of (level, key = cls + 2 * dof_kind)"""
+        """exchange plan of (level, key = Storage.plan_key(cls, dof_kind)): cls + 2 * dof_kind for the classes 0 and 1"""
         cls = key
         s = (C.c_int * 5)()
         _ck(lib().hyteg_host_plan_sizes(self.h, level, cls, s), "plan_sizes")
@@ -485,9 +704,10 @@ class Storage:
             self.h = None
 
 
-class P1Function(_Reductions):
+class P1Function(_Reductions, _BoundaryConditioned):
     """hyteg::P1Function<double>"""
     _reduce_fn = "hyteg_host_p1_reduce"
+    _bc_prefix = "hyteg_host_function"
 
     def __init__(self, storage: Storage, name: str, min_level: int, max_level: int, _borrowed=None):
         self.storage, self.min_level, self.max_level = storage, min_level, max_level
@@ -514,7 +734,10 @@ class P1Function(_Reductions):
         _ck(lib().hyteg_host_function_download_cell(self.h, c, level, a.ctypes.data_as(_dp)), "download_cell")
         return a
 
-    def interpolate(self, value, level, flag=All):
+    def interpolate(self, value, level, flag=All, boundary_uid=None):
+        """boundary_uid: on the primitives whose mesh flag belongs to that boundary of the function's condition (flag is not used)"""
+        if boundary_uid is not None:
+            return self._interpolate_on_boundary(value, level, boundary_uid)
         _ck(lib().hyteg_host_function_interpolate_constant(self.h, float(value), level, flag), "interpolate")
 
     def _vec(self, fn, scalars, funcs, level, flag):
@@ -807,8 +1030,21 @@ class Solver:
         self._callbacks = (cb_cycle, cb_prolongate, state)  # the C side keeps the function pointers
         return self
 
+    @classmethod
+    def mixed_precision_jacobi(cls, storage, min_level, max_level, relax=2.0 / 3.0, fp32_sweeps=2):
+        """MixedPrecisionJacobiSmoother on its own (inside a multigrid solver: Solver.gmg(smoother=JACOBI_FP32))"""
+        h = _vp()
+        _ck(lib().hyteg_host_mixed_precision_jacobi_create(storage.h, min_level, max_level, float(relax), int(fp32_sweeps), C.byref(h)),
+            "mixed_precision_jacobi_create")
+        return cls(h)
+
     def solve(self, laplace: P1ConstantOperator, x: P1Function, b: P1Function, level: int):
         _ck(lib().hyteg_host_solver_solve(self.h, laplace.h, x.h, b.h, level), "solve")
+        _raise_callback_exception(self)
+
+    def solve_steps(self, laplace: P1ConstantOperator, x: P1Function, b: P1Function, level: int, steps: int):
+        """Solver::solveSteps: `steps` calls of solve, which a smoother may fuse (what a multigrid cycle calls for pre / post smoothing)"""
+        _ck(lib().hyteg_host_solver_solve_steps(self.h, laplace.h, x.h, b.h, level, int(steps)), "solve_steps")
         _raise_callback_exception(self)
 
     def set_use_graphs(self, on: bool) -> None:
@@ -853,6 +1089,11 @@ class P1StokesFunction:
             self.components.append(P1Function(storage, "", min_level, max_level, _borrowed=c))
         self.u, self.v, self.w, self.p = self.components
         self.uvw = self.components[:3]
+
+    def set_velocity_boundary_condition(self, bc: BoundaryCondition, component=None):
+        """the condition of the velocity (component: of u, v or w alone); the pressure stays all-inner"""
+        for f in self.uvw if component is None else [self.uvw[component]]:
+            f.set_boundary_condition(bc)
 
     def assign(self, scalars, funcs, level, flag=All):
         sc = np.ascontiguousarray(scalars, dtype=np.float64)
@@ -943,9 +1184,10 @@ class StokesSolver:
         self.h = None
 
 
-class P2Function(_Reductions):
+class P2Function(_Reductions, _BoundaryConditioned):
     """hyteg::P2Function<double>: vertex DoFs (the P1 cell array) + edge DoFs (EdgeDoFIndexing.hpp layout)"""
     _reduce_fn = "hyteg_host_p2_reduce"
+    _bc_prefix = "hyteg_host_p2function"
 
     def __init__(self, storage: Storage, name: str, min_level: int, max_level: int, _borrowed=None):
         self.storage = storage
@@ -974,7 +1216,9 @@ class P2Function(_Reductions):
         _ck(lib().hyteg_host_p2function_download(self.h, cell, level, v.ctypes.data, e.ctypes.data), "P2Function.download")
         return v, e[:ne]
 
-    def interpolate(self, value, level, flag=All):
+    def interpolate(self, value, level, flag=All, boundary_uid=None):
+        if boundary_uid is not None:
+            return self._interpolate_on_boundary(value, level, boundary_uid)
         _ck(lib().hyteg_host_p2function_interpolate_constant(self.h, float(value), level, flag), "P2Function.interpolate")
 
     def _vec(self, fn, scalars, funcs, level, flag):
@@ -1141,6 +1385,11 @@ class TaylorHoodFunction:
         c = _vp()
         _ck(lib().hyteg_host_th_function_pressure(self.h, C.byref(c)), "th pressure")
         self.pressure = P1Function(storage, "", min_level, max_level, _borrowed=c)
+
+    def set_velocity_boundary_condition(self, bc: BoundaryCondition, component=None):
+        """the condition of the velocity (component: of one component alone); the pressure stays all-inner"""
+        for f in self.velocity if component is None else [self.velocity[component]]:
+            f.set_boundary_condition(bc)
 
     def assign(self, scalars, funcs, level, flag=All):
         n = len(funcs)

@@ -68,7 +68,7 @@ class InvDiagOperatorWrapper
    explicit InvDiagOperatorWrapper( const OperatorType& A )
    : A_( A )
    {}
-   void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
+   void apply( const srcType& src, const dstType& dst, uint_t level, const Selection& flag, UpdateType updateType = Replace ) const
    {
       if ( updateType != Replace )
          throw std::runtime_error( "InvDiagOperatorWrapper::apply: Replace only" );
@@ -87,7 +87,7 @@ namespace chebyshev {
 // radius = < x, D^-1 A x >, all with the flag All like the reference.  The inverse diagonals of this project's operators are
 // assembled on every point (P1ConstantOperator::computeInverseDiagonalOperatorValues sets the sum of the neighbour cells'
 // centre weights on all 14 boundary slots, fixed ones included; the elementwise operators sum element diagonals everywhere), so
-// `All` is usable as it stands; a function with the all-inner boundary condition translates it itself (effectiveFlag).
+// `All` is usable as it stands; every function reads it under its own boundary condition (effectiveFlag).
 // x: start vector (overwritten), tmp: work function.  Reads the dot products back on the host: not for recorded cycles.
 template < class OperatorType >
 double estimateRadius( const OperatorType& A, uint_t level, uint_t maxIter, const std::shared_ptr< PrimitiveStorage >&,
@@ -145,7 +145,7 @@ class ChebyshevSmoother : public Solver< OperatorType >
    , tmp1_( "cheb_tmp1", storage, minLevel, maxLevel )
    , tmp2_( "cheb_tmp2", storage, minLevel, maxLevel )
    , coefficients_( maxLevel - minLevel + 1 )
-   , lastFlag_( maxLevel - minLevel + 1, -1 )
+   , lastSelection_( maxLevel - minLevel + 1 )
    {}
 
    void setupCoefficients( uint_t order, const std::vector< double >& spectralRadii, double upperFactor = 1.2, double lowerFactor = 0.3 )
@@ -224,15 +224,11 @@ class ChebyshevSmoother : public Solver< OperatorType >
    // copyBCs( x, tmp ) of the reference, and zero on the points the flag does not select
    void prepareTemporaries( const FunctionType& x, uint_t level )
    {
-      int selected = (int) flag_;
-      if constexpr ( std::is_same< FunctionType, P1Function< double > >::value )
-      {
-         tmp1_.setBoundaryConditionAllInner( x.hasAllInnerBoundaryCondition() );
-         tmp2_.setBoundaryConditionAllInner( x.hasAllInnerBoundaryCondition() );
-         selected = (int) x.effectiveFlag( flag_ );
-      }
-      int& last = lastFlag_[level - minLevel_];
-      if ( last != -1 && last != selected )
+      tmp1_.copyBoundaryConditionFromFunction( x );
+      tmp2_.copyBoundaryConditionFromFunction( x );
+      const Selection             selected = x.effectiveFlag( flag_ );
+      std::optional< Selection >& last     = lastSelection_[level - minLevel_];
+      if ( last && *last != selected )
       {
          tmp1_.setToZero( level );
          tmp2_.setToZero( level );
@@ -240,12 +236,12 @@ class ChebyshevSmoother : public Solver< OperatorType >
       last = selected;
    }
 
-   DoFType                              flag_;
-   uint_t                               minLevel_, maxLevel_;
-   FunctionType                         tmp1_, tmp2_;
-   std::vector< std::vector< double > > coefficients_;
-   std::vector< int >                   lastFlag_;
-   bool                                 fused_ = true;
+   DoFType                                   flag_;
+   uint_t                                    minLevel_, maxLevel_;
+   FunctionType                              tmp1_, tmp2_;
+   std::vector< std::vector< double > >      coefficients_;
+   std::vector< std::optional< Selection > > lastSelection_; // per level: what the temporaries were last written under
+   bool                                      fused_ = true;
 };
 
 } // namespace hyteg

@@ -55,8 +55,8 @@ struct PackArgs
    unsigned*                   counter = nullptr;
 };
 
-// Moves plan.sendBuffer (segments per peer) into the peers' plan.recvBuffer.  `key` = cls + 2 * dofKind identifies the
-// plan of a level (boundary class 0 / 1; vertex-DoF / edge-DoF arrays).
+// Moves plan.sendBuffer (segments per peer) into the peers' plan.recvBuffer.  `key` = PrimitiveStorage::planKey( cls, dofKind ) identifies the
+// plan of a level (exchange class = mesh boundary flag; vertex-DoF / edge-DoF arrays).
 class Transport
 {
  public:

@@ -12,17 +12,17 @@ namespace hyteg {
 class P1toP1LinearRestriction
 {
  public:
-   void restrict( const P1Function< double >& function, const uint_t& sourceLevel, const DoFType& flagIn ) const
+   void restrict( const P1Function< double >& function, const uint_t& sourceLevel, const Selection& flagIn ) const
    {
       restrictInto( function, function, sourceLevel, flagIn );
    }
    // restriction of `fineFunction` at sourceLevel into `function` at sourceLevel - 1: what a multigrid cycle does with
    // restrict( tmp ) followed by b.assign( { 1 }, { tmp }, sourceLevel - 1 ) (GeometricMultigridSolver.hpp:262-266), without the copy
    void restrictInto( const P1Function< double >& fineFunction, const P1Function< double >& function, const uint_t& sourceLevel,
-                      const DoFType& flagIn ) const
+                      const Selection& flagIn ) const
    {
       ScopedTimer timerRestrict( function.getStorage()->getTimingTree(), "P1toP1LinearRestriction" );
-      const DoFType flag = function.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = function.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       auto         storage = function.getStorage();
       const uint_t dstLevel = sourceLevel - 1;
       if ( storage->useBatch( sourceLevel ) )
@@ -53,20 +53,19 @@ class P1toP1LinearRestriction
 class P1toP1LinearProlongation
 {
  public:
-   void prolongate( const P1Function< double >& function, const uint_t& sourceLevel, const DoFType& flag ) const
+   void prolongate( const P1Function< double >& function, const uint_t& sourceLevel, const Selection& flag ) const
    {
       run( function, function, sourceLevel, flag );
    }
-   void prolongateAndAdd( const P1Function< double >& function, const uint_t& sourceLevel, const DoFType& flagIn ) const
+   void prolongateAndAdd( const P1Function< double >& function, const uint_t& sourceLevel, const Selection& flagIn ) const
    {
-      const DoFType& flag = flagIn;
+      const Selection flag = function.effectiveFlag( flagIn ); // the function's boundary condition decides; the temporary follows it
       // the prolongated correction is formed in a temporary (Replace), summed over cells on shared points, then added.
       // The temporary needs no initialisation: the masked kernel writes every point `flag` selects, the sum over
       // shared copies and the add read only those.
       auto                 storage = function.getStorage();
       // no shell point selected (a macro-cell whose boundary values are fixed): nothing is shared, the kernel adds in place
       {
-         const DoFType flag = function.effectiveFlag( flagIn );
          if ( storage->numRanks() == 1 && !storage->useBatch( sourceLevel + 1 ) && !storage->anyShellSelected( flag ) )
          {
             ScopedTimer timerProlongate( storage->getTimingTree(), "P1toP1LinearProlongation" );
@@ -83,16 +82,15 @@ class P1toP1LinearProlongation
          }
       }
       P1Function< double > tmp( "prolongate_tmp", storage, sourceLevel + 1, sourceLevel + 1, true );
-      tmp.setBoundaryConditionAllInner( function.hasAllInnerBoundaryCondition() );
       run( function, tmp, sourceLevel, flag );
       function.add( { 1.0 }, { tmp }, sourceLevel + 1, flag );
    }
 
  private:
-   static void run( const P1Function< double >& src, const P1Function< double >& dst, uint_t sourceLevel, DoFType flagIn )
+   static void run( const P1Function< double >& src, const P1Function< double >& dst, uint_t sourceLevel, const Selection& flagIn )
    {
       ScopedTimer timerProlongate( src.getStorage()->getTimingTree(), "P1toP1LinearProlongation" );
-      const DoFType flag = dst.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = dst.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       auto storage = src.getStorage();
       if ( storage->useBatch( sourceLevel + 1 ) )
       {

@@ -4,6 +4,7 @@
 // against HyTeG reads the same here:
 //   MeshInfo                     src/hyteg/mesh/MeshInfo.hpp:221,512-585
 //   PrimitiveStorage             src/hyteg/primitivestorage/PrimitiveStorage.hpp, SetupPrimitiveStorage.cpp
+//   BoundaryCondition, BoundaryUID   src/hyteg/boundary/BoundaryConditions.hpp
 //   P1Function< double >         src/hyteg/p1functionspace/VertexDoFFunction.hpp/.cpp (interpolate, assign, add,
 //                                multElementwise, dotLocal, dotGlobal)
 //   P1ConstantOperator< Form >   src/constant_stencil_operator/P1ConstantOperator.hpp:33-168 + P1Operator.hpp:192-447
@@ -23,6 +24,7 @@
 #pragma once
 
 #include "types.hpp"
+#include "boundary.hpp"
 #include "mesh.hpp"
 #include "storage.hpp"
 #include "p1function.hpp"

@@ -74,6 +74,35 @@ std::vector< std::reference_wrapper< const P1Function< double > > > refs( int n,
       r.push_back( std::cref( F( fs[i] ) ) );
    return r;
 }
+// key = ( cls & 1 ) + 2 * dof_kind + 4 * ( cls >> 1 ): PrimitiveStorage::planKey
+const ExchangePlan& exchangePlanOfKey( hh_storage_t s, int level, int key )
+{
+   int cls, dofKind;
+   PrimitiveStorage::splitPlanKey( key, cls, dofKind );
+   return S( s ).exchangePlan( level, cls, dofKind );
+}
+const ExchangePlan& devicePlanOfKey( hh_storage_t s, int level, int key )
+{
+   int cls, dofKind;
+   PrimitiveStorage::splitPlanKey( key, cls, dofKind );
+   return S( s ).devicePlan( level, cls, dofKind );
+}
+struct BoundaryConditionH
+{
+   BoundaryCondition bc;
+};
+BoundaryCondition& BC( hh_boundary_condition_t b )
+{
+   if ( !b )
+      throw std::runtime_error( "null boundary condition" );
+   return static_cast< BoundaryConditionH* >( b )->bc;
+}
+// the selection of a C call: the DoFType flag, or -- boundary_uid >= 0 -- one boundary of the function's condition
+template < class Function >
+Selection selectionOf( const Function& f, int boundaryUid, const char* boundaryName )
+{
+   return f.boundarySelection( BoundaryUID{ boundaryUid, boundaryName ? boundaryName : "" } );
+}
 P2Function< double >& F2( hh_p2function_t f ) { return *static_cast< P2FunctionH* >( f )->p; }
 std::vector< std::reference_wrapper< const P2Function< double > > > refs2( int n, const hh_p2function_t* fs )
 {
@@ -335,6 +364,150 @@ HYTEG_HOST_API int hyteg_host_storage_mask( hh_storage_t s, int li, int flag, in
       *mask              = owned ? S( s ).ownedMaskFor( c, DoFType( flag ) ) : S( s ).maskFor( c, DoFType( flag ) );
    } );
 }
+HYTEG_HOST_API int hyteg_host_storage_mask_bc( hh_storage_t s, int li, int flag, int owned, hh_boundary_condition_t bc, unsigned* mask )
+{
+   return guarded( [&] {
+      const MacroCell& c = S( s ).getLocalCell( (uint_t) li );
+      const Selection  sel( DoFType( flag ), bc ? std::make_shared< const BoundaryCondition >( BC( bc ) ) : nullptr, -1, true );
+      *mask              = owned ? S( s ).ownedMaskFor( c, sel ) : S( s ).maskFor( c, sel );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flags_on_boundary( hh_storage_t s, unsigned long long flag_on_boundary,
+                                                                           unsigned long long flag_inner, int highest_dimension_always_inner )
+{
+   return guarded( [&] { S( s ).setMeshBoundaryFlagsOnBoundary( (uint_t) flag_on_boundary, (uint_t) flag_inner, highest_dimension_always_inner != 0 ); } );
+}
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flags_inner( hh_storage_t s, unsigned long long flag_inner, int highest_dimension_always_inner )
+{
+   return guarded( [&] { S( s ).setMeshBoundaryFlagsInner( (uint_t) flag_inner, highest_dimension_always_inner != 0 ); } );
+}
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flags_by_vertex_location( hh_storage_t s, unsigned long long flag,
+                                                                                  int ( *on_boundary )( void*, const double* ), void* user,
+                                                                                  int all_vertices )
+{
+   return guarded( [&] {
+      if ( !on_boundary )
+         throw std::runtime_error( "set_mesh_boundary_flags_by_vertex_location: null predicate" );
+      S( s ).setMeshBoundaryFlagsByVertexLocation( (uint_t) flag, [&]( const Point3D& x ) { return on_boundary( user, x.data() ) != 0; }, all_vertices != 0 );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flags_by_centroid_location( hh_storage_t s, unsigned long long flag,
+                                                                                    int ( *on_boundary )( void*, const double* ), void* user )
+{
+   return guarded( [&] {
+      if ( !on_boundary )
+         throw std::runtime_error( "set_mesh_boundary_flags_by_centroid_location: null predicate" );
+      S( s ).setMeshBoundaryFlagsByCentroidLocation( (uint_t) flag, [&]( const Point3D& x ) { return on_boundary( user, x.data() ) != 0; } );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flag( hh_storage_t s, int dim, int index, unsigned long long flag )
+{
+   return guarded( [&] {
+      if ( index < 0 )
+         throw std::runtime_error( "set_mesh_boundary_flag: negative index" );
+      S( s ).setMeshBoundaryFlag( dim, (uint_t) index, (uint_t) flag );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_storage_primitive( hh_storage_t s, int dim, int index, int* nvertices, int* vertex_ids3, double* coords9,
+                                                 unsigned long long* flag, int* on_boundary )
+{
+   return guarded( [&] {
+      if ( index < 0 )
+         throw std::runtime_error( "storage_primitive: negative index" );
+      const MacroPrimitive& p = S( s ).primitive( dim, (uint_t) index );
+      *nvertices              = (int) p.v.size();
+      for ( uint_t k = 0; k < p.v.size(); ++k )
+      {
+         vertex_ids3[k] = p.v[k];
+         for ( int r = 0; r < 3; ++r )
+            coords9[3 * k + (uint_t) r] = S( s ).getVertexCoordinates( (uint_t) p.v[k] )[(uint_t) r];
+      }
+      *flag        = p.meshBoundaryFlag;
+      *on_boundary = p.onBoundary ? 1 : 0;
+   } );
+}
+HYTEG_HOST_API int hyteg_host_storage_boundary_classes( hh_storage_t s, int* count, unsigned long long* flags )
+{
+   return guarded( [&] {
+      const auto& c = S( s ).boundaryClasses();
+      *count        = (int) c.size();
+      if ( flags )
+         std::copy( c.begin(), c.end(), flags );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_boundary_condition_create( int preset, hh_boundary_condition_t* out )
+{
+   return guarded( [&] {
+      if ( preset < 0 || preset > 2 )
+         throw std::runtime_error( "boundary_condition_create: preset 0 (no boundary), 1 (create0123BC) or 2 (createAllInnerBC)" );
+      *out = new BoundaryConditionH{ preset == 1 ? BoundaryCondition::create0123BC() :
+                                                   ( preset == 2 ? BoundaryCondition::createAllInnerBC() : BoundaryCondition() ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_boundary_condition_destroy( hh_boundary_condition_t bc )
+{
+   return guarded( [&] { delete static_cast< BoundaryConditionH* >( bc ); } );
+}
+HYTEG_HOST_API int hyteg_host_boundary_condition_create_domain( hh_boundary_condition_t bc, const char* name, int dof_type, int nflags,
+                                                                const unsigned long long* flags, int* uid )
+{
+   return guarded( [&] {
+      std::vector< uint_t > f;
+      for ( int i = 0; i < nflags; ++i )
+         f.push_back( (uint_t) flags[i] );
+      *uid = BC( bc ).createDomainBC( name ? name : "", DoFType( dof_type ), f ).id;
+   } );
+}
+HYTEG_HOST_API int hyteg_host_boundary_condition_type( hh_boundary_condition_t bc, unsigned long long flag, int* dof_type )
+{
+   return guarded( [&] { *dof_type = (int) BC( bc ).getBoundaryType( (uint_t) flag ); } );
+}
+HYTEG_HOST_API int hyteg_host_boundary_condition_uid( hh_boundary_condition_t bc, unsigned long long flag, int* uid, char* name, int buflen )
+{
+   return guarded( [&] {
+      const BoundaryUID& u = BC( bc ).getBoundaryUIDFromMeshFlag( (uint_t) flag );
+      *uid                 = u.id;
+      if ( name && buflen > 0 )
+      {
+         std::strncpy( name, u.name.c_str(), (size_t) buflen - 1 );
+         name[buflen - 1] = 0;
+      }
+   } );
+}
+HYTEG_HOST_API int hyteg_host_boundary_condition_equal( hh_boundary_condition_t a, hh_boundary_condition_t b, int* equal )
+{
+   return guarded( [&] { *equal = BC( a ) == BC( b ) ? 1 : 0; } );
+}
+HYTEG_HOST_API int hyteg_host_storage_default_boundary_condition( hh_storage_t s, hh_boundary_condition_t* out )
+{
+   return guarded( [&] { *out = new BoundaryConditionH{ S( s ).getDefaultBoundaryCondition() }; } );
+}
+HYTEG_HOST_API int hyteg_host_function_set_boundary_condition( hh_function_t f, hh_boundary_condition_t bc )
+{
+   return guarded( [&] { F( f ).setBoundaryCondition( BC( bc ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_function_boundary_condition( hh_function_t f, hh_boundary_condition_t* out )
+{
+   return guarded( [&] { *out = new BoundaryConditionH{ F( f ).getBoundaryCondition() }; } );
+}
+HYTEG_HOST_API int hyteg_host_function_interpolate_constant_on_boundary( hh_function_t f, double v, int level, int boundary_uid,
+                                                                         const char* boundary_name )
+{
+   return guarded( [&] { F( f ).interpolate( v, (uint_t) level, selectionOf( F( f ), boundary_uid, boundary_name ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2function_set_boundary_condition( hh_p2function_t f, hh_boundary_condition_t bc )
+{
+   return guarded( [&] { F2( f ).setBoundaryCondition( BC( bc ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2function_boundary_condition( hh_p2function_t f, hh_boundary_condition_t* out )
+{
+   return guarded( [&] { *out = new BoundaryConditionH{ F2( f ).getBoundaryCondition() }; } );
+}
+HYTEG_HOST_API int hyteg_host_p2function_interpolate_constant_on_boundary( hh_p2function_t f, double v, int level, int boundary_uid,
+                                                                           const char* boundary_name )
+{
+   return guarded( [&] { F2( f ).interpolate( v, (uint_t) level, selectionOf( F2( f ), boundary_uid, boundary_name ) ); } );
+}
 HYTEG_HOST_API int hyteg_host_storage_set_boundary_type( hh_storage_t s, int t )
 {
    return guarded( [&] { S( s ).setBoundaryType( DoFType( t ) ); } );
@@ -435,7 +608,7 @@ HYTEG_HOST_API int hyteg_host_storage_p2p_open( hh_storage_t s, const unsigned c
 HYTEG_HOST_API int hyteg_host_storage_p2p_layout( hh_storage_t s, int level, int key, long long* offsets )
 {
    return guarded( [&] {
-      const auto& plan = S( s ).devicePlan( level, key & 1, key >> 1 );
+      const auto& plan = devicePlanOfKey( s, level, key );
       const auto  o    = S( s ).p2p().layoutPlan( plan, level, key );
       if ( !o.empty() && !offsets )
          throw std::runtime_error( "storage_p2p_layout: null offsets" );
@@ -445,7 +618,7 @@ HYTEG_HOST_API int hyteg_host_storage_p2p_layout( hh_storage_t s, int level, int
 HYTEG_HOST_API int hyteg_host_storage_p2p_connect( hh_storage_t s, int level, int key, const long long* offsets )
 {
    return guarded( [&] {
-      const auto& plan = S( s ).devicePlan( level, key & 1, key >> 1 );
+      const auto& plan = devicePlanOfKey( s, level, key );
       if ( !plan.peers.empty() && !offsets )
          throw std::runtime_error( "storage_p2p_connect: null offsets" );
       S( s ).p2p().connectPlan( plan, level, key, offsets );
@@ -523,11 +696,11 @@ HYTEG_HOST_API int hyteg_host_storage_set_hooks( hh_storage_t s, int ( *exb )( v
       S( s ).setCommHooks( h );
    } );
 }
-// key = cls + 2 * dof_kind (dof_kind 0: vertex DoFs, 1: edge DoFs of P2 functions)
+// key = ( cls & 1 ) + 2 * dof_kind + 4 * ( cls >> 1 ) (dof_kind 0: vertex DoFs, 1: edge DoFs of P2 functions)
 HYTEG_HOST_API int hyteg_host_plan_sizes( hh_storage_t s, int level, int key, int* sizes )
 {
    return guarded( [&] {
-      const auto& P = S( s ).exchangePlan( level, key & 1, key >> 1 );
+      const auto& P = exchangePlanOfKey( s, level, key );
       sizes[0]      = P.ngroups();
       sizes[1]      = (int) P.entryBuf.size();
       sizes[2]      = (int) P.peers.size();
@@ -538,7 +711,7 @@ HYTEG_HOST_API int hyteg_host_plan_sizes( hh_storage_t s, int level, int key, in
 HYTEG_HOST_API int hyteg_host_plan_export( hh_storage_t s, int level, int key, int* gp, int* eb, int* eo, int* peers, int* sc, int* rc, int* sb, int* so )
 {
    return guarded( [&] {
-      const auto& P = S( s ).exchangePlan( level, key & 1, key >> 1 );
+      const auto& P = exchangePlanOfKey( s, level, key );
       std::copy( P.groupPtr.begin(), P.groupPtr.end(), gp );
       std::copy( P.entryBuf.begin(), P.entryBuf.end(), eb );
       std::copy( P.entryOff.begin(), P.entryOff.end(), eo );
@@ -917,6 +1090,26 @@ HYTEG_HOST_API int hyteg_host_gmg_create_chebyshev( hh_storage_t s, int minL, in
       using Op = P1ConstantLaplaceOperator;
       auto sm  = makeChebyshev< Op >( s, minL, maxL, order, radii, nRadii, upper, lower );
       *out = new SolverH{ makeGmg< Op >( SP( s ), sm, cgCoarse< Op >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_mixed_precision_jacobi_create( hh_storage_t s, int minL, int maxL, double relax, int fp32_sweeps, hh_solver_t* out )
+{
+   return guarded( [&] {
+      if ( fp32_sweeps < 0 )
+         throw std::runtime_error( "mixed_precision_jacobi_create: negative number of float sweeps" );
+      *out = new SolverH{ std::make_shared< MixedPrecisionJacobiSmoother< P1ConstantLaplaceOperator > >( SP( s ), (uint_t) minL, (uint_t) maxL, relax,
+                                                                                                         (uint_t) fp32_sweeps ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_solver_solve_steps( hh_solver_t solver, hh_operator_t laplace, hh_function_t x, hh_function_t b, int level, int steps )
+{
+   return guarded( [&] {
+      auto* h = static_cast< OperatorH* >( laplace );
+      if ( h->op.index() != 0 )
+         throw std::runtime_error( "solver_solve_steps: the solvers are instantiated for the Laplace operator" );
+      if ( steps < 0 )
+         throw std::runtime_error( "solver_solve_steps: negative number of steps" );
+      static_cast< SolverH* >( solver )->p->solveSteps( *std::get< 0 >( h->op ), F( x ), F( b ), (uint_t) level, (uint_t) steps );
    } );
 }
 HYTEG_HOST_API int hyteg_host_solver_solve( hh_solver_t solver, hh_operator_t laplace, hh_function_t x, hh_function_t b, int level )

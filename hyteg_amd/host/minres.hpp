@@ -37,6 +37,7 @@ class JacobiPreconditioner : public Solver< OperatorType >
    {}
    void solve( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level ) override
    {
+      tmp_.copyBoundaryConditionFromFunction( x );
       x.assign( { 1.0 }, { b }, level, flag_ );
       for ( uint_t i = 0; i < iterations_; ++i )
       {
@@ -54,8 +55,9 @@ class JacobiPreconditioner : public Solver< OperatorType >
 // dst = / += scale * src pointwise: the apply of the operators whose stencil is a centre weight only (P1LumpedInvMassOperator
 // below, P1PSPGInvDiagOperator of stokes.hpp).  Add goes through the operator's scratch function tmp.
 inline void applyPointwiseScaling( const P1Function< double >& scale, const P1Function< double >& tmp, const P1Function< double >& src,
-                                   const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType )
+                                   const P1Function< double >& dst, uint_t level, const Selection& flagIn, UpdateType updateType )
 {
+   const Selection flag = dst.effectiveFlag( flagIn ); // the destination's boundary condition decides; the temporary follows it
    if ( updateType == Replace )
    {
       dst.multElementwise( { scale, src }, level, flag );
@@ -184,7 +186,10 @@ class MinResSolver : public Solver< OperatorType >
       const FunctionType *vm = work_[0].get(), *v = work_[1].get(), *vp = work_[2].get(), *z = work_[3].get(), *zp = work_[4].get(),
                          *wm = work_[5].get(), *w = work_[6].get(), *wp = work_[7].get(), *r = work_[9].get();
       for ( auto& f : work_ )
+      {
+         f->copyBoundaryConditionFromFunction( x ); // copyBCs
          f->interpolate( 0.0, level, All ); // setToZero
+      }
 
       A.apply( x, *r, level, flag_ );
       v->assign( { 1.0, -1.0 }, { b, *r }, level, flag_ );

@@ -24,6 +24,7 @@ class P1ElementwiseDiffusion
    , minLevel_( minLevel )
    , maxLevel_( maxLevel )
    {
+      storage->markInUse(); // the mesh boundary flags are fixed from here on
       for ( uint_t l = std::max< uint_t >( minLevel, HYTEG_HIP_MIN_LEVEL ); l <= maxLevel; ++l )
          hipCheck( hyteg_hip_prepare_level( (int) l ), "P1ElementwiseDiffusion: prepare_level" );
    }
@@ -36,10 +37,10 @@ class P1ElementwiseDiffusion
    // All ^ flag.  Cell-centric storage: every copy of a shared DoF holds the same value (nothing to synchronise), a cell's
    // boundary entries are the DoFs themselves, so the kernel is restricted to the flagged point classes (Replace writes them,
    // so no zeroing pass), the shares of shared points are summed by the additive exchange while the inner points are computed.
-   void apply( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flagIn, UpdateType updateType = Replace ) const
+   void apply( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, const Selection& flagIn, UpdateType updateType = Replace ) const
    {
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerApply( storage_->getTimingTree(), "apply" );
-      const DoFType flag = dst.effectiveFlag( flagIn );
+      const Selection flag = dst.effectiveFlag( flagIn );
       if ( &src == &dst )
          throw std::runtime_error( "P1ElementwiseDiffusion::apply: src and dst must differ" );
       const int64_t n = int64_t( 1 ) << level;
@@ -110,7 +111,7 @@ class P1ElementwiseDiffusion
    // P1ElementwiseOperator::smooth_jac, src/hyteg/elementwiseoperators/P1ElementwiseOperator.cpp:288-331:
    //   dst = A src ; dst = rhs - dst ; dst = invDiag .* dst ; dst = src + omega dst      (four passes, as the reference writes it)
    void smooth_jac( const P1Function< double >& dst, const P1Function< double >& rhs, const P1Function< double >& src, double omega, uint_t level,
-                    DoFType flag ) const
+                    const Selection& flag ) const
    {
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerJac( storage_->getTimingTree(), "smooth_jac" );
       apply( src, dst, level, flag, Replace );

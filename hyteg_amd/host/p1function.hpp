@@ -25,9 +25,39 @@ class P1Function
    // the storage's boundary types (create0123BC).  Operators, grid transfer and the function's own methods translate the
    // DoFType flag they are given with the destination function's boundary condition, as the reference does with
    // dst.getBoundaryCondition().getBoundaryType( primitive.getMeshBoundaryFlag() ) (P1Operator.hpp:301-303).
-   void    setBoundaryConditionAllInner( bool on = true ) { allInner_ = on; }
-   bool    hasAllInnerBoundaryCondition() const { return allInner_; }
-   DoFType effectiveFlag( DoFType flag ) const { return allInner_ ? ( testFlag( flag, Inner ) ? All : DoFType( 0 ) ) : flag; }
+   // setBoundaryConditionAllInner( on ) is shorthand for setBoundaryCondition( createAllInnerBC() ) / the storage's default.
+   void setBoundaryConditionAllInner( bool on = true )
+   {
+      bc_  = on ? std::make_shared< const BoundaryCondition >( BoundaryCondition::createAllInnerBC() ) : nullptr;
+      uid_ = nextUid(); // a launch graph recorded with this function holds the masks of its former condition
+   }
+   bool hasAllInnerBoundaryCondition() const { return bc_ && bc_->allInner(); }
+   // Function::setBoundaryCondition / getBoundaryCondition: the function's own map from mesh boundary flags to DoFTypes
+   void setBoundaryCondition( const BoundaryCondition& bc )
+   {
+      bc_  = std::make_shared< const BoundaryCondition >( bc );
+      uid_ = nextUid(); // as above
+   }
+   const BoundaryCondition& getBoundaryCondition() const { return bc_ ? *bc_ : storage_->getDefaultBoundaryCondition(); }
+   // Function::copyBoundaryConditionFromFunction: what a temporary does with the function it stands in for
+   template < typename OtherFunction >
+   void copyBoundaryConditionFromFunction( const OtherFunction& other )
+   {
+      bc_ = other.boundaryConditionOrNull();
+   }
+   std::shared_ptr< const BoundaryCondition > boundaryConditionOrNull() const { return bc_; } // null: the storage's default
+   // The one selection every mask of this function comes from.  Every method takes its flag as a Selection: a bare DoFType (or a
+   // boundary of the condition, boundarySelection) is put under THIS function's condition here; one that an operator has already
+   // put under its destination's condition passes unchanged, so that the temporaries it works with select the same points.
+   Selection effectiveFlag( const Selection& s ) const { return s.resolved ? s : Selection( s.flag, bc_, s.uid, true ); }
+   // the points of the primitives whose mesh flag belongs to one boundary of the function's condition
+   Selection boundarySelection( const BoundaryUID& uid ) const
+   {
+      if ( !getBoundaryCondition().hasBoundary( uid ) )
+         throw std::runtime_error( "P1Function '" + name_ + "': its boundary condition has no boundary '" + uid.name + "' with id " +
+                                   std::to_string( uid.id ) + " (a BoundaryUID belongs to the condition that created it)" );
+      return Selection( All, bc_, uid.id, true );
+   }
 
    // scratch = true: arrays come from (and return to) the storage's scratch pool and are NOT zero-initialised
    P1Function( const std::string& name, const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel,
@@ -40,6 +70,7 @@ class P1Function
    {
       if ( maxLevel > HYTEG_HIP_MAX_LEVEL || minLevel > maxLevel )
          throw std::runtime_error( "P1Function: bad level range" );
+      storage->markInUse(); // the mesh boundary flags are fixed from here on
       const uint_t nLocal = storage->getNumberOfLocalCells();
       data_.resize( nLocal );
       for ( uint_t c = 0; c < nLocal; ++c )
@@ -93,10 +124,19 @@ class P1Function
    }
 
    // ---- interpolate ( VertexDoFFunction.cpp:380-392, :395-470 ) ----
-   void interpolate( ValueType constant, uint_t level, DoFType flagIn = All ) const
+   // Function::interpolate( constant | expr, level, BoundaryUID ): on the primitives whose mesh flag belongs to that boundary
+   void interpolate( ValueType constant, uint_t level, const BoundaryUID& boundary ) const
+   {
+      interpolate( constant, level, boundarySelection( boundary ) );
+   }
+   void interpolate( const std::function< ValueType( const Point3D& ) >& expr, uint_t level, const BoundaryUID& boundary ) const
+   {
+      interpolate( expr, level, boundarySelection( boundary ) );
+   }
+   void interpolate( ValueType constant, uint_t level, const Selection& flagIn = All ) const
    {
       ScopedTimer timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Interpolate" );
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       if ( storage_->useBatch( level ) )
       {
          const auto masks = storage_->masksFor( flag );
@@ -114,10 +154,10 @@ class P1Function
                    "interpolate" );
       } );
    }
-   void interpolate( const std::function< ValueType( const Point3D& ) >& expr, uint_t level, DoFType flagIn = All ) const
+   void interpolate( const std::function< ValueType( const Point3D& ) >& expr, uint_t level, const Selection& flagIn = All ) const
    {
       ScopedTimer timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Interpolate" );
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       // evaluated on the host at the micro-vertex coordinates of VertexDoFMacroCell.hpp:70-77, then uploaded
       const int64_t N = layout::width( (int) level ), size = layout::cellSize( (int) level );
       P1Function    tmp( "interpolate_tmp", storage_, level, level, true );
@@ -152,20 +192,20 @@ class P1Function
    void assign( const std::vector< ValueType >&                                           scalars,
                 const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions,
                 uint_t                                                                    level,
-                DoFType                                                                   flag = All ) const
+                const Selection&                                                          flag = All ) const
    {
       vectorOp( 0, scalars, functions, level, flag );
    }
    void add( const std::vector< ValueType >&                                           scalars,
              const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions,
              uint_t                                                                    level,
-             DoFType                                                                   flag = All ) const
+             const Selection&                                                          flag = All ) const
    {
       vectorOp( 1, scalars, functions, level, flag );
    }
    void multElementwise( const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions,
                          uint_t                                                                    level,
-                         DoFType                                                                   flag = All ) const
+                         const Selection&                                                          flag = All ) const
    {
       vectorOp( 2, {}, functions, level, flag );
    }
@@ -180,9 +220,9 @@ class P1Function
       return f;
    }
    // this += f on the macro-face, -edge and -vertex points `flag` selects, one launch per cell
-   void addOnShell( const P1Function< ValueType >& f, uint_t level, DoFType flagIn ) const
+   void addOnShell( const P1Function< ValueType >& f, uint_t level, const Selection& flagIn ) const
    {
-      const DoFType flag = effectiveFlag( flagIn );
+      const Selection flag = effectiveFlag( flagIn );
       forCells( [&]( uint_t c, const MacroCell& cell ) {
          const double* srcs[1] = { f.getCellPointer( c, level ) };
          const double  one[1]  = { 1.0 };
@@ -193,10 +233,10 @@ class P1Function
    }
 
    // ---- dot ( VertexDoFFunction.cpp:1710-1793 ) ----
-   ValueType dotLocal( const P1Function< ValueType >& rhs, uint_t level, DoFType flagIn = All ) const
+   ValueType dotLocal( const P1Function< ValueType >& rhs, uint_t level, const Selection& flagIn = All ) const
    {
       ScopedTimer timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Dot (local)" );
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       // one result slot per local cell, a single download (= one host synchronisation) per dot product; the
       // workspace is reused cell after cell, which is safe because all launches are ordered on one stream
       const uint_t nLocal = storage_->getNumberOfLocalCells();
@@ -235,7 +275,7 @@ class P1Function
          sum += v; // cells in ascending order: deterministic
       return sum;
    }
-   ValueType dotGlobal( const P1Function< ValueType >& rhs, uint_t level, DoFType flag = All ) const
+   ValueType dotGlobal( const P1Function< ValueType >& rhs, uint_t level, const Selection& flag = All ) const
    {
       const double local = dotLocal( rhs, level, flag );
       ScopedTimer  timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Dot (reduce)" );
@@ -261,10 +301,10 @@ class P1Function
          min = std::min( min, o.min ), max = std::max( max, o.max ), maxMagnitude = std::max( maxMagnitude, o.maxMagnitude );
       }
    };
-   Reduction reduceLocal( uint_t level, DoFType flagIn = All ) const
+   Reduction reduceLocal( uint_t level, const Selection& flagIn = All ) const
    {
       ScopedTimer timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Sum (local)" );
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       return reduceArrays( *storage_, flag, [&]( int first, int count, const unsigned* masks, double* results ) {
          const auto a = cellPointers( level, first, count );
          hipCheck( hyteg_hip_p1_reduce_cells( count, a.data(), (int) level, masks, results, storage_->reduceWorkspace(), storage_->stream() ),
@@ -273,7 +313,7 @@ class P1Function
    }
    // shared with the edge-DoF part of P2Function: launch( first, count, masks, results_dev ) reduces a chunk of cells
    template < typename Launch >
-   static Reduction reduceArrays( const PrimitiveStorage& storage, DoFType flag, Launch&& launch )
+   static Reduction reduceArrays( const PrimitiveStorage& storage, const Selection& flag, Launch&& launch )
    {
       const uint_t nLocal = storage.getNumberOfLocalCells();
       Reduction    r;
@@ -303,28 +343,28 @@ class P1Function
       }
       return r;
    }
-   ValueType sumLocal( uint_t level, DoFType flag = All, bool absolute = false ) const
+   ValueType sumLocal( uint_t level, const Selection& flag = All, bool absolute = false ) const
    {
       const Reduction r = reduceLocal( level, flag );
       return absolute ? r.sumAbs : r.sum;
    }
-   ValueType sumGlobal( uint_t level, DoFType flag = All, bool absolute = false ) const
+   ValueType sumGlobal( uint_t level, const Selection& flag = All, bool absolute = false ) const
    {
       const double local = sumLocal( level, flag, absolute );
       ScopedTimer  timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Sum (reduce)" );
       return storage_->allreduceSum( local, "sumGlobal" );
    }
-   ValueType getMaxDoFValue( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   ValueType getMaxDoFValue( uint_t level, const Selection& flag = All, bool mpiReduce = true ) const
    {
       const double local = reduceLocal( level, flag ).max;
       return mpiReduce ? storage_->allreduceMax( local, "getMaxDoFValue" ) : local;
    }
-   ValueType getMinDoFValue( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   ValueType getMinDoFValue( uint_t level, const Selection& flag = All, bool mpiReduce = true ) const
    {
       const double local = reduceLocal( level, flag ).min;
       return mpiReduce ? -storage_->allreduceMax( -local, "getMinDoFValue" ) : local; // as at VertexDoFFunction.cpp:2053
    }
-   ValueType getMaxDoFMagnitude( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   ValueType getMaxDoFMagnitude( uint_t level, const Selection& flag = All, bool mpiReduce = true ) const
    {
       const double local = reduceLocal( level, flag ).maxMagnitude;
       return mpiReduce ? storage_->allreduceMax( local, "getMaxDoFMagnitude" ) : local;
@@ -335,24 +375,24 @@ class P1Function
 
    // ---- shared-point exchange (the cell-centric replacement of communicate<> / communicateAdditively<>) ----
    // additive: every copy of a shared DoF := sum of all copies (VertexDoFAdditivePackInfo.hpp:676-745 + copy back)
-   void sumSharedCopies( uint_t level, DoFType flag = All ) const
+   void sumSharedCopies( uint_t level, const Selection& flag = All ) const
    {
       exchangeBegin( level, flag );
       exchangeEnd( level, flag, true );
    }
    // every copy := the copy held by the lowest-numbered neighbour cell
-   void syncSharedCopies( uint_t level, DoFType flag = All ) const
+   void syncSharedCopies( uint_t level, const Selection& flag = All ) const
    {
       exchangeBegin( level, flag );
       exchangeEnd( level, flag, false );
    }
    // split form: pack + start the transfer / wait + reduce.  Kernels that do not touch shared points may be
    // launched in between (the interior apply overlaps the halo exchange).
-   void beginSumSharedCopies( uint_t level, DoFType flag = All ) const { exchangeBegin( level, flag ); }
-   void endSumSharedCopies( uint_t level, DoFType flag = All ) const { exchangeEnd( level, flag, true ); }
+   void beginSumSharedCopies( uint_t level, const Selection& flag = All ) const { exchangeBegin( level, flag ); }
+   void endSumSharedCopies( uint_t level, const Selection& flag = All ) const { exchangeEnd( level, flag, true ); }
    // beginSumSharedCopies for a caller whose boundary-share kernel delivers the shares itself
    // (PrimitiveStorage::sharedExchangeBeginByShares); flag: effective flag
-   bool beginSumSharedCopiesByShares( uint_t level, DoFType flag, PrimitiveStorage::ShareSend& out ) const
+   bool beginSumSharedCopiesByShares( uint_t level, const Selection& flag, PrimitiveStorage::ShareSend& out ) const
    {
       checkLevel( level );
       return storage_->sharedExchangeBeginByShares( (int) level, flag, out );
@@ -390,9 +430,9 @@ class P1Function
                   const std::vector< ValueType >&                                           scalars,
                   const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions,
                   uint_t                                                                    level,
-                  DoFType                                                                   flagIn ) const
+                  const Selection&                                                          flagIn ) const
    {
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       static const char* kOpNames[3] = { "Assign", "Add", "Multiply elementwise" };
       ScopedTimer        timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), kOpNames[op] );
       if ( functions.empty() || functions.size() > HYTEG_HIP_MAX_SRCS || ( op != 2 && scalars.size() != functions.size() ) )
@@ -428,9 +468,9 @@ class P1Function
    // with at most HYTEG_HIP_MAX_BATCH local cells (one launch)
    void vectorOpDeviceScalars( int op, const std::vector< const double* >& scalarPtrs,
                                const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions, uint_t level,
-                               DoFType flagIn ) const
+                               const Selection& flagIn ) const
    {
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       const int  count = (int) storage_->getNumberOfLocalCells();
       const auto masks = storage_->masksFor( flag );
       const auto dst   = cellPointers( level, 0, count );
@@ -444,10 +484,10 @@ class P1Function
    }
    // cgScalars[slot] = <this, rhs> over the points `flag` selects (each shared point counted once), then phase `phase` of
    // the conjugate gradient recurrences (hyteg_hip_cg_scalars), in one launch; no host synchronisation
-   void dotLocalToCgScalars( const P1Function< ValueType >& rhs, uint_t level, DoFType flagIn, double* cgScalars, int slot, int phase,
+   void dotLocalToCgScalars( const P1Function< ValueType >& rhs, uint_t level, const Selection& flagIn, double* cgScalars, int slot, int phase,
                              double relTol, double absTol ) const
    {
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       const int  count = (int) storage_->getNumberOfLocalCells();
       const auto masks = storage_->masksFor( flag, true );
       const auto a = cellPointers( level, 0, count ), b = rhs.cellPointers( level, 0, count );
@@ -464,15 +504,15 @@ class P1Function
          a.push_back( getCellPointer( c, level ) );
       return a;
    }
-   void exchangeBegin( uint_t level, DoFType flagIn ) const
+   void exchangeBegin( uint_t level, const Selection& flagIn ) const
    {
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       checkLevel( level );
       storage_->sharedExchangeBegin( cellArrays( level ), (int) level, flag, 0 );
    }
-   void exchangeEnd( uint_t level, DoFType flagIn, bool additive ) const
+   void exchangeEnd( uint_t level, const Selection& flagIn, bool additive ) const
    {
-      const DoFType flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       storage_->sharedExchangeEnd( cellArrays( level ), (int) level, flag, 0, additive );
    }
 
@@ -480,7 +520,7 @@ class P1Function
    std::shared_ptr< PrimitiveStorage >                                   storage_;
    uint_t                                                                minLevel_, maxLevel_;
    bool                                                                  scratch_ = false;
-   bool                                                                  allInner_ = false;
+   std::shared_ptr< const BoundaryCondition >                            bc_; // null: the storage's default condition
    uint64_t                                                              uid_     = nextUid();
    std::vector< std::vector< double* > >                                 data_;
 };

@@ -24,6 +24,7 @@ class P1ConstantOperator
    , minLevel_( minLevel )
    , maxLevel_( maxLevel )
    {
+      storage->markInUse(); // the mesh boundary flags are fixed from here on
       // assembleStencils(), P1ConstantOperator.cpp:680-732: per level and cell
       for ( uint_t l = minLevel; l <= maxLevel; ++l )
       {
@@ -44,10 +45,10 @@ class P1ConstantOperator
    const stencil::CellStencils&        getCellStencils( int globalCellID, uint_t level ) const { return stencils_.at( level ).at( globalCellID ); }
 
    // Operator::apply, P1Operator.hpp:192-320
-   void apply( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flagIn, UpdateType updateType = Replace ) const
+   void apply( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, const Selection& flagIn, UpdateType updateType = Replace ) const
    {
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerApply( storage_->getTimingTree(), "Apply" );
-      const DoFType flag = dst.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = dst.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       if ( &src == &dst )
          throw std::runtime_error( "P1ConstantOperator::apply: src and dst must differ (P1Operator.hpp:198)" );
       if ( storage_->lanesOpen() )
@@ -138,7 +139,7 @@ class P1ConstantOperator
    // a single apply that reads all its sources and writes all its destinations, and is sized so that every lane still gets one.
    // Anything else is the plain loop.
    void applyRun( const std::vector< const P1Function< double >* >& srcs, const std::vector< const P1Function< double >* >& dsts, uint_t level,
-                  DoFType flagIn, UpdateType updateType = Replace ) const
+                  const Selection& flagIn, UpdateType updateType = Replace ) const
    {
       const int n       = (int) srcs.size();
       const int G       = storage_->applySteps();
@@ -147,7 +148,7 @@ class P1ConstantOperator
       bool      grouped = G > 1 && n > 1 && level <= 8 && storage_->getNumberOfLocalCells() == 1 && storage_->applyStepsUsable();
       for ( int k = 0; k < n && grouped; ++k )
       {
-         const DoFType flag = dsts[k]->effectiveFlag( flagIn );
+         const Selection flag = dsts[k]->effectiveFlag( flagIn );
          grouped            = srcs[k] != dsts[k] && pureInterior( level, flag );
          storage_->forLocalCells( [&]( uint_t, const MacroCell& cell ) { grouped = grouped && ( storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER ); } );
       }
@@ -192,9 +193,9 @@ class P1ConstantOperator
    // r = b - A x on the points `flag` selects: apply followed by assign( { 1, -1 }, { b, r } ) as the multigrid cycle writes it
    // (GeometricMultigridSolver.hpp:240-246); where no shell point is selected (one macro-cell with fixed boundary values) the
    // interior kernel forms the difference itself -- one launch, the same bits
-   void residual( const P1Function< double >& x, const P1Function< double >& b, const P1Function< double >& r, uint_t level, DoFType flagIn ) const
+   void residual( const P1Function< double >& x, const P1Function< double >& b, const P1Function< double >& r, uint_t level, const Selection& flagIn ) const
    {
-      const DoFType flag = r.effectiveFlag( flagIn );
+      const Selection flag = r.effectiveFlag( flagIn );
       if ( !pureInterior( level, flag ) || level > 10 || &x == &r )
       {
          apply( x, r, level, flagIn );
@@ -212,10 +213,10 @@ class P1ConstantOperator
 
    // P1Operator::smooth_jac, P1Operator.hpp:429-447
    void smooth_jac( const P1Function< double >& dst, const P1Function< double >& rhs, const P1Function< double >& src, double relax,
-                    uint_t level, DoFType flagIn ) const
+                    uint_t level, const Selection& flagIn ) const
    {
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerJac( storage_->getTimingTree(), "smooth_jac" );
-      const DoFType flag = dst.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = dst.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       if ( &src == &dst )
          throw std::runtime_error( "smooth_jac: src and dst must differ" );
       const auto& invDiag = *getInverseDiagonalValues();
@@ -257,10 +258,10 @@ class P1ConstantOperator
    // t = invDiag .* ( b - A x ) on the selected points; on the shell also x += c0 t.  On the interiors x is this launch's stencil
    // source: its update x += c0 t is carried out by the following chebyshevStep( ..., hasPrev = true ) or by chebyshevFinish.
    void chebyshevStart( const P1Function< double >& t, const P1Function< double >& b, const P1Function< double >& x, double c0, uint_t level,
-                        DoFType flagIn ) const
+                        const Selection& flagIn ) const
    {
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerCheb( storage_->getTimingTree(), "chebyshev" );
-      const DoFType flag = x.effectiveFlag( flagIn );
+      const Selection flag = x.effectiveFlag( flagIn );
       if ( &t == &x || &t == &b )
          throw std::runtime_error( "chebyshevStart: t must differ from x and b" );
       interiorsAndShares( t, x, level, flag, [&]( uint_t c, const double* inner ) {
@@ -274,10 +275,10 @@ class P1ConstantOperator
    // tOut = invDiag .* ( A tIn ) on the selected points; x = ( x + cPrev tIn ) + cCur tOut on the interiors (first term only if
    // hasPrev: the update chebyshevStart left open), x += cCur tOut on the shell
    void chebyshevStep( const P1Function< double >& tOut, const P1Function< double >& x, const P1Function< double >& tIn, double cPrev, double cCur,
-                       bool hasPrev, uint_t level, DoFType flagIn ) const
+                       bool hasPrev, uint_t level, const Selection& flagIn ) const
    {
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerCheb( storage_->getTimingTree(), "chebyshev" );
-      const DoFType flag = x.effectiveFlag( flagIn );
+      const Selection flag = x.effectiveFlag( flagIn );
       if ( &tOut == &tIn || &tOut == &x || &x == &tIn )
          throw std::runtime_error( "chebyshevStep: tOut, x and tIn must be three different functions" );
       interiorsAndShares( tOut, tIn, level, flag, [&]( uint_t c, const double* inner ) {
@@ -289,9 +290,9 @@ class P1ConstantOperator
       shellPasses( tOut, nullptr, *getInverseDiagonalValues(), x, cCur, x, level, flag );
    }
    // x += c t on the interiors: closes a smoother call of order 1 (no step follows the start)
-   void chebyshevFinish( const P1Function< double >& x, const P1Function< double >& t, double c, uint_t level, DoFType flagIn ) const
+   void chebyshevFinish( const P1Function< double >& x, const P1Function< double >& t, double c, uint_t level, const Selection& flagIn ) const
    {
-      const DoFType flag = x.effectiveFlag( flagIn );
+      const Selection flag = x.effectiveFlag( flagIn );
       storage_->forLocalCells( [&]( uint_t ci, const MacroCell& cell ) {
          const unsigned inner = storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_INNER;
          if ( !inner )
@@ -308,10 +309,10 @@ class P1ConstantOperator
    // macro-cell with Dirichlet values, or cells whose common faces are not selected by the flag) the sweeps of a cell do not
    // see anybody else's updates in between, and from level 5 on they run as one pipeline of block wavefronts
    // (hyteg_hip_p1_sor_cell_sweeps: bit-identical to the loop, 46 + 4 ( steps - 1 ) launches instead of 46 steps at level 8).
-   void smooth_sor_steps( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flagIn,
+   void smooth_sor_steps( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, const Selection& flagIn,
                           uint_t steps, bool backwards = false ) const
    {
-      const DoFType flag = dst.effectiveFlag( flagIn );
+      const Selection flag = dst.effectiveFlag( flagIn );
       if ( steps <= 1 || storage_->anyShellSelected( flag ) || storage_->numRanks() != 1 || storage_->useBatchSor( level ) || level < 5 )
       {
          for ( uint_t k = 0; k < steps; ++k )
@@ -336,7 +337,7 @@ class P1ConstantOperator
    //  sweep = every cell runs the vertex / edge / face sweeps on its own copies with the total weights (bit-identical
    //          copies, no further exchange), then the lexicographic macro-cell sweep.
    // Backwards the reference communicates before every class, so `rest` is rebuilt (and exchanged) per class.
-   void smooth_sor( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flagIn,
+   void smooth_sor( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, const Selection& flagIn,
                     bool backwards = false ) const
    {
       if ( &dst == &rhs )
@@ -350,12 +351,12 @@ class P1ConstantOperator
    // [function][cell]; every function sees exactly the kernels, tables and order of smooth_sor: results are bit-identical.
    // Falls back to one smooth_sor per function where the batched path does not apply (large levels, different boundary
    // conditions).
-   void smooth_sor_many( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, DoFType flagIn, bool backwards = false ) const
+   void smooth_sor_many( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, const Selection& flagIn, bool backwards = false ) const
    {
       const uint_t nf = dsts.size();
       if ( nf == 0 || rhss.size() != nf )
          throw std::runtime_error( "smooth_sor_many: need as many right-hand sides as functions" );
-      const DoFType flag     = dsts[0].get().effectiveFlag( flagIn );
+      const Selection flag     = dsts[0].get().effectiveFlag( flagIn );
       bool          together = nf > 1 && storage_->useBatch( level ) && storage_->useBatchSor( level );
       for ( uint_t k = 0; k < nf; ++k )
          together = together && dsts[k].get().effectiveFlag( flagIn ) == flag && &dsts[k].get() != &rhss[k].get();
@@ -370,11 +371,11 @@ class P1ConstantOperator
    // see the edge DoFs as well): the sweeps of the point classes in `bits` on every cell's copies with the total weights, `rest`
    // already summed over the cells; and the lexicographic macro-cell sweeps.
    void smooth_sor_shell_given_rest( const P1Function< double >& dst, const P1Function< double >& rhs, const P1Function< double >& rest,
-                                     double relax, uint_t level, DoFType flagIn, unsigned bits, bool backwards = false ) const
+                                     double relax, uint_t level, const Selection& flagIn, unsigned bits, bool backwards = false ) const
    {
       launchSorShell( { dst }, { rhs }, { rest }, relax, level, dst.effectiveFlag( flagIn ), bits, backwards );
    }
-   void smooth_sor_cells_only( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flagIn,
+   void smooth_sor_cells_only( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, const Selection& flagIn,
                                bool backwards = false ) const
    {
       launchSorCells( { dst }, { rhs }, relax, level, dst.effectiveFlag( flagIn ), backwards );
@@ -385,7 +386,7 @@ class P1ConstantOperator
    // interior of every cell where the flag selects it, every cell's share of A src on the shell points goes to dst and the
    // shares are summed over the cells
    template < typename Interior >
-   void interiorsAndShares( const P1Function< double >& dst, const P1Function< double >& src, uint_t level, DoFType flag, Interior&& interior ) const
+   void interiorsAndShares( const P1Function< double >& dst, const P1Function< double >& src, uint_t level, const Selection& flag, Interior&& interior ) const
    {
       storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
          const auto&    S    = getCellStencils( cell.id, level );
@@ -401,7 +402,7 @@ class P1ConstantOperator
    // the reference's passes on the shell points, after the shares of a stencil sum have been summed into t: t = rhs - t (if rhs),
    // t = invDiag .* t, out = base + c t -- operands in the reference's order
    void shellPasses( const P1Function< double >& t, const P1Function< double >* rhs, const P1Function< double >& invDiag,
-                     const P1Function< double >& base, double c, const P1Function< double >& out, uint_t level, DoFType flag ) const
+                     const P1Function< double >& base, double c, const P1Function< double >& out, uint_t level, const Selection& flag ) const
    {
       storage_->forLocalCells( [&]( uint_t ci, const MacroCell& cell ) {
          const unsigned shell = storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL;
@@ -426,7 +427,7 @@ class P1ConstantOperator
    // ---- smooth_sor for the functions of a list at once: the order of the classes, once.  Each of the three stages below is
    // one launch per chunk of the list [function][cell] ([cell] for one function) where the storage batches the sweeps
    // (useBatchSor), else one launch per function and cell. ----
-   void sorSchedule( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, DoFType flag, bool backwards ) const
+   void sorSchedule( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, const Selection& flag, bool backwards ) const
    {
       ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1Function to P1Function" ), timerSor( storage_->getTimingTree(), backwards ? "SOR backwards" : "SOR" );
       auto sweepCells = [&]() { launchSorCells( dsts, rhss, relax, level, flag, backwards ); };
@@ -476,7 +477,7 @@ class P1ConstantOperator
          p.push_back( fs[(uint_t) ( e / nc )].get().getCellPointer( (uint_t) ( e % nc ), level ) );
       return p;
    }
-   std::vector< unsigned > batchMasks( uint_t nf, DoFType flag, unsigned keep ) const
+   std::vector< unsigned > batchMasks( uint_t nf, const Selection& flag, unsigned keep ) const
    {
       const auto              once = storage_->masksFor( flag, false, keep );
       std::vector< unsigned > m;
@@ -485,7 +486,7 @@ class P1ConstantOperator
       return m;
    }
    // rest = stencil sum over the neighbours outside the closure of the primitives of the classes in `bits`, summed over the cells
-   void launchSorRest( const FunctionList& rests, const FunctionList& dsts, uint_t level, DoFType flag, unsigned bits ) const
+   void launchSorRest( const FunctionList& rests, const FunctionList& dsts, uint_t level, const Selection& flag, unsigned bits ) const
    {
       const uint_t nf = dsts.size();
       if ( storage_->useBatchSor( level ) )
@@ -511,7 +512,7 @@ class P1ConstantOperator
       for ( uint_t k = 0; k < nf; ++k )
          rests[k].get().sumSharedCopies( level, flag );
    }
-   void launchSorCells( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, DoFType flag, bool backwards ) const
+   void launchSorCells( const FunctionList& dsts, const FunctionList& rhss, double relax, uint_t level, const Selection& flag, bool backwards ) const
    {
       const uint_t nf = dsts.size();
       if ( storage_->useBatchSor( level ) )
@@ -535,7 +536,7 @@ class P1ConstantOperator
                          "smooth_sor: cell" );
          } );
    }
-   void launchSorShell( const FunctionList& dsts, const FunctionList& rhss, const FunctionList& rests, double relax, uint_t level, DoFType flag,
+   void launchSorShell( const FunctionList& dsts, const FunctionList& rhss, const FunctionList& rests, double relax, uint_t level, const Selection& flag,
                         unsigned bits, bool backwards ) const
    {
       const uint_t nf = dsts.size();
@@ -565,11 +566,11 @@ class P1ConstantOperator
    }
 
  public:
-   void smooth_gs( const P1Function< double >& dst, const P1Function< double >& rhs, uint_t level, DoFType flag ) const
+   void smooth_gs( const P1Function< double >& dst, const P1Function< double >& rhs, uint_t level, const Selection& flag ) const
    {
       smooth_sor( dst, rhs, 1.0, level, flag, false );
    }
-   void smooth_sor_backwards( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, DoFType flag ) const
+   void smooth_sor_backwards( const P1Function< double >& dst, const P1Function< double >& rhs, double relax, uint_t level, const Selection& flag ) const
    {
       smooth_sor( dst, rhs, relax, level, flag, true );
    }
@@ -640,7 +641,7 @@ class P1ConstantOperator
  private:
    // Operator::apply with one launch for all local cells: every selected point gets (this cell's share of) its stencil sum,
    // then the shares of the shared points are summed.  Add needs the summed shares in a temporary first.
-   void applyBatched( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType ) const
+   void applyBatched( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, const Selection& flag, UpdateType updateType ) const
    {
       const bool sharedAdd = updateType == Add && hasSharedPoints( level, flag );
       auto       run       = [&]( const P1Function< double >& out, unsigned keep, int update ) {
@@ -678,21 +679,31 @@ class P1ConstantOperator
       return storage_->numRanks() == 1 && n >= 1 && n <= HYTEG_HIP_MAX_BATCH &&
              (int64_t) n * layout::cellSize( (int) level ) <= hyteg_hip_p1_cg_small_max_entries();
    }
-   void cgSolveSmall( const P1Function< double >& x, const P1Function< double >& b, uint_t level, DoFType flagIn, uint_t maxIter, double relTol,
+   // the kernel takes the group lists of two exchange classes: with more taking part (three boundary parts that are all
+   // selected) the solve goes through the multi-launch device CG
+   bool cgSmallClassesFit( const P1Function< double >& x, uint_t level, const Selection& flagIn ) const
+   {
+      return sharedClasses( level, x.effectiveFlag( flagIn ) ).size() <= 2;
+   }
+   void cgSolveSmall( const P1Function< double >& x, const P1Function< double >& b, uint_t level, const Selection& flagIn, uint_t maxIter, double relTol,
                       double absTol, double* infoDev ) const
    {
-      const DoFType flag = x.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+      const Selection flag = x.effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       const int  count = (int) storage_->getNumberOfLocalCells();
       const auto masks = storage_->masksFor( flag ), owned = storage_->masksFor( flag, true );
       const auto xs = x.cellPointers( level, 0, count ), bs = b.cellPointers( level, 0, count );
       const int* gp[2] = { nullptr, nullptr }, *ec[2] = { nullptr, nullptr }, *eo[2] = { nullptr, nullptr };
       int        ng[2] = { 0, 0 };
-      for ( int cls = 0; cls < 2; ++cls )
+      // the kernel takes the group lists of two classes: the (at most two, cgSmallClassesFit) that take part, in ascending order
+      const std::vector< int > classes = sharedClasses( level, flag );
+      if ( classes.size() > 2 )
+         throw std::runtime_error( "cgSolveSmall: more than two exchange classes take part (cgSmallClassesFit)" );
+      int slot = 0;
+      for ( int cls : classes )
       {
-         if ( !testFlag( storage_->boundaryTypeOf( cls == 1 ), flag ) || storage_->exchangePlan( (int) level, cls ).ngroups() == 0 )
-            continue;
          const auto& plan = storage_->devicePlan( (int) level, cls );
-         gp[cls] = plan.dGroupPtr, ec[cls] = plan.dEntryBuf, eo[cls] = plan.dEntryOff, ng[cls] = plan.ngroups();
+         gp[slot] = plan.dGroupPtr, ec[slot] = plan.dEntryBuf, eo[slot] = plan.dEntryOff, ng[slot] = plan.ngroups();
+         ++slot;
       }
       hipCheck( hyteg_hip_p1_cg_small_cells( count, xs.data(), bs.data(), (int) level, stencilTable( level ), masks.data(), owned.data(), gp, ec,
                                              eo, ng, (int) maxIter, relTol, absTol, infoDev, storage_->stream() ),
@@ -831,16 +842,22 @@ class P1ConstantOperator
    }
    // one rank, per-cell kernels and no shell point selected on any local cell: an apply (or residual) on these arguments consists
    // of the cells' interior launches and nothing else
-   bool pureInterior( uint_t level, DoFType flag ) const
+   bool pureInterior( uint_t level, const Selection& flag ) const
    {
       return storage_->numRanks() == 1 && !storage_->useBatch( level ) && level >= HYTEG_HIP_MIN_LEVEL && !storage_->anyShellSelected( flag );
    }
-   bool hasSharedPoints( uint_t level, DoFType flag ) const
+   bool hasSharedPoints( uint_t level, const Selection& flag ) const
    {
-      for ( int cls = 0; cls < 2; ++cls )
-         if ( testFlag( storage_->boundaryTypeOf( cls == 1 ), flag ) && storage_->exchangePlan( (int) level, cls ).ngroups() > 0 )
-            return true;
-      return false;
+      return !sharedClasses( level, flag ).empty();
+   }
+   // the exchange classes that take part under the selection and have shared points on this rank
+   std::vector< int > sharedClasses( uint_t level, const Selection& flag ) const
+   {
+      std::vector< int > classes;
+      for ( int cls = 0; cls < storage_->numClasses(); ++cls )
+         if ( storage_->classSelected( cls, flag ) && storage_->exchangePlan( (int) level, cls ).ngroups() > 0 )
+            classes.push_back( cls );
+      return classes;
    }
 
    std::shared_ptr< PrimitiveStorage >                        storage_;

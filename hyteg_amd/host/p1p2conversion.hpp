@@ -11,7 +11,7 @@ namespace hyteg {
 // (hyteg_hip_p1_to_p2_cells: one launch per chunk of cells at every level).  The flag is translated with the SOURCE function's
 // boundary condition, as in the reference (P1toP2Conversion.cpp:36).  No exchange follows: the copies of a shared DoF are moved
 // cell by cell, so copies that were bit-identical stay so.
-inline void P1toP2Conversion( const P1Function< double >& src, const P2Function< double >& dst, const uint_t& P2Level, const DoFType& flag = All )
+inline void P1toP2Conversion( const P1Function< double >& src, const P2Function< double >& dst, const uint_t& P2Level, const Selection& flag = All )
 {
    auto        storage = src.getStorage();
    ScopedTimer timer( storage->getTimingTree(), "P1toP2Conversion" );
@@ -26,7 +26,7 @@ inline void P1toP2Conversion( const P1Function< double >& src, const P2Function<
 
 // The P1 function of level P1Level := the P2 function of level P1Level - 1 (the reference's level convention: this one takes the
 // P1 level, P2toP1Conversion.cpp:28-31)
-inline void P2toP1Conversion( const P2Function< double >& src, const P1Function< double >& dst, const uint_t& P1Level, const DoFType& flag = All )
+inline void P2toP1Conversion( const P2Function< double >& src, const P1Function< double >& dst, const uint_t& P1Level, const Selection& flag = All )
 {
    if ( P1Level == 0 )
       throw std::runtime_error( "P2toP1Conversion: the P1 level must be at least 1" );
@@ -56,7 +56,7 @@ class P1toP1QuadraticProlongationThroughP2Injection
    // The last conversion is `All`, as in the reference: the DoFs of level sourceLevel + 1 that `flag` excludes are overwritten with
    // what the temporary holds there -- zero, since nothing ever writes them.  A caller restores Dirichlet values afterwards (the
    // post-prolongate callback of FullMultigridSolver is the place).
-   void prolongate( const P1Function< double >& function, const uint_t& sourceLevel, const DoFType& flag ) const
+   void prolongate( const P1Function< double >& function, const uint_t& sourceLevel, const Selection& flag ) const
    {
       if ( sourceLevel == 0 )
          throw std::runtime_error( "P1toP1QuadraticProlongationThroughP2Injection: the source level must be at least 1" );

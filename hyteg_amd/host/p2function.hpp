@@ -46,6 +46,21 @@ class P2Function
    P2Function& operator=( const P2Function& ) = delete;
 
    const P1Function< ValueType >&      getVertexDoFFunction() const { return vertexDoFFunction_; }
+   // Function::setBoundaryCondition: one condition for the vertex- and the edge-DoF part
+   // (a new identity with it: a launch graph recorded with this function holds the masks of its former condition)
+   void setBoundaryCondition( const BoundaryCondition& bc ) { vertexDoFFunction_.setBoundaryCondition( bc ), uid_ = nextUid(); }
+   void setBoundaryConditionAllInner( bool on = true ) { vertexDoFFunction_.setBoundaryConditionAllInner( on ), uid_ = nextUid(); }
+   bool hasAllInnerBoundaryCondition() const { return vertexDoFFunction_.hasAllInnerBoundaryCondition(); }
+   const BoundaryCondition& getBoundaryCondition() const { return vertexDoFFunction_.getBoundaryCondition(); }
+   template < typename OtherFunction >
+   void copyBoundaryConditionFromFunction( const OtherFunction& other )
+   {
+      vertexDoFFunction_.copyBoundaryConditionFromFunction( other );
+   }
+   std::shared_ptr< const BoundaryCondition > boundaryConditionOrNull() const { return vertexDoFFunction_.boundaryConditionOrNull(); }
+   // the one selection every mask of this function comes from (see P1Function::effectiveFlag)
+   Selection effectiveFlag( const Selection& s ) const { return vertexDoFFunction_.effectiveFlag( s ); }
+   Selection boundarySelection( const BoundaryUID& uid ) const { return vertexDoFFunction_.boundarySelection( uid ); }
    std::shared_ptr< PrimitiveStorage > getStorage() const { return storage_; }
    // device pointer of the edge-DoF array of local cell c
    double* getEdgeCellPointer( uint_t c, uint_t level ) const
@@ -64,8 +79,18 @@ class P2Function
    }
    uint_t getNumberOfEdgeDoFs( uint_t level ) const { return hyteg_hip_p2_edge_array_size( (int) level ); }
 
-   void interpolate( ValueType constant, uint_t level, DoFType flag = All ) const
+   // Function::interpolate( constant | expr, level, BoundaryUID ): on the primitives whose mesh flag belongs to that boundary
+   void interpolate( ValueType constant, uint_t level, const BoundaryUID& boundary ) const
    {
+      interpolate( constant, level, boundarySelection( boundary ) );
+   }
+   void interpolate( const std::function< ValueType( const Point3D& ) >& expr, uint_t level, const BoundaryUID& boundary ) const
+   {
+      interpolate( expr, level, boundarySelection( boundary ) );
+   }
+   void interpolate( ValueType constant, uint_t level, const Selection& flagIn = All ) const
+   {
+      const Selection flag = effectiveFlag( flagIn ); // under this function's boundary condition
       vertexDoFFunction_.interpolate( constant, level, flag );
       if ( storage_->useBatch( level ) )
       {
@@ -87,8 +112,9 @@ class P2Function
       } );
    }
    // expression evaluated at the micro-vertices and at the edge midpoints (EdgeDoFFunction::interpolate)
-   void interpolate( const std::function< ValueType( const Point3D& ) >& expr, uint_t level, DoFType flag = All ) const
+   void interpolate( const std::function< ValueType( const Point3D& ) >& expr, uint_t level, const Selection& flagIn = All ) const
    {
+      const Selection flag = effectiveFlag( flagIn ); // under this function's boundary condition
       vertexDoFFunction_.interpolate( expr, level, flag );
       static const int ends[7][2][3] = { { { 0, 0, 0 }, { 1, 0, 0 } }, { { 0, 0, 0 }, { 0, 1, 0 } }, { { 0, 0, 0 }, { 0, 0, 1 } },
                                          { { 1, 0, 0 }, { 0, 1, 0 } }, { { 1, 0, 0 }, { 0, 0, 1 } }, { { 0, 1, 0 }, { 0, 0, 1 } },
@@ -139,21 +165,21 @@ class P2Function
    void assign( const std::vector< ValueType >&                                           scalars,
                 const std::vector< std::reference_wrapper< const P2Function< ValueType > > >& functions,
                 uint_t                                                                    level,
-                DoFType                                                                   flag = All ) const
+                const Selection&                                                          flag = All ) const
    {
       vectorOp( 0, scalars, functions, level, flag );
    }
    void add( const std::vector< ValueType >&                                           scalars,
              const std::vector< std::reference_wrapper< const P2Function< ValueType > > >& functions,
              uint_t                                                                    level,
-             DoFType                                                                   flag = All ) const
+             const Selection&                                                          flag = All ) const
    {
       vectorOp( 1, scalars, functions, level, flag );
    }
    // P2Function::multElementwise (P2Function.cpp: vertex- and edge-DoF parts separately)
    void multElementwise( const std::vector< std::reference_wrapper< const P2Function< ValueType > > >& functions,
                          uint_t                                                                    level,
-                         DoFType                                                                   flag = All ) const
+                         const Selection&                                                          flag = All ) const
    {
       vectorOp( 2, std::vector< ValueType >( functions.size(), ValueType( 1 ) ), functions, level, flag );
    }
@@ -162,23 +188,24 @@ class P2Function
    // per-type sweeps of the P2 Gauss-Seidel smoother
    // `keep`: further restriction to point classes (HYTEG_HIP_MASK_INNER: inside the macro-cells, HYTEG_HIP_MASK_SHELL: on shared primitives)
    void assignKinds( const std::vector< ValueType >& scalars, const std::vector< std::reference_wrapper< const P2Function< ValueType > > >& functions,
-                     uint_t level, DoFType flag, unsigned kinds, unsigned keep = HYTEG_HIP_MASK_ALL ) const
+                     uint_t level, const Selection& flag, unsigned kinds, unsigned keep = HYTEG_HIP_MASK_ALL ) const
    {
       vectorOp( 0, scalars, functions, level, flag, kinds, keep );
    }
    void addKinds( const std::vector< ValueType >& scalars, const std::vector< std::reference_wrapper< const P2Function< ValueType > > >& functions,
-                  uint_t level, DoFType flag, unsigned kinds, unsigned keep = HYTEG_HIP_MASK_ALL ) const
+                  uint_t level, const Selection& flag, unsigned kinds, unsigned keep = HYTEG_HIP_MASK_ALL ) const
    {
       vectorOp( 1, scalars, functions, level, flag, kinds, keep );
    }
-   void multElementwiseKinds( const std::vector< std::reference_wrapper< const P2Function< ValueType > > >& functions, uint_t level, DoFType flag,
+   void multElementwiseKinds( const std::vector< std::reference_wrapper< const P2Function< ValueType > > >& functions, uint_t level, const Selection& flag,
                               unsigned kinds, unsigned keep = HYTEG_HIP_MASK_ALL ) const
    {
       vectorOp( 2, std::vector< ValueType >( functions.size(), ValueType( 1 ) ), functions, level, flag, kinds, keep );
    }
    // a shared DoF is counted by its lowest-numbered neighbour cell only
-   ValueType dotLocal( const P2Function< ValueType >& rhs, uint_t level, DoFType flag = All ) const
+   ValueType dotLocal( const P2Function< ValueType >& rhs, uint_t level, const Selection& flagIn = All ) const
    {
+      const Selection flag = effectiveFlag( flagIn ); // under this function's boundary condition
       double       sum = vertexDoFFunction_.dotLocal( rhs.vertexDoFFunction_, level, flag );
       const uint_t nl  = storage_->getNumberOfLocalCells();
       if ( storage_->useBatch( level ) )
@@ -206,8 +233,9 @@ class P2Function
          sum += v;
       return sum;
    }
-   ValueType dotGlobal( const P2Function< ValueType >& rhs, uint_t level, DoFType flag = All ) const
+   ValueType dotGlobal( const P2Function< ValueType >& rhs, uint_t level, const Selection& flagIn = All ) const
    {
+      const Selection flag = effectiveFlag( flagIn ); // under this function's boundary condition
       return storage_->allreduceSum( dotLocal( rhs, level, flag ), "P2Function::dotGlobal" );
    }
 
@@ -216,8 +244,9 @@ class P2Function
    // one pass over the vertex-DoF arrays and one over the edge-DoF arrays (hyteg_hip_p2_edge_reduce_cells); masks as in
    // P1Function::reduceLocal -- the extrema of the reference's EdgeDoFFunction do not flag-test the macro-cells either (:1409)
    using Reduction = typename P1Function< ValueType >::Reduction;
-   Reduction reduceLocal( uint_t level, DoFType flag = All ) const
+   Reduction reduceLocal( uint_t level, const Selection& flagIn = All ) const
    {
+      const Selection flag = effectiveFlag( flagIn ); // under this function's boundary condition
       Reduction   r = vertexDoFFunction_.reduceLocal( level, flag );
       ScopedTimer timerFn( storage_->getTimingTree(), "P2Function" ), timerOp( storage_->getTimingTree(), "Sum (local)" );
       r.merge( P1Function< ValueType >::reduceArrays( *storage_, flag, [&]( int first, int count, const unsigned* masks, double* results ) {
@@ -227,28 +256,28 @@ class P2Function
       } ) );
       return r;
    }
-   ValueType sumLocal( uint_t level, DoFType flag = All, bool absolute = false ) const
+   ValueType sumLocal( uint_t level, const Selection& flag = All, bool absolute = false ) const
    {
       const Reduction r = reduceLocal( level, flag );
       return absolute ? r.sumAbs : r.sum;
    }
-   ValueType sumGlobal( uint_t level, DoFType flag = All, bool absolute = false ) const
+   ValueType sumGlobal( uint_t level, const Selection& flag = All, bool absolute = false ) const
    {
       const double local = sumLocal( level, flag, absolute );
       ScopedTimer  timerFn( storage_->getTimingTree(), "P2Function" ), timerOp( storage_->getTimingTree(), "Sum (reduce)" );
       return storage_->allreduceSum( local, "P2Function::sumGlobal" );
    }
-   ValueType getMaxDoFValue( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   ValueType getMaxDoFValue( uint_t level, const Selection& flag = All, bool mpiReduce = true ) const
    {
       const double local = reduceLocal( level, flag ).max;
       return mpiReduce ? storage_->allreduceMax( local, "P2Function::getMaxDoFValue" ) : local;
    }
-   ValueType getMinDoFValue( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   ValueType getMinDoFValue( uint_t level, const Selection& flag = All, bool mpiReduce = true ) const
    {
       const double local = reduceLocal( level, flag ).min;
       return mpiReduce ? -storage_->allreduceMax( -local, "P2Function::getMinDoFValue" ) : local;
    }
-   ValueType getMaxDoFMagnitude( uint_t level, DoFType flag = All, bool mpiReduce = true ) const
+   ValueType getMaxDoFMagnitude( uint_t level, const Selection& flag = All, bool mpiReduce = true ) const
    {
       const double local = reduceLocal( level, flag ).maxMagnitude;
       return mpiReduce ? storage_->allreduceMax( local, "P2Function::getMaxDoFMagnitude" ) : local;
@@ -258,7 +287,7 @@ class P2Function
    uint64_t numberOfGlobalDoFs( uint_t level ) const { return storage_->numberOfDoFs( level, 0, true ) + storage_->numberOfDoFs( level, 1, true ); }
 
    // every copy of a shared edge DoF := sum of all copies (communicateAdditively< Cell, Face / Edge > of the EdgeDoFFunction)
-   void sumSharedEdgeCopies( uint_t level, DoFType flag = All ) const
+   void sumSharedEdgeCopies( uint_t level, const Selection& flag = All ) const
    {
       std::vector< double* > arrays;
       forCells( [&]( uint_t c, const MacroCell& ) { arrays.push_back( getEdgeCellPointer( c, level ) ); } );
@@ -266,7 +295,7 @@ class P2Function
    }
 
    // every copy := the copy held by the lowest-numbered neighbour cell
-   void syncSharedEdgeCopies( uint_t level, DoFType flag = All ) const
+   void syncSharedEdgeCopies( uint_t level, const Selection& flag = All ) const
    {
       std::vector< double* > arrays;
       forCells( [&]( uint_t c, const MacroCell& ) { arrays.push_back( getEdgeCellPointer( c, level ) ); } );
@@ -294,8 +323,9 @@ class P2Function
    }
    // additive (or copy) exchange of the shared edge DoFs held in `arrays` (one edge-DoF array per local cell), over all
    // ranks: the edge-DoF plans (dofKind 1) of the storage travel through the same transport as the vertex-DoF ones
-   void exchangeEdges( const std::vector< double* >& arrays, uint_t level, DoFType flag, bool additive ) const
+   void exchangeEdges( const std::vector< double* >& arrays, uint_t level, const Selection& flagIn, bool additive ) const
    {
+      const Selection flag = effectiveFlag( flagIn ); // under this function's boundary condition
       storage_->sharedExchangeBegin( arrays, (int) level, flag, 1 );
       storage_->sharedExchangeEnd( arrays, (int) level, flag, 1, additive );
    }
@@ -303,10 +333,11 @@ class P2Function
                   const std::vector< ValueType >&                                           scalars,
                   const std::vector< std::reference_wrapper< const P2Function< ValueType > > >& functions,
                   uint_t                                                                    level,
-                  DoFType                                                                   flag,
+                  const Selection&                                                          flagIn,
                   unsigned                                                                  kinds = 0xFFu,
                   unsigned                                                                  keep  = HYTEG_HIP_MASK_ALL ) const
    {
+      const Selection flag = effectiveFlag( flagIn ); // under this function's boundary condition
       if ( functions.empty() || functions.size() > HYTEG_HIP_MAX_SRCS || scalars.size() != functions.size() )
          throw std::runtime_error( "P2Function::assign/add/multElementwise: bad number of functions or scalars" );
       std::vector< std::reference_wrapper< const P1Function< ValueType > > > vs;

@@ -14,13 +14,14 @@ class P2toP2QuadraticProlongation
 {
  public:
    // fine := quadratic interpolant of the coarse function on the DoFs `flag` selects
-   void prolongate( const P2Function< double >& function, const uint_t& sourceLevel, const DoFType& flag ) const
+   void prolongate( const P2Function< double >& function, const uint_t& sourceLevel, const Selection& flag ) const
    {
-      run( function, function, sourceLevel, flag );
+      run( function, function, sourceLevel, function.effectiveFlag( flag ) );
    }
    // fine += interpolant: formed in a temporary (Replace), made bit-identical on shared DoFs, then added
-   void prolongateAndAdd( const P2Function< double >& function, const uint_t& sourceLevel, const DoFType& flag ) const
+   void prolongateAndAdd( const P2Function< double >& function, const uint_t& sourceLevel, const Selection& flagIn ) const
    {
+      const Selection flag = function.effectiveFlag( flagIn ); // the temporary selects what the function selects
       // the temporary is kept per (storage, level): creating it allocates and clears an array pair per macro-cell, and a multigrid
       // cycle comes through here once per level and function
       auto& slot = tmp_[std::make_pair( function.getStorage().get(), sourceLevel + 1 )];
@@ -32,7 +33,7 @@ class P2toP2QuadraticProlongation
 
  private:
    mutable std::map< std::pair< const PrimitiveStorage*, uint_t >, std::unique_ptr< P2Function< double > > > tmp_;
-   static void run( const P2Function< double >& src, const P2Function< double >& dst, uint_t sourceLevel, DoFType flag )
+   static void run( const P2Function< double >& src, const P2Function< double >& dst, uint_t sourceLevel, const Selection& flag )
    {
       auto        storage = src.getStorage();
       ScopedTimer timer( storage->getTimingTree(), "P2toP2QuadraticProlongation" );
@@ -75,8 +76,9 @@ class P2toP2QuadraticRestriction
 {
  public:
    // coarse := P^T fine on the DoFs `flag` selects (level sourceLevel -> sourceLevel - 1)
-   void restrict( const P2Function< double >& function, const uint_t& sourceLevel, const DoFType& flag ) const
+   void restrict( const P2Function< double >& function, const uint_t& sourceLevel, const Selection& flagIn ) const
    {
+      const Selection flag = function.effectiveFlag( flagIn );
       auto         storage  = function.getStorage();
       ScopedTimer  timer( storage->getTimingTree(), "P2toP2QuadraticRestriction" );
       const uint_t dstLevel = sourceLevel - 1;

@@ -111,7 +111,9 @@ class P2ElementwiseOperator
    : storage_( storage )
    , minLevel_( minLevel )
    , maxLevel_( maxLevel )
-   {}
+   {
+      storage->markInUse(); // the mesh boundary flags are fixed from here on
+   }
    // the operator table whose apply to the function 1 gives the operator's diagonal (computeInverseDiagonalOperatorValues)
    virtual std::vector< double > diagonalTable( uint_t level, uint_t localCell ) const
    {
@@ -131,6 +133,7 @@ class P2ElementwiseOperator
    , minLevel_( minLevel )
    , maxLevel_( maxLevel )
    {
+      storage->markInUse(); // the mesh boundary flags are fixed from here on
       for ( uint_t l = minLevel; l <= maxLevel; ++l )
          for ( uint_t lc = 0; lc < storage->getNumberOfLocalCells(); ++lc )
             addElementMatrixTable( l, lc );
@@ -229,11 +232,12 @@ class P2ElementwiseOperator
 
    // apply restricted to destination kinds (bit 0: vertex DoFs, 1..7: edge DoFs X .. XYZ) and point classes (`keep`); the other
    // entries of dst are not meaningful afterwards (use a temporary)
-   void applyKinds( const P2Function< double >& src, const P2Function< double >& dst, uint_t level, DoFType flag, unsigned kinds,
+   void applyKinds( const P2Function< double >& src, const P2Function< double >& dst, uint_t level, const Selection& flagIn, unsigned kinds,
                     unsigned keep = HYTEG_HIP_MASK_ALL ) const
    {
       if ( &src == &dst )
          throw std::runtime_error( "P2ElementwiseOperator::applyKinds: src and dst must differ" );
+      const Selection flag = dst.effectiveFlag( flagIn ); // the destination's boundary condition decides; temporaries follow it
       launchWith( elementMatrices_.at( level ), 1.0, src, dst, level, flag, keep, HYTEG_HIP_REPLACE, kinds );
       if ( storage_->getCells().size() > 1 && ( keep & HYTEG_HIP_MASK_SHELL ) )
       {
@@ -262,11 +266,12 @@ class P2ElementwiseOperator
    //     shell DoFs of that type, and the copies are then overwritten with the owner's -- each shared DoF is updated exactly
    //     once per sweep.  DoFs of one colour with different owner cells can couple: there the sweep is a Jacobi step between
    //     them.  A Gauss-Seidel ordering of the same splitting, not the reference's iterates on multi-cell meshes.
-   void smooth_sor( const P2Function< double >& dst, const P2Function< double >& rhs, double relax, uint_t level, DoFType flag,
+   void smooth_sor( const P2Function< double >& dst, const P2Function< double >& rhs, double relax, uint_t level, const Selection& flagIn,
                     bool backwards = false ) const
    {
       if ( &dst == &rhs )
          throw std::runtime_error( "P2ElementwiseOperator::smooth_sor: dst and rhs must differ" );
+      const Selection flag = dst.effectiveFlag( flagIn ); // the destination's boundary condition decides; temporaries follow it
       if ( !v2v_ )
       {
          v2v_.reset( new P1ConstantOperator< forms::P2VertexToVertexForm< P2Form > >( storage_, minLevel_, maxLevel_ ) );
@@ -406,7 +411,7 @@ class P2ElementwiseOperator
    //             (p1_sor_shell.hip), edge-edge couplings inside a macro-face by hyteg_hip_p2_sor_face_edgedofs_cell; the edge DoFs
    //             of one macro-edge do not couple.
    template < typename CellEdgeSweep >
-   void smoothSorReferenceOrder( const P2Function< double >& dst, const P2Function< double >& rhs, double relax, uint_t level, DoFType flag,
+   void smoothSorReferenceOrder( const P2Function< double >& dst, const P2Function< double >& rhs, double relax, uint_t level, const Selection& flag,
                                  bool backwards, CellEdgeSweep&& cellEdgeSweep ) const
    {
       const SorTables& T = sorTables( level );
@@ -507,7 +512,7 @@ class P2ElementwiseOperator
    }
 
  public:
-   void smooth_gs( const P2Function< double >& dst, const P2Function< double >& rhs, uint_t level, DoFType flag ) const
+   void smooth_gs( const P2Function< double >& dst, const P2Function< double >& rhs, uint_t level, const Selection& flag ) const
    {
       smooth_sor( dst, rhs, 1.0, level, flag );
    }
@@ -515,7 +520,7 @@ class P2ElementwiseOperator
    // P2ElementwiseOperator::smooth_jac (P2ElementwiseOperator.cpp:344-374), statement by statement:
    //   dst = A src;  dst = rhs - dst;  dst = D^-1 dst;  dst = src + relax dst
    void smooth_jac( const P2Function< double >& dst, const P2Function< double >& rhs, const P2Function< double >& src, double relax,
-                    uint_t level, DoFType flag ) const
+                    uint_t level, const Selection& flag ) const
    {
       if ( &dst == &src )
          throw std::runtime_error( "P2ElementwiseOperator::smooth_jac: src and dst must differ" );
@@ -529,16 +534,17 @@ class P2ElementwiseOperator
    const std::vector< double >&        getElementMatrices( uint_t level, uint_t localCell = 0 ) const { return hostMatrices_.at( level ).at( localCell ); }
 
    // Operator::apply = gemv( 1, src, updateType == Replace ? 0 : 1, dst ), P2ElementwiseOperator.hpp:60-75
-   void apply( const P2Function< double >& src, const P2Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
+   void apply( const P2Function< double >& src, const P2Function< double >& dst, uint_t level, const Selection& flag, UpdateType updateType = Replace ) const
    {
       gemv( 1.0, src, updateType == Replace ? 0.0 : 1.0, dst, level, flag );
    }
    // every cell adds the contributions of its own micro-cells; on DoFs shared by several cells these are partial sums that the
    // additive exchange completes (communicateAdditively< Cell, ... > at the end of the reference's gemv, :225-235)
-   void gemv( double alpha, const P2Function< double >& src, double beta, const P2Function< double >& dst, uint_t level, DoFType flag ) const
+   void gemv( double alpha, const P2Function< double >& src, double beta, const P2Function< double >& dst, uint_t level, const Selection& flagIn ) const
    {
       if ( &src == &dst )
          throw std::runtime_error( "P2ElementwiseOperator::gemv: src and dst must differ" );
+      const Selection flag = dst.effectiveFlag( flagIn ); // the destination's boundary condition decides; temporaries follow it
       const bool shared = storage_->getCells().size() > 1; // also a rank with one cell shares DoFs with cells of other ranks
       if ( !shared )
       {
@@ -563,13 +569,13 @@ class P2ElementwiseOperator
    }
 
  protected:
-   void launch( double alpha, const P2Function< double >& src, const P2Function< double >& dst, uint_t level, DoFType flag, unsigned keep,
+   void launch( double alpha, const P2Function< double >& src, const P2Function< double >& dst, uint_t level, const Selection& flag, unsigned keep,
                 int update ) const
    {
       launchWith( elementMatrices_.at( level ), alpha, src, dst, level, flag, keep, update );
    }
    void launchWith( const std::vector< const double* >& tables, double alpha, const P2Function< double >& src, const P2Function< double >& dst,
-                    uint_t level, DoFType flag, unsigned keep, int update, unsigned kinds = 0xFFu ) const
+                    uint_t level, const Selection& flag, unsigned keep, int update, unsigned kinds = 0xFFu ) const
    {
       std::vector< double* >       dv, de;
       std::vector< const double* > sv, se;

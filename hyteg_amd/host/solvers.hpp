@@ -50,6 +50,7 @@ class WeightedJacobiSmoother : public Solver< OperatorType >
    {}
    void solve( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level ) override
    {
+      tmp_.copyBoundaryConditionFromFunction( x ); // copyBCs
       tmp_.assign( { 1.0 }, { x }, level, All );
       A.smooth_jac( x, b, tmp_, relax_, level, flag_ );
    }
@@ -60,6 +61,7 @@ class WeightedJacobiSmoother : public Solver< OperatorType >
    {
       if ( steps == 0 )
          return;
+      tmp_.copyBoundaryConditionFromFunction( x ); // copyBCs
       tmp_.assign( { 1.0 }, { x }, level, All );
       for ( uint_t i = 0; i < steps; ++i )
       {
@@ -111,6 +113,7 @@ class MixedPrecisionJacobiSmoother : public Solver< OperatorType >
    {
       if ( floatLevel( level ) && fp32Sweeps_ >= 2 )
          floatSweeps( A, x, b, level, fp32Sweeps_ );
+      tmp_.copyBoundaryConditionFromFunction( x ); // copyBCs
       tmp_.assign( { 1.0 }, { x }, level, All );
       A.smooth_jac( x, b, tmp_, relax_, level, flag_ );
    }
@@ -130,7 +133,7 @@ class MixedPrecisionJacobiSmoother : public Solver< OperatorType >
    // x += e_n on the inner points of every local cell, e_n = n float Jacobi sweeps on A e = b - A x from e = 0
    void floatSweeps( const OperatorType& A, const P1Function< double >& x, const P1Function< double >& b, uint_t level, uint_t n )
    {
-      const DoFType flag = x.effectiveFlag( flag_ );
+      const Selection flag = x.effectiveFlag( flag_ );
       for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
       {
          const MacroCell& cell = storage_->getLocalCell( c );
@@ -256,6 +259,8 @@ class CGSolver : public Solver< OperatorType >
    void solve( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level ) override
    {
       iterationsOnDevice_ = false;
+      for ( FunctionType* f : { &p_, &z_, &ap_, &r_ } )
+         f->copyBoundaryConditionFromFunction( x ); // copyBCs
       if ( deviceScalarsUsable( x, level ) )
       {
          solveWithDeviceScalars( A, x, b, level );
@@ -338,7 +343,7 @@ class CGSolver : public Solver< OperatorType >
          scalars_ = static_cast< double* >( d );
       }
       double* const S = scalars_;
-      if ( useSingleLaunch_ && A.canCgSolveSmall( level ) )
+      if ( useSingleLaunch_ && A.canCgSolveSmall( level ) && A.cgSmallClassesFit( x, level, flag_ ) )
       {
          A.cgSolveSmall( x, b, level, flag_, maxIter_, relTol_, absTol_, S );
          iterationsOnDevice_ = true;
@@ -457,6 +462,7 @@ class GeometricMultigridSolver : public Solver< OperatorType >
    {
       ScopedTimer timerGmg( storage_->getTimingTree(), "Geometric Multigrid Solver" );
       invokedLevel_ = level;
+      tmp_.copyBoundaryConditionFromFunction( x ); // copyBCs
       if ( !graphsUsable() )
       {
          solveRecursively( A, x, b, level );

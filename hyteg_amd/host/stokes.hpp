@@ -44,6 +44,20 @@ class VectorFunction
    uint_t                getDimension() const { return 3; }
    const ScalarFunction& operator[]( uint_t k ) const { return *comp_.at( k ); }
 
+   // Function::setBoundaryCondition: one condition for all components, or ( bc, k ) for component k alone
+   void setBoundaryCondition( const BoundaryCondition& bc )
+   {
+      for ( auto& c : comp_ )
+         c->setBoundaryCondition( bc );
+   }
+   void setBoundaryCondition( const BoundaryCondition& bc, uint_t k ) { comp_.at( k )->setBoundaryCondition( bc ); }
+   // component by component (copyBCs)
+   void copyBoundaryConditionFromFunction( const VectorFunction& other )
+   {
+      for ( uint_t k = 0; k < 3; ++k )
+         comp_[k]->copyBoundaryConditionFromFunction( other[k] );
+   }
+
    void interpolate( ValueType constant, uint_t level, DoFType flag = All ) const
    {
       for ( auto& c : comp_ )
@@ -86,7 +100,8 @@ template < typename ValueType >
 using P1VectorFunction = VectorFunction< P1Function< ValueType > >;
 
 // P1StokesFunction (composites/P1StokesFunction.hpp) / P2P1TaylorHoodFunction (composites/P2P1TaylorHoodFunction.hpp):
-// velocity with the storage's boundary types (create0123BC), P1 pressure with createAllInnerBC
+// velocity with the storage's default boundary condition (create0123BC) unless setVelocityBoundaryCondition gives it another,
+// P1 pressure with createAllInnerBC
 template < class VelocityScalarFunction >
 class StokesFunction
 {
@@ -103,6 +118,16 @@ class StokesFunction
    const VectorFunction< VelocityScalarFunction >& uvw() const { return uvw_; }
    const P1Function< ValueType >&                  p() const { return p_; }
    uint64_t                                        uid() const { return p_.uid(); }
+   // the boundary condition of the velocity: all components, or component k alone.  The pressure stays all-inner
+   // (composites/P1StokesFunction.hpp:41-42).  To be set before a multigrid solver records launch graphs with this function: the
+   // composite's identity is that of its pressure
+   void setVelocityBoundaryCondition( const BoundaryCondition& bc ) { uvw_.setBoundaryCondition( bc ); }
+   void setVelocityBoundaryCondition( const BoundaryCondition& bc, uint_t k ) { uvw_.setBoundaryCondition( bc, k ); }
+   void copyBoundaryConditionFromFunction( const StokesFunction& other )
+   {
+      uvw_.copyBoundaryConditionFromFunction( other.uvw() );
+      p_.copyBoundaryConditionFromFunction( other.p() );
+   }
 
    void interpolate( ValueType constant, uint_t level, DoFType flag = All ) const
    {
@@ -361,6 +386,7 @@ class UzawaSmoother : public Solver< OperatorType >
 
    void solve( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level ) override
    {
+      r_.copyBoundaryConditionFromFunction( x ); // copyBCs
       A.divT.apply( x.p(), r_.uvw(), level, flag_, Replace );
       r_.uvw().assign( { 1.0, -1.0 }, { b.uvw(), r_.uvw() }, level, flag_ );
       for ( uint_t i = 0; i < numGSIterationsVelocity_; ++i )
@@ -463,8 +489,15 @@ class DenseCoarseGridSolver : public Solver< OperatorType >
    {
       if ( level != level_ )
          throw std::runtime_error( "DenseCoarseGridSolver: built for another level" );
-      if ( !factorised_ )
+      // the matrix holds identity rows where x's boundary conditions fix a DoF: factorised for them, and again if they change
+      if ( !factorised_ || !sameConditions( x ) )
+      {
+         e_.copyBoundaryConditionFromFunction( x ); // copyBCs
+         Ae_.copyBoundaryConditionFromFunction( x );
+         for ( uint_t c = 0; c < 4; ++c )
+            conditions_[c] = comp( x, c ).boundaryConditionOrNull();
          factorise( A );
+      }
       // right-hand side: b on free DoFs; Dirichlet velocity DoFs keep the value x has there (identity rows)
       std::vector< double > rhs( n_ + 1, 0.0 ), xv = gather( x ), bv = gather( b );
       for ( uint_t i = 0; i < n_; ++i )
@@ -599,6 +632,17 @@ class DenseCoarseGridSolver : public Solver< OperatorType >
                       "dense coarse solver: scatter" );
       hipCheck( hyteg_hip_stream_synchronize( storage_->stream() ), "dense coarse solver: sync" ); // v may go out of scope
    }
+   // x's components carry the conditions the factors were computed for (null: the storage's default condition)
+   bool sameConditions( const FunctionType& x ) const
+   {
+      for ( uint_t c = 0; c < 4; ++c )
+      {
+         const auto bc = comp( x, c ).boundaryConditionOrNull();
+         if ( bc != conditions_[c] && !( bc && conditions_[c] && *bc == *conditions_[c] ) )
+            return false;
+      }
+      return true;
+   }
    void factorise( const OperatorType& A )
    {
       enumeratePoints();
@@ -671,6 +715,7 @@ class DenseCoarseGridSolver : public Solver< OperatorType >
    uint_t                              level_;
    FunctionType                        e_, Ae_;
    bool                                factorised_ = false;
+   std::shared_ptr< const BoundaryCondition > conditions_[4]; // of the velocity components and the pressure at factorisation
    uint_t                              np_ = 0, n_ = 0;
    std::vector< PointRef >             reps_;
    std::vector< std::vector< int > >   pointOf_;

@@ -3,6 +3,7 @@
 // communication hooks (src/hyteg/primitivestorage/, src/hyteg/communication/BufferedCommunication.cpp)
 #pragma once
 
+#include "boundary.hpp"
 #include "comm.hpp"
 #include "lanes.hpp"
 #include "mesh.hpp"
@@ -31,6 +32,7 @@ struct MacroPrimitive
    std::vector< int > v;     // sorted global vertex ids (1, 2 or 3)
    std::vector< int > cells; // adjacent global cell ids, ascending
    bool               onBoundary = false;
+   uint_t             meshBoundaryFlag = 0; // Primitive::getMeshBoundaryFlag(); set by the storage's setMeshBoundaryFlags*
    uint_t             getNumNeighborCells() const { return cells.size(); }
 };
 
@@ -48,6 +50,7 @@ class PrimitiveStorage
          throw std::runtime_error( "PrimitiveStorage: bad rank / number of ranks" );
       std::map< std::vector< int >, int > edgeId, faceId;
       vertices_.resize( mesh.vertices.size() );
+      coords_ = mesh.vertices;
       for ( uint_t i = 0; i < vertices_.size(); ++i )
          vertices_[i].v = { (int) i };
       for ( uint_t c = 0; c < mesh.cells.size(); ++c )
@@ -113,6 +116,7 @@ class PrimitiveStorage
             }
          }
       }
+      setMeshBoundaryFlagsOnBoundary( 1, 0, true );
       for ( auto& c : cells_ )
          if ( c.rank == rank_ )
          {
@@ -177,9 +181,107 @@ class PrimitiveStorage
          fn( c, cells_[localCells_[c]] );
    }
 
-   // boundary type of every primitive on the domain boundary (BoundaryCondition::create0123BC maps flag 1 -> Dirichlet)
-   void    setBoundaryType( DoFType t ) { boundaryType_ = t; }
-   DoFType boundaryTypeOf( bool onBoundary ) const { return onBoundary ? boundaryType_ : Inner; }
+   // ---- mesh boundary flags (SetupPrimitiveStorage.cpp:977-1090) ------------------------------------------------------
+   // Every macro-vertex, -edge and -face carries a flag; a BoundaryCondition maps flags to DoFTypes.  Default: 1 on the domain
+   // boundary, 0 elsewhere.  The macro-cells share one flag (that of the interior) and the location setters leave it alone: a
+   // macro-cell is never on the boundary.  Every rank sets the flags of the whole mesh, as it builds the whole topology.
+   // Masks, exchange plans and device tables are cached by whoever asked for them, so the setters throw once a function, an
+   // operator or a plan exists on the storage (in the reference the flags belong to the set-up storage for the same reason).
+   void setMeshBoundaryFlagsOnBoundary( uint_t flagOnBoundary, uint_t flagInner, bool /* highestDimensionAlwaysInner */ = true )
+   {
+      checkFlagsOpen();
+      forAllPrimitives( [&]( MacroPrimitive& p ) { p.meshBoundaryFlag = p.onBoundary ? flagOnBoundary : flagInner; } );
+      cellMeshBoundaryFlag_ = flagInner; // a cell has no face of its own on the boundary: inner with or without the switch
+   }
+   void setMeshBoundaryFlagsInner( uint_t flagInner, bool /* highestDimensionAlwaysInner */ = true )
+   {
+      checkFlagsOpen();
+      forAllPrimitives( [&]( MacroPrimitive& p ) {
+         if ( !p.onBoundary )
+            p.meshBoundaryFlag = flagInner;
+      } );
+      cellMeshBoundaryFlag_ = flagInner;
+   }
+   // allVertices: every vertex of the primitive satisfies the predicate; otherwise at least one does
+   void setMeshBoundaryFlagsByVertexLocation( uint_t flag, const std::function< bool( const Point3D& ) >& onBoundary, bool allVertices = true )
+   {
+      checkFlagsOpen();
+      forAllPrimitives( [&]( MacroPrimitive& p ) {
+         uint_t hits = 0;
+         for ( int v : p.v )
+            hits += onBoundary( coords_[(size_t) v] ) ? 1 : 0;
+         if ( allVertices ? hits == p.v.size() : hits > 0 )
+            p.meshBoundaryFlag = flag;
+      } );
+   }
+   // the centroid of the primitive's vertices satisfies the predicate (cells are affine: there is no geometry map to apply)
+   void setMeshBoundaryFlagsByCentroidLocation( uint_t flag, const std::function< bool( const Point3D& ) >& onBoundary )
+   {
+      checkFlagsOpen();
+      forAllPrimitives( [&]( MacroPrimitive& p ) {
+         if ( onBoundary( centroid( p ) ) )
+            p.meshBoundaryFlag = flag;
+      } );
+   }
+   // dim 0: macro-vertex, 1: -edge, 2: -face
+   void setMeshBoundaryFlag( int dim, uint_t id, uint_t flag )
+   {
+      checkFlagsOpen();
+      primitivesOf( dim ).at( id ).meshBoundaryFlag = flag;
+   }
+   const MacroPrimitive& primitive( int dim, uint_t id ) const { return primitivesOf( dim ).at( id ); }
+   uint_t                 getMeshBoundaryFlag( int dim, uint_t id ) const { return primitive( dim, id ).meshBoundaryFlag; }
+   bool                   onBoundary( int dim, uint_t id ) const { return primitive( dim, id ).onBoundary; }
+   uint_t                 getCellMeshBoundaryFlag() const { return cellMeshBoundaryFlag_; }
+   const Point3D&         getVertexCoordinates( uint_t id ) const { return coords_.at( id ); }
+   std::vector< Point3D > getCoordinates( int dim, uint_t id ) const
+   {
+      std::vector< Point3D > c;
+      for ( int v : primitive( dim, id ).v )
+         c.push_back( coords_[(size_t) v] );
+      return c;
+   }
+   Point3D centroid( const MacroPrimitive& p ) const
+   {
+      Point3D c{ 0.0, 0.0, 0.0 };
+      for ( int v : p.v )
+         for ( int r = 0; r < 3; ++r )
+            c[r] += coords_[(size_t) v][r];
+      for ( int r = 0; r < 3; ++r )
+         c[r] *= 1.0 / double( p.v.size() );
+      return c;
+   }
+   // called by whatever caches something that depends on the flags: functions, operators, exchange plans
+   void markInUse() const { flagsFrozen_ = true; }
+
+   // ---- the default boundary condition: that of every function that was given none.  create0123BC; setBoundaryType re-types
+   // flag 1, the flag of the domain boundary unless the application has set others
+   void                     setBoundaryType( DoFType t ) { defaultBC_.retype( 1, t ); }
+   const BoundaryCondition& getDefaultBoundaryCondition() const { return defaultBC_; }
+   // does the selection take the points of a primitive with this mesh flag?
+   bool selects( uint_t meshFlag, const Selection& sel ) const { return sel.selects( meshFlag, defaultBC_ ); }
+
+   // ---- exchange classes: the flags 0 and 1 and every other mesh flag of a macro-vertex, -edge or -face, ascending.  The shared points of a
+   // level and DoF kind are split into one plan per class, so that plans depend on flags only and a boundary condition picks
+   // whole plans: class c takes part under a selection iff the selection takes the flag of the class.
+   const std::vector< uint_t >& boundaryClasses() const
+   {
+      if ( classes_.empty() )
+      {
+         std::set< uint_t > flags{ 0, 1 }; // always there, so that the keys 0-3 keep their meaning on every storage
+         forAllPrimitives( [&]( const MacroPrimitive& p ) { flags.insert( p.meshBoundaryFlag ); } );
+         classes_.assign( flags.begin(), flags.end() );
+         markInUse();
+      }
+      return classes_;
+   }
+   int    numClasses() const { return (int) boundaryClasses().size(); }
+   uint_t flagOfClass( int cls ) const { return boundaryClasses().at( (size_t) cls ); }
+   bool   classSelected( int cls, const Selection& sel ) const { return selects( flagOfClass( cls ), sel ); }
+   // key of a (class, DoF kind) pair for transports and registered buffers: cls + 2 * dofKind for the classes 0 and 1, which
+   // is what it was when there were two
+   static int  planKey( int cls, int dofKind ) { return ( cls & 1 ) + 2 * dofKind + 4 * ( cls >> 1 ); }
+   static void splitPlanKey( int key, int& cls, int& dofKind ) { cls = ( key & 1 ) + 2 * ( key >> 2 ), dofKind = ( key >> 1 ) & 1; }
 
    // the macro-primitive behind slot s (0..13) of a cell
    const MacroPrimitive& primitiveOfSlot( const MacroCell& c, int s ) const
@@ -192,17 +294,18 @@ class PrimitiveStorage
    }
 
    // point mask of a cell for a DoFType flag: the per-primitive test of P1Operator.hpp:213-303
-   unsigned maskFor( const MacroCell& c, DoFType flag ) const
+   // under the selection's boundary condition: dst.getBoundaryCondition().getBoundaryType( primitive.getMeshBoundaryFlag() )
+   unsigned maskFor( const MacroCell& c, const Selection& sel ) const
    {
-      unsigned m = testFlag( Inner, flag ) ? HYTEG_HIP_MASK_INNER : 0u; // a macro-cell is never on the mesh boundary
+      unsigned m = selects( cellMeshBoundaryFlag_, sel ) ? HYTEG_HIP_MASK_INNER : 0u;
       for ( int s = 0; s < 14; ++s )
-         if ( testFlag( boundaryTypeOf( primitiveOfSlot( c, s ).onBoundary ), flag ) )
+         if ( selects( primitiveOfSlot( c, s ).meshBoundaryFlag, sel ) )
             m |= 1u << s;
       return m;
    }
    // does `flag` select a macro-face, -edge or -vertex point of any local cell?  If not (every cell's shell is fixed), nothing
    // the flag selects is shared between cells
-   bool anyShellSelected( DoFType flag ) const
+   bool anyShellSelected( const Selection& flag ) const
    {
       for ( int id : localCells_ )
          if ( maskFor( cells_[id], flag ) & HYTEG_HIP_MASK_SHELL )
@@ -210,7 +313,7 @@ class PrimitiveStorage
       return false;
    }
    // like maskFor but a shared primitive is counted by its lowest-numbered neighbour cell only (dot products)
-   unsigned ownedMaskFor( const MacroCell& c, DoFType flag ) const
+   unsigned ownedMaskFor( const MacroCell& c, const Selection& flag ) const
    {
       unsigned m = maskFor( c, flag );
       for ( int s = 0; s < 14; ++s )
@@ -263,7 +366,7 @@ class PrimitiveStorage
       return all && localCells_.size() > 1 && batchMaxLevel_ >= 0 && level <= 10;
    }
    void setBatchMaxLevel( int l ) { batchMaxLevel_ = l; }
-   std::vector< unsigned > masksFor( DoFType flag, bool owned = false, unsigned keep = HYTEG_HIP_MASK_ALL ) const
+   std::vector< unsigned > masksFor( const Selection& flag, bool owned = false, unsigned keep = HYTEG_HIP_MASK_ALL ) const
    {
       std::vector< unsigned > m;
       for ( int id : localCells_ )
@@ -528,7 +631,7 @@ class PrimitiveStorage
    // OFF by default (HYTEG_AMD_SIDE_STREAM=1 enables it; =2 also on one rank, to measure): the two cross-stream event
    // dependencies per apply cost more than the overlap gains -- two level-8 cells on one rank 39.4 -> 49.3 us per apply,
    // two ranks sharing a GPU 39.7 -> 150-170 us (profiles/r02_p2p_probe.txt).
-   bool sideChainUsable( int level, DoFType flag, int dofKind ) const
+   bool sideChainUsable( int level, const Selection& flag, int dofKind ) const
    {
       if ( sideEnabled_ < 0 )
       {
@@ -542,10 +645,10 @@ class PrimitiveStorage
       if ( !sideEnabled_ || mainStream_ )
          return false;
       bool any = false;
-      for ( int cls = 0; cls < 2; ++cls )
-         if ( testFlag( boundaryTypeOf( cls == 1 ), flag ) && !exchangePlan( level, cls, dofKind ).peers.empty() )
+      for ( int cls = 0; cls < numClasses(); ++cls )
+         if ( classSelected( cls, flag ) && !exchangePlan( level, cls, dofKind ).peers.empty() )
          {
-            if ( !transport_->anyStream( level, cls + 2 * dofKind ) )
+            if ( !transport_->anyStream( level, planKey( cls, dofKind ) ) )
                return false;
             any = true;
          }
@@ -717,20 +820,20 @@ class PrimitiveStorage
    // received copies in a fixed order (additive: every copy := sum of all copies, VertexDoFAdditivePackInfo.hpp:676-745;
    // otherwise every copy := the copy of the lowest-numbered neighbour cell).  Kernels that do not touch shared points
    // may be enqueued between Begin and End: they overlap the transfer.
-   void sharedExchangeBegin( const std::vector< double* >& arrays, int level, DoFType flag, int dofKind ) const
+   void sharedExchangeBegin( const std::vector< double* >& arrays, int level, const Selection& flag, int dofKind ) const
    {
       if ( nranks_ == 1 )
          return;
       Transport& T = requireTransport( "exchange" );
-      for ( int cls = 0; cls < 2; ++cls )
+      for ( int cls = 0; cls < numClasses(); ++cls )
       {
-         if ( !testFlag( boundaryTypeOf( cls == 1 ), flag ) )
+         if ( !classSelected( cls, flag ) )
             continue;
          const ExchangePlan& host = exchangePlan( level, cls, dofKind );
          if ( host.peers.empty() && !T.collective() )
             continue;
          const ExchangePlan& plan = devicePlan( level, cls, dofKind );
-         const int key = cls + 2 * dofKind;
+         const int key = planKey( cls, dofKind );
          if ( !plan.peers.empty() )
          {
             double** bases = basesTable( arrays, plan, plan.recvBuffer );
@@ -753,7 +856,7 @@ class PrimitiveStorage
       PackArgs   a;
       const int *first = nullptr, *list = nullptr; // CSR over the shell enumeration of the boundary kernel
    };
-   bool sharedExchangeBeginByShares( int level, DoFType flag, ShareSend& out ) const
+   bool sharedExchangeBeginByShares( int level, const Selection& flag, ShareSend& out ) const
    {
       if ( nranks_ == 1 || !transport_ || localCells_.size() != 1 )
          return false;
@@ -764,8 +867,8 @@ class PrimitiveStorage
       if ( minValues <= 0 )
          return false;
       int active = -1;
-      for ( int cls = 0; cls < 2; ++cls )
-         if ( testFlag( boundaryTypeOf( cls == 1 ), flag ) && !exchangePlan( level, cls, 0 ).peers.empty() )
+      for ( int cls = 0; cls < numClasses(); ++cls )
+         if ( classSelected( cls, flag ) && !exchangePlan( level, cls, 0 ).peers.empty() )
          {
             if ( active >= 0 )
                return false;
@@ -775,27 +878,27 @@ class PrimitiveStorage
          return false;
       const ExchangePlan& plan = devicePlan( level, active, 0 );
       const auto&         tbl  = shareSendTable( level, active, plan );
-      if ( !transport_->packArgs( plan, level, active, out.a, stream() ) )
+      if ( !transport_->packArgs( plan, level, planKey( active, 0 ), out.a, stream() ) )
          return false;
       out.first = tbl.first, out.list = tbl.list;
       // as sharedExchangeBegin: a collective transport is entered for the class without peers as well
-      for ( int cls = 0; cls < 2; ++cls )
+      for ( int cls = 0; cls < numClasses(); ++cls )
       {
-         if ( !testFlag( boundaryTypeOf( cls == 1 ), flag ) )
+         if ( !classSelected( cls, flag ) )
             continue;
          if ( cls == active || transport_->collective() )
-            transport_->exchangeBegin( devicePlan( level, cls, 0 ), level, cls, stream() );
+            transport_->exchangeBegin( devicePlan( level, cls, 0 ), level, planKey( cls, 0 ), stream() );
       }
       return true;
    }
-   void sharedExchangeEnd( const std::vector< double* >& arrays, int level, DoFType flag, int dofKind, bool additive ) const
+   void sharedExchangeEnd( const std::vector< double* >& arrays, int level, const Selection& flag, int dofKind, bool additive ) const
    {
-      for ( int cls = 0; cls < 2; ++cls )
+      for ( int cls = 0; cls < numClasses(); ++cls )
       {
-         if ( !testFlag( boundaryTypeOf( cls == 1 ), flag ) )
+         if ( !classSelected( cls, flag ) )
             continue;
          const ExchangePlan& host = exchangePlan( level, cls, dofKind );
-         const int           key  = cls + 2 * dofKind;
+         const int           key  = planKey( cls, dofKind );
          if ( nranks_ > 1 && ( !host.peers.empty() || requireTransport( "exchange" ).collective() ) )
             transport_->exchangeEnd( devicePlan( level, cls, dofKind ), level, key, stream() );
          if ( host.ngroups() == 0 )
@@ -948,9 +1051,10 @@ class PrimitiveStorage
    }
 
    // ---------------------------------------------------------------------------------------------------
-   // Additive exchange plan of one (level, boundary class): every DoF on a macro-face/edge/vertex with at least
+   // Additive exchange plan of one (level, exchange class): every DoF on a macro-face/edge/vertex with at least
    // two neighbour cells, at least one of them local, is a group; its entries are its copies in ascending global
-   // cell order.  cls 0: primitives in the interior of the domain, cls 1: primitives on the domain boundary.
+   // cell order.  cls: index into boundaryClasses(), the primitives with that mesh boundary flag (default flags: cls 0 = in the
+   // interior of the domain, cls 1 = on the domain boundary).
    // ---------------------------------------------------------------------------------------------------
    using ExchangePlan = hyteg::ExchangePlan;
 
@@ -958,7 +1062,9 @@ class PrimitiveStorage
    // dofKind 0: vertex DoFs (P1 arrays); 1: edge DoFs (the edge-DoF arrays of P2 functions)
    const ExchangePlan& exchangePlan( int level, int cls, int dofKind = 0 ) const
    {
-      auto key = std::make_pair( level, cls + 2 * dofKind );
+      if ( cls < 0 || cls >= numClasses() || dofKind < 0 || dofKind > 1 )
+         throw std::runtime_error( "exchangePlan: no such boundary class or DoF kind" );
+      auto key = std::make_pair( level, planKey( cls, dofKind ) );
       auto it  = plans_.find( key );
       if ( it == plans_.end() )
          it = plans_.emplace( key, buildPlan( level, cls, dofKind ) ).first;
@@ -991,7 +1097,9 @@ class PrimitiveStorage
    // multi-rank: the application owns the communication buffers (e.g. torch tensors) and registers them here
    void registerCommBuffers( int level, int key, double* send, double* recv ) const
    {
-      auto& p = const_cast< ExchangePlan& >( exchangePlan( level, key & 1, key >> 1 ) ); // key = cls + 2 * dofKind
+      int cls, dofKind;
+      splitPlanKey( key, cls, dofKind );
+      auto& p = const_cast< ExchangePlan& >( exchangePlan( level, cls, dofKind ) );
       if ( p.ownsBuffers )
       {
          hyteg_hip_free( p.sendBuffer );
@@ -1076,11 +1184,12 @@ class PrimitiveStorage
       ExchangePlan  P;
       const int64_t N = layout::width( level ), n = N - 1;
       const int     nLocal = (int) localCells_.size();
+      const uint_t  classFlag = flagOfClass( cls );
       // peers: ranks of remote cells sharing a primitive of this class with a local cell
       std::set< int > peerSet;
       auto            involves = [&]( const MacroPrimitive& p, bool& local ) {
          local = false;
-         if ( p.cells.size() < 2 || ( p.onBoundary ? 1 : 0 ) != cls )
+         if ( p.cells.size() < 2 || p.meshBoundaryFlag != classFlag )
             return false;
          for ( int c : p.cells )
             local = local || cells_[c].rank == rank_;
@@ -1094,6 +1203,7 @@ class PrimitiveStorage
          for ( const auto& p : vertices_ )
             fn( p );
       };
+      markInUse();
       forAllPrimitives( [&]( const MacroPrimitive& p ) {
          bool local;
          if ( involves( p, local ) && local )
@@ -1223,7 +1333,53 @@ class PrimitiveStorage
    std::vector< MacroCell >                                cells_;
    std::vector< MacroPrimitive >                           faces_, edges_, vertices_;
    std::vector< int >                                      localCells_;
-   DoFType                                                 boundaryType_ = DirichletBoundary;
+   std::vector< Point3D >                                  coords_; // of the macro-vertices
+   BoundaryCondition                                       defaultBC_ = BoundaryCondition::create0123BC();
+   uint_t                                                  cellMeshBoundaryFlag_ = 0;
+   mutable bool                                            flagsFrozen_ = false;
+   mutable std::vector< uint_t >                           classes_; // empty: not asked for yet
+   template < typename F >
+   void forAllPrimitives( F&& fn )
+   {
+      for ( auto& p : faces_ )
+         fn( p );
+      for ( auto& p : edges_ )
+         fn( p );
+      for ( auto& p : vertices_ )
+         fn( p );
+   }
+   template < typename F >
+   void forAllPrimitives( F&& fn ) const
+   {
+      for ( const auto& p : faces_ )
+         fn( p );
+      for ( const auto& p : edges_ )
+         fn( p );
+      for ( const auto& p : vertices_ )
+         fn( p );
+   }
+   // the macro-vertices (dim 0), -edges (1) or -faces (2)
+   static void checkDimension( int dim )
+   {
+      if ( dim < 0 || dim > 2 )
+         throw std::runtime_error( "PrimitiveStorage: primitive dimension 0 (vertex), 1 (edge) or 2 (face)" );
+   }
+   std::vector< MacroPrimitive >& primitivesOf( int dim )
+   {
+      checkDimension( dim );
+      return dim == 0 ? vertices_ : ( dim == 1 ? edges_ : faces_ );
+   }
+   const std::vector< MacroPrimitive >& primitivesOf( int dim ) const
+   {
+      checkDimension( dim );
+      return dim == 0 ? vertices_ : ( dim == 1 ? edges_ : faces_ );
+   }
+   void checkFlagsOpen() const
+   {
+      if ( flagsFrozen_ )
+         throw std::runtime_error( "PrimitiveStorage: mesh boundary flags are fixed once a function, an operator or an exchange "
+                                   "plan exists on the storage" );
+   }
    // NOTE: inside an open LaneScope launches may be pending on the lanes.  Whoever launches on, waits for or replaces stream_
    // goes through stream() / joinLanes() first (they record the lanes' events and reset the planner, which is why the lane
    // state is mutable); a raw use of stream_ is only right where the lanes are known to be joined or are being joined.

@@ -100,10 +100,9 @@ class P2ToP1Operator : public P2ElementwiseOperator< Form >
    , tmp_( "p2_to_p1_tmp", storage, minLevel, maxLevel )
    , tmpP1_( "p2_to_p1_tmp_p1", storage, minLevel, maxLevel )
    {}
-   void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flagIn, UpdateType updateType = Replace ) const
+   void apply( const srcType& src, const dstType& dst, uint_t level, const Selection& flagIn, UpdateType updateType = Replace ) const
    {
-      const DoFType flag = dst.effectiveFlag( flagIn );
-      tmpP1_.setBoundaryConditionAllInner( dst.hasAllInnerBoundaryCondition() );
+      const Selection flag = dst.effectiveFlag( flagIn ); // the destination's boundary condition decides; the temporary follows it
       std::vector< double* >       dv, de;
       std::vector< const double* > sv, se;
       for ( uint_t c = 0; c < this->storage_->getNumberOfLocalCells(); ++c )
@@ -113,11 +112,11 @@ class P2ToP1Operator : public P2ElementwiseOperator< Form >
       }
       this->launchPointers( this->elementMatrices_.at( level ), 1.0, sv, se, dv, de, level, this->storage_->masksFor( flag ), HYTEG_HIP_REPLACE, 1u );
       if ( this->storage_->getCells().size() > 1 )
-         tmpP1_.sumSharedCopies( level, flagIn );
+         tmpP1_.sumSharedCopies( level, flag );
       if ( updateType == Replace )
-         dst.assign( { 1.0 }, { tmpP1_ }, level, flagIn );
+         dst.assign( { 1.0 }, { tmpP1_ }, level, flag );
       else
-         dst.add( { 1.0 }, { tmpP1_ }, level, flagIn );
+         dst.add( { 1.0 }, { tmpP1_ }, level, flag );
    }
 
  private:
@@ -139,8 +138,9 @@ class P1ToP2Operator : public P2ElementwiseOperator< Form >
    , tmp_( "p1_to_p2_tmp", storage, minLevel, maxLevel )
    , zero_( "p1_to_p2_zero", storage, minLevel, maxLevel )
    {}
-   void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
+   void apply( const srcType& src, const dstType& dst, uint_t level, const Selection& flagIn, UpdateType updateType = Replace ) const
    {
+      const Selection flag = dst.effectiveFlag( flagIn ); // the destination's boundary condition decides; the temporary follows it
       std::vector< double* >       dv, de;
       std::vector< const double* > sv, se;
       for ( uint_t c = 0; c < this->storage_->getNumberOfLocalCells(); ++c )
@@ -188,12 +188,12 @@ using P2P1StokesToP2P1StokesRestriction  = StokesRestriction< P2toP2QuadraticRes
 using P2P1StokesToP2P1StokesProlongation = StokesProlongation< P2toP2QuadraticProlongation >;
 
 // P1toP2Conversion / P2toP1Conversion of vector functions (P1toP2Conversion.cpp:141-149, P2toP1Conversion.cpp:142-150): component by component
-inline void P1toP2Conversion( const P1VectorFunction< double >& src, const P2VectorFunction< double >& dst, const uint_t& P2Level, const DoFType& flag = All )
+inline void P1toP2Conversion( const P1VectorFunction< double >& src, const P2VectorFunction< double >& dst, const uint_t& P2Level, const Selection& flag = All )
 {
    for ( uint_t k = 0; k < src.getDimension(); ++k )
       P1toP2Conversion( src[k], dst[k], P2Level, flag );
 }
-inline void P2toP1Conversion( const P2VectorFunction< double >& src, const P1VectorFunction< double >& dst, const uint_t& P1Level, const DoFType& flag = All )
+inline void P2toP1Conversion( const P2VectorFunction< double >& src, const P1VectorFunction< double >& dst, const uint_t& P1Level, const Selection& flag = All )
 {
    for ( uint_t k = 0; k < src.getDimension(); ++k )
       P2toP1Conversion( src[k], dst[k], P1Level, flag );

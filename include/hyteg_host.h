@@ -32,6 +32,7 @@ typedef void* hh_elementwise_t;
 typedef void* hh_stokes_function_t;
 typedef void* hh_stokes_operator_t;
 typedef void* hh_stokes_solver_t;
+typedef void* hh_boundary_condition_t;
 
 HYTEG_HOST_API const char* hyteg_host_last_error( void );
 
@@ -43,7 +44,53 @@ HYTEG_HOST_API int hyteg_host_storage_destroy( hh_storage_t s );
 HYTEG_HOST_API int hyteg_host_storage_counts( hh_storage_t s, int* counts );
 HYTEG_HOST_API int hyteg_host_storage_local_cell( hh_storage_t s, int local_index, int* global_id, double* coords12, double* nnc14 );
 HYTEG_HOST_API int hyteg_host_storage_mask( hh_storage_t s, int local_index, int flag, int owned, unsigned* mask );
+/* PrimitiveStorage::setBoundaryType: re-types mesh flag 1 of the storage's default boundary condition (create0123BC) */
 HYTEG_HOST_API int hyteg_host_storage_set_boundary_type( hh_storage_t s, int dof_type );
+/* the mask under a boundary condition of its own (bc == NULL: the storage's default one):
+ * bc.getBoundaryType( primitive.getMeshBoundaryFlag() ) tested against `flag`, P1Operator.hpp:301-303 */
+HYTEG_HOST_API int hyteg_host_storage_mask_bc( hh_storage_t s, int local_index, int flag, int owned, hh_boundary_condition_t bc, unsigned* mask );
+/* ---- mesh boundary flags of the macro-vertices, -edges and -faces (SetupPrimitiveStorage.cpp:977-1090).  Default: 1 on the domain
+ * boundary, 0 elsewhere.  Every rank sets the flags of the whole mesh.  The setters fail once a function, an operator or an
+ * exchange plan exists on the storage.  The macro-cells share the flag of the interior and the location setters leave it alone. */
+/* SetupPrimitiveStorage::setMeshBoundaryFlagsOnBoundary */
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flags_on_boundary( hh_storage_t s, unsigned long long flag_on_boundary,
+                                                                           unsigned long long flag_inner, int highest_dimension_always_inner );
+/* SetupPrimitiveStorage::setMeshBoundaryFlagsInner */
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flags_inner( hh_storage_t s, unsigned long long flag_inner, int highest_dimension_always_inner );
+/* SetupPrimitiveStorage::setMeshBoundaryFlagsByVertexLocation; on_boundary( user, xyz ) != 0: the point is on that boundary */
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flags_by_vertex_location( hh_storage_t s, unsigned long long flag,
+                                                                                  int ( *on_boundary )( void*, const double* ), void* user,
+                                                                                  int all_vertices );
+/* SetupPrimitiveStorage::setMeshBoundaryFlagsByCentroidLocation (without a geometry map: cells are affine) */
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flags_by_centroid_location( hh_storage_t s, unsigned long long flag,
+                                                                                    int ( *on_boundary )( void*, const double* ), void* user );
+/* SetupPrimitiveStorage::setMeshBoundaryFlag; dim 0: macro-vertex, 1: -edge, 2: -face, index as counted by storage_counts */
+HYTEG_HOST_API int hyteg_host_storage_set_mesh_boundary_flag( hh_storage_t s, int dim, int index, unsigned long long flag );
+/* Primitive::getMeshBoundaryFlag / getCoordinates, SetupPrimitiveStorage::onBoundary: the primitive's (sorted) global vertex ids,
+ * their coordinates, its flag and whether it lies on the domain boundary */
+HYTEG_HOST_API int hyteg_host_storage_primitive( hh_storage_t s, int dim, int index, int* nvertices, int* vertex_ids3, double* coords9,
+                                                 unsigned long long* flag, int* on_boundary );
+/* the exchange classes: the mesh flags 0 and 1 and every other flag present, ascending; class c has the plans of key
+ * ( c & 1 ) + 2 * dof_kind + 4 * ( c >> 1 ).  flags may be NULL (count only).  No counterpart in the reference, whose
+ * communication is per primitive. */
+HYTEG_HOST_API int hyteg_host_storage_boundary_classes( hh_storage_t s, int* count, unsigned long long* flags );
+/* a copy of the condition of functions that were given none (create0123BC, flag 1 re-typed by set_boundary_type) */
+HYTEG_HOST_API int hyteg_host_storage_default_boundary_condition( hh_storage_t s, hh_boundary_condition_t* out );
+
+/* ---- BoundaryCondition (src/hyteg/boundary/BoundaryConditions.hpp), a value: functions copy it ---- */
+/* preset 0: BoundaryCondition() (every flag Inner), 1: BoundaryCondition::create0123BC, 2: BoundaryCondition::createAllInnerBC */
+HYTEG_HOST_API int hyteg_host_boundary_condition_create( int preset, hh_boundary_condition_t* out );
+HYTEG_HOST_API int hyteg_host_boundary_condition_destroy( hh_boundary_condition_t bc );
+/* BoundaryCondition::createDomainBC (dof_type Inner: createInnerBC, Dirichlet: createDirichletBC, Neumann: createNeumannBC,
+ * Freeslip: createFreeslipBC); *uid = id of the new BoundaryUID */
+HYTEG_HOST_API int hyteg_host_boundary_condition_create_domain( hh_boundary_condition_t bc, const char* name, int dof_type, int nflags,
+                                                                const unsigned long long* flags, int* uid );
+/* BoundaryCondition::getBoundaryType */
+HYTEG_HOST_API int hyteg_host_boundary_condition_type( hh_boundary_condition_t bc, unsigned long long flag, int* dof_type );
+/* BoundaryCondition::getBoundaryUIDFromMeshFlag; uid 0 = the boundary of the flags that were given none */
+HYTEG_HOST_API int hyteg_host_boundary_condition_uid( hh_boundary_condition_t bc, unsigned long long flag, int* uid, char* name, int buflen );
+/* BoundaryCondition::operator== */
+HYTEG_HOST_API int hyteg_host_boundary_condition_equal( hh_boundary_condition_t a, hh_boundary_condition_t b, int* equal );
 HYTEG_HOST_API int hyteg_host_storage_set_stream( hh_storage_t s, void* stream );
 /* levels <= `level` use the batched kernels (one launch for all local cells, inner and boundary points together) when the
  * rank owns more than one cell; -1 disables batching.  Default 6, or the environment variable HYTEG_AMD_BATCH_MAX_LEVEL. */
@@ -134,7 +181,7 @@ HYTEG_HOST_API int hyteg_host_storage_p2_number_of_dofs( hh_storage_t s, int lev
 HYTEG_HOST_API int hyteg_host_storage_set_hooks( hh_storage_t s, int ( *exchange_begin )( void*, int, int ),
                                                  int ( *exchange_end )( void*, int, int ),
                                                  int ( *allreduce_sum )( void*, double*, int ), void* user );
-/* exchange plan of (level, key = cls + 2 * dof_kind; dof_kind 0: vertex DoFs, 1: edge DoFs of P2 functions) -- host
+/* exchange plan of (level, key = ( cls & 1 ) + 2 * dof_kind + 4 * ( cls >> 1 ), cls an index into storage_boundary_classes; dof_kind 0: vertex DoFs, 1: edge DoFs of P2 functions) -- host
  * data, works without a GPU.  sizes[0..4] = ngroups, nentries, npeers, total_send, total_recv */
 HYTEG_HOST_API int hyteg_host_plan_sizes( hh_storage_t s, int level, int key, int* sizes );
 HYTEG_HOST_API int hyteg_host_plan_export( hh_storage_t s, int level, int key, int* group_ptr, int* entry_buf, int* entry_off,
@@ -160,6 +207,13 @@ HYTEG_HOST_API int hyteg_host_function_sum_shared( hh_function_t f, int level, i
 HYTEG_HOST_API int hyteg_host_function_sync_shared( hh_function_t f, int level, int flag );
 /* BoundaryCondition::createAllInnerBC() for this function (the pressure of a Stokes function): every point counts as Inner */
 HYTEG_HOST_API int hyteg_host_function_set_all_inner( hh_function_t f, int on );
+/* Function::setBoundaryCondition / getBoundaryCondition (the latter a copy, to be destroyed by the caller) */
+HYTEG_HOST_API int hyteg_host_function_set_boundary_condition( hh_function_t f, hh_boundary_condition_t bc );
+HYTEG_HOST_API int hyteg_host_function_boundary_condition( hh_function_t f, hh_boundary_condition_t* out );
+/* Function::interpolate( constant, level, BoundaryUID ): on the primitives whose mesh flag belongs to that boundary of the
+ * function's condition.  Id and name as hyteg_host_boundary_condition_create_domain / _uid gave them: a uid of another condition fails */
+HYTEG_HOST_API int hyteg_host_function_interpolate_constant_on_boundary( hh_function_t f, double value, int level, int boundary_uid,
+                                                                         const char* boundary_name );
 
 /* ---- P1ConstantOperator< Form > (src/constant_stencil_operator/P1ConstantOperator.hpp:165-210)
  * form 0: Laplace, 1: mass, 2-4: P1Div{x,y,z}Operator, 5-7: P1DivT{x,y,z}Operator, 8: P1PSPGOperator ---- */
@@ -271,6 +325,14 @@ HYTEG_HOST_API int hyteg_host_cg_set_use_device_scalars( hh_solver_t solver, int
 HYTEG_HOST_API int hyteg_host_cg_iterations( hh_solver_t solver, int* iterations );
 HYTEG_HOST_API int hyteg_host_cg_create( hh_storage_t s, int min_level, int max_level, int max_iter, double tol, hh_solver_t* out );
 HYTEG_HOST_API int hyteg_host_solver_solve( hh_solver_t solver, hh_operator_t laplace, hh_function_t x, hh_function_t b, int level );
+/* Solver::solveSteps (Solver.hpp): `steps` calls of solve, which a smoother may fuse -- what GeometricMultigridSolver calls for its
+ * pre- and post-smoothing */
+HYTEG_HOST_API int hyteg_host_solver_solve_steps( hh_solver_t solver, hh_operator_t laplace, hh_function_t x, hh_function_t b, int level, int steps );
+/* MixedPrecisionJacobiSmoother( storage, minLevel, maxLevel, relax, fp32Sweeps ) on its own (hyteg_amd/host/solvers.hpp; no class of
+ * the reference: its pieces are the float instantiation of the generated kernels and VertexDoFFunction::copyFrom); inside a
+ * multigrid solver it is smoother 3 of hyteg_host_gmg_create */
+HYTEG_HOST_API int hyteg_host_mixed_precision_jacobi_create( hh_storage_t s, int min_level, int max_level, double relax, int fp32_sweeps,
+                                                             hh_solver_t* out );
 HYTEG_HOST_API int hyteg_host_solver_destroy( hh_solver_t solver );
 
 /* ---- P1-P1 Stokes: P1StokesFunction (composites/P1StokesFunction.hpp: velocity with the storage's boundary types, pressure
@@ -318,6 +380,11 @@ HYTEG_HOST_API int hyteg_host_p2function_pointers( hh_p2function_t f, int local_
 HYTEG_HOST_API int hyteg_host_p2function_upload( hh_p2function_t f, int local_cell, int level, const double* vertex_host, const double* edge_host );
 HYTEG_HOST_API int hyteg_host_p2function_download( hh_p2function_t f, int local_cell, int level, double* vertex_host, double* edge_host );
 HYTEG_HOST_API int hyteg_host_p2function_interpolate_constant( hh_p2function_t f, double value, int level, int flag );
+/* P2Function::setBoundaryCondition (vertex- and edge-DoF part) / getBoundaryCondition / interpolate( constant, level, BoundaryUID ) */
+HYTEG_HOST_API int hyteg_host_p2function_set_boundary_condition( hh_p2function_t f, hh_boundary_condition_t bc );
+HYTEG_HOST_API int hyteg_host_p2function_boundary_condition( hh_p2function_t f, hh_boundary_condition_t* out );
+HYTEG_HOST_API int hyteg_host_p2function_interpolate_constant_on_boundary( hh_p2function_t f, double value, int level, int boundary_uid,
+                                                                           const char* boundary_name );
 HYTEG_HOST_API int hyteg_host_p2function_assign( hh_p2function_t dst, int n, const double* scalars, const hh_p2function_t* srcs, int level, int flag );
 HYTEG_HOST_API int hyteg_host_p2function_add( hh_p2function_t dst, int n, const double* scalars, const hh_p2function_t* srcs, int level, int flag );
 /* P2Function::multElementwise (src/hyteg/p2functionspace/P2Function.cpp: vertex- and edge-DoF parts separately) */
