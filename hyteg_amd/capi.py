@@ -106,6 +106,8 @@ SIGNATURES = {
     "hyteg_hip_p1_copy_cell_to_face": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "hyteg_hip_p1_vector_cells": (_i, [_i, _i, C.POINTER(_vp), _i, C.POINTER(_vp), _dp, _i, C.POINTER(C.c_uint), _vp]),
     "hyteg_hip_p1_dot_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp, _vp, _vp]),
+    "hyteg_hip_p1_cg_update_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _d, _i, C.POINTER(C.c_uint),
+                                          C.POINTER(C.c_uint), _vp, _vp, _vp]),
     "hyteg_hip_reduce_workspace_bytes": (_sz, []),
     "hyteg_hip_p1_reduce_cells": (_i, [_i, C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp, _vp, _vp]),
     "hyteg_hip_p2_edge_reduce_cells": (_i, [_i, C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp, _vp, _vp]),
@@ -508,6 +510,14 @@ def p1_vector_cells(op, dst, srcs, scalars, level, masks, stream=0):
 
 def p1_dot_cells(a, b, level, masks, result_dev, workspace_dev, stream=0):
     check(lib().hyteg_hip_p1_dot_cells(len(a), _ptrs(a), _ptrs(b), level, _masks(masks), result_dev, workspace_dev, stream), "p1_dot_cells")
+
+
+def p1_cg_update_cells(x, r, p, ap, alpha, level, update_masks, dot_masks, result_dev, workspace_dev, stream=0):
+    """x += alpha p, r -= alpha ap on the points of update_masks, then result = sum of r * r over the points of dot_masks, in one pass;
+    x, r, p, ap: lists of device pointers, one per cell"""
+    check(lib().hyteg_hip_p1_cg_update_cells(len(x) if x is not None else 1, *[_ptrs(a) if a is not None else None for a in (x, r, p, ap)],
+                                             float(alpha), level, *[_masks(m) if m is not None else None for m in (update_masks, dot_masks)],
+                                             result_dev, workspace_dev, stream), "p1_cg_update_cells")
 
 
 # statistics of the reduction, in the order of a cell's results (HYTEG_HIP_REDUCE_*)

@@ -15,6 +15,8 @@ _LIB_PATH = _PKG / "lib" / "libhyteg_host.so"
 Inner, DirichletBoundary, NeumannBoundary, FreeslipBoundary, All, Boundary = 1, 2, 4, 8, 15, 14
 Replace, Add = 0, 1
 JACOBI, GAUSS_SEIDEL, SOR, JACOBI_FP32 = 0, 1, 2, 3  # JACOBI_FP32: MixedPrecisionJacobiSmoother (float sweeps on cell interiors)
+SYMMETRIC_GAUSS_SEIDEL, SYMMETRIC_SOR = 5, 6  # a forward sweep followed by a backward one (SymmetricSORSmoother.hpp)
+IDENTITY = -1  # IdentityPreconditioner, for Solver.smoother / P2Solver.smoother only
 CHEBYSHEV = 4  # ChebyshevSmoother: not a code of hyteg_host_gmg_create (it has its own entry points: Solver.chebyshev / gmg_chebyshev)
 
 _vp, _i, _d, _u = C.c_void_p, C.c_int, C.c_double, C.c_uint
@@ -170,6 +172,12 @@ SIGNATURES = {
     "hyteg_host_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
     "hyteg_host_gmg_replayed_cycles": (_i, [_vp, C.POINTER(_i)]),
     "hyteg_host_cg_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_cg_create_preconditioned": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
+    "hyteg_host_cg_set_use_fused_update": (_i, [_vp, _i]),
+    "hyteg_host_smoother_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2_cg_create_preconditioned": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
+    "hyteg_host_p2_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_p2_smoother_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_solver_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
     "hyteg_host_solver_solve_steps": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
     "hyteg_host_mixed_precision_jacobi_create": (_i, [_vp, _i, _i, _d, _i, C.POINTER(_vp)]),
@@ -1003,10 +1011,30 @@ class Solver:
         _ck(lib().hyteg_host_chebyshev_set_fused(self.h, int(bool(on))), "chebyshev_set_fused")
 
     @classmethod
-    def cg(cls, storage, min_level, max_level, max_iter=1000, tol=1e-14):
+    def cg(cls, storage, min_level, max_level, max_iter=1000, tol=1e-14, preconditioner=None):
+        """hyteg::CGSolver< P1ConstantLaplaceOperator >; preconditioner: any Solver (a multigrid solver, Solver.smoother, a Chebyshev
+        smoother), None: the loop without one"""
         h = _vp()
-        _ck(lib().hyteg_host_cg_create(storage.h, min_level, max_level, max_iter, float(tol), C.byref(h)), "cg_create")
+        if preconditioner is None:
+            _ck(lib().hyteg_host_cg_create(storage.h, min_level, max_level, max_iter, float(tol), C.byref(h)), "cg_create")
+            return cls(h)
+        _ck(lib().hyteg_host_cg_create_preconditioned(storage.h, min_level, max_level, max_iter, float(tol), preconditioner.h, C.byref(h)),
+            "cg_create_preconditioned")
+        self = cls(h)
+        self._preconditioner = preconditioner  # stays usable as long as this solver is
+        return self
+
+    @classmethod
+    def smoother(cls, storage, min_level, max_level, smoother, relax=1.0):
+        """a smoother on its own (JACOBI, GAUSS_SEIDEL, SOR, JACOBI_FP32, SYMMETRIC_GAUSS_SEIDEL, SYMMETRIC_SOR) or IDENTITY, the
+        IdentityPreconditioner: solve = one smoother call; also what Solver.cg takes as preconditioner"""
+        h = _vp()
+        _ck(lib().hyteg_host_smoother_create(storage.h, min_level, max_level, int(smoother), float(relax), C.byref(h)), "smoother_create")
         return cls(h)
+
+    def set_use_fused_update(self, on: bool) -> None:
+        """CGSolver::setUseFusedUpdate of a preconditioned CG solver: x, r and <r,r> in one pass (default) or the three composed calls"""
+        _ck(lib().hyteg_host_cg_set_use_fused_update(self.h, int(bool(on))), "cg_set_use_fused_update")
 
     @classmethod
     def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, jacobi_iterations=0):
@@ -1309,7 +1337,7 @@ class P2Solver:
                  smoother=JACOBI):
         self.storage = storage
         h = _vp()
-        kind = {JACOBI: 0, GAUSS_SEIDEL: 1, SOR: 2}[smoother]
+        kind = {JACOBI: 0, GAUSS_SEIDEL: 1, SOR: 2, SYMMETRIC_GAUSS_SEIDEL: 5, SYMMETRIC_SOR: 6}[smoother]
         _ck(lib().hyteg_host_p2_gmg_create(storage.h, min_level, max_level, kind, float(relax), pre, post, int(bool(wcycle)), cg_max_iter,
                                            float(cg_tol), C.byref(h)), "P2 gmg")
         self.h = h
@@ -1334,6 +1362,31 @@ class P2Solver:
         _ck(lib().hyteg_host_p2_gmg_create_chebyshev(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), pre, post,
                                                      int(bool(wcycle)), cg_max_iter, float(cg_tol), C.byref(self.h)), "P2 gmg chebyshev")
         return self
+
+    @classmethod
+    def cg(cls, storage, min_level, max_level, max_iter=1000, tol=1e-14, preconditioner=None):
+        """hyteg::CGSolver< P2ElementwiseLaplaceOperator >; preconditioner: a P2Solver, None: IdentityPreconditioner"""
+        self = cls.__new__(cls)
+        self.storage, self.h = storage, _vp()
+        self._preconditioner = preconditioner if preconditioner is not None else cls.smoother(storage, min_level, max_level, IDENTITY)
+        _ck(lib().hyteg_host_p2_cg_create_preconditioned(storage.h, min_level, max_level, max_iter, float(tol), self._preconditioner.h,
+                                                         C.byref(self.h)), "P2 cg_create_preconditioned")
+        return self
+
+    @classmethod
+    def smoother(cls, storage, min_level, max_level, smoother, relax=1.0):
+        """a P2 smoother on its own (JACOBI, GAUSS_SEIDEL, SOR, SYMMETRIC_GAUSS_SEIDEL, SYMMETRIC_SOR) or IDENTITY"""
+        self = cls.__new__(cls)
+        self.storage, self.h = storage, _vp()
+        _ck(lib().hyteg_host_p2_smoother_create(storage.h, min_level, max_level, int(smoother), float(relax), C.byref(self.h)), "P2 smoother_create")
+        return self
+
+    @property
+    def iterations(self) -> int:
+        """CGSolver::getIterations of the last solve (P2Solver.cg)"""
+        n = _i(0)
+        _ck(lib().hyteg_host_p2_cg_iterations(self.h, C.byref(n)), "P2 cg_iterations")
+        return n.value
 
     @classmethod
     def fmg(cls, storage, gmg_solver, min_level, max_level, cycles_per_level=1, post_cycle=None, post_prolongate=None):

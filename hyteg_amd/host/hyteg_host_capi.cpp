@@ -152,7 +152,8 @@ void applyCycle( hh_operator_t op, int npairs, const hh_function_t* srcs, const 
    lanes.join();
 }
 // scalar smoother of an integer code: 0 weighted Jacobi, 1 Gauss-Seidel, 2 SOR, 3 mixed-precision Jacobi (P1 only: BASELINE config 5's
-// "fp32 smoother"); null for any other code, which each caller maps in its own way
+// "fp32 smoother"), 5 symmetric Gauss-Seidel, 6 symmetric SOR (4 is the Chebyshev smoother, which has entry points of its own); null for
+// any other code, which each caller maps in its own way
 template < class Op >
 std::shared_ptr< Solver< Op > > scalarSmoother( int code, const std::shared_ptr< PrimitiveStorage >& storage, int minL, int maxL, double relax )
 {
@@ -165,7 +166,39 @@ std::shared_ptr< Solver< Op > > scalarSmoother( int code, const std::shared_ptr<
    if constexpr ( std::is_same< Op, P1ConstantLaplaceOperator >::value )
       if ( code == 3 )
          return std::make_shared< MixedPrecisionJacobiSmoother< Op > >( storage, (uint_t) minL, (uint_t) maxL, relax );
+   if ( code == 5 )
+      return std::make_shared< SymmetricGaussSeidelSmoother< Op > >();
+   if ( code == 6 )
+      return std::make_shared< SymmetricSORSmoother< Op > >( relax );
    return nullptr;
+}
+// the facade of a smoother on its own and of a preconditioned CG solver, for either operator
+template < class Op, class Handle >
+void smootherCreate( const char* who, hh_storage_t s, int minL, int maxL, int code, double relax, void** out )
+{
+   std::shared_ptr< Solver< Op > > sm = scalarSmoother< Op >( code, SP( s ), minL, maxL, relax );
+   if ( code == -1 )
+      sm = std::make_shared< IdentityPreconditioner< Op > >();
+   if ( !sm )
+      throw std::runtime_error( std::string( who ) + ": unknown smoother code" );
+   *out = new Handle{ sm };
+}
+template < class Op, class Handle >
+void cgCreatePreconditioned( const char* who, hh_storage_t s, int minL, int maxL, int maxIter, double tol, void* preconditioner, void** out )
+{
+   if ( !preconditioner || !static_cast< Handle* >( preconditioner )->p )
+      throw std::runtime_error( std::string( who ) + ": needs a preconditioner" );
+   // the solver shares ownership of the preconditioner: the caller may destroy its handle
+   *out = new Handle{ std::make_shared< CGSolver< Op > >( SP( s ), (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, tol, tol,
+                                                          static_cast< Handle* >( preconditioner )->p ) };
+}
+template < class Op, class Handle >
+void cgIterations( const char* who, void* solver, int* iterations )
+{
+   auto cg = std::dynamic_pointer_cast< CGSolver< Op > >( static_cast< Handle* >( solver )->p );
+   if ( !cg )
+      throw std::runtime_error( std::string( who ) + ": not a CG solver" );
+   *iterations = (int) cg->getIterations();
 }
 // CG on the coarsest level of a multigrid solver
 template < class Op >
@@ -1027,12 +1060,7 @@ HYTEG_HOST_API int hyteg_host_cg_set_use_device_scalars( hh_solver_t solver, int
 }
 HYTEG_HOST_API int hyteg_host_cg_iterations( hh_solver_t solver, int* iterations )
 {
-   return guarded( [&] {
-      auto cg = std::dynamic_pointer_cast< CGSolver< P1ConstantLaplaceOperator > >( static_cast< SolverH* >( solver )->p );
-      if ( !cg )
-         throw std::runtime_error( "cg_iterations: not a CG solver" );
-      *iterations = (int) cg->getIterations();
-   } );
+   return guarded( [&] { cgIterations< P1ConstantLaplaceOperator, SolverH >( "cg_iterations", solver, iterations ); } );
 }
 HYTEG_HOST_API int hyteg_host_gmg_replayed_cycles( hh_solver_t solver, int* count )
 {
@@ -1048,6 +1076,26 @@ HYTEG_HOST_API int hyteg_host_cg_create( hh_storage_t s, int minL, int maxL, int
    return guarded( [&] {
       *out = new SolverH{ std::make_shared< CGSolver< P1ConstantLaplaceOperator > >( SP( s ), (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, tol, tol ) };
    } );
+}
+HYTEG_HOST_API int hyteg_host_cg_create_preconditioned( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_solver_t preconditioner,
+                                                        hh_solver_t* out )
+{
+   return guarded( [&] {
+      cgCreatePreconditioned< P1ConstantLaplaceOperator, SolverH >( "cg_create_preconditioned", s, minL, maxL, maxIter, tol, preconditioner, out );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_cg_set_use_fused_update( hh_solver_t solver, int on )
+{
+   return guarded( [&] {
+      auto cg = std::dynamic_pointer_cast< CGSolver< P1ConstantLaplaceOperator > >( static_cast< SolverH* >( solver )->p );
+      if ( !cg )
+         throw std::runtime_error( "cg_set_use_fused_update: not a CG solver" );
+      cg->setUseFusedUpdate( on != 0 );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_smoother_create( hh_storage_t s, int minL, int maxL, int smoother, double relax, hh_solver_t* out )
+{
+   return guarded( [&] { smootherCreate< P1ConstantLaplaceOperator, SolverH >( "smoother_create", s, minL, maxL, smoother, relax, out ); } );
 }
 /* ---- ChebyshevSmoother (src/hyteg/solvers/ChebyshevSmoother.hpp) ---- */
 HYTEG_HOST_API int hyteg_host_chebyshev_coefficients( int order, double lower, double upper, double* out )
@@ -1453,6 +1501,22 @@ HYTEG_HOST_API int hyteg_host_p2_solver_solve( hh_p2solver_t solver, hh_p2operat
 HYTEG_HOST_API int hyteg_host_p2_solver_destroy( hh_p2solver_t solver )
 {
    return guarded( [&] { delete static_cast< P2SolverH* >( solver ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2_cg_create_preconditioned( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_p2solver_t preconditioner,
+                                                           hh_p2solver_t* out )
+{
+   return guarded( [&] {
+      cgCreatePreconditioned< P2ElementwiseLaplaceOperator, P2SolverH >( "p2_cg_create_preconditioned", s, minL, maxL, maxIter, tol, preconditioner,
+                                                                        out );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2_cg_iterations( hh_p2solver_t solver, int* iterations )
+{
+   return guarded( [&] { cgIterations< P2ElementwiseLaplaceOperator, P2SolverH >( "p2_cg_iterations", solver, iterations ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2_smoother_create( hh_storage_t s, int minL, int maxL, int smoother, double relax, hh_p2solver_t* out )
+{
+   return guarded( [&] { smootherCreate< P2ElementwiseLaplaceOperator, P2SolverH >( "p2_smoother_create", s, minL, maxL, smoother, relax, out ); } );
 }
 HYTEG_HOST_API int hyteg_host_p2_cg_solve( hh_storage_t s, hh_p2operator_t op, hh_p2function_t x, hh_p2function_t b, int level, int maxIter,
                                            double tol, int* iterations )

@@ -282,6 +282,38 @@ class P1Function
       return storage_->allreduceSum( local, "dotGlobal" );
    }
 
+   // ---- the vector body of a conjugate gradient iteration ( CGSolver.hpp:152-154 ) in one pass over the arrays:
+   //      this->add( { alpha }, { p } );   r.add( { -alpha }, { ap } );   return r.dotGlobal( r )
+   // One hyteg_hip_p1_cg_update_cells per chunk of cells (every copy of a shared DoF is updated, each DoF is counted once), one download,
+   // one allreduce.  `this` and r carry the same boundary condition (CGSolver copies it).
+   ValueType cgUpdate( const P1Function< ValueType >& r, const P1Function< ValueType >& p, const P1Function< ValueType >& ap, ValueType alpha,
+                       uint_t level, const Selection& flagIn = All ) const
+   {
+      double local = 0.0;
+      {
+         ScopedTimer     timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "CG update" );
+         const Selection flag        = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
+         const auto      updateMasks = storage_->masksFor( flag ), dotMasks = storage_->masksFor( flag, true );
+         int             nchunk      = 0;
+         storage_->forCellChunks( [&]( int first, int count ) {
+            const auto xs = cellPointers( level, first, count ), rs = r.cellPointers( level, first, count );
+            const auto ps = p.cellPointers( level, first, count ), aps = ap.cellPointers( level, first, count );
+            hipCheck( hyteg_hip_p1_cg_update_cells( count, xs.data(), rs.data(), ps.data(), aps.data(), alpha, (int) level, updateMasks.data() + first,
+                                                    dotMasks.data() + first, storage_->dotResult() + nchunk, storage_->dotWorkspace(),
+                                                    storage_->stream() ),
+                      "cgUpdate" );
+            ++nchunk;
+         } );
+         std::vector< double > parts( (size_t) nchunk, 0.0 );
+         if ( nchunk > 0 )
+            hipCheck( hyteg_hip_download( parts.data(), storage_->dotResult(), parts.size() * sizeof( double ), storage_->stream() ),
+                      "cgUpdate: download" );
+         for ( double v : parts )
+            local += v; // chunks in ascending order: deterministic
+      }
+      ScopedTimer timerFn( storage_->getTimingTree(), "P1Function" ), timerOp( storage_->getTimingTree(), "Dot (reduce)" );
+      return storage_->allreduceSum( local, "cgUpdate" );
+   }
    // ---- sum / max / min / max magnitude ( VertexDoFFunction.cpp:1796-1851, :1909-2057 ) ----
    // The statistics of this rank's DoFs, all from one pass over the arrays (hyteg_hip_p1_reduce_cells): one launch per chunk of
    // cells, one download, cells combined in ascending order.

@@ -226,15 +226,51 @@ class GaussSeidelSmoother : public SORSmoother< OperatorType >
    {}
 };
 
-// CGSolver.hpp:88-205 (no preconditioner: IdentityPreconditioner)
+// SymmetricSORSmoother.hpp:29-65, SymmetricGaussSeidelSmoother.hpp: a forward sweep followed by a backward one.  On one macro-cell the
+// pair is a symmetric operator; on several it is not quite (the backward sweep refreshes the communicated values before every
+// primitive class, the forward sweep does not: P1Operator.hpp:373-412) -- the reference's schedule, kept as it is.
+template < class OperatorType >
+class SymmetricSORSmoother : public Solver< OperatorType >
+{
+ public:
+   using FunctionType = typename OperatorType::srcType; // P1Function or P2Function
+   explicit SymmetricSORSmoother( double relax )
+   : relax_( relax )
+   , flag_( Inner | NeumannBoundary )
+   {}
+   void solve( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level ) override
+   {
+      A.smooth_sor( x, b, relax_, level, flag_ );
+      A.smooth_sor( x, b, relax_, level, flag_, true );
+   }
+
+ private:
+   double  relax_;
+   DoFType flag_;
+};
+template < class OperatorType >
+class SymmetricGaussSeidelSmoother : public SymmetricSORSmoother< OperatorType >
+{
+ public:
+   SymmetricGaussSeidelSmoother()
+   : SymmetricSORSmoother< OperatorType >( 1.0 )
+   {}
+};
+
+// CGSolver.hpp:44-205, :340-358.  Without a preconditioner (nullptr) the loop is the reference's with IdentityPreconditioner, minus the
+// copy z = r and its second reduction; with one -- an explicit IdentityPreconditioner included -- it is the reference's statement by
+// statement.  restartFrequency, lowMemoryMode and the iteration hook are not carried.
 template < class OperatorType >
 class CGSolver : public Solver< OperatorType >
 {
  public:
    using FunctionType = typename OperatorType::srcType;
    CGSolver( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel, uint_t maxIter = 1000,
-             double relativeTolerance = 1e-16, double absoluteTolerance = 1e-16 )
-   : p_( "p", storage, minLevel, maxLevel )
+             double relativeTolerance = 1e-16, double absoluteTolerance = 1e-16,
+             std::shared_ptr< Solver< OperatorType > > preconditioner = nullptr )
+   : preconditioner_( preconditioner )
+   , storage_( storage )
+   , p_( "p", storage, minLevel, maxLevel )
    , z_( "z", storage, minLevel, maxLevel )
    , ap_( "ap", storage, minLevel, maxLevel )
    , r_( "r", storage, minLevel, maxLevel )
@@ -261,6 +297,11 @@ class CGSolver : public Solver< OperatorType >
       iterationsOnDevice_ = false;
       for ( FunctionType* f : { &p_, &z_, &ap_, &r_ } )
          f->copyBoundaryConditionFromFunction( x ); // copyBCs
+      if ( preconditioner_ )
+      {
+         solvePreconditioned( A, x, b, level );
+         return;
+      }
       if ( deviceScalarsUsable( x, level ) )
       {
          solveWithDeviceScalars( A, x, b, level );
@@ -313,8 +354,63 @@ class CGSolver : public Solver< OperatorType >
    }
    // levels whose cell arrays together fit one workgroup are solved by ONE launch (hyteg_hip_p1_cg_small_cells); off: false
    void setUseSingleLaunch( bool on ) { useSingleLaunch_ = on; }
+   // the preconditioned loop updates x and r and reduces <r,r> in one pass over P1 functions (P1Function::cgUpdate); off: the
+   // three composed calls of the reference
+   void setUseFusedUpdate( bool on ) { useFusedUpdate_ = on; }
 
  private:
+   // CGSolver.hpp:94-203 with init() of :340-358
+   void solvePreconditioned( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level )
+   {
+      iterations_ = 0;
+      if ( maxIter_ == 0 )
+         return;
+      ScopedTimer timer( storage_->getTimingTree(), "CG Solver" );
+      p_.setToZero( level );
+      z_.setToZero( level );
+      ap_.setToZero( level );
+      r_.setToZero( level );
+      // init(): r = b - A x ; z = 0 ; M z = r ; p = z ; prsold = <r,z>
+      A.apply( x, p_, level, flag_, Replace );
+      r_.assign( { 1.0, -1.0 }, { b, p_ }, level, flag_ );
+      preconditioner_->solve( A, z_, r_, level ); // z is zero on All from above
+      p_.assign( { 1.0 }, { z_ }, level, flag_ );
+      double       prsold    = r_.dotGlobal( z_, level, flag_ );
+      const double res_start = std::sqrt( r_.dotGlobal( r_, level, flag_ ) );
+      if ( res_start < absTol_ )
+         return;
+      for ( uint_t i = 0; i < maxIter_; ++i )
+      {
+         A.apply( p_, ap_, level, flag_, Replace );
+         const double pAp     = p_.dotGlobal( ap_, level, flag_ );
+         const double alpha   = prsold / pAp;
+         const double rsnew   = updateAndReduce( x, alpha, level );
+         const double sqrsnew = std::sqrt( rsnew );
+         iterations_          = i + 1;
+         if ( sqrsnew / res_start < relTol_ || sqrsnew < absTol_ )
+            break;
+         z_.setToZero( level );
+         preconditioner_->solve( A, z_, r_, level );
+         const double prsnew = r_.dotGlobal( z_, level, flag_ );
+         const double beta   = prsnew / prsold;
+         p_.assign( { 1.0, beta }, { z_, p_ }, level, flag_ );
+         prsold = prsnew;
+      }
+   }
+   // x += alpha p ; r -= alpha ap ; <r,r>  (CGSolver.hpp:152-154)
+   template < typename F >
+   double updateAndReduce( const F& x, double alpha, uint_t level )
+   {
+      x.add( { alpha }, { p_ }, level, flag_ );
+      r_.add( { -alpha }, { ap_ }, level, flag_ );
+      return r_.dotGlobal( r_, level, flag_ );
+   }
+   double updateAndReduce( const P1Function< double >& x, double alpha, uint_t level )
+   {
+      if ( useFusedUpdate_ ) // measured faster than the composed calls on small and on large levels
+         return x.cgUpdate( r_, p_, ap_, alpha, level, flag_ );
+      return updateAndReduce< P1Function< double > >( x, alpha, level );
+   }
    template < typename F >
    bool deviceScalarsUsable( const F&, uint_t ) const
    {
@@ -376,7 +472,9 @@ class CGSolver : public Solver< OperatorType >
       }
    }
 
-   bool                 useDeviceScalars_ = true, useSingleLaunch_ = true;
+   std::shared_ptr< Solver< OperatorType > > preconditioner_;
+   std::shared_ptr< PrimitiveStorage >       storage_;
+   bool                 useDeviceScalars_ = true, useSingleLaunch_ = true, useFusedUpdate_ = true;
    mutable bool         iterationsOnDevice_ = false;
    hyteg_hip_stream_t   iterationsStream_   = nullptr;
    double*              scalars_          = nullptr;

@@ -573,6 +573,30 @@ HYTEG_HIP_API int hyteg_hip_p1_dot_cells( int                  ncells,
                                           double*              result_dev,
                                           void*                workspace_dev,
                                           hyteg_hip_stream_t   stream );
+/* The vector body of a conjugate gradient iteration in ONE pass over the arrays (48 bytes per DoF instead of the 56 of the composed
+ * calls): replaces  x.add( { alpha }, { p } );  r.add( { -alpha }, { ap } );  rsnew = r.dotGlobal( r )  of CGSolver::solve
+ * (src/hyteg/solvers/CGSolver.hpp:152-154), i.e. VertexDoFFunction::add (VertexDoFFunction.cpp:1408-1484) twice and dotLocal
+ * (:1710-1793).  On the points update_masks[c] selects in cell c:  x += alpha p,  r -= alpha ap  (each one fused multiply-add); every
+ * other entry of x and r keeps its bits, p and ap are only read.  Then *result_dev = sum over all cells and the points dot_masks[c]
+ * selects of r * r, with the values of r after the update.  Two masks because a caller updates every copy of a DoF that cells share
+ * and counts it once.  Masks: the 15-bit point masks of hyteg_hip_p1_vector_cells; a cell whose two masks are 0 is not touched.
+ * Up to 128 workgroups (tiles of 1024 entries, cells together): one launch, the workgroup that finishes last reduces the partial
+ * sums; more: a second launch does; fixed order either way: the result does not depend on timing.  Stream-ordered, no allocation
+ * beyond the cached tile table, no synchronisation.  Levels 0..11; x, r, p, ap and the masks: HOST arrays of ncells entries;
+ * workspace_dev: hyteg_hip_dot_workspace_bytes().  EINVAL before any GPU work for a bad level or ncells, a null pointer, and x[c] or
+ * r[c] equal to another array of the same cell. */
+HYTEG_HIP_API int hyteg_hip_p1_cg_update_cells( int                  ncells,
+                                                double* const*       x,
+                                                double* const*       r,
+                                                const double* const* p,
+                                                const double* const* ap,
+                                                double               alpha,
+                                                int                  level,
+                                                const unsigned*      update_masks,
+                                                const unsigned*      dot_masks,
+                                                double*              result_dev,
+                                                void*                workspace_dev,
+                                                hyteg_hip_stream_t   stream );
 /* The statistics of a function on every macro-cell of a rank in ONE pass over its arrays (8 bytes read per DoF, nothing written):
  * results_dev[c * HYTEG_HIP_REDUCE_COUNT + q] = statistic q of the points of cell c that masks[c] selects (the 15-bit point mask of
  * hyteg_hip_p1_dot_cells).  Replaces the per-primitive loops of VertexDoFFunction::sumLocal (VertexDoFFunction.cpp:1805-1851, with and

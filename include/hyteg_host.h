@@ -276,7 +276,9 @@ HYTEG_HOST_API int hyteg_host_quadratic_prolongation_prolongate( hh_quadratic_pr
 HYTEG_HOST_API int hyteg_host_quadratic_prolongation_destroy( hh_quadratic_prolongation_t p );
 
 /* ---- solvers on the Laplace operator ----
- * smoother: 0 = weighted Jacobi (relax), 1 = Gauss-Seidel, 2 = SOR (relax).  Coarse grid: CG. */
+ * smoother: 0 = weighted Jacobi (relax), 1 = Gauss-Seidel, 2 = SOR (relax), 3 = mixed-precision Jacobi (relax), 5 = symmetric
+ * Gauss-Seidel, 6 = symmetric SOR (relax): SymmetricGaussSeidelSmoother / SymmetricSORSmoother (SymmetricSORSmoother.hpp:29-65), a forward
+ * sweep followed by a backward one.  Coarse grid: CG. */
 HYTEG_HOST_API int hyteg_host_gmg_create( hh_storage_t s, int min_level, int max_level, int smoother, double relax, int pre, int post,
                                           int wcycle, int cg_max_iter, double cg_tol, hh_solver_t* out );
 /* ---- ChebyshevSmoother (replaces src/hyteg/solvers/ChebyshevSmoother.hpp:40-555 at its call sites) ----
@@ -324,6 +326,16 @@ HYTEG_HOST_API int hyteg_host_cg_set_use_device_scalars( hh_solver_t solver, int
 /* CGSolver::getIterations of the last solve */
 HYTEG_HOST_API int hyteg_host_cg_iterations( hh_solver_t solver, int* iterations );
 HYTEG_HOST_API int hyteg_host_cg_create( hh_storage_t s, int min_level, int max_level, int max_iter, double tol, hh_solver_t* out );
+/* CGSolver with a preconditioner (CGSolver.hpp:44-63, eighth constructor argument): any solver handle -- a multigrid solver, a smoother
+ * of hyteg_host_smoother_create, a Chebyshev smoother.  The CG solver shares ownership of the preconditioner, so its handle may be
+ * destroyed first.  The loop is the reference's (init() :340-358, iteration :146-201); on P1 functions the update of x and r and the
+ * reduction <r,r> are one pass (hyteg_hip_p1_cg_update_cells), which set_use_fused_update( 0 ) replaces by the three composed calls. */
+HYTEG_HOST_API int hyteg_host_cg_create_preconditioned( hh_storage_t s, int min_level, int max_level, int max_iter, double tol,
+                                                        hh_solver_t preconditioner, hh_solver_t* out );
+HYTEG_HOST_API int hyteg_host_cg_set_use_fused_update( hh_solver_t solver, int on );
+/* a smoother on its own, for hyteg_host_solver_solve or as a preconditioner: the codes of hyteg_host_gmg_create, and -1 =
+ * IdentityPreconditioner (x = b) */
+HYTEG_HOST_API int hyteg_host_smoother_create( hh_storage_t s, int min_level, int max_level, int smoother, double relax, hh_solver_t* out );
 HYTEG_HOST_API int hyteg_host_solver_solve( hh_solver_t solver, hh_operator_t laplace, hh_function_t x, hh_function_t b, int level );
 /* Solver::solveSteps (Solver.hpp): `steps` calls of solve, which a smoother may fuse -- what GeometricMultigridSolver calls for its
  * pre- and post-smoothing */
@@ -420,7 +432,8 @@ HYTEG_HOST_API int hyteg_host_p2operator_smooth_jac( hh_p2operator_t op, hh_p2fu
 /* smooth_sor: P2ConstantOperator::smooth_sor (P2ConstantOperator.cpp:113-153; macro-cell part :913-1200: vertex DoFs in
  * lexicographic order, then the edge DoFs type by type; backwards: reversed).  Exactly the reference's sweep inside a macro-cell;
  * on DoFs shared between macro-cells a different Gauss-Seidel ordering of the same splitting.  Needs
- * compute_inverse_diagonal.  gmg smoother: 0 weighted Jacobi( relax ), 1 Gauss-Seidel, 2 SOR( relax ). */
+ * compute_inverse_diagonal.  gmg smoother: 0 weighted Jacobi( relax ), 1 Gauss-Seidel, 2 SOR( relax ), 5 symmetric Gauss-Seidel,
+ * 6 symmetric SOR( relax ) (a forward sweep, then a backward one). */
 HYTEG_HOST_API int hyteg_host_p2operator_smooth_sor( hh_p2operator_t op, hh_p2function_t dst, hh_p2function_t rhs, double relax, int level, int flag,
                                                      int backwards );
 HYTEG_HOST_API int hyteg_host_p2_gmg_create( hh_storage_t s, int min_level, int max_level, int smoother, double relax, int pre, int post, int wcycle,
@@ -441,6 +454,11 @@ HYTEG_HOST_API int hyteg_host_p2_fmg_create( hh_storage_t s, hh_p2solver_t gmg, 
                                              hh_level_callback_t post_prolongate, void* post_prolongate_user, hh_p2solver_t* out );
 HYTEG_HOST_API int hyteg_host_p2_solver_solve( hh_p2solver_t solver, hh_p2operator_t op, hh_p2function_t x, hh_p2function_t b, int level );
 HYTEG_HOST_API int hyteg_host_p2_solver_destroy( hh_p2solver_t solver );
+/* the P2 twins of hyteg_host_cg_create_preconditioned, hyteg_host_cg_iterations and hyteg_host_smoother_create (codes 0, 1, 2, 5, 6, -1) */
+HYTEG_HOST_API int hyteg_host_p2_cg_create_preconditioned( hh_storage_t s, int min_level, int max_level, int max_iter, double tol,
+                                                           hh_p2solver_t preconditioner, hh_p2solver_t* out );
+HYTEG_HOST_API int hyteg_host_p2_cg_iterations( hh_p2solver_t solver, int* iterations );
+HYTEG_HOST_API int hyteg_host_p2_smoother_create( hh_storage_t s, int min_level, int max_level, int smoother, double relax, hh_p2solver_t* out );
 /* CGSolver< P2ElementwiseLaplaceOperator > on one level, flags Inner | NeumannBoundary as in the reference's CGSolver */
 HYTEG_HOST_API int hyteg_host_p2_cg_solve( hh_storage_t s, hh_p2operator_t op, hh_p2function_t x, hh_p2function_t b, int level, int max_iter,
                                            double tol, int* iterations );

@@ -135,6 +135,20 @@ def main():
     timeit("add 1 source", lambda k: capi.p1_add_cell(p(B, k), [2.0], [p(A, k)], L, sh), 24 * inner, inner)
     timeit("multElementwise 2 sources", lambda k: capi.p1_mult_cell(p(B, k), [p(A, k), p(Cc, k)], L, sh), 24 * inner, inner)
     timeit("dot", lambda k: capi.p1_dot_cell(p(A, k), p(B, k), L, res.data_ptr(), ws.data_ptr(), sh), 16 * inner, inner)
+    # the vector body of a CG iteration: x += alpha p, r -= alpha ap and <r,r> in one pass, beside the three calls the host
+    # layer composes it from on one macro-cell (the inner points); information, no threshold is attached
+    D4 = [torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)]
+    timeit("CG update, fused (x += a p, r -= a Ap, <r,r>)",
+           lambda k: capi.p1_cg_update_cells([p(A, k)], [p(B, k)], [p(Cc, k)], [p(D4, k)], 1e-3, L, [0x4000], [0x4000], res.data_ptr(), ws.data_ptr(), sh),
+           48 * inner, inner)
+
+    def cg_update_composed(k):
+        capi.p1_vector_cell_masked(1, p(A, k), [1e-3], [p(Cc, k)], L, 0x4000, sh)
+        capi.p1_vector_cell_masked(1, p(B, k), [-1e-3], [p(D4, k)], L, 0x4000, sh)
+        capi.p1_dot_cell_masked(p(B, k), p(B, k), L, 0x4000, res.data_ptr(), ws.data_ptr(), sh)
+
+    timeit("CG update, composed (add, add, dot)", cg_update_composed, 56 * inner, inner)
+    del D4
     # the statistics reduction of the function classes (sum, sum of magnitudes, min, max, max magnitude in one pass over the
     # array, all point classes) beside the dot product of the same array with itself through the batched entry, which decodes the same
     # point classes; a diagnostic kernel: the figures are information, no threshold is attached
