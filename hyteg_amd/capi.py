@@ -110,6 +110,12 @@ SIGNATURES = {
                                           C.POINTER(C.c_uint), _vp, _vp, _vp]),
     "hyteg_hip_reduce_workspace_bytes": (_sz, []),
     "hyteg_hip_p1_reduce_cells": (_i, [_i, C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp, _vp, _vp]),
+    "hyteg_hip_p1_project_normal_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp]),
+    "hyteg_hip_p2_edge_project_normal_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp]),
+    "hyteg_hip_p2_edge_shell_size": (_i, [_i]),
+    "hyteg_hip_p2_edge_shell_enumeration": (_i, [_i, C.POINTER(_i)]),
+    "hyteg_hip_p1_shell_size": (_i, [_i]),
+    "hyteg_hip_p1_shell_enumeration": (_i, [_i, C.POINTER(_i)]),
     "hyteg_hip_p2_edge_reduce_cells": (_i, [_i, C.POINTER(_vp), _i, C.POINTER(C.c_uint), _vp, _vp, _vp]),
     "hyteg_hip_p1_apply_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), _i, _vp, C.POINTER(C.c_uint), _i, _vp]),
     "hyteg_hip_p1_jacobi_cells": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _vp, _d,
@@ -526,6 +532,45 @@ REDUCE_COUNT = 5
 
 
 def reduce_workspace_bytes(): return int(lib().hyteg_hip_reduce_workspace_bytes())
+
+
+def p1_shell_size(level):
+    """entries of the shell enumeration of a macro-cell: 4 tri(2^level + 1)"""
+    return int(lib().hyteg_hip_p1_shell_size(level))
+
+
+def p1_shell_enumeration(level):
+    """list of (x, y, z, slot) per q of the shell enumeration; slot -1 where the kernels skip q.  Host only."""
+    n = p1_shell_size(level)
+    out = (_i * (4 * max(n, 1)))()
+    check(lib().hyteg_hip_p1_shell_enumeration(level, out), "p1_shell_enumeration")
+    return [tuple(out[4 * q:4 * q + 4]) for q in range(n)]
+
+
+def p1_project_normal_cells(u, v, w, normals, level, masks, stream=0):
+    """(u, v, w) -= ((u, v, w) . n) n at the shell points masks[c] selects; u, v, w, normals: lists of device pointers, one per
+    cell; normals[c]: table [3][shell size] in the order of p1_shell_enumeration"""
+    check(lib().hyteg_hip_p1_project_normal_cells(len(u), _ptrs(u), _ptrs(v), _ptrs(w), _ptrs(normals), level, _masks(masks), stream),
+          "p1_project_normal_cells")
+
+
+def p2_edge_shell_size(level):
+    """entries of the shell edge-DoF enumeration of a macro-cell: 12 tri(2^level)"""
+    return int(lib().hyteg_hip_p2_edge_shell_size(level))
+
+
+def p2_edge_shell_enumeration(level):
+    """list of (x, y, z, orientation, slot) per q of the shell edge-DoF enumeration; slot -1 where the kernel skips q.  Host only."""
+    n = p2_edge_shell_size(level)
+    out = (_i * (5 * max(n, 1)))()
+    check(lib().hyteg_hip_p2_edge_shell_enumeration(level, out), "p2_edge_shell_enumeration")
+    return [tuple(out[5 * q:5 * q + 5]) for q in range(n)]
+
+
+def p2_edge_project_normal_cells(u, v, w, normals, level, masks, stream=0):
+    """p1_project_normal_cells on edge-DoF arrays, over the order of p2_edge_shell_enumeration"""
+    check(lib().hyteg_hip_p2_edge_project_normal_cells(len(u), _ptrs(u), _ptrs(v), _ptrs(w), _ptrs(normals), level, _masks(masks), stream),
+          "p2_edge_project_normal_cells")
 
 
 def p1_reduce_cells(a, level, masks, results_dev, workspace_dev, stream=0):

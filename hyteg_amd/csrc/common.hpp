@@ -81,7 +81,7 @@ __host__ __device__ inline int cell_index( int N, int x, int y, int z )
 }
 
 // Row of the slice-local offset j in a slice whose row 0 has length W: largest y with row_start(W,y) <= j.
-__device__ inline int row_of( int W, int j )
+__host__ __device__ inline int row_of( int W, int j )
 {
    const float b    = (float) ( 2 * W + 1 );
    const float disc = b * b - 8.0f * (float) j;

@@ -1,6 +1,7 @@
 // Shell of a macro-cell (the points on its macro-faces / -edges / -vertices): enumeration, the macro-primitive slot of a
-// point, and this cell's share of the stencil sum at a shell point.  Shared by p1_boundary.hip (one launch per step) and
-// p1_apply_rank.hip (shares, pack and interior of a rank's cell in one launch).
+// point, and this cell's share of the stencil sum at a shell point.  Shared by p1_boundary.hip (one launch per step),
+// p1_apply_rank.hip (shares, pack and interior of a rank's cell in one launch) and p1_project_normal.hip, whose normal tables the
+// host layer builds in the order of shell_point (hence __host__ as well).
 #pragma once
 
 #include "cell_geometry.hpp"
@@ -15,7 +16,7 @@ struct Slots14x15
 
 // Enumerates every shell point exactly once: q in [0, 4 tri(N)) -> (x,y,z,slot); returns false for the
 // duplicates (a point on an edge/vertex is visited through its lowest-numbered face only) and padding.
-__device__ inline bool shell_point( int N, int q, int& x, int& y, int& z, int& slot )
+__host__ __device__ inline bool shell_point( int N, int q, int& x, int& y, int& z, int& slot )
 {
    const int T = tri( N );
    if ( q >= 4 * T )

@@ -25,6 +25,7 @@ EXCHANGE_CB = C.CFUNCTYPE(_i, _vp, _i, _i)
 ALLREDUCE_CB = C.CFUNCTYPE(_i, _vp, _dp, _i)
 LOCATION_CB = C.CFUNCTYPE(_i, _vp, _dp)  # the predicate of set_mesh_boundary_flags_by_*_location: (user, xyz) -> 0 / 1
 _ull = C.c_ulonglong
+NORMAL_CB = C.CFUNCTYPE(_i, _vp, _dp, _dp)  # hh_normal_callback_t: (user, xyz, normal out) -> 0, the normal function of the projection
 LEVEL_CB = C.CFUNCTYPE(None, C.c_uint64, _vp)  # hh_level_callback_t: the callbacks of FullMultigridSolver
 
 SIGNATURES = {
@@ -131,6 +132,32 @@ SIGNATURES = {
     "hyteg_host_stokes_gmg_create_with_coarse": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_stokes_minres_create": (_i, [_vp, _i, _i, _i, _d, _i, _i, C.POINTER(_vp)]),
     "hyteg_host_stokes_minres_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_storage_shell_size": (_i, [_i, _ip]),
+    "hyteg_host_storage_shell_points": (_i, [_vp, _i, _i, _dp]),
+    "hyteg_host_project_normal_create": (_i, [_vp, _i, _i, NORMAL_CB, _vp, C.POINTER(_vp)]),
+    "hyteg_host_project_normal_destroy": (_i, [_vp]),
+    "hyteg_host_project_normal_project": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
+    "hyteg_host_project_normal_project_stokes": (_i, [_vp, _vp, _i, _i]),
+    "hyteg_host_stokes_freeslip_wrapper_create": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "hyteg_host_stokes_freeslip_wrapper_destroy": (_i, [_vp]),
+    "hyteg_host_stokes_freeslip_wrapper_apply": (_i, [_vp, _vp, _vp, _i, _i]),
+    "hyteg_host_stokes_freeslip_minres_create": (_i, [_vp, _i, _i, _i, _d, _i, _i, C.POINTER(_vp)]),
+    "hyteg_host_stokes_freeslip_minres_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_stokes_freeslip_minres_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_stokes_freeslip_minres_destroy": (_i, [_vp]),
+    "hyteg_host_storage_edge_shell_size": (_i, [_i, _ip]),
+    "hyteg_host_storage_edge_shell_points": (_i, [_vp, _i, _i, _dp]),
+    "hyteg_host_p2_project_normal_create": (_i, [_vp, _i, _i, NORMAL_CB, _vp, C.POINTER(_vp)]),
+    "hyteg_host_p2_project_normal_destroy": (_i, [_vp]),
+    "hyteg_host_p2_project_normal_project": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
+    "hyteg_host_p2_project_normal_project_stokes": (_i, [_vp, _vp, _i, _i]),
+    "hyteg_host_th_freeslip_wrapper_create": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "hyteg_host_th_freeslip_wrapper_destroy": (_i, [_vp]),
+    "hyteg_host_th_freeslip_wrapper_apply": (_i, [_vp, _vp, _vp, _i, _i]),
+    "hyteg_host_th_freeslip_minres_create": (_i, [_vp, _i, _i, _i, _d, _i, _i, C.POINTER(_vp)]),
+    "hyteg_host_th_freeslip_minres_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_th_freeslip_minres_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_th_freeslip_minres_destroy": (_i, [_vp]),
     "hyteg_host_solver_create_minres": (_i, [_vp, _i, _i, _i, _d, _i, C.POINTER(_vp)]),
     "hyteg_host_stokes_solver_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
     "hyteg_host_stokes_solver_destroy": (_i, [_vp]),
@@ -469,6 +496,25 @@ class Storage:
         _ck(lib().hyteg_host_storage_local_cell(self.h, i, C.byref(gid), co.ctypes.data_as(_dp), nnc.ctypes.data_as(_dp)),
             "storage_local_cell")
         return gid.value, co.reshape(4, 3), nnc
+
+    def shell_points(self, i, level):
+        """(shell size, 3): the coordinates, in the order of the shell enumeration (capi.p1_shell_enumeration), at which a
+        P1ProjectNormalOperator evaluates its normal function in local cell i: the vertex DoFs on the macro-faces with one neighbour
+        cell and on their edges and vertices.  NaN at every other entry.  Host only."""
+        n = _i()
+        _ck(lib().hyteg_host_storage_shell_size(int(level), C.byref(n)), "storage_shell_size")
+        out = np.empty((n.value, 3))
+        _ck(lib().hyteg_host_storage_shell_points(self.h, int(i), int(level), out.ctypes.data_as(_dp)), "storage_shell_points")
+        return out
+
+    def edge_shell_points(self, i, level):
+        """shell_points for the edge DoFs of a P2ProjectNormalOperator: (edge shell size, 3) midpoints of the micro-edges on the
+        boundary primitives of local cell i, in the order of capi.p2_edge_shell_enumeration; NaN elsewhere.  Host only."""
+        n = _i()
+        _ck(lib().hyteg_host_storage_edge_shell_size(int(level), C.byref(n)), "storage_edge_shell_size")
+        out = np.empty((n.value, 3))
+        _ck(lib().hyteg_host_storage_edge_shell_points(self.h, int(i), int(level), out.ctypes.data_as(_dp)), "storage_edge_shell_points")
+        return out
 
     def mask(self, i, flag, owned=False, bc=None):
         """point mask of local cell i under `flag`; bc: a BoundaryCondition (None: the storage's default one)"""
@@ -1162,6 +1208,100 @@ class P1P1StokesOperator:
         self.h = None
 
 
+class P1ProjectNormalOperator:
+    """hyteg::P1ProjectNormalOperator: ( u, v, w ) -= ( ( u, v, w ) . n ) n at the boundary points `flag` selects.  normal(x, y, z) ->
+    (nx, ny, nz), not necessarily of unit length, is called once per boundary point and level, here in the constructor; an exception
+    it raises ends the constructor and is the cause of the HytegHostError."""
+    _prefix = "hyteg_host_project_normal"
+
+    def __init__(self, storage: Storage, min_level: int, max_level: int, normal):
+        self.storage = storage
+
+        def call(_user, xyz, out):
+            global _hook_exception
+            try:
+                n = normal(xyz[0], xyz[1], xyz[2])
+                out[0], out[1], out[2] = float(n[0]), float(n[1]), float(n[2])
+                return 0
+            except BaseException as e:  # noqa: BLE001 - must not propagate into the C frames
+                if _hook_exception is None:
+                    _hook_exception = e
+                return 1
+
+        h = _vp()
+        _ck(getattr(lib(), self._prefix + "_create")(storage.h, min_level, max_level, NORMAL_CB(call), None, C.byref(h)),
+            "project_normal_create")
+        self.h = h
+
+    def project(self, target, level, flag=FreeslipBoundary):
+        """target: a Stokes function of the operator's discretisation, or its three velocity components"""
+        if isinstance(target, (list, tuple)):
+            u, v, w = target
+            _ck(getattr(lib(), self._prefix + "_project")(self.h, u.h, v.h, w.h, level, flag), "project_normal_project")
+        else:
+            _ck(getattr(lib(), self._prefix + "_project_stokes")(self.h, target.h, level, flag), "project_normal_project")
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._prefix + "_destroy")(self.h)
+        self.h = None
+
+
+class P2ProjectNormalOperator(P1ProjectNormalOperator):
+    """hyteg::P2ProjectNormalOperator: the projection on the vertex DoFs and, with normals evaluated at the midpoints of the
+    micro-edges, on the edge DoFs of three P2Functions or of a TaylorHoodFunction"""
+    _prefix = "hyteg_host_p2_project_normal"
+
+
+class StrongFreeSlipWrapper:
+    """hyteg::StrongFreeSlipWrapper< Operator, ProjectNormalOperator, pre_projection >: op followed by the projection (and preceded
+    by it on a copy of the source with pre_projection); flag None (0) switches the projections off"""
+
+    def __init__(self, op, projection, flag=FreeslipBoundary, pre_projection=False):
+        self.op, self.projection, self.pre_projection = op, projection, bool(pre_projection)
+        self._prefix = "hyteg_host_th_freeslip" if isinstance(op, TaylorHoodStokesOperator) else "hyteg_host_stokes_freeslip"
+        h = _vp()
+        _ck(getattr(lib(), self._prefix + "_wrapper_create")(op.h, projection.h, int(flag), int(self.pre_projection), C.byref(h)),
+            "freeslip_wrapper_create")
+        self.h = h
+
+    def apply(self, src, dst, level, flag):
+        _ck(getattr(lib(), self._prefix + "_wrapper_apply")(self.h, src.h, dst.h, level, flag), "freeslip_wrapper_apply")
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._prefix + "_wrapper_destroy")(self.h)
+        self.h = None
+
+
+class _FreeSlipMinres:
+    """MinResSolver< StrongFreeSlipWrapper< ... > >: what StokesSolver.minres / TaylorHoodSolver.minres return with free_slip=True"""
+
+    def __init__(self, prefix, storage, min_level, max_level, max_iter, rel_tol, preconditioner, pre_projection):
+        self._prefix = prefix
+        h = _vp()
+        _ck(getattr(lib(), prefix + "_minres_create")(storage.h, min_level, max_level, int(max_iter), float(rel_tol),
+                                                      {"identity": 0, "pressure": 1, "block": 2}[preconditioner], int(bool(pre_projection)),
+                                                      C.byref(h)), "freeslip_minres_create")
+        self.h = h
+
+    @property
+    def minres_iterations(self) -> int:
+        n = _i(0)
+        _ck(getattr(lib(), self._prefix + "_minres_iterations")(self.h, C.byref(n)), "freeslip_minres_iterations")
+        return n.value
+
+    def solve(self, op: StrongFreeSlipWrapper, x, b, level: int):
+        if not isinstance(op, StrongFreeSlipWrapper):
+            raise TypeError("a solver created with free_slip=True solves a StrongFreeSlipWrapper")
+        _ck(getattr(lib(), self._prefix + "_minres_solve")(self.h, op.h, x.h, b.h, level), "freeslip_minres_solve")
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._prefix + "_minres_destroy")(self.h)
+        self.h = None
+
+
 class StokesSolver:
     def __init__(self, handle, keep=()):
         self.h = handle
@@ -1188,9 +1328,14 @@ class StokesSolver:
         return cls(h, keep=(smoother,))
 
     @classmethod
-    def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, preconditioner="pressure", velocity_steps=2):
+    def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, preconditioner="pressure", velocity_steps=2,
+               free_slip=False, pre_projection=False):
         """hyteg::MinResSolver< P1P1StokesOperator >; preconditioner "identity", "pressure" (StokesPressureBlockPreconditioner with the
-        lumped inverse mass operator) or "block" (StokesBlockDiagonalPreconditioner: V(2,2) Laplace cycles on the velocity)"""
+        lumped inverse mass operator) or "block" (StokesBlockDiagonalPreconditioner: V(2,2) Laplace cycles on the velocity).
+        free_slip=True: the solver of a StrongFreeSlipWrapper with that pre_projection ("identity" or "pressure" only)"""
+        if free_slip:
+            return _FreeSlipMinres("hyteg_host_stokes_freeslip", storage, min_level, max_level, max_iter, rel_tol, preconditioner,
+                                   pre_projection)
         h = _vp()
         _ck(lib().hyteg_host_stokes_minres_create(storage.h, min_level, max_level, int(max_iter), float(rel_tol),
                                                   {"identity": 0, "pressure": 1, "block": 2}[preconditioner], velocity_steps, C.byref(h)),
@@ -1503,7 +1648,11 @@ class TaylorHoodSolver:
         return cls(h)
 
     @classmethod
-    def minres(cls, storage, min_level, max_level, max_iter=100, rel_tol=1e-10):
+    def minres(cls, storage, min_level, max_level, max_iter=100, rel_tol=1e-10, free_slip=False, pre_projection=False):
+        """MinResSolver with the pressure-block preconditioner; free_slip=True: the solver of a StrongFreeSlipWrapper with that
+        pre_projection"""
+        if free_slip:
+            return _FreeSlipMinres("hyteg_host_th_freeslip", storage, min_level, max_level, max_iter, rel_tol, "pressure", pre_projection)
         h = _vp()
         _ck(lib().hyteg_host_th_minres_create(storage.h, min_level, max_level, max_iter, float(rel_tol), C.byref(h)), "th minres")
         return cls(h)

@@ -12,6 +12,7 @@
 //   P1toP2Conversion / P2toP1Conversion, P1toP1QuadraticProlongationThroughP2Injection           src/hyteg/gridtransferoperators/
 //   WeightedJacobiSmoother, GaussSeidelSmoother, SORSmoother, CGSolver, GeometricMultigridSolver,
 //   FullMultigridSolver                                                                           src/hyteg/solvers/
+//   P1ProjectNormalOperator, StrongFreeSlipWrapper   src/hyteg/p1functionspace/P1ProjectNormalOperator.hpp, src/hyteg/composites/StrongFreeSlipWrapper.hpp
 //   ChebyshevSmoother, chebyshev::estimateRadius, InvDiagOperatorWrapper                         src/hyteg/solvers/ChebyshevSmoother.hpp
 //
 // Data model: one device array per (macro-cell, level) in HyTeG's cell layout.  The DoFs
@@ -40,3 +41,4 @@
 #include "chebyshev.hpp"
 #include "stokes.hpp"
 #include "taylorhood.hpp"
+#include "projectnormal.hpp"

@@ -329,6 +329,117 @@ struct StokesFacade
 using P1P1 = StokesFacade< P1P1StokesOperator, FunctionH >;
 using TH   = StokesFacade< P2P1TaylorHoodStokesOperator, P2FunctionH >;
 
+// The strong free-slip group of the facade, written once over a Stokes facade and its projection operator: the wrapper with and
+// without pre-projection (two types in C++, one handle with a switch here) and the MINRES solver of a wrapped operator.
+template < class Facade, class Projection >
+struct FreeSlipFacade
+{
+   using Op   = typename Facade::Op;
+   using Post = StrongFreeSlipWrapper< Op, Projection, false >;
+   using Both = StrongFreeSlipWrapper< Op, Projection, true >;
+   struct ProjectionHandle
+   {
+      std::shared_ptr< Projection > p;
+   };
+   struct WrapperHandle
+   {
+      std::shared_ptr< Post > post;
+      std::shared_ptr< Both > both;
+   };
+   struct SolverHandle
+   {
+      std::shared_ptr< MinResSolver< Post > > post;
+      std::shared_ptr< MinResSolver< Both > > both;
+   };
+   // normal( user, xyz, n ) != 0: the callback failed (a Python exception is waiting on the other side)
+   static int projectionCreate( hh_storage_t s, int minL, int maxL, hh_normal_callback_t normal, void* user, void** out )
+   {
+      return guarded( [&] {
+         if ( !normal )
+            throw std::runtime_error( "project_normal_create: needs a normal function" );
+         auto fn = [normal, user]( const Point3D& x, Point3D& n ) {
+            if ( normal( user, x.data(), n.data() ) != 0 )
+               throw std::runtime_error( "project_normal_create: the normal function failed" );
+         };
+         *out = new ProjectionHandle{ std::make_shared< Projection >( SP( s ), (uint_t) minL, (uint_t) maxL, fn ) };
+      } );
+   }
+   static Projection& projection( void* p ) { return *static_cast< ProjectionHandle* >( p )->p; }
+   static int         wrapperCreate( void* op, void* proj, int flag, int preProjection, void** out )
+   {
+      return guarded( [&] {
+         auto  A = static_cast< typename Facade::OperatorHandle* >( op )->p;
+         auto  P = static_cast< ProjectionHandle* >( proj )->p;
+         auto* h = new WrapperHandle{};
+         if ( preProjection )
+            h->both = std::make_shared< Both >( A, P, DoFType( flag ) );
+         else
+            h->post = std::make_shared< Post >( A, P, DoFType( flag ) );
+         *out = h;
+      } );
+   }
+   static int wrapperApply( void* w, void* src, void* dst, int level, int flag )
+   {
+      return guarded( [&] {
+         auto* h = static_cast< WrapperHandle* >( w );
+         if ( h->both )
+            h->both->apply( Facade::fn( src ), Facade::fn( dst ), (uint_t) level, DoFType( flag ) );
+         else
+            h->post->apply( Facade::fn( src ), Facade::fn( dst ), (uint_t) level, DoFType( flag ) );
+      } );
+   }
+   // preconditioner 0 identity, 1 pressure block (lumped inverse mass): both act as the identity on the velocity, so they keep a
+   // projected vector projected.  The block-diagonal preconditioner smooths the velocity of the unwrapped operator and does not.
+   template < class W >
+   static std::shared_ptr< MinResSolver< W > > makeMinres( hh_storage_t s, int minL, int maxL, int maxIter, double relTol, int preconditioner )
+   {
+      std::shared_ptr< Solver< W > > prec;
+      if ( preconditioner == 0 )
+         prec = std::make_shared< IdentityPreconditioner< W > >();
+      else if ( preconditioner == 1 )
+         prec = std::make_shared< StokesPressureBlockPreconditioner< W, P1LumpedInvMassOperator > >( SP( s ), (uint_t) minL, (uint_t) maxL );
+      else if ( preconditioner == 2 )
+         throw std::runtime_error( "free-slip minres: the \"block\" preconditioner does not keep projected velocities projected; use "
+                                   "\"identity\" or \"pressure\" with a StrongFreeSlipWrapper" );
+      else
+         throw std::runtime_error( "free-slip minres: unknown preconditioner" );
+      return std::make_shared< MinResSolver< W > >( SP( s ), (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, relTol, 1e-16, prec );
+   }
+   static int minresCreate( hh_storage_t s, int minL, int maxL, int maxIter, double relTol, int preconditioner, int preProjection, void** out )
+   {
+      return guarded( [&] {
+         auto h = std::make_unique< SolverHandle >();
+         if ( preProjection )
+            h->both = makeMinres< Both >( s, minL, maxL, maxIter, relTol, preconditioner );
+         else
+            h->post = makeMinres< Post >( s, minL, maxL, maxIter, relTol, preconditioner );
+         *out = h.release();
+      } );
+   }
+   static int solve( void* solver, void* w, void* x, void* b, int level )
+   {
+      return guarded( [&] {
+         auto* sh = static_cast< SolverHandle* >( solver );
+         auto* wh = static_cast< WrapperHandle* >( w );
+         if ( sh->both && wh->both )
+            sh->both->solve( *wh->both, Facade::fn( x ), Facade::fn( b ), (uint_t) level );
+         else if ( sh->post && wh->post )
+            sh->post->solve( *wh->post, Facade::fn( x ), Facade::fn( b ), (uint_t) level );
+         else
+            throw std::runtime_error( "free-slip minres: solver and wrapper differ in pre_projection" );
+      } );
+   }
+   static int iterations( void* solver, int* out )
+   {
+      return guarded( [&] {
+         auto* sh = static_cast< SolverHandle* >( solver );
+         *out     = (int) ( sh->both ? sh->both->getIterations() : sh->post->getIterations() );
+      } );
+   }
+};
+using P1FreeSlip = FreeSlipFacade< P1P1, P1ProjectNormalOperator >;
+using THFreeSlip = FreeSlipFacade< TH, P2ProjectNormalOperator >;
+
 // ChebyshevSmoother with its coefficients set up (one spectral radius for all levels, or one per level)
 template < class Op >
 std::shared_ptr< ChebyshevSmoother< Op > > makeChebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
@@ -1288,6 +1399,140 @@ HYTEG_HOST_API int hyteg_host_stokes_minres_iterations( hh_stokes_solver_t solve
          throw std::runtime_error( "stokes_minres_iterations: not a MinResSolver" );
       *iterations = (int) m->getIterations();
    } );
+}
+/* ---- strong free-slip (P1ProjectNormalOperator.hpp, composites/StrongFreeSlipWrapper.hpp) ---- */
+HYTEG_HOST_API int hyteg_host_storage_shell_size( int level, int* out )
+{
+   return guarded( [&] {
+      *out = hyteg_hip_p1_shell_size( level );
+      if ( *out == 0 )
+         throw std::runtime_error( "storage_shell_size: level out of range" );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_storage_shell_points( hh_storage_t s, int li, int level, double* xyz )
+{
+   return guarded( [&] {
+      const auto pts = freeslip::shellPoints( S( s ), S( s ).getLocalCell( (uint_t) li ), (uint_t) level );
+      for ( size_t q = 0; q < pts.size(); ++q )
+         for ( size_t r = 0; r < 3; ++r )
+            xyz[3 * q + r] = pts[q][r];
+   } );
+}
+HYTEG_HOST_API int hyteg_host_project_normal_create( hh_storage_t s, int minL, int maxL, hh_normal_callback_t normal, void* user,
+                                                     hh_project_normal_t* out )
+{
+   return P1FreeSlip::projectionCreate( s, minL, maxL, normal, user, out );
+}
+HYTEG_HOST_API int hyteg_host_project_normal_destroy( hh_project_normal_t p )
+{
+   return guarded( [&] { delete static_cast< P1FreeSlip::ProjectionHandle* >( p ); } );
+}
+HYTEG_HOST_API int hyteg_host_project_normal_project( hh_project_normal_t p, hh_function_t u, hh_function_t v, hh_function_t w, int level, int flag )
+{
+   return guarded( [&] { P1FreeSlip::projection( p ).project( F( u ), F( v ), F( w ), (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_project_normal_project_stokes( hh_project_normal_t p, hh_stokes_function_t f, int level, int flag )
+{
+   return guarded( [&] { P1FreeSlip::projection( p ).project( P1P1::fn( f ), (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_wrapper_create( hh_stokes_operator_t op, hh_project_normal_t p, int flag, int pre_projection,
+                                                              hh_freeslip_wrapper_t* out )
+{
+   return P1FreeSlip::wrapperCreate( op, p, flag, pre_projection, out );
+}
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_wrapper_destroy( hh_freeslip_wrapper_t w )
+{
+   return guarded( [&] { delete static_cast< P1FreeSlip::WrapperHandle* >( w ); } );
+}
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_wrapper_apply( hh_freeslip_wrapper_t w, hh_stokes_function_t src, hh_stokes_function_t dst, int level,
+                                                             int flag )
+{
+   return P1FreeSlip::wrapperApply( w, src, dst, level, flag );
+}
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_minres_create( hh_storage_t s, int minL, int maxL, int max_iter, double rel_tol, int preconditioner,
+                                                             int pre_projection, hh_freeslip_solver_t* out )
+{
+   return P1FreeSlip::minresCreate( s, minL, maxL, max_iter, rel_tol, preconditioner, pre_projection, out );
+}
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_minres_solve( hh_freeslip_solver_t solver, hh_freeslip_wrapper_t w, hh_stokes_function_t x,
+                                                            hh_stokes_function_t b, int level )
+{
+   return P1FreeSlip::solve( solver, w, x, b, level );
+}
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_minres_iterations( hh_freeslip_solver_t solver, int* iterations )
+{
+   return P1FreeSlip::iterations( solver, iterations );
+}
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_minres_destroy( hh_freeslip_solver_t solver )
+{
+   return guarded( [&] { delete static_cast< P1FreeSlip::SolverHandle* >( solver ); } );
+}
+/* the same for P2 velocities (P2ProjectNormalOperator.hpp) and the Taylor-Hood operator */
+HYTEG_HOST_API int hyteg_host_storage_edge_shell_size( int level, int* out )
+{
+   return guarded( [&] {
+      *out = hyteg_hip_p2_edge_shell_size( level );
+      if ( *out == 0 )
+         throw std::runtime_error( "storage_edge_shell_size: level out of range" );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_storage_edge_shell_points( hh_storage_t s, int li, int level, double* xyz )
+{
+   return guarded( [&] {
+      const auto pts = freeslip::edgeShellPoints( S( s ), S( s ).getLocalCell( (uint_t) li ), (uint_t) level );
+      for ( size_t q = 0; q < pts.size(); ++q )
+         for ( size_t r = 0; r < 3; ++r )
+            xyz[3 * q + r] = pts[q][r];
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2_project_normal_create( hh_storage_t s, int minL, int maxL, hh_normal_callback_t normal, void* user,
+                                                        hh_p2_project_normal_t* out )
+{
+   return THFreeSlip::projectionCreate( s, minL, maxL, normal, user, out );
+}
+HYTEG_HOST_API int hyteg_host_p2_project_normal_destroy( hh_p2_project_normal_t p )
+{
+   return guarded( [&] { delete static_cast< THFreeSlip::ProjectionHandle* >( p ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2_project_normal_project( hh_p2_project_normal_t p, hh_p2function_t u, hh_p2function_t v, hh_p2function_t w, int level,
+                                                         int flag )
+{
+   return guarded( [&] { THFreeSlip::projection( p ).project( F2( u ), F2( v ), F2( w ), (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2_project_normal_project_stokes( hh_p2_project_normal_t p, hh_th_function_t f, int level, int flag )
+{
+   return guarded( [&] { THFreeSlip::projection( p ).project( TH::fn( f ), (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_th_freeslip_wrapper_create( hh_th_operator_t op, hh_p2_project_normal_t p, int flag, int pre_projection,
+                                                          hh_freeslip_wrapper_t* out )
+{
+   return THFreeSlip::wrapperCreate( op, p, flag, pre_projection, out );
+}
+HYTEG_HOST_API int hyteg_host_th_freeslip_wrapper_destroy( hh_freeslip_wrapper_t w )
+{
+   return guarded( [&] { delete static_cast< THFreeSlip::WrapperHandle* >( w ); } );
+}
+HYTEG_HOST_API int hyteg_host_th_freeslip_wrapper_apply( hh_freeslip_wrapper_t w, hh_th_function_t src, hh_th_function_t dst, int level, int flag )
+{
+   return THFreeSlip::wrapperApply( w, src, dst, level, flag );
+}
+HYTEG_HOST_API int hyteg_host_th_freeslip_minres_create( hh_storage_t s, int minL, int maxL, int max_iter, double rel_tol, int preconditioner,
+                                                         int pre_projection, hh_freeslip_solver_t* out )
+{
+   return THFreeSlip::minresCreate( s, minL, maxL, max_iter, rel_tol, preconditioner, pre_projection, out );
+}
+HYTEG_HOST_API int hyteg_host_th_freeslip_minres_solve( hh_freeslip_solver_t solver, hh_freeslip_wrapper_t w, hh_th_function_t x, hh_th_function_t b,
+                                                        int level )
+{
+   return THFreeSlip::solve( solver, w, x, b, level );
+}
+HYTEG_HOST_API int hyteg_host_th_freeslip_minres_iterations( hh_freeslip_solver_t solver, int* iterations )
+{
+   return THFreeSlip::iterations( solver, iterations );
+}
+HYTEG_HOST_API int hyteg_host_th_freeslip_minres_destroy( hh_freeslip_solver_t solver )
+{
+   return guarded( [&] { delete static_cast< THFreeSlip::SolverHandle* >( solver ); } );
 }
 // MinResSolver< P1ConstantLaplaceOperator > with JacobiPreconditioner( jacobi_iterations ) (0: identity), as
 // tests/hyteg/convergence/P1MinResConvergenceTest.cpp:68-72

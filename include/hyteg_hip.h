@@ -1223,6 +1223,51 @@ HYTEG_HIP_API int hyteg_hip_p2_elementwise_diffusion_element_matrices( const dou
                                                                        int64_t       micro_edges_per_macro_edge,
                                                                        double*       elmat /* 600 */ );
 
+/* ---- strong free-slip: projection onto the tangential plane ----------------------------------------------------------
+ * Replaces vertexdof::macroface::projectNormal3D, vertexdof::macroedge::projectNormal3D and
+ * vertexdof::macrovertex::projectNormal3D (src/hyteg/p1functionspace/freeslip/VertexDoFProjectNormal.hpp:43-97, 200-249,
+ * 383-425) for all macro-cells of a chunk in ONE launch (grid.y = cell) at every level 0..11: at each shell point of cell c
+ * whose macro-primitive slot bit is set in masks[c] (bit 14, the inner points, is ignored: they are never projected)
+ *    d = n0 u + n1 v + n2 w;   u -= d n0,  v -= d n1,  w -= d n2        = ( I - n n^T ) ( u, v, w ), n NOT normalised.
+ * u, v, w, normals: HOST arrays of `ncells` device pointers (1 <= ncells <= HYTEG_HIP_MAX_BATCH); normals[c] is the table
+ * [3][hyteg_hip_p1_shell_size( level )] of cell c, component-major, indexed by the shell enumeration q below -- the reference
+ * calls normal_function at every point of every call, here the caller evaluates it once.  No allocation, no upload, no
+ * synchronisation: the call can be recorded into a graph. */
+HYTEG_HIP_API int hyteg_hip_p1_project_normal_cells( int                  ncells,
+                                                     double* const*       u,
+                                                     double* const*       v,
+                                                     double* const*       w,
+                                                     const double* const* normals,
+                                                     int                  level,
+                                                     const unsigned*      masks,
+                                                     hyteg_hip_stream_t   stream );
+/* The shell enumeration of the kernels above and of hyteg_hip_p1_apply_cell_boundary, on the host: out[4 q + 0..3] =
+ * x, y, z, slot of q in [0, hyteg_hip_p1_shell_size( level )); slot (0..13: edge0..5, face0..3, vertex0..3) is -1 for the q
+ * the kernels skip (a point on a macro-edge or -vertex is visited through its lowest-numbered face only).  Replaces the
+ * iterators vertexdof::macroface::Iterator( level, 1 ) / macroedge::Iterator( level, 1 ) of the loops cited above.
+ * hyteg_hip_p1_shell_size: 4 tri( 2^level + 1 ), 0 for a level outside 0..11. */
+HYTEG_HIP_API int hyteg_hip_p1_shell_size( int level );
+HYTEG_HIP_API int hyteg_hip_p1_shell_enumeration( int level, int* out );
+
+/* The same projection on the edge-DoF arrays of three P2 functions (replaces edgedof::macroface::projectNormal3D and
+ * edgedof::macroedge::projectNormal3D, src/hyteg/edgedofspace/freeslip/EdgeDoFProjectNormal.hpp), levels 0..HYTEG_HIP_P2_MAX_LEVEL,
+ * over the enumeration of the shell edge DoFs: per face of the cell the three orientations that lie in it, an edge DoF on a
+ * macro-edge through its lowest-numbered face only -- every edge DoF of a macro-face or macro-edge slot once, no other.
+ * normals[c]: [3][hyteg_hip_p2_edge_shell_size( level )], evaluated at the midpoints of the micro-edges; masks: bits 0..9.
+ * hyteg_hip_p2_edge_shell_enumeration: out[5 q + 0..4] = x, y, z, orientation (0..5: X, Y, Z, XY, XZ, YZ), slot (-1: skipped);
+ * hyteg_hip_p2_edge_shell_size: 12 tri( 2^level ), 0 for a level out of range.  They replace edgedof::macroface::Iterator /
+ * edgedof::macroedge::Iterator of those loops. */
+HYTEG_HIP_API int hyteg_hip_p2_edge_project_normal_cells( int                  ncells,
+                                                          double* const*       u,
+                                                          double* const*       v,
+                                                          double* const*       w,
+                                                          const double* const* normals,
+                                                          int                  level,
+                                                          const unsigned*      masks,
+                                                          hyteg_hip_stream_t   stream );
+HYTEG_HIP_API int hyteg_hip_p2_edge_shell_size( int level );
+HYTEG_HIP_API int hyteg_hip_p2_edge_shell_enumeration( int level, int* out );
+
 #ifdef __cplusplus
 }
 #endif

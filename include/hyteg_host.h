@@ -495,6 +495,67 @@ HYTEG_HOST_API int hyteg_host_th_project_pressure_mean( hh_th_function_t f, int 
  * zero), 1 = divT (p1_to_p2_tet_divt_tet, edge columns zero); component k; coords[4][3] */
 HYTEG_HOST_API int hyteg_host_th_form_element_matrix( int which, int k, const double* coords12, double* out100 );
 
+/* ---- strong free-slip boundaries (src/hyteg/p1functionspace/P1ProjectNormalOperator.hpp,
+ * src/hyteg/composites/StrongFreeSlipWrapper.hpp) ----
+ * hyteg_host_project_normal_create: P1ProjectNormalOperator( storage, minLevel, maxLevel, normal_function ).  normal( user, xyz, n )
+ * writes the (not necessarily unit) normal at xyz and returns 0; another value fails the call.  It is evaluated once, in this call,
+ * at the vertex DoFs of the macro-faces with one neighbour cell and of their edges and vertices, on every level -- the points
+ * hyteg_host_storage_shell_points returns -- and nowhere else. */
+typedef void* hh_project_normal_t;
+typedef void* hh_freeslip_wrapper_t;
+typedef void* hh_freeslip_solver_t;
+typedef int ( *hh_normal_callback_t )( void* user, const double* xyz, double* normal );
+/* entries of the shell enumeration of a macro-cell, 4 tri( 2^level + 1 ) (hyteg_hip_p1_shell_enumeration) */
+HYTEG_HOST_API int hyteg_host_storage_shell_size( int level, int* out );
+/* xyz[3 q + r]: coordinates of entry q of the shell enumeration of local cell li where the normal function is evaluated, NaN
+ * where it is not (skipped entries, primitives inside the domain).  Host only: touches no device. */
+HYTEG_HOST_API int hyteg_host_storage_shell_points( hh_storage_t s, int local_cell, int level, double* xyz );
+HYTEG_HOST_API int hyteg_host_project_normal_create( hh_storage_t s, int min_level, int max_level, hh_normal_callback_t normal, void* user,
+                                                     hh_project_normal_t* out );
+HYTEG_HOST_API int hyteg_host_project_normal_destroy( hh_project_normal_t p );
+/* project( u, v, w, level, flag ) and project( P1StokesFunction, level, flag ): ( u, v, w ) -= ( ( u, v, w ) . n ) n on the primitives
+ * `flag` selects under the boundary condition of u; fails if that takes a macro-face between two cells */
+HYTEG_HOST_API int hyteg_host_project_normal_project( hh_project_normal_t p, hh_function_t u, hh_function_t v, hh_function_t w, int level, int flag );
+HYTEG_HOST_API int hyteg_host_project_normal_project_stokes( hh_project_normal_t p, hh_stokes_function_t f, int level, int flag );
+/* StrongFreeSlipWrapper< P1P1StokesOperator, P1ProjectNormalOperator, pre_projection >( op, projection, flag ); apply is Replace only */
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_wrapper_create( hh_stokes_operator_t op, hh_project_normal_t p, int flag, int pre_projection,
+                                                              hh_freeslip_wrapper_t* out );
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_wrapper_destroy( hh_freeslip_wrapper_t w );
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_wrapper_apply( hh_freeslip_wrapper_t w, hh_stokes_function_t src, hh_stokes_function_t dst, int level,
+                                                             int flag );
+/* MinResSolver< StrongFreeSlipWrapper< ... > >; preconditioner 0 identity, 1 pressure block; 2 (block diagonal) is refused: it does
+ * not keep projected velocities projected.  solve() needs a wrapper with the same pre_projection. */
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_minres_create( hh_storage_t s, int min_level, int max_level, int max_iter, double rel_tol,
+                                                             int preconditioner, int pre_projection, hh_freeslip_solver_t* out );
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_minres_solve( hh_freeslip_solver_t solver, hh_freeslip_wrapper_t w, hh_stokes_function_t x,
+                                                            hh_stokes_function_t b, int level );
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_minres_iterations( hh_freeslip_solver_t solver, int* iterations );
+HYTEG_HOST_API int hyteg_host_stokes_freeslip_minres_destroy( hh_freeslip_solver_t solver );
+/* The same for P2 velocities and the Taylor-Hood operator: P2ProjectNormalOperator (src/hyteg/p2functionspace/P2ProjectNormalOperator.hpp)
+ * is the vertex projection on the vertex-DoF parts plus the projection on the edge-DoF parts, whose normals are evaluated at the
+ * midpoints of the micro-edges -- the points hyteg_host_storage_edge_shell_points returns in the order of
+ * hyteg_hip_p2_edge_shell_enumeration (NaN where the function is not evaluated; host only). */
+typedef void* hh_p2_project_normal_t;
+HYTEG_HOST_API int hyteg_host_storage_edge_shell_size( int level, int* out );
+HYTEG_HOST_API int hyteg_host_storage_edge_shell_points( hh_storage_t s, int local_cell, int level, double* xyz );
+HYTEG_HOST_API int hyteg_host_p2_project_normal_create( hh_storage_t s, int min_level, int max_level, hh_normal_callback_t normal, void* user,
+                                                        hh_p2_project_normal_t* out );
+HYTEG_HOST_API int hyteg_host_p2_project_normal_destroy( hh_p2_project_normal_t p );
+HYTEG_HOST_API int hyteg_host_p2_project_normal_project( hh_p2_project_normal_t p, hh_p2function_t u, hh_p2function_t v, hh_p2function_t w, int level,
+                                                         int flag );
+HYTEG_HOST_API int hyteg_host_p2_project_normal_project_stokes( hh_p2_project_normal_t p, hh_th_function_t f, int level, int flag );
+/* StrongFreeSlipWrapper< P2P1TaylorHoodStokesOperator, P2ProjectNormalOperator, pre_projection > and its MINRES solver */
+HYTEG_HOST_API int hyteg_host_th_freeslip_wrapper_create( hh_th_operator_t op, hh_p2_project_normal_t p, int flag, int pre_projection,
+                                                          hh_freeslip_wrapper_t* out );
+HYTEG_HOST_API int hyteg_host_th_freeslip_wrapper_destroy( hh_freeslip_wrapper_t w );
+HYTEG_HOST_API int hyteg_host_th_freeslip_wrapper_apply( hh_freeslip_wrapper_t w, hh_th_function_t src, hh_th_function_t dst, int level, int flag );
+HYTEG_HOST_API int hyteg_host_th_freeslip_minres_create( hh_storage_t s, int min_level, int max_level, int max_iter, double rel_tol,
+                                                         int preconditioner, int pre_projection, hh_freeslip_solver_t* out );
+HYTEG_HOST_API int hyteg_host_th_freeslip_minres_solve( hh_freeslip_solver_t solver, hh_freeslip_wrapper_t w, hh_th_function_t x, hh_th_function_t b,
+                                                        int level );
+HYTEG_HOST_API int hyteg_host_th_freeslip_minres_iterations( hh_freeslip_solver_t solver, int* iterations );
+HYTEG_HOST_API int hyteg_host_th_freeslip_minres_destroy( hh_freeslip_solver_t solver );
+
 #ifdef __cplusplus
 }
 #endif

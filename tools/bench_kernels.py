@@ -193,6 +193,20 @@ def main():
     timeit("SOR shell backward", lambda k: capi.p1_sor_shell_cell(p(B, k), p(A, k), p(Cc, k), L, T["edge_verts"], T["edge_w"], T["face_verts"],
                                                                   T["face_w"], T["vertex_w"], 1.0, 0x3FFF, True, sh),
            40 * shell_pts, shell_pts, r=max(3, reps // 10))
+    # the normal projection of the strong free-slip condition on tet_1el with all four faces selected: one launch for the
+    # three components, beside three launches of the masked shell vector kernel (one add per component) that touch the same points
+    ntab = torch.rand(3 * shell_pts, dtype=torch.float64, device="cuda") / 2  # | n | < 1: repeated projections do not grow
+    timeit("project normal (u, v, w; 4 faces selected)",
+           lambda k: capi.p1_project_normal_cells([p(A, k)], [p(B, k)], [p(Cc, k)], [ntab.data_ptr()], L, [0x3FFF], sh),
+           72 * shell_pts, 3 * shell_pts)
+
+    def project_yardstick(k):
+        capi.p1_vector_cell_masked(1, p(A, k), [1e-3], [p(B, k)], L, 0x3FFF, sh)
+        capi.p1_vector_cell_masked(1, p(B, k), [1e-3], [p(Cc, k)], L, 0x3FFF, sh)
+        capi.p1_vector_cell_masked(1, p(Cc, k), [1e-3], [p(A, k)], L, 0x3FFF, sh)
+
+    timeit("project yardstick: 3 masked shell vector launches", project_yardstick, 72 * shell_pts, 3 * shell_pts)
+    del ntab
     # P2 elementwise Laplace apply on one macro-cell, level 7 as in BASELINE config 4
     L2 = min(L, 7)
     nv2, ne2 = capi.cell_size(L2), capi.p2_edge_array_size(L2)
