@@ -74,6 +74,8 @@ SIGNATURES = {
     "hyteg_hip_p1_residual_jacobi_start_f32": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _d, _vp]),
     "hyteg_hip_p1_jacobi_accumulate_f32": (_i, [_vp, _vp, _vp, _i, _dp, _d, _vp]),
     "hyteg_hip_set_apply_shape": (_i, [_i, _i, _i]),
+    "hyteg_hip_set_apply_steps_xs": (_i, [_i]),
+    "hyteg_hip_p1_apply_brick_coverage": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_ubyte), C.POINTER(_i)]),
     "hyteg_hip_p1_apply_cell_f32": (_i, [_vp, _vp, _i, _dp, _i, _vp]),
     "hyteg_hip_p1_jacobi_cell_f32": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _d, _vp]),
     "hyteg_hip_convert_f64_to_f32": (_i, [_vp, _vp, _sz, _vp]),
@@ -330,6 +332,22 @@ def p1_jacobi_accumulate_f32(x, rhs_f32, e_f32, level, w, relax, stream=0):
 def set_apply_shape(ny=0, lz=0, pfd=0) -> None:
     """tuning knob: brick shape of the z-march kernels (0, 0, 0 = per-level defaults)"""
     check(lib().hyteg_hip_set_apply_shape(ny, lz, pfd), "set_apply_shape")
+
+
+def set_apply_steps_xs(xs=0) -> None:
+    """tuning knob: x-stride of the bricks of p1_apply_cell_steps (62, or 56 = aligned store windows; 0 = default of mode and level)"""
+    check(lib().hyteg_hip_set_apply_steps_xs(xs), "set_apply_steps_xs")
+
+
+def p1_apply_brick_coverage(level, ny, lz, xs=62, dst_phase=0):
+    """host only: (how many waves of the z-march store each entry of the level's cell array, bricks of the table)"""
+    import numpy as np
+
+    count = np.zeros(cell_size(level), dtype=np.uint8)
+    nb = _i(0)
+    check(lib().hyteg_hip_p1_apply_brick_coverage(level, ny, lz, xs, dst_phase, count.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(nb)),
+          "p1_apply_brick_coverage")
+    return count, nb.value
 
 
 def p1_apply_kernel_name(level, update=REPLACE) -> str:

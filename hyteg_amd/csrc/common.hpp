@@ -133,7 +133,7 @@ struct BrickTable
    const BrickTask* dev   = nullptr;
    int              count = 0;
 };
-int get_bricks( int level, int NY, int LZ, BrickTable* out );
+int get_bricks( int level, int NY, int LZ, BrickTable* out, int XS = 62 );
 
 // ticket counter of the single-launch reductions (p1_batch.hip), one per (device, stream); zero between launches
 int dot_counter( hipStream_t stream, unsigned** out );

@@ -18,15 +18,20 @@
 //
 // The march has ONE compiled form per ( MODE, NY, LZ, PFD, T ): the brick comes from the per-level table (get_bricks), bricks are
 // 62 outputs wide, dst is stored nontemporally, the source is loaded with the plain policy, and the policy of a mode's second
-// array follows from the mode (kExAux below).  Variants that were measured and rejected live in the history, not here:
+// array follows from the mode (kExAux below).  The steps kernel alone has a second x-stride (XS = 56, aligned store windows: see
+// zmarch_body).  Variants that were measured and rejected live in the history, not here:
 //   * round 1's ablation switches (reference summation order, all-loads-first, unmasked loads, per-lane addressing ...) and their
 //     harness: commit ceeab28, hyteg_amd/csrc/exp/apply_bench.hip; measurements profiles/r01_apply_*.txt.
-//   * commit 896fb24 is the last one that carries the following three as template parameters of zmarch_body:
+//   * commit 896fb24 is the last one that carries the following three as template parameters of zmarch_body (the second is back
+//     for the steps launch; what is recorded here is its single-launch measurement):
 //       - decode mode (DEC: the brick computed from the task index and z-chunk starts in the kernel arguments, no table load):
 //         12.0 against 10.0 us, HBM regime 13.6-13.7 against 12.1-12.3 us -- ~200 scalar instructions per wave on a scalar unit
 //         that eight waves share (docs/TUNING_LOG_r01_r02.md 3.1, profiles/r03_apply_shape_sweep_hbm.txt);
 //       - aligned store windows (XS = 56: every row segment begins on a 64-byte line of dst): 11.7 against 9.5 us, write requests
-//         389 k -> 383 k -- the extra requests are the lines at row ends, not the segment boundaries;
+//         389 k -> 383 k -- the extra requests are the lines at row ends, not the segment boundaries.  That was ONE
+//         launch on the Infinity-Cache-sized ring, whose ~2250 bricks did not fit the 2048 wave slots.  In a steps launch, level 8,
+//         HBM regime (profiles/apply_steps_shapes_level8.txt): 4 x 8 / 2 is 9.19-9.23 us with it and 9.18-9.35 without (nothing),
+//         6 x 8 / 2 is 8.90-9.03 with it and 9.83 without, 8 x 8 / 2 8.93-8.97 and 9.79; written bytes 23.88 -> 23.5 MB per apply;
 //       - cache-policy axes (ST_AUX, SRC_AUX, EX_AUX): nontemporal stores + plain loads 12.4-12.6 us, every other combination
 //         12.5-15.4 us (profiles/r03_apply_shape_sweep_hbm.txt);
 //     and the entry without preloaded arguments (p1_apply_zmarch_kernel; the trace harness exp/apply_trace.hip has its own).
@@ -148,12 +153,32 @@ __host__ __device__ inline void zm_fill_bases( BrickTask& t, int LZ )
    }
 }
 
+// Aligned store window (XS = 56) of one row segment: the wave stores lanes [lo, hi).  io: entry index of the segment's lane 0
+// (x = xb) in dst; dst_phase: entry index of dst's first byte modulo one 64-byte line; R: entries of the row; live: the slice
+// exists.  lo is the lane in 1..7 whose entry begins a 64-byte line of dst (lane 4 = a 32-byte boundary when that lane would be
+// 8: lanes 8..63 would end on lane 63, which has no right neighbour); the row's first brick starts at x = 1 instead; hi = lo + 56
+// clipped to the last inner x.  The neighbour brick (xb + 56) computes the same lo for this row, so the windows tile the row.
+__host__ __device__ inline void zm_aligned_window( int io, int dst_phase, int R, int xb, bool live, int& lo, int& hi )
+{
+   int l = ( ( -( io + dst_phase ) - 1 ) & 7 ) + 1; // 1 .. 8: first lane whose entry index is a multiple of 8
+   l     = l == 8 ? 4 : l;
+   const int end = R - 1 - xb;
+   hi            = live ? ( l + 56 < end ? l + 56 : end ) : 0;
+   lo            = xb == 0 ? 1 : l;
+   hi            = hi > lo ? hi : lo;
+}
+
 // PFD: how many slices ahead of the one being computed the loads run.
 // T: value type of the arrays and of the arithmetic (double or float; the weights travel as doubles and are converted).
 // srcp / dstp: the source and the destination array of this launch (A.src / A.dst), or of this workgroup's step of a steps launch.
-template < int MODE, int NY, int LZ, int PFD, typename T >
+// XS: x-stride between neighbouring bricks = outputs per row segment.  62: lanes 1..62 of every row are stored.  56: aligned store
+// windows -- every row segment begins at the first boundary of 8 entries of dst (64 bytes) inside lanes 1..7 (at a boundary of 4
+// entries in lane 4 where it would fall on lane 8) and is 56 entries long, so that no 64-byte line of dst is written by two waves
+// except the first and the last line of a row.  Table mode of the steps launch, Replace / Add, double.
+template < int MODE, int NY, int LZ, int PFD, typename T, int XS = 62 >
 __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks, int ntasks, int xcd_chunk, const void* srcp, void* dstp )
 {
+   static_assert( XS == 62 || ( XS == 56 && ( MODE == APPLY_REPLACE || MODE == APPLY_ADD ) ), "x-stride: 62 (plain) or 56 (aligned store windows)" );
    static_assert( LZ + 2 <= kBrickMaxSlices, "the table carries the slice bases of bricks of up to kBrickMaxSlices - 2 slices" );
    constexpr int SZ = (int) sizeof( T );
    ZM_TRACE( 0 );
@@ -185,6 +210,8 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
 
    const int lane_off = lane * SZ;
    const int ym       = t.y0 - 1; // first row held per slice
+   // aligned windows: entry index of dst's first byte in units of the value type, modulo one 64-byte line
+   const int dst_phase = XS == 56 ? (int) ( ( reinterpret_cast< uintptr_t >( dstp ) / SZ ) & 7 ) : 0;
 
    // S[q][r]: slice z0-1+q, row ym+r (r = 0..NY+1), x = xb + lane.  q = 0..LZ+1.
    T S[LZ + 2][NY + 2];
@@ -331,6 +358,14 @@ __device__ inline void zmarch_body( const ZMarchArgs& A, const BrickTask* tasks,
             out = EX1[s][j] * acc;
          else
             out = a0 + relax * ( EX1[s][j] * ( EX0[s][j] - acc ) );
+         if constexpr ( XS == 56 )
+         {
+            int lo, hi; // wave-uniform
+            zm_aligned_window( io, dst_phase, R, t.xb, s < t.nz, lo, hi );
+            zm_store2< T, kStAux >( rd, (unsigned) ( lane - lo ) < (unsigned) ( hi - lo ) ? lane_off : -8, io * SZ, out );
+            io += R;
+            continue;
+         }
          // outputs are lanes 1 .. min( 62, R - 2 - xb ) of slices that exist: one unsigned compare of (lane - 1)
          const int      cnt = s < t.nz ? min( 62, R - 2 - t.xb ) : 0; // wave-uniform
          const unsigned lm1 = (unsigned) ( lane - 1 );
@@ -393,17 +428,17 @@ struct ZMarchStepPtrs
    void*       dsts[kZMarchMaxSteps];
 };
 
-template < int MODE, int NY, int LZ, int PFD, typename T >
+template < int MODE, int NY, int LZ, int PFD, typename T, int XS = 62 >
 __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void p1_apply_zmarch_steps_kernel( const BrickTask* tasks, int ntasks, int xcd_chunk,
                                                                                             const ZMarchArgs A, const ZMarchStepPtrs P )
 {
    static_assert( MODE == APPLY_REPLACE || MODE == APPLY_ADD, "a steps launch has one source and one destination per step" );
    const unsigned step = blockIdx.y < (unsigned) kZMarchMaxSteps ? blockIdx.y : 0u; // the host never launches more
-   zmarch_body< MODE, NY, LZ, PFD, T >( A, tasks, ntasks, xcd_chunk, P.srcs[step], P.dsts[step] );
+   zmarch_body< MODE, NY, LZ, PFD, T, XS >( A, tasks, ntasks, xcd_chunk, P.srcs[step], P.dsts[step] );
 }
 
-// host: bricks of NY rows x 62 outputs x LZ slices, ordered z-chunk, y-chunk, x-chunk (memory order)
-inline void build_brick_tasks( int level, int NY, int LZ, std::vector< BrickTask >& out )
+// host: bricks of NY rows x XS outputs x LZ slices, ordered z-chunk, y-chunk, x-chunk (memory order)
+inline void build_brick_tasks( int level, int NY, int LZ, std::vector< BrickTask >& out, int XS = 62 )
 {
    const int N = ( 1 << level ) + 1;
    out.clear();
@@ -413,7 +448,7 @@ inline void build_brick_tasks( int level, int NY, int LZ, std::vector< BrickTask
       for ( int y0 = 1; y0 <= W - 3; y0 += NY )
       {
          const int xmax = W - y0 - 2; // last interior x of the brick's longest row
-         for ( int x0 = 1; x0 <= xmax; x0 += 62 )
+         for ( int x0 = 1; x0 <= xmax; x0 += XS )
          {
             BrickTask t{};
             t.xb = x0 - 1;

@@ -30,6 +30,8 @@ BrickShape g_shape_override{ 0, 0, 0 }; // hyteg_hip_set_apply_shape (tuning kno
 // generations, HBM either way) 4 x 4, two ahead.  The first sweep of round 3 (profiles/r03_apply_shape_sweep.txt) ran on rings
 // whose SOURCE arrays fitted into the Infinity Cache and preferred 2 x 8, one slice ahead, for level-8 Replace (9.15 against
 // 9.50 us); read from HBM that shape is the slower one (13.3 against 12.5 us).
+// All of this is the SINGLE launch (one generation of at most 2048 waves that start together); it is also the form of a steps
+// launch wherever steps_shape below says nothing else.
 inline BrickShape default_shape( int mode, int level, bool f32 )
 {
    if ( level <= 7 )
@@ -39,8 +41,9 @@ inline BrickShape default_shape( int mode, int level, bool f32 )
    return BrickShape{ 4, 4, 2 };
 }
 
-// the shapes compiled in: the defaults and the runners-up of the sweep (so that the sweep can be repeated on another box)
-#define HYTEG_ZM_SHAPES( X ) X( 2, 8, 1 ) X( 4, 8, 2 ) X( 4, 8, 1 ) X( 4, 4, 2 ) X( 4, 4, 1 ) X( 2, 4, 1 ) X( 8, 4, 2 )
+// the shapes compiled in: the defaults (6 x 8: the steps launch) and the runners-up of the sweep (so that the sweep can be
+// repeated on another box)
+#define HYTEG_ZM_SHAPES( X ) X( 2, 8, 1 ) X( 4, 8, 2 ) X( 4, 8, 1 ) X( 4, 4, 2 ) X( 4, 4, 1 ) X( 2, 4, 1 ) X( 8, 4, 2 ) X( 6, 8, 2 )
 
 // run-time shape -> compile-time ( NY, LZ, PFD ): calls f with the three as std::integral_constant arguments if s is compiled
 // in and says whether it is.  The one expansion of HYTEG_ZM_SHAPES.
@@ -62,7 +65,7 @@ inline bool shape_compiled( const BrickShape& s )
 
 // the shape of a launch: hyteg_hip_set_apply_shape, else HYTEG_HIP_APPLY_SHAPE=NYxLZxPFD from the environment (read once;
 // lets tools/gpu/r03_shapes.sh A/B whole bench.py runs), else the default of the mode and level
-inline BrickShape current_shape( int mode, int level, bool f32 )
+inline bool overridden_shape( BrickShape& s )
 {
    static const BrickShape env = [] {
       BrickShape  e{ 0, 0, 0 };
@@ -72,20 +75,59 @@ inline BrickShape current_shape( int mode, int level, bool f32 )
       return e;
    }();
    if ( g_shape_override.ny )
-      return g_shape_override;
+      return s = g_shape_override, true;
    if ( env.ny )
-      return env;
-   return default_shape( mode, level, f32 );
+      return s = env, true;
+   return false;
+}
+inline BrickShape current_shape( int mode, int level, bool f32 )
+{
+   BrickShape s;
+   return overridden_shape( s ) ? s : default_shape( mode, level, f32 );
+}
+
+// The steps launch has a form of its own: brick shape and x-stride (62: plain row segments; 56: store windows aligned to the
+// 64-byte lines of dst, kernels_apply_zmarch.hpp).  Its bricks stream through the wave slots without a common start, so the
+// wave count of one apply is not tied to the slot count and the reasons for 4 x 8 above (one generation of ~2000 waves) do not
+// hold.  Level-8 Replace, groups of 13 on two lanes, one bench.py run each (profiles/apply_steps_shapes_level8.txt):
+//            4x8/2   8x8/2   8x8/3   6x8/2   4x8/3    parent
+//   XS 62    9.50    9.79    9.78    9.83    9.35     9.37 .. 9.53
+//   XS 56    9.25    9.28    9.55    9.20    9.48
+// Taller bricks lose on their own (fewer, longer waves), aligned windows gain nothing on their own (4 x 8: 9.19-9.23 against
+// 9.18-9.35 us in the alternating rounds); together they win: 6 x 8 and 8 x 8, two ahead, 56 wide, 8.90-9.03 us.  The other
+// modes and levels keep the shape of the single apply, 62 wide (Add was not measured; levels <= 7 are cache-resident).
+// Overrides keep priority: the shape of hyteg_hip_set_apply_shape / HYTEG_HIP_APPLY_SHAPE, the x-stride of
+// hyteg_hip_set_apply_steps_xs / HYTEG_HIP_APPLY_STEPS_XS (read once).
+struct StepsForm
+{
+   BrickShape shape;
+   int        xs;
+};
+int g_steps_xs_override = 0; // hyteg_hip_set_apply_steps_xs (tuning knob; 0 = the default of the mode and level)
+
+inline StepsForm steps_shape( int mode, int level )
+{
+   static const int envXs = [] {
+      const char* v = getenv( "HYTEG_HIP_APPLY_STEPS_XS" );
+      return v ? atoi( v ) : 0;
+   }();
+   StepsForm f = ( level == 8 && mode == APPLY_REPLACE ) ? StepsForm{ BrickShape{ 6, 8, 2 }, 56 } : StepsForm{ default_shape( mode, level, false ), 62 };
+   overridden_shape( f.shape );
+   if ( g_steps_xs_override )
+      f.xs = g_steps_xs_override;
+   else if ( envXs )
+      f.xs = envXs;
+   return f;
 }
 
 // what every z-march launch of a level and shape carries whatever its arrays: brick table, extents, stencil, XCD slab map.
 // nblocks = 0 on return: no bricks, nothing to launch
 template < typename T >
-int zmarch_common_args( ZMarchArgs& A, int& nblocks, int NY, int LZ, int level, const double* w )
+int zmarch_common_args( ZMarchArgs& A, int& nblocks, int NY, int LZ, int level, const double* w, int XS = 62 )
 {
    nblocks = 0;
    BrickTable bt;
-   int        rc = get_bricks( level, NY, LZ, &bt );
+   int        rc = get_bricks( level, NY, LZ, &bt, XS );
    if ( rc != HYTEG_HIP_OK || bt.count == 0 )
       return rc;
    A.tasks  = bt.dev;
@@ -149,13 +191,13 @@ inline unsigned steps_lds_request( int level )
 }
 
 // nsteps (2 .. kZMarchMaxSteps) independent applies of one stencil in one launch, double Replace / Add
-template < int MODE, int NY, int LZ, int PFD >
+template < int MODE, int NY, int LZ, int PFD, int XS >
 int launch_zmarch_steps_shape( void* const* dsts, const void* const* srcs, int nsteps, int level, const double* w, hipStream_t stream )
 {
    static_assert( MODE == APPLY_REPLACE || MODE == APPLY_ADD, "steps launch: Replace and Add" );
    ZMarchArgs A{};
    int        nblocks = 0;
-   const int  rc      = zmarch_common_args< double >( A, nblocks, NY, LZ, level, w );
+   const int  rc      = zmarch_common_args< double >( A, nblocks, NY, LZ, level, w, XS );
    if ( rc != HYTEG_HIP_OK || nblocks == 0 )
       return rc;
    ZMarchStepPtrs P{};
@@ -166,7 +208,7 @@ int launch_zmarch_steps_shape( void* const* dsts, const void* const* srcs, int n
    }
    A.src = P.srcs[0];
    A.dst = P.dsts[0];
-   auto           kern = p1_apply_zmarch_steps_kernel< MODE, NY, LZ, PFD, double >;
+   auto           kern = p1_apply_zmarch_steps_kernel< MODE, NY, LZ, PFD, double, XS >;
    const unsigned lds  = steps_lds_request( level );
    if ( lds > 0 )
    {
@@ -198,10 +240,14 @@ template < int MODE >
 int launch_zmarch_steps( void* const* dsts, const void* const* srcs, int nsteps, int level, const double* w, hipStream_t stream )
 {
    int        rc       = HYTEG_HIP_OK;
-   const bool compiled = with_compiled_shape( current_shape( MODE, level, false ), [&]( auto ny, auto lz, auto pfd ) {
-      rc = launch_zmarch_steps_shape< MODE, decltype( ny )::value, decltype( lz )::value, decltype( pfd )::value >( dsts, srcs, nsteps, level, w, stream );
+   const StepsForm form     = steps_shape( MODE, level );
+   const bool      compiled = ( form.xs == 56 || form.xs == 62 ) && with_compiled_shape( form.shape, [&]( auto ny, auto lz, auto pfd ) {
+      if ( form.xs == 56 )
+         rc = launch_zmarch_steps_shape< MODE, decltype( ny )::value, decltype( lz )::value, decltype( pfd )::value, 56 >( dsts, srcs, nsteps, level, w, stream );
+      else
+         rc = launch_zmarch_steps_shape< MODE, decltype( ny )::value, decltype( lz )::value, decltype( pfd )::value, 62 >( dsts, srcs, nsteps, level, w, stream );
    } );
-   return compiled ? rc : fail( HYTEG_HIP_EINVAL, "apply steps: brick shape not compiled in" );
+   return compiled ? rc : fail( HYTEG_HIP_EINVAL, "apply steps: brick shape or x-stride not compiled in" );
 }
 
 // Does this level run the z-march register kernel?  Yes whenever the byte offsets of the array fit its 32-bit buffer addressing
@@ -483,6 +529,47 @@ HYTEG_HIP_API int hyteg_hip_set_apply_shape( int ny, int lz, int pfd )
    }
    HH_REQUIRE( shape_compiled( BrickShape{ ny, lz, pfd } ), "set_apply_shape: this brick shape is not compiled in (p1_apply.hip: HYTEG_ZM_SHAPES)" );
    g_shape_override = BrickShape{ ny, lz, pfd };
+   return HYTEG_HIP_OK;
+}
+
+// host only: the brick table of ( level, ny, lz, xs ) and the store window of every row segment, as the kernel forms them
+HYTEG_HIP_API int hyteg_hip_p1_apply_brick_coverage( int level, int ny, int lz, int xs, int dst_phase, unsigned char* count, int* nbricks )
+{
+   HH_REQUIRE( count && nbricks, "p1_apply_brick_coverage: null pointer" );
+   HH_REQUIRE( level >= HYTEG_HIP_MIN_LEVEL && level <= 8, "p1_apply_brick_coverage: level out of range [2,8]" );
+   HH_REQUIRE( ny >= 1 && lz >= 1 && lz + 2 <= kBrickMaxSlices && ( xs == 56 || xs == 62 ) && dst_phase >= 0 && dst_phase < 8,
+               "p1_apply_brick_coverage: bad shape, x-stride or phase" );
+   const int                N = ( 1 << level ) + 1;
+   std::vector< BrickTask > tasks;
+   build_brick_tasks( level, ny, lz, tasks, xs );
+   *nbricks = (int) tasks.size();
+   std::fill( count, count + tet64( N ), (unsigned char) 0 );
+   for ( const BrickTask& t : tasks )
+      for ( int s = 0; s < lz; ++s )
+      {
+         const int W  = t.W0 - ( s + 1 );
+         int       io = t.base[s + 1] + ( W - ( t.y0 - 1 ) ); // (xb, y0, z0 + s)
+         for ( int j = 0; j < ny; ++j )
+         {
+            const int R  = W - ( t.y0 + j );
+            int       lo = 1, hi = 1 + std::max( s < t.nz ? std::min( 62, R - 2 - t.xb ) : 0, 0 ); // XS = 62: lanes 1 .. min( 62, R - 2 - xb )
+            if ( xs == 56 )
+               zm_aligned_window( io, dst_phase, R, t.xb, s < t.nz, lo, hi );
+            for ( int l = lo; l < hi; ++l )
+            {
+               HH_REQUIRE( l <= 62 && io + l >= 0 && io + l < tet64( N ), "p1_apply_brick_coverage: a store window leaves the wave or the array" );
+               count[io + l] += 1;
+            }
+            io += R;
+         }
+      }
+   return HYTEG_HIP_OK;
+}
+
+HYTEG_HIP_API int hyteg_hip_set_apply_steps_xs( int xs )
+{
+   HH_REQUIRE( xs == 0 || xs == 56 || xs == 62, "set_apply_steps_xs: the x-stride is 62 (plain), 56 (aligned store windows) or 0 (default)" );
+   g_steps_xs_override = xs;
    return HYTEG_HIP_OK;
 }
 

@@ -102,8 +102,10 @@ int get_tiles( int level, TileKind kind, int capacity, TileTable* out )
    return rc;
 }
 
-int get_bricks( int level, int NY, int LZ, BrickTable* out )
+int get_bricks( int level, int NY, int LZ, BrickTable* out, int XS )
 {
+   const int rows = NY;
+   NY             = NY * 1000 + XS; // the key's shape entry carries the x-stride
    // hot path: the same (level, shape) is asked for on every launch
    thread_local int        lastKey[4] = { -1, -1, -1, -1 };
    thread_local BrickTable lastVal;
@@ -119,7 +121,7 @@ int get_bricks( int level, int NY, int LZ, BrickTable* out )
    const int rc = cache.get_on( dev0, std::make_tuple( level, NY, LZ ),
                                 [&]( BrickTable& b ) {
                                    std::vector< BrickTask > host;
-                                   build_brick_tasks( level, NY, LZ, host );
+                                   build_brick_tasks( level, rows, LZ, host, XS );
                                    b.count = (int) host.size();
                                    return upload_table( host, &b.dev );
                                 },

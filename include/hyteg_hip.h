@@ -201,6 +201,15 @@ HYTEG_HIP_API int hyteg_hip_p1_apply_kernel_name( int level, int update, char* b
  * Only shapes compiled into the library are accepted (EINVAL otherwise); ( 0, 0, 0 ) restores the per-level defaults.
  * Results do not depend on the shape (same terms in the same order at every point). */
 HYTEG_HIP_API int hyteg_hip_set_apply_shape( int ny, int lz, int pfd );
+/* Tuning knob of hyteg_hip_p1_apply_cell_steps alone: x-stride of its bricks for all later launches of this process -- 62 (every
+ * wave stores lanes 1..62 of its rows) or 56 (every row segment begins on a 64-byte line of the destination); 0 restores the
+ * default of the mode and level; any other value is EINVAL.  Results do not depend on it. */
+HYTEG_HIP_API int hyteg_hip_set_apply_steps_xs( int xs );
+/* Test support, host only (no device is touched): count[i] = how many waves of the z-march store entry i of a level's cell array
+ * (count: host, cell size of the level) with bricks of ny rows x lz slices and x-stride xs, for a destination whose first byte is
+ * dst_phase (0..7) entries past a 64-byte line; *nbricks = bricks of the table.  A correct table gives 1 on the entries the apply
+ * writes and 0 elsewhere.  Levels 2..8; a store window that leaves the wave or the array is EINVAL. */
+HYTEG_HIP_API int hyteg_hip_p1_apply_brick_coverage( int level, int ny, int lz, int xs, int dst_phase, unsigned char* count /* host */, int* nbricks );
 
 /* ---- a4: weighted Jacobi sweep, fused ------------------------------------------------------------------
  * replaces the 1 apply + 3 vector passes of P1Operator::smooth_jac

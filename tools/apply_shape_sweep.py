@@ -13,7 +13,7 @@ import torch  # noqa: E402
 
 from hyteg_amd import capi  # noqa: E402
 
-SHAPES = [(2, 8, 1), (4, 8, 2), (4, 8, 1), (4, 4, 2), (4, 4, 1), (2, 4, 1), (8, 4, 2)]  # HYTEG_ZM_SHAPES of p1_apply.hip (2x8x2 was in the first sweep)
+SHAPES = [(2, 8, 1), (4, 8, 2), (4, 8, 1), (4, 4, 2), (4, 4, 1), (2, 4, 1), (8, 4, 2), (6, 8, 2)]  # HYTEG_ZM_SHAPES of p1_apply.hip (2x8x2 was in the first sweep)
 
 
 def main():
