@@ -171,6 +171,11 @@ SIGNATURES = {
     "hyteg_hip_p1_apply_cell_boundary_f32": (_i, [_vp, _vp, _i, _dp, C.c_uint, _i, _vp]),
     "hyteg_hip_p2_elementwise_diffusion_apply_macro_3d": (_i, [_vp, _vp, _vp, _vp, _dp, _i64, _d, _vp]),
     "hyteg_hip_p2_elementwise_diffusion_element_matrices": (_i, [_dp, _i64, _dp]),
+    "hyteg_hip_p1_elementwise_divkgrad_apply_macro_3d_masked": (_i, [_vp, _vp, _vp, _dp, _i64, C.c_uint, _i, _vp]),
+    "hyteg_hip_p1_elementwise_divkgrad_jacobi_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _vp]),
+    "hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d": (_i, [_vp, _vp, _dp, _i64, _vp]),
+    "hyteg_hip_p1_elementwise_divkgrad_set_shape": (_i, [_i, _i]),
+    "hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points": (_i, [_i]),
 }
 MASK_INNER, MASK_SHELL, MASK_ALL = 1 << 14, 0x3FFF, 0x7FFF
 
@@ -880,6 +885,38 @@ def p2_elementwise_diffusion_element_matrices(coords, micro_edges):
     out = (C.c_double * 600)()
     check(lib().hyteg_hip_p2_elementwise_diffusion_element_matrices(a, int(micro_edges), out), "p2_elementwise_diffusion_element_matrices")
     return list(out)
+
+
+# ---- variable-coefficient diffusion -div( k grad u ): the seam of the generated P1ElementwiseDivKGrad ----
+def p1_elementwise_divkgrad_apply_macro_3d_masked(dst, src, k, coords, micro_edges, mask=MASK_ALL, update=REPLACE, stream=0):
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_divkgrad_apply_macro_3d_masked(dst, src, k, a, int(micro_edges), mask, update, stream),
+          "p1_elementwise_divkgrad_apply_macro_3d_masked")
+
+
+def p1_elementwise_divkgrad_jacobi_macro_3d(dst, src, rhs, inv_diag, k, coords, micro_edges, omega, stream=0):
+    """dst = src + omega * inv_diag .* ( rhs - A src ) at the inner points"""
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_divkgrad_jacobi_macro_3d(dst, src, rhs, inv_diag, k, a, int(micro_edges), float(omega), stream),
+          "p1_elementwise_divkgrad_jacobi_macro_3d")
+
+
+def p1_elementwise_divkgrad_diagonal_macro_3d(diag, k, coords, micro_edges, stream=0):
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d(diag, k, a, int(micro_edges), stream),
+          "p1_elementwise_divkgrad_diagonal_macro_3d")
+
+
+def p1_elementwise_divkgrad_set_shape(ny=0, lz=0):
+    """brick shape (rows, slices) of the inner-point kernel; (0, 0): the default of the level"""
+    check(lib().hyteg_hip_p1_elementwise_divkgrad_set_shape(ny, lz), "p1_elementwise_divkgrad_set_shape")
+
+
+DIVKGRAD_SHAPES = ((2, 4), (2, 8), (1, 8))  # the shapes compiled in (p1_divkgrad.hip)
+
+
+def p1_elementwise_divkgrad_set_inner_by_points(on):
+    check(lib().hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points(1 if on else 0), "p1_elementwise_divkgrad_set_inner_by_points")
 
 
 # ---- the constant-stencil P2 operator's kernel seam (P2ConstantOperator's four sub-operators) ----

@@ -24,7 +24,7 @@ static const int kMicroCellVerts[6][4][3] = {
     { { 1, 0, 1 }, { 0, 1, 1 }, { 0, 0, 1 }, { 0, 1, 0 } }, { { 0, 1, 0 }, { 1, 1, 0 }, { 1, 0, 1 }, { 0, 1, 1 } } };
 
 // the 15 stencil directions in the C-ABI's weight order (std::map< indexing::Index > order: z, then y, then x)
-constexpr auto& kDirs = kStencilOffsC;
+static constexpr auto& kDirs = kStencilOffsC; // static: a reference has external linkage, and two .hip files include this header
 inline int dir_index( int dx, int dy, int dz )
 {
    for ( int k = 0; k < 15; ++k )

@@ -178,6 +178,22 @@ SIGNATURES = {
     "hyteg_host_elementwise_compute_inverse_diagonal": (_i, [_vp]),
     "hyteg_host_elementwise_inverse_diagonal": (_i, [_vp, C.POINTER(_vp)]),
     "hyteg_host_elementwise_smooth_jac": (_i, [_vp, _vp, _vp, _vp, _d, _i, _i]),
+    "hyteg_host_divkgrad_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_divkgrad_destroy": (_i, [_vp]),
+    "hyteg_host_divkgrad_apply": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "hyteg_host_divkgrad_compute_inverse_diagonal": (_i, [_vp]),
+    "hyteg_host_divkgrad_inverse_diagonal": (_i, [_vp, C.POINTER(_vp)]),
+    "hyteg_host_divkgrad_smooth_jac": (_i, [_vp, _vp, _vp, _vp, _d, _i, _i]),
+    "hyteg_host_divkgrad_set_fused": (_i, [_vp, _i]),
+    "hyteg_host_divkgrad_cg_create": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
+    "hyteg_host_divkgrad_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_divkgrad_smoother_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_divkgrad_gmg_create": (_i, [_vp, _i, _i, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_divkgrad_chebyshev_estimate_radius": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(_d)]),
+    "hyteg_host_divkgrad_chebyshev_create": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, C.POINTER(_vp)]),
+    "hyteg_host_divkgrad_gmg_create_chebyshev": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_divkgrad_solver_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_divkgrad_solver_destroy": (_i, [_vp]),
     "hyteg_host_restrict": (_i, [_vp, _i, _i]),
     "hyteg_host_prolongate": (_i, [_vp, _i, _i]),
     "hyteg_host_prolongate_and_add": (_i, [_vp, _i, _i]),
@@ -301,6 +317,8 @@ def estimate_radius(op, level: int, max_iter: int, x, tmp) -> float:
     op: P1ConstantOperator with P1Functions, or a P2 Laplace operator with P2Functions (inverse diagonal computed)"""
     r = _d()
     fn = lib().hyteg_host_p2_chebyshev_estimate_radius if isinstance(op, P2ElementwiseLaplaceOperator) else lib().hyteg_host_chebyshev_estimate_radius
+    if isinstance(op, P1ElementwiseDivKGrad):
+        fn = lib().hyteg_host_divkgrad_chebyshev_estimate_radius
     _ck(fn(op.h, int(level), int(max_iter), x.h, tmp.h, C.byref(r)), "chebyshev_estimate_radius")
     return r.value
 
@@ -932,6 +950,112 @@ class P1ElementwiseDiffusion:
     def close(self):
         if self.h:
             lib().hyteg_host_elementwise_destroy(self.h)
+            self.h = None
+
+
+class P1ElementwiseDivKGrad:
+    """hyteg::operatorgeneration::P1ElementwiseDivKGrad( storage, minLevel, maxLevel, k ): -div( k grad u ) with the P1 coefficient
+    function k, which holds values on every level min_level..max_level (the operator at level l reads k at level l; levels 0..8).
+    Every apply goes through the C-ABI seam hyteg_hip_p1_elementwise_divkgrad_apply_macro_3d_masked."""
+
+    def __init__(self, storage: Storage, min_level: int, max_level: int, k: "P1Function"):
+        self.storage = storage
+        self.min_level, self.max_level = min_level, max_level
+        self.k = k  # the operator reads k on every apply: k outlives it
+        h = _vp()
+        _ck(lib().hyteg_host_divkgrad_create(storage.h, min_level, max_level, k.h, C.byref(h)), "divkgrad_create")
+        self.h = h
+
+    def apply(self, src, dst, level, flag, update=Replace):
+        _ck(lib().hyteg_host_divkgrad_apply(self.h, src.h, dst.h, level, flag, update), "divkgrad apply")
+
+    def compute_inverse_diagonal_operator_values(self):
+        _ck(lib().hyteg_host_divkgrad_compute_inverse_diagonal(self.h), "computeInverseDiagonalOperatorValues")
+
+    def inverse_diagonal(self):
+        h = _vp()
+        _ck(lib().hyteg_host_divkgrad_inverse_diagonal(self.h, C.byref(h)), "getInverseDiagonalValues")
+        return P1Function(self.storage, "invdiag", self.min_level, self.max_level, _borrowed=h)
+
+    def smooth_jac(self, dst, rhs, src, relax, level, flag):
+        _ck(lib().hyteg_host_divkgrad_smooth_jac(self.h, dst.h, rhs.h, src.h, float(relax), level, flag), "divkgrad smooth_jac")
+
+    def set_fused(self, on: bool):
+        """smooth_jac: the fused launch on the inner points (default) or the four composed passes everywhere"""
+        _ck(lib().hyteg_host_divkgrad_set_fused(self.h, int(bool(on))), "divkgrad set_fused")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_divkgrad_destroy(self.h)
+            self.h = None
+
+
+class DivKGradSolver:
+    """The solvers instantiated for P1ElementwiseDivKGrad: CGSolver, GeometricMultigridSolver (linear P1 transfer, CG on the coarsest
+    level) with a weighted-Jacobi or a Chebyshev smoother, and the smoothers on their own.  Built by the class methods."""
+
+    def __init__(self, storage, h, keep=None):
+        self.storage, self.h, self._keep = storage, h, keep
+
+    @classmethod
+    def cg(cls, storage, min_level, max_level, max_iter=1000, tol=1e-14, preconditioner=None):
+        """hyteg::CGSolver< P1ElementwiseDivKGrad >; preconditioner: a DivKGradSolver or None"""
+        h = _vp()
+        _ck(lib().hyteg_host_divkgrad_cg_create(storage.h, min_level, max_level, max_iter, float(tol),
+                                                preconditioner.h if preconditioner is not None else None, C.byref(h)), "divkgrad cg_create")
+        return cls(storage, h, preconditioner)
+
+    @classmethod
+    def gmg(cls, storage, min_level, max_level, smoother=JACOBI, relax=2.0 / 3.0, pre=3, post=3, wcycle=False, cg_max_iter=1000, cg_tol=1e-14):
+        """hyteg::GeometricMultigridSolver with WeightedJacobiSmoother( relax ) (the operator has no Gauss-Seidel sweep)"""
+        if smoother != JACOBI:
+            raise HytegHostError("DivKGradSolver.gmg: smoother JACOBI (gmg_chebyshev for the Chebyshev smoother)")
+        h = _vp()
+        _ck(lib().hyteg_host_divkgrad_gmg_create(storage.h, min_level, max_level, float(relax), pre, post, int(bool(wcycle)), cg_max_iter,
+                                                 float(cg_tol), C.byref(h)), "divkgrad gmg_create")
+        return cls(storage, h)
+
+    @classmethod
+    def chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3):
+        """hyteg::ChebyshevSmoother< P1ElementwiseDivKGrad > on its own (solve = one smoother call)"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_divkgrad_chebyshev_create(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower),
+                                                       C.byref(h)), "divkgrad chebyshev_create")
+        return cls(storage, h)
+
+    @classmethod
+    def gmg_chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3, pre=1, post=1, wcycle=False, cg_max_iter=1000,
+                      cg_tol=1e-14):
+        """the multigrid solver smoothing with ChebyshevSmoother( order ); radii: one spectral radius (estimate_radius) or one per level"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_divkgrad_gmg_create_chebyshev(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), pre,
+                                                           post, int(bool(wcycle)), cg_max_iter, float(cg_tol), C.byref(h)),
+            "divkgrad gmg_create_chebyshev")
+        return cls(storage, h)
+
+    @classmethod
+    def smoother(cls, storage, min_level, max_level, smoother=JACOBI, relax=1.0):
+        """WeightedJacobiSmoother( relax ) (JACOBI) or IdentityPreconditioner (IDENTITY) on its own"""
+        h = _vp()
+        _ck(lib().hyteg_host_divkgrad_smoother_create(storage.h, min_level, max_level, {JACOBI: 0, IDENTITY: -1}[smoother], float(relax),
+                                                      C.byref(h)), "divkgrad smoother_create")
+        return cls(storage, h)
+
+    @property
+    def iterations(self) -> int:
+        """CGSolver::getIterations of the last solve (DivKGradSolver.cg)"""
+        n = _i(0)
+        _ck(lib().hyteg_host_divkgrad_cg_iterations(self.h, C.byref(n)), "divkgrad cg_iterations")
+        return n.value
+
+    def solve(self, op: P1ElementwiseDivKGrad, x: "P1Function", b: "P1Function", level):
+        _ck(lib().hyteg_host_divkgrad_solver_solve(self.h, op.h, x.h, b.h, level), "divkgrad solve")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_divkgrad_solver_destroy(self.h)
             self.h = None
 
 

@@ -8,6 +8,7 @@
 //   P1Function< double >         src/hyteg/p1functionspace/VertexDoFFunction.hpp/.cpp (interpolate, assign, add,
 //                                multElementwise, dotLocal, dotGlobal)
 //   P1ConstantOperator< Form >   src/constant_stencil_operator/P1ConstantOperator.hpp:33-168 + P1Operator.hpp:192-447
+//   operatorgeneration::P1ElementwiseDiffusion, P1ElementwiseDivKGrad   module hyteg_operators (generated classes)
 //   P1toP1LinearRestriction / P1toP1LinearProlongation   src/hyteg/gridtransferoperators/
 //   P1toP2Conversion / P2toP1Conversion, P1toP1QuadraticProlongationThroughP2Injection           src/hyteg/gridtransferoperators/
 //   WeightedJacobiSmoother, GaussSeidelSmoother, SORSmoother, CGSolver, GeometricMultigridSolver,
@@ -33,6 +34,7 @@
 #include "forms.hpp"
 #include "p1operator.hpp"
 #include "p1elementwise.hpp"
+#include "p1divkgrad.hpp"
 #include "p2operator.hpp"
 #include "p2gridtransfer.hpp"
 #include "gridtransfer.hpp"

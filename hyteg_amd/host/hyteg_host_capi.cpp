@@ -1072,6 +1072,136 @@ HYTEG_HOST_API int hyteg_host_elementwise_smooth_jac( hh_elementwise_t op, hh_fu
    return guarded( [&] { static_cast< ElementwiseH* >( op )->p->smooth_jac( F( dst ), F( rhs ), F( src ), relax, (uint_t) level, DoFType( flag ) ); } );
 }
 
+// ---- the generated variable-coefficient operator: P1ElementwiseDivKGrad, and the solvers instantiated for it ----
+using DivKGrad = operatorgeneration::P1ElementwiseDivKGrad;
+struct DivKGradH
+{
+   std::shared_ptr< P1Function< double > > k; // the operator holds a reference: the handle keeps the function alive
+   std::shared_ptr< DivKGrad >             p;
+   FunctionH                               invDiag; // borrowed view
+};
+struct DivKGradSolverH
+{
+   std::shared_ptr< Solver< DivKGrad > > p;
+};
+static DivKGrad& DK( hh_divkgrad_t op )
+{
+   if ( !op )
+      throw std::runtime_error( "null divkgrad operator" );
+   return *static_cast< DivKGradH* >( op )->p;
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_create( hh_storage_t s, int minL, int maxL, hh_function_t k, hh_divkgrad_t* out )
+{
+   return guarded( [&] {
+      if ( !k || minL < 0 || maxL < minL )
+         throw std::runtime_error( "divkgrad_create: needs a coefficient function and 0 <= min_level <= max_level" );
+      auto* h = new DivKGradH{};
+      h->k    = static_cast< FunctionH* >( k )->p;
+      try
+      {
+         h->p = std::make_shared< DivKGrad >( SP( s ), (uint_t) minL, (uint_t) maxL, *h->k );
+      } catch ( ... )
+      {
+         delete h;
+         throw;
+      }
+      *out = h;
+   } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_destroy( hh_divkgrad_t op )
+{
+   return guarded( [&] { delete static_cast< DivKGradH* >( op ); } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_apply( hh_divkgrad_t op, hh_function_t src, hh_function_t dst, int level, int flag, int update )
+{
+   return guarded( [&] { DK( op ).apply( F( src ), F( dst ), (uint_t) level, DoFType( flag ), update ? Add : Replace ); } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_compute_inverse_diagonal( hh_divkgrad_t op )
+{
+   return guarded( [&] { DK( op ).computeInverseDiagonalOperatorValues(); } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_inverse_diagonal( hh_divkgrad_t op, hh_function_t* out )
+{
+   return guarded( [&] {
+      auto* h      = static_cast< DivKGradH* >( op );
+      h->invDiag.p = DK( op ).getInverseDiagonalValues();
+      *out         = &h->invDiag;
+   } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_smooth_jac( hh_divkgrad_t op, hh_function_t dst, hh_function_t rhs, hh_function_t src, double relax, int level,
+                                                   int flag )
+{
+   return guarded( [&] { DK( op ).smooth_jac( F( dst ), F( rhs ), F( src ), relax, (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_set_fused( hh_divkgrad_t op, int on )
+{
+   return guarded( [&] { DK( op ).setFused( on != 0 ); } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_cg_create( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_divkgrad_solver_t preconditioner,
+                                                  hh_divkgrad_solver_t* out )
+{
+   return guarded( [&] {
+      if ( preconditioner )
+         cgCreatePreconditioned< DivKGrad, DivKGradSolverH >( "divkgrad_cg_create", s, minL, maxL, maxIter, tol, preconditioner, out );
+      else
+         *out = new DivKGradSolverH{ std::make_shared< CGSolver< DivKGrad > >( SP( s ), (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, tol, tol ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_cg_iterations( hh_divkgrad_solver_t solver, int* iterations )
+{
+   return guarded( [&] { cgIterations< DivKGrad, DivKGradSolverH >( "divkgrad_cg_iterations", solver, iterations ); } );
+}
+// the operator has no Gauss-Seidel sweep: weighted Jacobi (0) and the identity (-1)
+static std::shared_ptr< Solver< DivKGrad > > divkgradSmoother( hh_storage_t s, int minL, int maxL, int code, double relax )
+{
+   if ( code == 0 )
+      return std::make_shared< WeightedJacobiSmoother< DivKGrad > >( SP( s ), (uint_t) minL, (uint_t) maxL, relax );
+   if ( code == -1 )
+      return std::make_shared< IdentityPreconditioner< DivKGrad > >();
+   throw std::runtime_error( "divkgrad_smoother_create: smoother 0 (weighted Jacobi) or -1 (identity)" );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_smoother_create( hh_storage_t s, int minL, int maxL, int smoother, double relax, hh_divkgrad_solver_t* out )
+{
+   return guarded( [&] { *out = new DivKGradSolverH{ divkgradSmoother( s, minL, maxL, smoother, relax ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_gmg_create( hh_storage_t s, int minL, int maxL, double relax, int pre, int post, int wcycle, int cgMaxIter,
+                                                   double cgTol, hh_divkgrad_solver_t* out )
+{
+   return guarded( [&] {
+      *out = new DivKGradSolverH{ makeGmg< DivKGrad >( SP( s ), divkgradSmoother( s, minL, maxL, 0, relax ),
+                                                       cgCoarse< DivKGrad >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0,
+                                                       cycleOf( wcycle ) ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_chebyshev_estimate_radius( hh_divkgrad_t op, int level, int maxIter, hh_function_t x, hh_function_t tmp,
+                                                                  double* radius )
+{
+   return guarded( [&] { *radius = chebyshev::estimateRadius( DK( op ), (uint_t) level, (uint_t) maxIter, F( x ).getStorage(), F( x ), F( tmp ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_chebyshev_create( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                         double lower, hh_divkgrad_solver_t* out )
+{
+   return guarded( [&] { *out = new DivKGradSolverH{ makeChebyshev< DivKGrad >( s, minL, maxL, order, radii, nRadii, upper, lower ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_gmg_create_chebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii,
+                                                             double upper, double lower, int pre, int post, int wcycle, int cgMaxIter, double cgTol,
+                                                             hh_divkgrad_solver_t* out )
+{
+   return guarded( [&] {
+      std::shared_ptr< Solver< DivKGrad > > sm = makeChebyshev< DivKGrad >( s, minL, maxL, order, radii, nRadii, upper, lower );
+      *out = new DivKGradSolverH{ makeGmg< DivKGrad >( SP( s ), sm, cgCoarse< DivKGrad >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0,
+                                                       cycleOf( wcycle ) ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_solver_solve( hh_divkgrad_solver_t solver, hh_divkgrad_t op, hh_function_t x, hh_function_t b, int level )
+{
+   return guarded( [&] { static_cast< DivKGradSolverH* >( solver )->p->solve( DK( op ), F( x ), F( b ), (uint_t) level ); } );
+}
+HYTEG_HOST_API int hyteg_host_divkgrad_solver_destroy( hh_divkgrad_solver_t solver )
+{
+   return guarded( [&] { delete static_cast< DivKGradSolverH* >( solver ); } );
+}
+
 HYTEG_HOST_API int hyteg_host_restrict( hh_function_t f, int sourceLevel, int flag )
 {
    return guarded( [&] { P1toP1LinearRestriction().restrict( F( f ), (uint_t) sourceLevel, DoFType( flag ) ); } );

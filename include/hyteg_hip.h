@@ -1232,6 +1232,49 @@ HYTEG_HIP_API int hyteg_hip_p2_elementwise_diffusion_element_matrices( const dou
                                                                        int64_t       micro_edges_per_macro_edge,
                                                                        double*       elmat /* 600 */ );
 
+/* ---- b-4: variable-coefficient diffusion -div( k grad u ), the seam of the generated P1ElementwiseDivKGrad ------------------
+ * Replaces apply_macro_3D of operatorgeneration::P1ElementwiseDivKGrad( storage, minLevel, maxLevel, const P1Function< real_t >& k )
+ * (module hyteg_operators; used in tests/hyteg/convergence/ElementwiseDivKGradCGConvergenceTest.cpp).  The generated source is
+ * absent from the snapshot, so the ORDER of the array arguments (dst, src, k) is this header's convention (parity unpinned for
+ * the argument order), and the arithmetic is pinned by the identity below, not by the generated code: with k a P1 function the
+ * element matrix of micro-cell e is  mean( k at the 4 vertices of e ) * K_e,  K_e the P1 Laplace element matrix of e's type (a
+ * generator may integrate with a rule of lower exactness and differ by rounding).  Per macro-cell semantics of
+ * hyteg_hip_p1_elementwise_diffusion_apply_macro_3d_masked: at every point of the classes of `mask` the sum over the micro-cells
+ * of THIS macro-cell that contain the point (24 at an inner point, this cell's share on the shell); entries outside the mask are
+ * not written.  k: the coefficient's cell array at the same level.  Levels 0..8; dst must not alias src or k. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_apply_macro_3d_masked( double*            dst,
+                                                                           const double*      src,
+                                                                           const double*      k,
+                                                                           const double*      macro_vertex_coords /* 12 */,
+                                                                           int64_t            micro_edges_per_macro_edge,
+                                                                           unsigned           mask,
+                                                                           int                update,
+                                                                           hyteg_hip_stream_t stream );
+/* Fused form of P1ElementwiseOperator::smooth_jac (src/hyteg/elementwiseoperators/P1ElementwiseOperator.cpp:288-331: one apply
+ * and three vector passes) for this operator, at the INNER points only:  dst = src + omega * inv_diag .* ( rhs - A src ).
+ * dst must not alias an input.  Levels 0..8 (nothing to do below level 2). */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_jacobi_macro_3d( double*            dst,
+                                                                     const double*      src,
+                                                                     const double*      rhs,
+                                                                     const double*      inv_diag,
+                                                                     const double*      k,
+                                                                     const double*      macro_vertex_coords,
+                                                                     int64_t            micro_edges_per_macro_edge,
+                                                                     double             omega,
+                                                                     hyteg_hip_stream_t stream );
+/* Replaces computeInverseDiagonalOperatorValues_macro_3D of the same class: diag += sum over the adjacent micro-cells e of this
+ * macro-cell of mean_k( e ) * K_e[i,i], at all points of the cell array. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d( double*            diag,
+                                                                       const double*      k,
+                                                                       const double*      macro_vertex_coords,
+                                                                       int64_t            micro_edges_per_macro_edge,
+                                                                       hyteg_hip_stream_t stream );
+/* Tuning knobs of the kernels above (no counterpart in the reference): the brick shape of the inner-point z-march (rows x slices
+ * per wave; 0, 0 = the default of the level; EINVAL for a shape that is not compiled in), and the inner points by the
+ * one-thread-per-point kernel instead (the form the z-march is measured against).  Every choice computes the same bits. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_set_shape( int ny, int lz );
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points( int on );
+
 /* ---- strong free-slip: projection onto the tangential plane ----------------------------------------------------------
  * Replaces vertexdof::macroface::projectNormal3D, vertexdof::macroedge::projectNormal3D and
  * vertexdof::macrovertex::projectNormal3D (src/hyteg/p1functionspace/freeslip/VertexDoFProjectNormal.hpp:43-97, 200-249,

@@ -253,6 +253,42 @@ HYTEG_HOST_API int hyteg_host_elementwise_inverse_diagonal( hh_elementwise_t op,
 HYTEG_HOST_API int hyteg_host_elementwise_smooth_jac( hh_elementwise_t op, hh_function_t dst, hh_function_t rhs, hh_function_t src, double relax,
                                                       int level, int flag );
 
+/* hyteg::operatorgeneration::P1ElementwiseDivKGrad( storage, minLevel, maxLevel, k ) (module hyteg_operators; call site
+ * tests/hyteg/convergence/ElementwiseDivKGradCGConvergenceTest.cpp:73-81): -div( k grad u ) with a P1 coefficient function that
+ * holds values on every level min_level..max_level (levels 0..8).  The handle shares ownership of k.  apply / inverse diagonal /
+ * smooth_jac as for the class above; smooth_jac is one fused launch on the inner points unless set_fused( 0 ) selects the four
+ * composed passes of P1ElementwiseOperator.cpp:288-331 everywhere. */
+typedef void* hh_divkgrad_t;
+typedef void* hh_divkgrad_solver_t;
+HYTEG_HOST_API int hyteg_host_divkgrad_create( hh_storage_t s, int min_level, int max_level, hh_function_t k, hh_divkgrad_t* out );
+HYTEG_HOST_API int hyteg_host_divkgrad_destroy( hh_divkgrad_t op );
+HYTEG_HOST_API int hyteg_host_divkgrad_apply( hh_divkgrad_t op, hh_function_t src, hh_function_t dst, int level, int flag, int update );
+HYTEG_HOST_API int hyteg_host_divkgrad_compute_inverse_diagonal( hh_divkgrad_t op );
+HYTEG_HOST_API int hyteg_host_divkgrad_inverse_diagonal( hh_divkgrad_t op, hh_function_t* out /* borrowed */ );
+HYTEG_HOST_API int hyteg_host_divkgrad_smooth_jac( hh_divkgrad_t op, hh_function_t dst, hh_function_t rhs, hh_function_t src, double relax, int level,
+                                                   int flag );
+HYTEG_HOST_API int hyteg_host_divkgrad_set_fused( hh_divkgrad_t op, int on );
+/* Solvers for this operator type: CGSolver (preconditioner: any solver of this group, or null), GeometricMultigridSolver with the
+ * linear P1 transfer, a CG coarse-grid solver and WeightedJacobiSmoother( relax ) or ChebyshevSmoother (composed steps; radii: one
+ * spectral radius, or one per level) as its smoother, the two smoothers on their own (smoother: 0 weighted Jacobi, -1 identity),
+ * and chebyshev::estimateRadius (ChebyshevSmoother.hpp:655-666). */
+HYTEG_HOST_API int hyteg_host_divkgrad_cg_create( hh_storage_t s, int min_level, int max_level, int max_iter, double tol,
+                                                  hh_divkgrad_solver_t preconditioner /* or null */, hh_divkgrad_solver_t* out );
+HYTEG_HOST_API int hyteg_host_divkgrad_cg_iterations( hh_divkgrad_solver_t solver, int* iterations );
+HYTEG_HOST_API int hyteg_host_divkgrad_smoother_create( hh_storage_t s, int min_level, int max_level, int smoother, double relax,
+                                                        hh_divkgrad_solver_t* out );
+HYTEG_HOST_API int hyteg_host_divkgrad_gmg_create( hh_storage_t s, int min_level, int max_level, double relax, int pre, int post, int wcycle,
+                                                   int cg_max_iter, double cg_tol, hh_divkgrad_solver_t* out );
+HYTEG_HOST_API int hyteg_host_divkgrad_chebyshev_estimate_radius( hh_divkgrad_t op, int level, int max_iter, hh_function_t x, hh_function_t tmp,
+                                                                  double* radius );
+HYTEG_HOST_API int hyteg_host_divkgrad_chebyshev_create( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                         double upper, double lower, hh_divkgrad_solver_t* out );
+HYTEG_HOST_API int hyteg_host_divkgrad_gmg_create_chebyshev( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                             double upper, double lower, int pre, int post, int wcycle, int cg_max_iter,
+                                                             double cg_tol, hh_divkgrad_solver_t* out );
+HYTEG_HOST_API int hyteg_host_divkgrad_solver_solve( hh_divkgrad_solver_t solver, hh_divkgrad_t op, hh_function_t x, hh_function_t b, int level );
+HYTEG_HOST_API int hyteg_host_divkgrad_solver_destroy( hh_divkgrad_solver_t solver );
+
 /* ---- grid transfer ---- */
 HYTEG_HOST_API int hyteg_host_restrict( hh_function_t f, int source_level, int flag );
 HYTEG_HOST_API int hyteg_host_prolongate( hh_function_t f, int source_level, int flag );

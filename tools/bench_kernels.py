@@ -113,6 +113,33 @@ def main():
            24 * inner, inner)
     timeit("Jacobi fused (inverse-diagonal function)",
            lambda k: capi.p1_jacobi_cell(p(B, k), p(Cc, k), p(A, k), L, w, 0.66, p(Cc, k + 1), sh), 32 * inner, inner)
+    # variable-coefficient diffusion -div( k grad u ) (levels <= 8): the inner points by the z-march and by the
+    # one-thread-per-point kernel, the fused Jacobi step, and in the same run the constant-coefficient apply and a copy floor that moves
+    # the same three arrays (two read, one written).  182 fp64 instructions (254 flop) per point; --only div-k-grad times these rows alone
+    if L <= 8:
+        tet = [list(map(float, v)) for v in st.local_cell(0)[1]]
+        K = [1.0 + 0.5 * t for t in Cc]  # the coefficient ring: k in [1, 1.5]
+        dkg_flop = 254 * inner
+        before = len(rows)
+        timeit("div-k-grad apply Replace, inner points (z-march)",
+               lambda k: capi.p1_elementwise_divkgrad_apply_macro_3d_masked(p(B, k), p(A, k), p(K, k), tet, 1 << L, 1 << 14, 0, sh), 24 * inner, inner)
+        capi.p1_elementwise_divkgrad_set_inner_by_points(True)
+        timeit("div-k-grad apply Replace, inner points (one thread per point)",
+               lambda k: capi.p1_elementwise_divkgrad_apply_macro_3d_masked(p(B, k), p(A, k), p(K, k), tet, 1 << L, 1 << 14, 0, sh), 24 * inner, inner)
+        capi.p1_elementwise_divkgrad_set_inner_by_points(False)
+        timeit("div-k-grad Jacobi fused (z-march)",
+               lambda k: capi.p1_elementwise_divkgrad_jacobi_macro_3d(p(B, k), p(A, k), p(Cc, k), p(Cc, k + 1), p(K, k), tet, 1 << L, 0.66, sh),
+               40 * inner, inner)
+        for r_ in rows[before:]:
+            r_["fp64_TFLOPs"] = dkg_flop / r_["us"] * 1e-6
+            print(f"    {r_['kernel']}: {r_['fp64_TFLOPs']:.2f} TFLOP/s fp64")
+        # set-up work (one thread per point, all points): diag += the element diagonals; k read, diag read and written
+        timeit("div-k-grad diagonal (set-up, one thread per point)",
+               lambda k: capi.p1_elementwise_divkgrad_diagonal_macro_3d(p(B, k), p(K, k), tet, 1 << L, sh), 24 * n, n, r=max(3, reps // 10))
+        timeit("div-k-grad yardstick: constant-coefficient apply Replace", lambda k: capi.p1_apply_cell(p(B, k), p(A, k), L, w, 0, sh), 16 * inner, inner)
+        timeit("div-k-grad copy floor (assign 2 sources: two arrays read, one written)",
+               lambda k: capi.p1_assign_cell(p(B, k), [2.0, -1.0], [p(A, k), p(K, k)], L, sh), 24 * inner, inner)
+        del K
     # one step of the Chebyshev smoother: t_out = invDiag .* (A t_in), x += c_prev t_in + c_cur t_out -- fused into one launch,
     # and composed from the kernels of the smoother's generic path (apply, multElementwise, assign) on rings of their own
     X = [torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)]
