@@ -176,6 +176,12 @@ SIGNATURES = {
     "hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d": (_i, [_vp, _vp, _dp, _i64, _vp]),
     "hyteg_hip_p1_elementwise_divkgrad_set_shape": (_i, [_i, _i]),
     "hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points": (_i, [_i]),
+    "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_masked": (_i, [_vp, _vp, _vp, _dp, _i64, C.c_uint, _i, _vp]),
+    "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_component_masks": (_i, [_vp, _vp, _vp, _dp, _i64, C.POINTER(C.c_uint), _i, _vp]),
+    "hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _vp]),
+    "hyteg_hip_p1_elementwise_epsilon_diagonal_macro_3d": (_i, [_vp, _vp, _dp, _i64, _vp]),
+    "hyteg_hip_p1_elementwise_epsilon_set_shape": (_i, [_i, _i]),
+    "hyteg_hip_p1_elementwise_epsilon_set_inner_by_points": (_i, [_i]),
 }
 MASK_INNER, MASK_SHELL, MASK_ALL = 1 << 14, 0x3FFF, 0x7FFF
 
@@ -917,6 +923,51 @@ DIVKGRAD_SHAPES = ((2, 4), (2, 8), (1, 8))  # the shapes compiled in (p1_divkgra
 
 def p1_elementwise_divkgrad_set_inner_by_points(on):
     check(lib().hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points(1 if on else 0), "p1_elementwise_divkgrad_set_inner_by_points")
+
+
+# ---- variable-viscosity epsilon operator -div( 2 mu eps(u) ): the nine blocks of P1ElementwiseAffineEpsilonOperator in one pass ----
+def _ptr3(ptrs):
+    """host array of the three component pointers (None where the caller passed none: the library rejects it)"""
+    if ptrs is None:
+        return None
+    return (C.c_void_p * 3)(*[None if q is None else int(q) for q in ptrs])
+
+
+def p1_elementwise_epsilon_apply_macro_3d_masked(dst, src, mu, coords, micro_edges, mask=MASK_ALL, update=REPLACE, stream=0):
+    """dst, src: three device pointers each (u, v, w); mask: one 15-bit class mask, or three (one per destination component)"""
+    a = (C.c_double * 12)(*_c12(coords))
+    if isinstance(mask, (tuple, list)):
+        m = (C.c_uint * 3)(*[int(x) for x in mask])
+        check(lib().hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_component_masks(_ptr3(dst), _ptr3(src), mu, a, int(micro_edges), m, update, stream),
+              "p1_elementwise_epsilon_apply_macro_3d_component_masks")
+        return
+    check(lib().hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_masked(_ptr3(dst), _ptr3(src), mu, a, int(micro_edges), mask, update, stream),
+          "p1_elementwise_epsilon_apply_macro_3d_masked")
+
+
+def p1_elementwise_epsilon_jacobi_macro_3d(dst, src, rhs, inv_diag, mu, coords, micro_edges, omega, stream=0):
+    """dst_i = src_i + omega * inv_diag_i .* ( rhs_i - ( A src )_i ) at the inner points; three device pointers per argument"""
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d(_ptr3(dst), _ptr3(src), _ptr3(rhs), _ptr3(inv_diag), mu, a, int(micro_edges),
+                                                                 float(omega), stream), "p1_elementwise_epsilon_jacobi_macro_3d")
+
+
+def p1_elementwise_epsilon_diagonal_macro_3d(diag, mu, coords, micro_edges, stream=0):
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_epsilon_diagonal_macro_3d(_ptr3(diag), mu, a, int(micro_edges), stream),
+          "p1_elementwise_epsilon_diagonal_macro_3d")
+
+
+def p1_elementwise_epsilon_set_shape(ny=0, lz=0):
+    """brick shape (rows, slices) of the inner-point kernel; (0, 0): the default of the level"""
+    check(lib().hyteg_hip_p1_elementwise_epsilon_set_shape(ny, lz), "p1_elementwise_epsilon_set_shape")
+
+
+EPSILON_SHAPES = ((1, 4), (1, 8), (2, 4))  # the shapes compiled in (p1_epsilon.hip)
+
+
+def p1_elementwise_epsilon_set_inner_by_points(on):
+    check(lib().hyteg_hip_p1_elementwise_epsilon_set_inner_by_points(1 if on else 0), "p1_elementwise_epsilon_set_inner_by_points")
 
 
 # ---- the constant-stencil P2 operator's kernel seam (P2ConstantOperator's four sub-operators) ----

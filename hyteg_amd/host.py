@@ -194,6 +194,21 @@ SIGNATURES = {
     "hyteg_host_divkgrad_gmg_create_chebyshev": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_divkgrad_solver_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
     "hyteg_host_divkgrad_solver_destroy": (_i, [_vp]),
+    "hyteg_host_epsilon_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_destroy": (_i, [_vp]),
+    "hyteg_host_epsilon_apply": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i]),
+    "hyteg_host_epsilon_compute_inverse_diagonal": (_i, [_vp]),
+    "hyteg_host_epsilon_inverse_diagonal": (_i, [_vp, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_smooth_jac": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _d, _i, _i]),
+    "hyteg_host_epsilon_set_fused": (_i, [_vp, _i]),
+    "hyteg_host_epsilon_stokes_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_stokes_destroy": (_i, [_vp]),
+    "hyteg_host_epsilon_stokes_apply": (_i, [_vp, _vp, _vp, _i, _i]),
+    "hyteg_host_epsilon_stokes_minres_create": (_i, [_vp, _i, _i, _i, _d, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_stokes_minres_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_epsilon_stokes_minres_precondition": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_epsilon_stokes_minres_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_epsilon_stokes_minres_destroy": (_i, [_vp]),
     "hyteg_host_restrict": (_i, [_vp, _i, _i]),
     "hyteg_host_prolongate": (_i, [_vp, _i, _i]),
     "hyteg_host_prolongate_and_add": (_i, [_vp, _i, _i]),
@@ -1478,6 +1493,113 @@ class StokesSolver:
     def close(self):
         if self.h:
             lib().hyteg_host_stokes_solver_destroy(self.h)
+        self.h = None
+
+
+def _handles3(fs):
+    """three component functions (u, v, w) as an array of handles"""
+    fs = list(fs)
+    if len(fs) != 3:
+        raise HytegHostError("a vector function has three components")
+    return (_vp * 3)(*[f.h for f in fs])
+
+
+class P1ElementwiseAffineEpsilonOperator:
+    """hyteg::P1ElementwiseAffineEpsilonOperator( storage, minLevel, maxLevel, viscosity ): -div( 2 mu eps(u) ) on a P1 vector
+    function, given as its three component functions (for instance P1StokesFunction.uvw).  The reference takes the viscosity as a
+    std::function sampled at the points of a degree-2 rule; here mu is a P1Function that holds values on every level
+    min_level..max_level (levels 0..8).  The two coincide where mu is linear on every micro-cell, in particular for mu = 1.  Every
+    component is masked by its own boundary condition."""
+
+    def __init__(self, storage: Storage, min_level: int, max_level: int, mu: "P1Function"):
+        self.storage = storage
+        self.min_level, self.max_level = min_level, max_level
+        self.mu = mu  # the operator reads mu on every apply: mu outlives it
+        h = _vp()
+        _ck(lib().hyteg_host_epsilon_create(storage.h, min_level, max_level, mu.h, C.byref(h)), "epsilon_create")
+        self.h = h
+
+    def apply(self, src, dst, level, flag, update=Replace):
+        _ck(lib().hyteg_host_epsilon_apply(self.h, _handles3(src), _handles3(dst), level, flag, update), "epsilon apply")
+
+    def compute_inverse_diagonal(self):
+        _ck(lib().hyteg_host_epsilon_compute_inverse_diagonal(self.h), "epsilon computeInverseDiagonalOperatorValues")
+
+    def inverse_diagonal(self):
+        """the inverse diagonals of the three diagonal blocks: three P1Functions (borrowed: they live as long as the operator)"""
+        hs = (_vp * 3)()
+        _ck(lib().hyteg_host_epsilon_inverse_diagonal(self.h, hs), "epsilon getInverseDiagonalValues")
+        return [P1Function(self.storage, "invdiag", self.min_level, self.max_level, _borrowed=_vp(hs[k])) for k in range(3)]
+
+    def smooth_jac(self, dst, rhs, src, relax, level, flag):
+        _ck(lib().hyteg_host_epsilon_smooth_jac(self.h, _handles3(dst), _handles3(rhs), _handles3(src), float(relax), level, flag),
+            "epsilon smooth_jac")
+
+    def set_fused(self, on: bool):
+        """smooth_jac: the fused launch on the inner points (default) or the composed passes everywhere"""
+        _ck(lib().hyteg_host_epsilon_set_fused(self.h, int(bool(on))), "epsilon set_fused")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_epsilon_destroy(self.h)
+            self.h = None
+
+
+class P1P1EpsilonStokesOperator:
+    """hyteg::P1P1ElementwiseAffineEpsilonStokesOperator( storage, minLevel, maxLevel, viscosity ): the epsilon operator on the
+    velocity, div / divT and the PSPG block; mu: a P1Function as for P1ElementwiseAffineEpsilonOperator"""
+
+    def __init__(self, storage: Storage, min_level: int, max_level: int, mu: "P1Function"):
+        self.storage, self.mu = storage, mu
+        h = _vp()
+        _ck(lib().hyteg_host_epsilon_stokes_create(storage.h, min_level, max_level, mu.h, C.byref(h)), "epsilon_stokes_create")
+        self.h = h
+
+    def apply(self, src: "P1StokesFunction", dst: "P1StokesFunction", level, flag):
+        _ck(lib().hyteg_host_epsilon_stokes_apply(self.h, src.h, dst.h, level, flag), "epsilon_stokes_apply")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_epsilon_stokes_destroy(self.h)
+        self.h = None
+
+
+class EpsilonStokesSolver:
+    """The solver instantiated for P1P1EpsilonStokesOperator: MinResSolver (class method minres)"""
+
+    def __init__(self, handle, keep=()):
+        self.h = handle
+        self._keep = keep
+
+    @classmethod
+    def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, preconditioner="pressure", mu=None):
+        """hyteg::MinResSolver< P1P1ElementwiseAffineEpsilonStokesOperator >; preconditioner "identity", "pressure"
+        (StokesPressureBlockPreconditioner with the lumped inverse mass operator, the reference's stokesMinResSolver) or
+        "pressure_viscosity" (pressure action x.p = mu .* invLumpedMass .* b.p; needs mu, the viscosity function)"""
+        kind = {"identity": 0, "pressure": 1, "pressure_viscosity": 2}[preconditioner]
+        if kind == 2 and mu is None:
+            raise HytegHostError("EpsilonStokesSolver.minres: the pressure_viscosity preconditioner needs mu")
+        h = _vp()
+        _ck(lib().hyteg_host_epsilon_stokes_minres_create(storage.h, min_level, max_level, int(max_iter), float(rel_tol), kind,
+                                                          mu.h if kind == 2 else None, C.byref(h)), "epsilon_stokes_minres_create")
+        return cls(h, keep=(mu,))
+
+    @property
+    def minres_iterations(self) -> int:
+        n = _i(0)
+        _ck(lib().hyteg_host_epsilon_stokes_minres_iterations(self.h, C.byref(n)), "epsilon_stokes_minres_iterations")
+        return n.value
+
+    def solve(self, op: P1P1EpsilonStokesOperator, x: "P1StokesFunction", b: "P1StokesFunction", level: int):
+        _ck(lib().hyteg_host_epsilon_stokes_minres_solve(self.h, op.h, x.h, b.h, level), "epsilon_stokes_minres_solve")
+
+    def precondition(self, op: P1P1EpsilonStokesOperator, x: "P1StokesFunction", b: "P1StokesFunction", level: int):
+        """the solver's preconditioner on its own: x = M^-1 b"""
+        _ck(lib().hyteg_host_epsilon_stokes_minres_precondition(self.h, op.h, x.h, b.h, level), "epsilon_stokes_minres_precondition")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_epsilon_stokes_minres_destroy(self.h)
         self.h = None
 
 

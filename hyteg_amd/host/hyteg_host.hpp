@@ -9,6 +9,8 @@
 //                                multElementwise, dotLocal, dotGlobal)
 //   P1ConstantOperator< Form >   src/constant_stencil_operator/P1ConstantOperator.hpp:33-168 + P1Operator.hpp:192-447
 //   operatorgeneration::P1ElementwiseDiffusion, P1ElementwiseDivKGrad   module hyteg_operators (generated classes)
+//   P1ElementwiseAffineEpsilonOperator, P1P1ElementwiseAffineEpsilonStokesOperator   src/mixed_operator/P1EpsilonOperator.hpp,
+//                                P1P1ElementwiseAffineEpsilonStokesOperator.hpp (viscosity: a P1Function)
 //   P1toP1LinearRestriction / P1toP1LinearProlongation   src/hyteg/gridtransferoperators/
 //   P1toP2Conversion / P2toP1Conversion, P1toP1QuadraticProlongationThroughP2Injection           src/hyteg/gridtransferoperators/
 //   WeightedJacobiSmoother, GaussSeidelSmoother, SORSmoother, CGSolver, GeometricMultigridSolver,
@@ -42,5 +44,6 @@
 #include "solvers.hpp"
 #include "chebyshev.hpp"
 #include "stokes.hpp"
+#include "p1epsilon.hpp"
 #include "taylorhood.hpp"
 #include "projectnormal.hpp"

@@ -1685,6 +1685,161 @@ HYTEG_HOST_API int hyteg_host_stokes_solver_solve( hh_stokes_solver_t solver, hh
 }
 HYTEG_HOST_API int hyteg_host_stokes_solver_destroy( hh_stokes_solver_t solver ) { return P1P1::destroy< P1P1::SolverHandle >( solver ); }
 
+// ---- variable-viscosity Stokes: P1ElementwiseAffineEpsilonOperator, P1P1ElementwiseAffineEpsilonStokesOperator, MinResSolver ----
+using Epsilon       = P1ElementwiseAffineEpsilonOperator;
+using EpsilonStokes = P1P1ElementwiseAffineEpsilonStokesOperator;
+struct EpsilonH
+{
+   std::shared_ptr< P1Function< double > > mu; // the operator holds a reference: the handle keeps the function alive
+   std::shared_ptr< Epsilon >              p;
+   FunctionH                               invDiag[3]; // borrowed views
+};
+struct EpsilonStokesH
+{
+   std::shared_ptr< P1Function< double > > mu;
+   std::shared_ptr< EpsilonStokes >        p;
+};
+struct EpsilonStokesSolverH
+{
+   std::shared_ptr< P1Function< double > >        mu; // of the viscosity-weighted preconditioner, or null
+   std::shared_ptr< Solver< EpsilonStokes > >     preconditioner;
+   std::shared_ptr< MinResSolver< EpsilonStokes > > p;
+};
+static Epsilon& EP( hh_epsilon_t op )
+{
+   if ( !op )
+      throw std::runtime_error( "null epsilon operator" );
+   return *static_cast< EpsilonH* >( op )->p;
+}
+static EpsilonStokes& EPS( hh_epsilon_stokes_t op )
+{
+   if ( !op )
+      throw std::runtime_error( "null epsilon Stokes operator" );
+   return *static_cast< EpsilonStokesH* >( op )->p;
+}
+// three function handles as one P1VectorFunction (a view: the handles keep the components)
+static P1VectorFunction< double > vectorOf( const hh_function_t* f )
+{
+   if ( !f || !f[0] || !f[1] || !f[2] )
+      throw std::runtime_error( "epsilon: three component functions" );
+   return P1VectorFunction< double >( { static_cast< FunctionH* >( f[0] )->p, static_cast< FunctionH* >( f[1] )->p, static_cast< FunctionH* >( f[2] )->p } );
+}
+static std::shared_ptr< P1Function< double > > viscosityOf( const char* who, hh_function_t mu, int minL, int maxL )
+{
+   if ( !mu || minL < 0 || maxL < minL )
+      throw std::runtime_error( std::string( who ) + ": needs a viscosity function and 0 <= min_level <= max_level" );
+   return static_cast< FunctionH* >( mu )->p;
+}
+HYTEG_HOST_API int hyteg_host_epsilon_create( hh_storage_t s, int minL, int maxL, hh_function_t mu, hh_epsilon_t* out )
+{
+   return guarded( [&] {
+      auto h = std::make_unique< EpsilonH >();
+      h->mu  = viscosityOf( "epsilon_create", mu, minL, maxL );
+      h->p   = std::make_shared< Epsilon >( SP( s ), (uint_t) minL, (uint_t) maxL, *h->mu );
+      *out   = h.release();
+   } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_destroy( hh_epsilon_t op )
+{
+   return guarded( [&] { delete static_cast< EpsilonH* >( op ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_apply( hh_epsilon_t op, const hh_function_t* src, const hh_function_t* dst, int level, int flag, int update )
+{
+   return guarded( [&] { EP( op ).apply( vectorOf( src ), vectorOf( dst ), (uint_t) level, DoFType( flag ), update ? Add : Replace ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_compute_inverse_diagonal( hh_epsilon_t op )
+{
+   return guarded( [&] { EP( op ).computeInverseDiagonalOperatorValues(); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_inverse_diagonal( hh_epsilon_t op, hh_function_t* out )
+{
+   return guarded( [&] {
+      auto*      h = static_cast< EpsilonH* >( op );
+      const auto d = EP( op ).getInverseDiagonalValues();
+      for ( int k = 0; k < 3; ++k )
+      {
+         h->invDiag[k].p = viewOf( d, ( *d )[(uint_t) k] );
+         out[k]          = &h->invDiag[k];
+      }
+   } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_smooth_jac( hh_epsilon_t op, const hh_function_t* dst, const hh_function_t* rhs, const hh_function_t* src,
+                                                  double relax, int level, int flag )
+{
+   return guarded( [&] { EP( op ).smooth_jac( vectorOf( dst ), vectorOf( rhs ), vectorOf( src ), relax, (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_set_fused( hh_epsilon_t op, int on )
+{
+   return guarded( [&] { EP( op ).setFused( on != 0 ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_create( hh_storage_t s, int minL, int maxL, hh_function_t mu, hh_epsilon_stokes_t* out )
+{
+   return guarded( [&] {
+      auto h = std::make_unique< EpsilonStokesH >();
+      h->mu  = viscosityOf( "epsilon_stokes_create", mu, minL, maxL );
+      h->p   = std::make_shared< EpsilonStokes >( SP( s ), (uint_t) minL, (uint_t) maxL, *h->mu );
+      *out   = h.release();
+   } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_destroy( hh_epsilon_stokes_t op )
+{
+   return guarded( [&] { delete static_cast< EpsilonStokesH* >( op ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_apply( hh_epsilon_stokes_t op, hh_stokes_function_t src, hh_stokes_function_t dst, int level, int flag )
+{
+   return guarded( [&] { EPS( op ).apply( P1P1::fn( src ), P1P1::fn( dst ), (uint_t) level, DoFType( flag ) ); } );
+}
+// MinResSolver< P1P1ElementwiseAffineEpsilonStokesOperator >; preconditioner 0 identity, 1 StokesPressureBlockPreconditioner< .,
+// P1LumpedInvMassOperator > (solvertemplates::stokesMinResSolver, StokesSolverTemplates.hpp:54-69), 2 the same weighted with mu
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_create( hh_storage_t s, int minL, int maxL, int max_iter, double rel_tol, int preconditioner,
+                                                            hh_function_t mu, hh_epsilon_stokes_solver_t* out )
+{
+   return guarded( [&] {
+      auto storage = SP( s );
+      auto h       = std::make_unique< EpsilonStokesSolverH >();
+      if ( preconditioner == 0 )
+         h->preconditioner = std::make_shared< IdentityPreconditioner< EpsilonStokes > >();
+      else if ( preconditioner == 1 )
+         h->preconditioner =
+             std::make_shared< StokesPressureBlockPreconditioner< EpsilonStokes, P1LumpedInvMassOperator > >( storage, (uint_t) minL, (uint_t) maxL );
+      else if ( preconditioner == 2 )
+      {
+         h->mu             = viscosityOf( "epsilon_stokes_minres_create (viscosity-weighted preconditioner)", mu, minL, maxL );
+         h->preconditioner = std::make_shared< StokesViscosityWeightedPressureBlockPreconditioner< EpsilonStokes > >( storage, (uint_t) minL,
+                                                                                                                     (uint_t) maxL, *h->mu );
+      }
+      else
+         throw std::runtime_error( "epsilon_stokes_minres_create: unknown preconditioner" );
+      h->p = std::make_shared< MinResSolver< EpsilonStokes > >( storage, (uint_t) minL, (uint_t) maxL, (uint_t) max_iter, rel_tol, 1e-16,
+                                                                h->preconditioner );
+      *out = h.release();
+   } );
+}
+static EpsilonStokesSolverH& EPSS( hh_epsilon_stokes_solver_t solver )
+{
+   if ( !solver )
+      throw std::runtime_error( "null epsilon Stokes solver" );
+   return *static_cast< EpsilonStokesSolverH* >( solver );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_solve( hh_epsilon_stokes_solver_t solver, hh_epsilon_stokes_t op, hh_stokes_function_t x,
+                                                           hh_stokes_function_t b, int level )
+{
+   return guarded( [&] { EPSS( solver ).p->solve( EPS( op ), P1P1::fn( x ), P1P1::fn( b ), (uint_t) level ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_precondition( hh_epsilon_stokes_solver_t solver, hh_epsilon_stokes_t op, hh_stokes_function_t x,
+                                                                  hh_stokes_function_t b, int level )
+{
+   return guarded( [&] { EPSS( solver ).preconditioner->solve( EPS( op ), P1P1::fn( x ), P1P1::fn( b ), (uint_t) level ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_iterations( hh_epsilon_stokes_solver_t solver, int* iterations )
+{
+   return guarded( [&] { *iterations = (int) EPSS( solver ).p->getIterations(); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_destroy( hh_epsilon_stokes_solver_t solver )
+{
+   return guarded( [&] { delete static_cast< EpsilonStokesSolverH* >( solver ); } );
+}
+
 /* ---- P2 (single macro-cell) ---- */
 HYTEG_HOST_API int hyteg_host_p2function_create( hh_storage_t s, const char* name, int minL, int maxL, hh_p2function_t* out )
 {

@@ -41,6 +41,13 @@ class VectorFunction
       for ( int k = 0; k < 3; ++k )
          comp_.push_back( std::make_shared< ScalarFunction >( name + suffix[k], storage, minLevel, maxLevel ) );
    }
+   // a view of three existing scalar functions as the components of one vector function (shared ownership)
+   explicit VectorFunction( const std::vector< std::shared_ptr< ScalarFunction > >& components )
+   : comp_( components )
+   {
+      if ( comp_.size() != 3 || !comp_[0] || !comp_[1] || !comp_[2] )
+         throw std::runtime_error( "VectorFunction: three components" );
+   }
    uint_t                getDimension() const { return 3; }
    const ScalarFunction& operator[]( uint_t k ) const { return *comp_.at( k ); }
 

@@ -1275,6 +1275,58 @@ HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d( double*  
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_set_shape( int ny, int lz );
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points( int on );
 
+/* ---- b-5: variable-viscosity epsilon operator -div( 2 mu eps(u) ), eps(u) = ( grad u + grad u^T ) / 2 ------------------------
+ * Replaces, in ONE pass over the three velocity components, the nine P1ElementwiseOperator::apply calls of
+ * P1ElementwiseAffineEpsilonOperator::apply (src/mixed_operator/P1EpsilonOperator.hpp:89-164; forms::p1_epsilonvar_i_j_affine_q2)
+ * on one macro-cell.  The viscosity is a P1 function (its cell array `mu` at the same level), where the reference samples a
+ * std::function at the points of a degree-2 rule; the two coincide where mu is linear per micro-cell.  With constant barycentric
+ * gradients g_a the block for test component i and trial component j of micro-cell e is exact and closed:
+ *    A_e^{ij}[a][b] = mean( mu at the 4 vertices of e ) * |e| * ( delta_ij g_a . g_b + g_a[j] g_b[i] ).
+ * dst, src: HOST arrays of three device pointers (the cell arrays of the components).  Semantics per macro-cell as in b-4: at every
+ * point of the classes of `mask` the sum over the micro-cells of THIS macro-cell that contain the point; entries outside the mask
+ * are not written.  Levels 0..8; no dst may alias a src, mu or another dst. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_masked( double* const*       dst /* 3 */,
+                                                                          const double* const* src /* 3 */,
+                                                                          const double*        mu,
+                                                                          const double*        macro_vertex_coords /* 12 */,
+                                                                          int64_t              micro_edges_per_macro_edge,
+                                                                          unsigned             mask,
+                                                                          int                  update,
+                                                                          hyteg_hip_stream_t   stream );
+/* The same with a class mask per destination component (masks[3]): the components of a P1VectorFunction may carry different
+ * boundary conditions (P1EpsilonOperator.hpp applies block (i, j) with the flag on dst component i); a point that masks[i]
+ * excludes is not written in dst[i].  One launch per kernel kind for all three components. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_component_masks( double* const*       dst,
+                                                                                   const double* const* src,
+                                                                                   const double*        mu,
+                                                                                   const double*        macro_vertex_coords,
+                                                                                   int64_t              micro_edges_per_macro_edge,
+                                                                                   const unsigned*      masks /* 3 */,
+                                                                                   int                  update,
+                                                                                   hyteg_hip_stream_t   stream );
+/* Fused form of P1ElementwiseOperator::smooth_jac (src/hyteg/elementwiseoperators/P1ElementwiseOperator.cpp:288-331) on the three
+ * components, at the INNER points only:  dst_i = src_i + omega * inv_diag_i .* ( rhs_i - ( A src )_i ).  No dst may alias an input. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d( double* const*       dst,
+                                                                    const double* const* src,
+                                                                    const double* const* rhs,
+                                                                    const double* const* inv_diag,
+                                                                    const double*        mu,
+                                                                    const double*        macro_vertex_coords,
+                                                                    int64_t              micro_edges_per_macro_edge,
+                                                                    double               omega,
+                                                                    hyteg_hip_stream_t   stream );
+/* Replaces computeInverseDiagonalOperatorValues of the three diagonal blocks (what P1EpsilonOperator.hpp's extractInverseDiagonal
+ * reads): diag[i] += sum over the adjacent micro-cells e of this macro-cell of A_e^{ii}[a][a], at all points of the cell array. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_diagonal_macro_3d( double* const*     diag,
+                                                                      const double*      mu,
+                                                                      const double*      macro_vertex_coords,
+                                                                      int64_t            micro_edges_per_macro_edge,
+                                                                      hyteg_hip_stream_t stream );
+/* Tuning knobs as in b-4 (no counterpart in the reference): the brick shape of the inner-point z-march (0, 0 = the default of the
+ * level; EINVAL for a shape that is not compiled in), and the inner points by the one-thread-per-point kernel instead. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_set_shape( int ny, int lz );
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_set_inner_by_points( int on );
+
 /* ---- strong free-slip: projection onto the tangential plane ----------------------------------------------------------
  * Replaces vertexdof::macroface::projectNormal3D, vertexdof::macroedge::projectNormal3D and
  * vertexdof::macrovertex::projectNormal3D (src/hyteg/p1functionspace/freeslip/VertexDoFProjectNormal.hpp:43-97, 200-249,

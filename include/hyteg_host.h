@@ -289,6 +289,44 @@ HYTEG_HOST_API int hyteg_host_divkgrad_gmg_create_chebyshev( hh_storage_t s, int
 HYTEG_HOST_API int hyteg_host_divkgrad_solver_solve( hh_divkgrad_solver_t solver, hh_divkgrad_t op, hh_function_t x, hh_function_t b, int level );
 HYTEG_HOST_API int hyteg_host_divkgrad_solver_destroy( hh_divkgrad_solver_t solver );
 
+/* hyteg::P1ElementwiseAffineEpsilonOperator( storage, minLevel, maxLevel, viscosity ) (src/mixed_operator/P1EpsilonOperator.hpp:
+ * 89-164): -div( 2 mu eps(u) ) on a P1VectorFunction, here given as its three component functions (src / dst / rhs: arrays of three
+ * handles, e.g. the velocity components of a Stokes function).  The reference's viscosity is a std::function sampled at the points
+ * of a degree-2 rule; here mu is a P1 function that holds values on every level min_level..max_level (levels 0..8): the same
+ * operator where mu is linear per micro-cell.  The handle shares ownership of mu.  Every component is masked by its own boundary
+ * condition.  inverse_diagonal: three borrowed handles (the diagonals of the diagonal blocks, extractInverseDiagonal); smooth_jac
+ * is one fused launch on the inner points unless set_fused( 0 ) selects the composed passes of P1ElementwiseOperator.cpp:288-331. */
+typedef void* hh_epsilon_t;
+typedef void* hh_epsilon_stokes_t;
+typedef void* hh_epsilon_stokes_solver_t;
+HYTEG_HOST_API int hyteg_host_epsilon_create( hh_storage_t s, int min_level, int max_level, hh_function_t mu, hh_epsilon_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_destroy( hh_epsilon_t op );
+HYTEG_HOST_API int hyteg_host_epsilon_apply( hh_epsilon_t op, const hh_function_t* src /* 3 */, const hh_function_t* dst /* 3 */, int level, int flag,
+                                             int update );
+HYTEG_HOST_API int hyteg_host_epsilon_compute_inverse_diagonal( hh_epsilon_t op );
+HYTEG_HOST_API int hyteg_host_epsilon_inverse_diagonal( hh_epsilon_t op, hh_function_t* out /* 3, borrowed */ );
+HYTEG_HOST_API int hyteg_host_epsilon_smooth_jac( hh_epsilon_t op, const hh_function_t* dst, const hh_function_t* rhs, const hh_function_t* src,
+                                                  double relax, int level, int flag );
+HYTEG_HOST_API int hyteg_host_epsilon_set_fused( hh_epsilon_t op, int on );
+/* hyteg::P1P1ElementwiseAffineEpsilonStokesOperator( storage, minLevel, maxLevel, viscosity )
+ * (src/mixed_operator/P1P1ElementwiseAffineEpsilonStokesOperator.hpp:32-92) on P1 Stokes functions: the operator above on the
+ * velocity, the constant-stencil div / divT blocks and the PSPG block.  MinResSolver for it: preconditioner 0 identity, 1
+ * StokesPressureBlockPreconditioner< ., P1LumpedInvMassOperator > (solvertemplates::stokesMinResSolver,
+ * src/hyteg/solvers/solvertemplates/StokesSolverTemplates.hpp:54-69), 2 the same with the pressure action
+ * x.p = mu .* invLumpedMass .* b.p (mu: the viscosity function; null for 0 and 1).  minres_precondition applies the solver's
+ * preconditioner on its own: x = M^-1 b. */
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_create( hh_storage_t s, int min_level, int max_level, hh_function_t mu, hh_epsilon_stokes_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_destroy( hh_epsilon_stokes_t op );
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_apply( hh_epsilon_stokes_t op, hh_stokes_function_t src, hh_stokes_function_t dst, int level, int flag );
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_create( hh_storage_t s, int min_level, int max_level, int max_iter, double rel_tol,
+                                                            int preconditioner, hh_function_t mu /* or null */, hh_epsilon_stokes_solver_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_solve( hh_epsilon_stokes_solver_t solver, hh_epsilon_stokes_t op, hh_stokes_function_t x,
+                                                           hh_stokes_function_t b, int level );
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_precondition( hh_epsilon_stokes_solver_t solver, hh_epsilon_stokes_t op, hh_stokes_function_t x,
+                                                                  hh_stokes_function_t b, int level );
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_iterations( hh_epsilon_stokes_solver_t solver, int* iterations );
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_destroy( hh_epsilon_stokes_solver_t solver );
+
 /* ---- grid transfer ---- */
 HYTEG_HOST_API int hyteg_host_restrict( hh_function_t f, int source_level, int flag );
 HYTEG_HOST_API int hyteg_host_prolongate( hh_function_t f, int source_level, int flag );

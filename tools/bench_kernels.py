@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel timings of the whole P1 hot path on one GPU (level 8 by default) with algorithmic GB/s, plus V-cycle
 timings through the host layer.  Not the headline bench (that is bench.py); this is the evidence table for
-DESIGN.md section 3.  Usage: python tools/bench_kernels.py [--level 8] [--reps 200]"""
+DESIGN.md section 3.  Usage: python tools/bench_kernels.py [--level 8] [--reps 200]
+--only epsilon: the rows of the epsilon operator alone, levels 6..level."""
 import argparse
 import json
 import sys
@@ -57,6 +58,74 @@ def cpu_rows(L, w, rows):
         print(f"{'CPU 1 core: ' + name:58s} {us:12.1f} us  {nbytes / us * 1e-3:8.2f} GB/s  {updates / us * 1e-3:8.3f} GDoF/s", flush=True)
 
 
+def epsilon_rows(top_level, reps):
+    """--only epsilon: one macro-cell, inner points, levels 6..top_level.  Per level, in the same run: the fused epsilon
+    apply and Jacobi step (z-march), every compiled brick shape, the one-thread-per-point form, NINE div-k-grad applies (what a
+    block-composed epsilon operator costs at the least) and a copy of the same seven arrays.  Every operand class is a ring of its
+    own, each 2.2 x the Infinity Cache, as for the div-k-grad rows."""
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    st = host.Storage.from_gmsh(ROOT / "hyteg_amd/data/meshes/tet_1el.msh")
+    st.set_stream(sh)
+    tet = [list(map(float, v)) for v in st.local_cell(0)[1]]
+    rows = []
+    for L in range(6, top_level + 1):
+        n, inner = capi.cell_size(L), capi.cell_inner_size(L)
+        nbuf = max(6, -(-int(2.2 * 256 * 2**20) // (n * 8)))
+        nbuf += -nbuf % 3  # three consecutive arrays per call
+        S, D, X = ([torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)] for _ in range(3))
+        M = [0.5 + 49.5 * torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf // 3)]  # the viscosity ring
+        p3 = lambda t, k, o=0: [t[(3 * k + o + c) % nbuf].data_ptr() for c in range(3)]  # noqa: E731
+        pm = lambda k: M[k % len(M)].data_ptr()  # noqa: E731
+
+        def timeit(name, fn, nbytes, r=reps):
+            for k in range(5):
+                fn(k)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for k in range(r):
+                fn(k)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) * 1e3 / r
+            rows.append(dict(kernel=name, level=L, us=us, GBps=nbytes / us * 1e-3, GDoFps=3 * inner / us * 1e-3, algorithmic_bytes=nbytes))
+            print(f"level {L}  {name:62s} {us:10.2f} us  {nbytes / us * 1e-3:8.1f} GB/s  {3 * inner / us * 1e-3:8.2f} GDoF/s", flush=True)
+
+        apply_ = lambda k: capi.p1_elementwise_epsilon_apply_macro_3d_masked(p3(D, k), p3(S, k), pm(k), tet, 1 << L, 1 << 14, 0, sh)  # noqa: E731
+        timeit("epsilon apply Replace, inner points (z-march, default shape)", apply_, 56 * inner)
+        for ny, lz in capi.EPSILON_SHAPES:
+            capi.p1_elementwise_epsilon_set_shape(ny, lz)
+            timeit(f"epsilon apply Replace, inner points (z-march, shape {ny} x {lz})", apply_, 56 * inner)
+        capi.p1_elementwise_epsilon_set_shape(0, 0)
+        timeit("epsilon apply Add, inner points (z-march)",
+               lambda k: capi.p1_elementwise_epsilon_apply_macro_3d_masked(p3(D, k), p3(S, k), pm(k), tet, 1 << L, 1 << 14, 1, sh), 80 * inner)
+        timeit("epsilon Jacobi fused (z-march)",
+               lambda k: capi.p1_elementwise_epsilon_jacobi_macro_3d(p3(D, k), p3(S, k), p3(X, 2 * k), p3(X, 2 * k, 3), pm(k), tet, 1 << L, 0.66, sh),
+               104 * inner)
+        capi.p1_elementwise_epsilon_set_inner_by_points(True)
+        timeit("epsilon apply Replace, inner points (one thread per point)", apply_, 56 * inner, r=max(3, reps // 10))
+        capi.p1_elementwise_epsilon_set_inner_by_points(False)
+
+        def nine_divkgrad(k):
+            d, s_ = p3(D, k), p3(S, k)
+            for i in range(3):
+                for j in range(3):
+                    capi.p1_elementwise_divkgrad_apply_macro_3d_masked(d[i], s_[j], pm(k), tet, 1 << L, 1 << 14, 0 if j == 0 else 1, sh)
+
+        timeit("epsilon yardstick: nine div-k-grad applies (3 Replace, 6 Add)", nine_divkgrad, (3 * 24 + 6 * 32) * inner)
+
+        def copy7(k):
+            d, s_ = p3(D, k), p3(S, k)
+            capi.p1_assign_cell(d[0], [2.0, -1.0], [s_[0], pm(k)], L, sh)
+            capi.p1_assign_cell(d[1], [2.0], [s_[1]], L, sh)
+            capi.p1_assign_cell(d[2], [2.0], [s_[2]], L, sh)
+
+        timeit("epsilon copy floor (assign: four arrays read, three written)", copy7, 56 * inner)
+        del S, D, X, M
+    print(json.dumps({"levels": list(range(6, top_level + 1)), "device": capi.device_name(), "kernels": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", type=int, default=8)
@@ -67,6 +136,9 @@ def main():
                          "SOR, the Jacobi composition, restriction and prolongation (BASELINE.md section 2) -- a reported baseline")
     args = ap.parse_args()
     L, reps = args.level, args.reps
+    if args.only == "epsilon":
+        epsilon_rows(min(L, 8), reps)
+        return
     n, inner = capi.cell_size(L), capi.cell_inner_size(L)
     nc = capi.cell_size(L - 1)
     stream = torch.cuda.current_stream()
