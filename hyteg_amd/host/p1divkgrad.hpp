@@ -81,14 +81,7 @@ class P1ElementwiseDivKGrad
                       "P1ElementwiseDivKGrad: diagonal" );
          } );
          invDiag_->sumSharedCopies( l, All );
-         // invertElementwise: set-up time, on the host
-         std::vector< double > h( (size_t) hyteg_hip_cell_size( (int) l ) );
-         storage_->forLocalCells( [&]( uint_t c, const MacroCell& ) {
-            invDiag_->copyCellToHost( c, l, h.data() );
-            for ( double& v : h )
-               v = v != 0.0 ? 1.0 / v : 0.0;
-            invDiag_->copyCellFromHost( c, l, h.data() );
-         } );
+         invertElementwise( *invDiag_, l );
       }
    }
    std::shared_ptr< P1Function< double > > getInverseDiagonalValues() const
@@ -135,18 +128,7 @@ class P1ElementwiseDivKGrad
       } );
       dst.endSumSharedCopies( level, flag );
       storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
-         const unsigned shell = storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL;
-         if ( !shell )
-            return;
-         double*       d     = dst.getCellPointer( c, level );
-         const double* a[2]  = { rhs.getCellPointer( c, level ), d };
-         const double  s1[2] = { 1.0, -1.0 };
-         hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, a, s1, (int) level, shell, storage_->stream() ), "smooth_jac: shell residual" );
-         const double* m[2] = { invDiag.getCellPointer( c, level ), d };
-         hipCheck( hyteg_hip_p1_vector_cell_masked( 2, d, 2, m, nullptr, (int) level, shell, storage_->stream() ), "smooth_jac: shell scale" );
-         const double* u[2]  = { src.getCellPointer( c, level ), d };
-         const double  s2[2] = { 1.0, omega };
-         hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, u, s2, (int) level, shell, storage_->stream() ), "smooth_jac: shell update" );
+         smoothJacShellPasses( dst, rhs, invDiag, src, omega, c, level, storage_->maskFor( cell, flag ) & HYTEG_HIP_MASK_SHELL );
       } );
    }
 
@@ -159,12 +141,6 @@ class P1ElementwiseDivKGrad
    }
 
  private:
-   static void coordsOf( const MacroCell& cell, double cc[12] )
-   {
-      for ( int v = 0; v < 4; ++v )
-         for ( int r = 0; r < 3; ++r )
-            cc[3 * v + r] = cell.coords[v][r];
-   }
    void kernel( const P1Function< double >& out, const P1Function< double >& src, uint_t c, const MacroCell& cell, uint_t level, unsigned mask,
                 int update ) const
    {

@@ -53,9 +53,7 @@ class P1ElementwiseDiffusion
          if ( mask == 0 )
             return;
          double cc[12];
-         for ( int v = 0; v < 4; ++v )
-            for ( int r = 0; r < 3; ++r )
-               cc[3 * v + r] = cell.coords[v][r];
+         coordsOf( cell, cc );
          hipCheck( hyteg_hip_p1_elementwise_diffusion_apply_macro_3d_masked( out.getCellPointer( c, level ), src.getCellPointer( c, level ), cc, n, mask,
                                                                              update, storage_->stream() ),
                    "P1ElementwiseDiffusion::apply: apply_macro_3D" );
@@ -82,22 +80,13 @@ class P1ElementwiseDiffusion
          invDiag_->interpolate( 0.0, l, All );
          storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
             double cc[12];
-            for ( int v = 0; v < 4; ++v )
-               for ( int r = 0; r < 3; ++r )
-                  cc[3 * v + r] = cell.coords[v][r];
+            coordsOf( cell, cc );
             const int64_t n = int64_t( 1 ) << l;
             hipCheck( hyteg_hip_p1_elementwise_diffusion_diagonal_macro_3d( invDiag_->getCellPointer( c, l ), cc, n, double( n ), storage_->stream() ),
                       "P1ElementwiseDiffusion: diagonal" );
          } );
          invDiag_->sumSharedCopies( l, All );
-         // invertElementwise: set-up time, on the host
-         std::vector< double > h( (size_t) hyteg_hip_cell_size( (int) l ) );
-         storage_->forLocalCells( [&]( uint_t c, const MacroCell& ) {
-            invDiag_->copyCellToHost( c, l, h.data() );
-            for ( double& v : h )
-               v = v != 0.0 ? 1.0 / v : 0.0;
-            invDiag_->copyCellFromHost( c, l, h.data() );
-         } );
+         invertElementwise( *invDiag_, l );
       }
    }
    std::shared_ptr< P1Function< double > > getInverseDiagonalValues() const

@@ -90,18 +90,10 @@ class P1ElementwiseAffineEpsilonOperator
             hipCheck( hyteg_hip_p1_elementwise_epsilon_diagonal_macro_3d( d, mu_.getCellPointer( c, l ), cc, int64_t( 1 ) << l, storage_->stream() ),
                       "P1ElementwiseAffineEpsilonOperator: diagonal" );
          } );
-         std::vector< double > h( (size_t) hyteg_hip_cell_size( (int) l ) );
          for ( uint_t k = 0; k < 3; ++k )
          {
-            const P1Function< double >& f = ( *invDiag_ )[k];
-            f.sumSharedCopies( l, All );
-            // invertElementwise: set-up time, on the host
-            storage_->forLocalCells( [&]( uint_t c, const MacroCell& ) {
-               f.copyCellToHost( c, l, h.data() );
-               for ( double& v : h )
-                  v = v != 0.0 ? 1.0 / v : 0.0;
-               f.copyCellFromHost( c, l, h.data() );
-            } );
+            ( *invDiag_ )[k].sumSharedCopies( l, All );
+            invertElementwise( ( *invDiag_ )[k], l );
          }
       }
    }
@@ -163,30 +155,11 @@ class P1ElementwiseAffineEpsilonOperator
          dst[k].sumSharedCopies( level, flag[k] );
       storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
          for ( uint_t k = 0; k < 3; ++k )
-         {
-            const unsigned shell = storage_->maskFor( cell, flag[k] ) & HYTEG_HIP_MASK_SHELL;
-            if ( !shell )
-               continue;
-            double*       d     = dst[k].getCellPointer( c, level );
-            const double* a[2]  = { rhs[k].getCellPointer( c, level ), d };
-            const double  s1[2] = { 1.0, -1.0 };
-            hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, a, s1, (int) level, shell, storage_->stream() ), "smooth_jac: shell residual" );
-            const double* m[2] = { invDiag[k].getCellPointer( c, level ), d };
-            hipCheck( hyteg_hip_p1_vector_cell_masked( 2, d, 2, m, nullptr, (int) level, shell, storage_->stream() ), "smooth_jac: shell scale" );
-            const double* u[2]  = { src[k].getCellPointer( c, level ), d };
-            const double  s2[2] = { 1.0, omega };
-            hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, u, s2, (int) level, shell, storage_->stream() ), "smooth_jac: shell update" );
-         }
+            smoothJacShellPasses( dst[k], rhs[k], invDiag[k], src[k], omega, c, level, storage_->maskFor( cell, flag[k] ) & HYTEG_HIP_MASK_SHELL );
       } );
    }
 
  private:
-   static void coordsOf( const MacroCell& cell, double cc[12] )
-   {
-      for ( int v = 0; v < 4; ++v )
-         for ( int r = 0; r < 3; ++r )
-            cc[3 * v + r] = cell.coords[v][r];
-   }
    void checkDistinct( const char* who, const dstType& dst, std::initializer_list< const srcType* > inputs ) const
    {
       bool bad = false;

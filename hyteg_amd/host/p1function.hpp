@@ -557,4 +557,45 @@ class P1Function
    std::vector< std::vector< double* > >                                 data_;
 };
 
+// ---- what the elementwise operators share (p1elementwise.hpp, p1divkgrad.hpp, p1epsilon.hpp) ----
+
+// a macro-cell's vertices as the macro_vertex_coords of the C-ABI
+inline void coordsOf( const MacroCell& cell, double cc[12] )
+{
+   for ( int v = 0; v < 4; ++v )
+      for ( int r = 0; r < 3; ++r )
+         cc[3 * v + r] = cell.coords[v][r];
+}
+
+// P1Function::invertElementwise of an assembled diagonal: set-up time, on the host
+inline void invertElementwise( const P1Function< double >& f, uint_t level )
+{
+   std::vector< double > h( (size_t) hyteg_hip_cell_size( (int) level ) );
+   f.getStorage()->forLocalCells( [&]( uint_t c, const MacroCell& ) {
+      f.copyCellToHost( c, level, h.data() );
+      for ( double& v : h )
+         v = v != 0.0 ? 1.0 / v : 0.0;
+      f.copyCellFromHost( c, level, h.data() );
+   } );
+}
+
+// the three vector passes of P1ElementwiseOperator::smooth_jac that follow dst = A src (P1ElementwiseOperator.cpp:288-331),
+//   dst = rhs - dst ; dst = invDiag .* dst ; dst = src + omega dst,   on the shell classes `shell` of cell c
+inline void smoothJacShellPasses( const P1Function< double >& dst, const P1Function< double >& rhs, const P1Function< double >& invDiag,
+                                  const P1Function< double >& src, double omega, uint_t c, uint_t level, unsigned shell )
+{
+   if ( !shell )
+      return;
+   const hyteg_hip_stream_t stream = dst.getStorage()->stream();
+   double*                  d      = dst.getCellPointer( c, level );
+   const double*            a[2]   = { rhs.getCellPointer( c, level ), d };
+   const double             s1[2]  = { 1.0, -1.0 };
+   hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, a, s1, (int) level, shell, stream ), "smooth_jac: shell residual" );
+   const double* m[2] = { invDiag.getCellPointer( c, level ), d };
+   hipCheck( hyteg_hip_p1_vector_cell_masked( 2, d, 2, m, nullptr, (int) level, shell, stream ), "smooth_jac: shell scale" );
+   const double* u[2]  = { src.getCellPointer( c, level ), d };
+   const double  s2[2] = { 1.0, omega };
+   hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, u, s2, (int) level, shell, stream ), "smooth_jac: shell update" );
+}
+
 } // namespace hyteg
