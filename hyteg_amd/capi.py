@@ -173,12 +173,18 @@ SIGNATURES = {
     "hyteg_hip_p2_elementwise_diffusion_element_matrices": (_i, [_dp, _i64, _dp]),
     "hyteg_hip_p1_elementwise_divkgrad_apply_macro_3d_masked": (_i, [_vp, _vp, _vp, _dp, _i64, C.c_uint, _i, _vp]),
     "hyteg_hip_p1_elementwise_divkgrad_jacobi_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _vp]),
+    "hyteg_hip_p1_elementwise_divkgrad_residual_macro_3d": (_i, [_vp, _vp, _vp, _vp, _dp, _i64, _vp]),
+    "hyteg_hip_p1_elementwise_divkgrad_chebyshev_start_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _vp]),
+    "hyteg_hip_p1_elementwise_divkgrad_chebyshev_step_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _d, _i, _vp]),
     "hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d": (_i, [_vp, _vp, _dp, _i64, _vp]),
     "hyteg_hip_p1_elementwise_divkgrad_set_shape": (_i, [_i, _i]),
     "hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points": (_i, [_i]),
     "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_masked": (_i, [_vp, _vp, _vp, _dp, _i64, C.c_uint, _i, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_component_masks": (_i, [_vp, _vp, _vp, _dp, _i64, C.POINTER(C.c_uint), _i, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _vp]),
+    "hyteg_hip_p1_elementwise_epsilon_residual_macro_3d": (_i, [_vp, _vp, _vp, _vp, _dp, _i64, C.c_uint, _vp]),
+    "hyteg_hip_p1_elementwise_epsilon_chebyshev_start_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, C.c_uint, _vp]),
+    "hyteg_hip_p1_elementwise_epsilon_chebyshev_step_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _d, _i, C.c_uint, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_diagonal_macro_3d": (_i, [_vp, _vp, _dp, _i64, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_set_shape": (_i, [_i, _i]),
     "hyteg_hip_p1_elementwise_epsilon_set_inner_by_points": (_i, [_i]),
@@ -907,6 +913,28 @@ def p1_elementwise_divkgrad_jacobi_macro_3d(dst, src, rhs, inv_diag, k, coords, 
           "p1_elementwise_divkgrad_jacobi_macro_3d")
 
 
+def p1_elementwise_divkgrad_residual_macro_3d(dst, src, rhs, k, coords, micro_edges, stream=0):
+    """dst = rhs - A src at the inner points"""
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_divkgrad_residual_macro_3d(dst, src, rhs, k, a, int(micro_edges), stream),
+          "p1_elementwise_divkgrad_residual_macro_3d")
+
+
+def p1_elementwise_divkgrad_chebyshev_start_macro_3d(t_out, rhs, x, inv_diag, k, coords, micro_edges, stream=0):
+    """t_out = inv_diag .* ( rhs - A x ) at the inner points; x is not updated"""
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_divkgrad_chebyshev_start_macro_3d(t_out, rhs, x, inv_diag, k, a, int(micro_edges), stream),
+          "p1_elementwise_divkgrad_chebyshev_start_macro_3d")
+
+
+def p1_elementwise_divkgrad_chebyshev_step_macro_3d(t_out, x, t_in, inv_diag, k, coords, micro_edges, c_prev, c_cur, has_prev, stream=0):
+    """t_out = inv_diag .* ( A t_in ), x = ( x + c_prev t_in ) + c_cur t_out (first summand only if has_prev) at the inner points"""
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_divkgrad_chebyshev_step_macro_3d(t_out, x, t_in, inv_diag, k, a, int(micro_edges), float(c_prev),
+                                                                          float(c_cur), 1 if has_prev else 0, stream),
+          "p1_elementwise_divkgrad_chebyshev_step_macro_3d")
+
+
 def p1_elementwise_divkgrad_diagonal_macro_3d(diag, k, coords, micro_edges, stream=0):
     a = (C.c_double * 12)(*_c12(coords))
     check(lib().hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d(diag, k, a, int(micro_edges), stream),
@@ -950,6 +978,30 @@ def p1_elementwise_epsilon_jacobi_macro_3d(dst, src, rhs, inv_diag, mu, coords, 
     a = (C.c_double * 12)(*_c12(coords))
     check(lib().hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d(_ptr3(dst), _ptr3(src), _ptr3(rhs), _ptr3(inv_diag), mu, a, int(micro_edges),
                                                                  float(omega), stream), "p1_elementwise_epsilon_jacobi_macro_3d")
+
+
+def p1_elementwise_epsilon_residual_macro_3d(dst, src, rhs, mu, coords, micro_edges, comps=7, stream=0):
+    """dst_i = rhs_i - ( A src )_i at the inner points; three device pointers per argument; comps: bit i = component i is written"""
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_epsilon_residual_macro_3d(_ptr3(dst), _ptr3(src), _ptr3(rhs), mu, a, int(micro_edges), int(comps), stream),
+          "p1_elementwise_epsilon_residual_macro_3d")
+
+
+def p1_elementwise_epsilon_chebyshev_start_macro_3d(t_out, rhs, x, inv_diag, mu, coords, micro_edges, comps=7, stream=0):
+    """t_out_i = inv_diag_i .* ( rhs_i - ( A x )_i ) at the inner points; x is not updated"""
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_epsilon_chebyshev_start_macro_3d(_ptr3(t_out), _ptr3(rhs), _ptr3(x), _ptr3(inv_diag), mu, a,
+                                                                          int(micro_edges), int(comps), stream),
+          "p1_elementwise_epsilon_chebyshev_start_macro_3d")
+
+
+def p1_elementwise_epsilon_chebyshev_step_macro_3d(t_out, x, t_in, inv_diag, mu, coords, micro_edges, c_prev, c_cur, has_prev, comps=7, stream=0):
+    """t_out_i = inv_diag_i .* ( A t_in )_i, x_i = ( x_i + c_prev t_in_i ) + c_cur t_out_i (first summand only if has_prev)"""
+    a = (C.c_double * 12)(*_c12(coords))
+    check(lib().hyteg_hip_p1_elementwise_epsilon_chebyshev_step_macro_3d(_ptr3(t_out), _ptr3(x), _ptr3(t_in), _ptr3(inv_diag), mu, a,
+                                                                         int(micro_edges), float(c_prev), float(c_cur), 1 if has_prev else 0,
+                                                                         int(comps), stream),
+          "p1_elementwise_epsilon_chebyshev_step_macro_3d")
 
 
 def p1_elementwise_epsilon_diagonal_macro_3d(diag, mu, coords, micro_edges, stream=0):

@@ -12,6 +12,8 @@
 //  * zmarch_kernel: the inner points (24 micro-cells each), a register z-march in the manner of kernels_apply_zmarch.hpp.  A wave
 //    owns a brick of NY rows x 64 x-positions x LZ slices, loads every row segment of the NC sources AND of the coefficient once
 //    through buffer loads with wave-uniform bases, keeps the live slices of all of them in registers and stores dst nontemporally.
+//    Modes (enum Mode): Replace, Add, the fused Jacobi step, and the fused steps of a multigrid cycle -- the residual and the two
+//    kinds of Chebyshev step, the second with x as a second store stream.
 //    The x-1 / x+1 neighbours are DPP wave shifts of the loaded rows themselves: coefficient * K * u is not linear in a partial sum
 //    that could be shifted instead, as the constant-stencil kernel does.
 //  * shell_kernel / inner_point_kernel: one thread per point, testing which of the point's 24 micro-cells lie inside the macro-cell
@@ -67,8 +69,15 @@ enum Mode
    REPLACE = 0,
    ADD     = 1,
    JACOBI  = 2, // dst_i = src_i + omega * invdiag_i * ( rhs_i - ( A src )_i )
-   DIAG    = 3  // dst_i += diagonal of A^{ii} (point kernels only; src unused)
+   DIAG    = 3, // dst_i += diagonal of A^{ii} (point kernels only; src unused)
+   // the fused steps of a multigrid residual and of a Chebyshev smoother (inner points only; the shell is composed by the host layer)
+   RESIDUAL   = 4, // dst_i = rhs_i - ( A src )_i
+   CHEB_START = 5, // dst_i = invdiag_i * ( rhs_i - ( A src )_i )
+   CHEB_STEP  = 6  // dst_i = invdiag_i * ( A src )_i,  x_i = ( x_i + cPrev * src_i ) + cCur * dst_i  (first summand only if hasPrev);
+                   // src is t_in and dst is t_out.  x is no stencil source: read and rewritten at the output points only, as Add reads dst
 };
+constexpr bool reads_rhs( int m ) { return m == JACOBI || m == RESIDUAL || m == CHEB_START; }
+constexpr bool reads_invdiag( int m ) { return m == JACOBI || m == CHEB_START || m == CHEB_STEP; }
 
 template < class OP >
 struct Args
@@ -77,8 +86,8 @@ struct Args
    double*              dst[NC];
    const double*        src[NC];
    const double*        coef;
-   const double*        rhs[NC];     // JACOBI
-   const double*        invdiag[NC]; // JACOBI
+   const double*        rhs[NC];     // JACOBI, RESIDUAL, CHEB_START
+   const double*        invdiag[NC]; // JACOBI, CHEB_START, CHEB_STEP
    unsigned             bytes;       // size of a cell array in bytes (buffer range)
    int                  N;           // 2^level + 1
    unsigned             comps;       // z-march / inner point kernel: bit i = destination component i is written.  Tested where
@@ -86,6 +95,10 @@ struct Args
    unsigned             masks[NC];   // shell kernel: the class mask of each destination component
    double               omega;
    typename OP::Weights W;
+   // CHEB_STEP (behind W: the kernel argument offsets of the other modes stay where they were)
+   double* x[NC];
+   double  cPrev, cCur;
+   int     hasPrev;
 };
 
 // the 15 stencil values of one marched array around slice Q, row j + 1, in the C-ABI's direction order (kStencilOffsC);
@@ -141,8 +154,10 @@ __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void zmarch_kernel( co
    {
       rs[c] = __builtin_amdgcn_make_buffer_rsrc( const_cast< double* >( A.src[c] ), 0, A.bytes, 0x00020000 );
       rd[c] = __builtin_amdgcn_make_buffer_rsrc( A.dst[c], 0, A.bytes, 0x00020000 );
-      rr[c] = __builtin_amdgcn_make_buffer_rsrc( const_cast< double* >( MODE == JACOBI ? A.rhs[c] : A.src[c] ), 0, A.bytes, 0x00020000 );
-      ri[c] = __builtin_amdgcn_make_buffer_rsrc( const_cast< double* >( MODE == JACOBI ? A.invdiag[c] : A.src[c] ), 0, A.bytes, 0x00020000 );
+      // rr: the rhs, or the x of CHEB_STEP (its second store stream)
+      rr[c] = __builtin_amdgcn_make_buffer_rsrc( const_cast< double* >( MODE == CHEB_STEP ? A.x[c] : ( reads_rhs( MODE ) ? A.rhs[c] : A.src[c] ) ), 0,
+                                                 A.bytes, 0x00020000 );
+      ri[c] = __builtin_amdgcn_make_buffer_rsrc( const_cast< double* >( reads_invdiag( MODE ) ? A.invdiag[c] : A.src[c] ), 0, A.bytes, 0x00020000 );
    }
    rs[NC] = __builtin_amdgcn_make_buffer_rsrc( const_cast< double* >( A.coef ), 0, A.bytes, 0x00020000 );
 
@@ -180,7 +195,7 @@ __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void zmarch_kernel( co
    [&]< int... Is >( std::integer_sequence< int, Is... > ) { ( load_slice( std::integral_constant< int, Is >{}, baseq[Is], Wqs[Is] ), ... ); }
    ( std::make_integer_sequence < int, ( 2 + PFD <= LZ + 2 ? 2 + PFD : LZ + 2 ) > {} );
 
-   // the further arrays of Add / Jacobi at the output points, PFD slices ahead of their use like the source slices
+   // the further arrays of every mode but Replace at the output points, PFD slices ahead of their use like the source slices
    double EX0[NC][LZ][NY], EX1[NC][LZ][NY];
    auto   load_extra = [&]( auto sc ) {
       constexpr int s = decltype( sc )::value;
@@ -199,10 +214,16 @@ __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void zmarch_kernel( co
             {
                if constexpr ( MODE == ADD )
                   EX0[c][s][j] = zm_load2< double, 2 >( rd[c], vo, ie * 8 ); // read once, rewritten right after: nontemporal
+               else if constexpr ( MODE == CHEB_STEP )
+               {
+                  EX0[c][s][j] = zm_load2< double, 2 >( rr[c], vo, ie * 8 ); // x: as Add's dst
+                  EX1[c][s][j] = zm_load2< double >( ri[c], vo, ie * 8 );
+               }
                else
                {
                   EX0[c][s][j] = zm_load2< double >( rr[c], vo, ie * 8 );
-                  EX1[c][s][j] = zm_load2< double >( ri[c], vo, ie * 8 );
+                  if constexpr ( reads_invdiag( MODE ) )
+                     EX1[c][s][j] = zm_load2< double >( ri[c], vo, ie * 8 );
                }
             }
             ie += W - ( t.y0 + j );
@@ -257,10 +278,21 @@ __global__ __launch_bounds__( 64 * kZMarchWavesPerBlock ) void zmarch_kernel( co
                out = acc[c];
             else if constexpr ( MODE == ADD )
                out = acc[c] + EX0[c][s][j];
-            else
+            else if constexpr ( MODE == JACOBI )
                out = a0[c] + A.omega * ( EX1[c][s][j] * ( EX0[c][s][j] - acc[c] ) );
+            else if constexpr ( MODE == RESIDUAL )
+               out = EX0[c][s][j] - acc[c];
+            else if constexpr ( MODE == CHEB_START )
+               out = EX1[c][s][j] * ( EX0[c][s][j] - acc[c] );
+            else
+               out = EX1[c][s][j] * acc[c];
             const bool write = on && ( NC == 1 || ( ( A.comps >> c ) & 1u ) );
             zm_store2< double, kStAux >( rd[c], write ? lane_off : -8, io * 8, out );
+            if constexpr ( MODE == CHEB_STEP )
+            {
+               const double xp = A.hasPrev ? EX0[c][s][j] + A.cPrev * a0[c] : EX0[c][s][j];
+               zm_store2< double, kStAux >( rr[c], write ? lane_off : -8, io * 8, xp + A.cCur * out );
+            }
          }
          io += R;
       }
@@ -376,6 +408,16 @@ __global__ __launch_bounds__( kPointThreads ) void inner_point_kernel( const Arg
             out = acc[c];
          else if ( MODE == JACOBI )
             out = A.src[c][i] + A.omega * ( A.invdiag[c][i] * ( A.rhs[c][i] - acc[c] ) );
+         else if ( MODE == RESIDUAL )
+            out = A.rhs[c][i] - acc[c];
+         else if ( MODE == CHEB_START )
+            out = A.invdiag[c][i] * ( A.rhs[c][i] - acc[c] );
+         else if ( MODE == CHEB_STEP )
+         {
+            out             = A.invdiag[c][i] * acc[c];
+            const double xp = A.hasPrev ? A.x[c][i] + A.cPrev * A.src[c][i] : A.x[c][i];
+            A.x[c][i]       = xp + A.cCur * out;
+         }
          else
             out = acc[c] + A.dst[c][i];
          A.dst[c][i] = out;

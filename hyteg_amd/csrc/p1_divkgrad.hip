@@ -1,7 +1,8 @@
 // C-ABI entry points of the variable-coefficient P1 diffusion operator -div( k grad u ) on one macro-cell: the seam of the generated
 // operatorgeneration::P1ElementwiseDivKGrad (apply_macro_3D / computeInverseDiagonalOperatorValues_macro_3D of module
 // hyteg_operators; known-answer test tests/hyteg/convergence/ElementwiseDivKGradCGConvergenceTest.cpp) and the fused form of
-// P1ElementwiseOperator::smooth_jac (src/hyteg/elementwiseoperators/P1ElementwiseOperator.cpp:288-331).  Kernels: kernels_varcoef.hpp with the policy of kernels_divkgrad.hpp.
+// P1ElementwiseOperator::smooth_jac (src/hyteg/elementwiseoperators/P1ElementwiseOperator.cpp:288-331), of the residual of a multigrid
+// cycle (GeometricMultigridSolver.hpp:240-246) and of the steps of ChebyshevSmoother::solve (ChebyshevSmoother.hpp:165-212).  Kernels: kernels_varcoef.hpp with the policy of kernels_divkgrad.hpp.
 #include "kernels_divkgrad.hpp"
 #include "varcoef_launch.hpp"
 
@@ -19,7 +20,12 @@ struct Launch
 {
    using OP     = DivKGrad;
    using Shapes = Bricks< Brick< 2, 4 >, Brick< 2, 8 >, Brick< 1, 8 > >;
-   static Shape level_shape( int level ) { return level <= 7 ? Shape{ 2, 4 } : Shape{ 2, 8 }; }
+   template < int MODE, int NY, int LZ >
+   static constexpr bool compiled()
+   {
+      return true;
+   }
+   static Shape level_shape( int level, int /* mode */ ) { return level <= 7 ? Shape{ 2, 4 } : Shape{ 2, 8 }; }
    static inline Shape shape_override{ 0, 0 };
    // measurement switch (tools/bench_kernels.py): the inner points by the one-thread-per-point kernel instead of the z-march
    static inline bool inner_by_points = false;
@@ -103,6 +109,49 @@ HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_jacobi_macro_3d( double*    
       return rc;
    A.dst[0] = dst, A.src[0] = src, A.coef = k, A.rhs[0] = rhs, A.invdiag[0] = inv_diag, A.omega = omega, A.comps = 1u;
    return launch_inner< Launch, JACOBI >( A, level, as_stream( stream ) );
+}
+
+// the residual of a multigrid cycle (GeometricMultigridSolver.hpp:240-246) and the steps of ChebyshevSmoother::solve
+// (ChebyshevSmoother.hpp:165-212), each in one launch over the inner points
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_residual_macro_3d( double*            dst,
+                                                                       const double*      src,
+                                                                       const double*      rhs,
+                                                                       const double*      k,
+                                                                       const double*      macro_vertex_coords,
+                                                                       int64_t            micro_edges_per_macro_edge,
+                                                                       hyteg_hip_stream_t stream )
+{
+   return residual_entry< Launch, false >( "p1_elementwise_divkgrad_residual_macro_3d", prepare, &dst, &src, &rhs, nullptr, k, macro_vertex_coords,
+                                           micro_edges_per_macro_edge, 1u, as_stream( stream ) );
+}
+
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_chebyshev_start_macro_3d( double*            t_out,
+                                                                              const double*      rhs,
+                                                                              const double*      x,
+                                                                              const double*      inv_diag,
+                                                                              const double*      k,
+                                                                              const double*      macro_vertex_coords,
+                                                                              int64_t            micro_edges_per_macro_edge,
+                                                                              hyteg_hip_stream_t stream )
+{
+   return residual_entry< Launch, true >( "p1_elementwise_divkgrad_chebyshev_start_macro_3d", prepare, &t_out, &x, &rhs, &inv_diag, k,
+                                          macro_vertex_coords, micro_edges_per_macro_edge, 1u, as_stream( stream ) );
+}
+
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_chebyshev_step_macro_3d( double*            t_out,
+                                                                             double*            x,
+                                                                             const double*      t_in,
+                                                                             const double*      inv_diag,
+                                                                             const double*      k,
+                                                                             const double*      macro_vertex_coords,
+                                                                             int64_t            micro_edges_per_macro_edge,
+                                                                             double             c_prev,
+                                                                             double             c_cur,
+                                                                             int                has_prev,
+                                                                             hyteg_hip_stream_t stream )
+{
+   return chebyshev_step_entry< Launch >( "p1_elementwise_divkgrad_chebyshev_step_macro_3d", prepare, &t_out, &x, &t_in, &inv_diag, k,
+                                          macro_vertex_coords, micro_edges_per_macro_edge, c_prev, c_cur, has_prev, 1u, as_stream( stream ) );
 }
 
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d( double*            diag,

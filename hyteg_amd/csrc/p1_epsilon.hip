@@ -1,8 +1,9 @@
 // C-ABI entry points of the variable-viscosity P1 epsilon operator -div( 2 mu eps(u) ) on one macro-cell: the fused form of the nine
 // P1ElementwiseOperator blocks of P1ElementwiseAffineEpsilonOperator (src/mixed_operator/P1EpsilonOperator.hpp:89-164; each
 // block: P1ElementwiseOperator::apply, src/hyteg/elementwiseoperators/P1ElementwiseOperator.cpp), of its extractInverseDiagonal
-// (the diagonals of the three diagonal blocks) and of P1ElementwiseOperator::smooth_jac (P1ElementwiseOperator.cpp:288-331) on the
-// three components.  The viscosity is a P1 function: the same operator as the reference's where mu is linear per micro-cell.
+// (the diagonals of the three diagonal blocks), of P1ElementwiseOperator::smooth_jac (P1ElementwiseOperator.cpp:288-331), of the
+// residual of a multigrid cycle (GeometricMultigridSolver.hpp:240-246) and of the steps of ChebyshevSmoother::solve
+// (ChebyshevSmoother.hpp:165-212) on the three components.  The viscosity is a P1 function: the same operator as the reference's where mu is linear per micro-cell.
 // Kernels: kernels_varcoef.hpp with the policy of kernels_epsilon.hpp.
 #include "kernels_epsilon.hpp"
 #include "varcoef_launch.hpp"
@@ -22,7 +23,16 @@ struct Launch
 {
    using OP     = Epsilon;
    using Shapes = Bricks< Brick< 1, 4 >, Brick< 1, 8 >, Brick< 2, 4 > >;
-   static Shape level_shape( int level ) { return level <= 7 ? Shape{ 1, 4 } : Shape{ 2, 4 }; }
+   // the Chebyshev step with its second store stream needs scratch at 2 x 4 and is not compiled there: level 8 marches 1 x 8
+   template < int MODE, int NY, int LZ >
+   static constexpr bool compiled()
+   {
+      return !( MODE == CHEB_STEP && NY == 2 && LZ == 4 );
+   }
+   static Shape level_shape( int level, int mode )
+   {
+      return level <= 7 ? Shape{ 1, 4 } : ( mode == CHEB_STEP ? Shape{ 1, 8 } : Shape{ 2, 4 } );
+   }
    static inline Shape shape_override{ 0, 0 };
    // the inner points by the one-thread-per-point kernel instead of the z-march (tests, tools/bench_kernels.py)
    static inline bool inner_by_points = false;
@@ -137,6 +147,52 @@ HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d( double* cons
    for ( int c = 0; c < 3; ++c )
       A.dst[c] = dst[c], A.src[c] = src[c], A.rhs[c] = rhs[c], A.invdiag[c] = inv_diag[c];
    return launch_inner< Launch, JACOBI >( A, level, as_stream( stream ) );
+}
+
+// the residual of a multigrid cycle (GeometricMultigridSolver.hpp:240-246) and the steps of ChebyshevSmoother::solve
+// (ChebyshevSmoother.hpp:165-212) on the three components, each in one launch over the inner points
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_residual_macro_3d( double* const*       dst,
+                                                                      const double* const* src,
+                                                                      const double* const* rhs,
+                                                                      const double*        mu,
+                                                                      const double*        macro_vertex_coords,
+                                                                      int64_t              micro_edges_per_macro_edge,
+                                                                      unsigned             comps,
+                                                                      hyteg_hip_stream_t   stream )
+{
+   return residual_entry< Launch, false >( "p1_elementwise_epsilon_residual_macro_3d", prepare, dst, src, rhs, nullptr, mu, macro_vertex_coords,
+                                           micro_edges_per_macro_edge, comps, as_stream( stream ) );
+}
+
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_chebyshev_start_macro_3d( double* const*       t_out,
+                                                                             const double* const* rhs,
+                                                                             const double* const* x,
+                                                                             const double* const* inv_diag,
+                                                                             const double*        mu,
+                                                                             const double*        macro_vertex_coords,
+                                                                             int64_t              micro_edges_per_macro_edge,
+                                                                             unsigned             comps,
+                                                                             hyteg_hip_stream_t   stream )
+{
+   return residual_entry< Launch, true >( "p1_elementwise_epsilon_chebyshev_start_macro_3d", prepare, t_out, x, rhs, inv_diag, mu, macro_vertex_coords,
+                                          micro_edges_per_macro_edge, comps, as_stream( stream ) );
+}
+
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_chebyshev_step_macro_3d( double* const*       t_out,
+                                                                            double* const*       x,
+                                                                            const double* const* t_in,
+                                                                            const double* const* inv_diag,
+                                                                            const double*        mu,
+                                                                            const double*        macro_vertex_coords,
+                                                                            int64_t              micro_edges_per_macro_edge,
+                                                                            double               c_prev,
+                                                                            double               c_cur,
+                                                                            int                  has_prev,
+                                                                            unsigned             comps,
+                                                                            hyteg_hip_stream_t   stream )
+{
+   return chebyshev_step_entry< Launch >( "p1_elementwise_epsilon_chebyshev_step_macro_3d", prepare, t_out, x, t_in, inv_diag, mu, macro_vertex_coords,
+                                          micro_edges_per_macro_edge, c_prev, c_cur, has_prev, comps, as_stream( stream ) );
 }
 
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_diagonal_macro_3d( double* const*     diag,

@@ -184,6 +184,7 @@ SIGNATURES = {
     "hyteg_host_divkgrad_compute_inverse_diagonal": (_i, [_vp]),
     "hyteg_host_divkgrad_inverse_diagonal": (_i, [_vp, C.POINTER(_vp)]),
     "hyteg_host_divkgrad_smooth_jac": (_i, [_vp, _vp, _vp, _vp, _d, _i, _i]),
+    "hyteg_host_divkgrad_residual": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
     "hyteg_host_divkgrad_set_fused": (_i, [_vp, _i]),
     "hyteg_host_divkgrad_cg_create": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
     "hyteg_host_divkgrad_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
@@ -201,10 +202,21 @@ SIGNATURES = {
     "hyteg_host_epsilon_inverse_diagonal": (_i, [_vp, C.POINTER(_vp)]),
     "hyteg_host_epsilon_smooth_jac": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _d, _i, _i]),
     "hyteg_host_epsilon_set_fused": (_i, [_vp, _i]),
+    "hyteg_host_epsilon_residual": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i]),
+    "hyteg_host_epsilon_chebyshev_estimate_radius": (_i, [_vp, _i, _i, C.POINTER(_d)]),
+    "hyteg_host_epsilon_cg_create": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_epsilon_smoother_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_gmg_create": (_i, [_vp, _i, _i, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_chebyshev_create": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_gmg_create_chebyshev": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_solver_solve": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _i]),
+    "hyteg_host_epsilon_solver_destroy": (_i, [_vp]),
     "hyteg_host_epsilon_stokes_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
     "hyteg_host_epsilon_stokes_destroy": (_i, [_vp]),
     "hyteg_host_epsilon_stokes_apply": (_i, [_vp, _vp, _vp, _i, _i]),
     "hyteg_host_epsilon_stokes_minres_create": (_i, [_vp, _i, _i, _i, _d, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_epsilon_stokes_minres_create_block": (_i, [_vp, _i, _i, _i, _d, _i, _vp, _i, _i, _i, _dp, _i, _d, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_epsilon_stokes_minres_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
     "hyteg_host_epsilon_stokes_minres_precondition": (_i, [_vp, _vp, _vp, _vp, _i]),
     "hyteg_host_epsilon_stokes_minres_iterations": (_i, [_vp, C.POINTER(_i)]),
@@ -995,8 +1007,13 @@ class P1ElementwiseDivKGrad:
     def smooth_jac(self, dst, rhs, src, relax, level, flag):
         _ck(lib().hyteg_host_divkgrad_smooth_jac(self.h, dst.h, rhs.h, src.h, float(relax), level, flag), "divkgrad smooth_jac")
 
+    def residual(self, x, b, r, level, flag):
+        """r = b - A x as a multigrid cycle forms it: one fused launch on the inner points, or apply + assign with set_fused(False)"""
+        _ck(lib().hyteg_host_divkgrad_residual(self.h, x.h, b.h, r.h, level, flag), "divkgrad residual")
+
     def set_fused(self, on: bool):
-        """smooth_jac: the fused launch on the inner points (default) or the four composed passes everywhere"""
+        """smooth_jac, residual and the steps of the Chebyshev smoother: the fused launches on the inner points (default) or the
+        composed passes everywhere"""
         _ck(lib().hyteg_host_divkgrad_set_fused(self.h, int(bool(on))), "divkgrad set_fused")
 
     def close(self):
@@ -1535,13 +1552,100 @@ class P1ElementwiseAffineEpsilonOperator:
         _ck(lib().hyteg_host_epsilon_smooth_jac(self.h, _handles3(dst), _handles3(rhs), _handles3(src), float(relax), level, flag),
             "epsilon smooth_jac")
 
+    def residual(self, x, b, r, level, flag):
+        """r = b - A x as a multigrid cycle forms it (three components each): one fused launch on the inner points, or apply + assign
+        with set_fused(False)"""
+        _ck(lib().hyteg_host_epsilon_residual(self.h, _handles3(x), _handles3(b), _handles3(r), level, flag), "epsilon residual")
+
+    def estimate_radius(self, level: int, iterations: int) -> float:
+        """chebyshev::estimateRadius: spectral radius of D^-1 A by power iterations from a fixed start vector (inverse diagonal
+        computed)"""
+        r = _d()
+        _ck(lib().hyteg_host_epsilon_chebyshev_estimate_radius(self.h, int(level), int(iterations), C.byref(r)), "epsilon estimate_radius")
+        return r.value
+
     def set_fused(self, on: bool):
-        """smooth_jac: the fused launch on the inner points (default) or the composed passes everywhere"""
+        """smooth_jac, residual and the steps of the Chebyshev smoother: the fused launches on the inner points (default) or the
+        composed passes everywhere"""
         _ck(lib().hyteg_host_epsilon_set_fused(self.h, int(bool(on))), "epsilon set_fused")
 
     def close(self):
         if self.h:
             lib().hyteg_host_epsilon_destroy(self.h)
+            self.h = None
+
+
+class EpsilonSolver:
+    """The solvers instantiated for P1ElementwiseAffineEpsilonOperator, acting on three component functions: CGSolver,
+    GeometricMultigridSolver (the linear P1 transfer on every component, CG on the coarsest level) with a weighted-Jacobi or a
+    Chebyshev smoother, and the smoothers on their own.  Built by the class methods; mirrors DivKGradSolver."""
+
+    def __init__(self, storage, h, keep=None):
+        self.storage, self.h, self._keep = storage, h, keep
+
+    @classmethod
+    def cg(cls, storage, min_level, max_level, max_iter=1000, tol=1e-14, preconditioner=None):
+        """hyteg::CGSolver< P1ElementwiseAffineEpsilonOperator >; preconditioner: an EpsilonSolver or None"""
+        h = _vp()
+        _ck(lib().hyteg_host_epsilon_cg_create(storage.h, min_level, max_level, max_iter, float(tol),
+                                               preconditioner.h if preconditioner is not None else None, C.byref(h)), "epsilon cg_create")
+        return cls(storage, h, preconditioner)
+
+    @classmethod
+    def gmg(cls, storage, min_level, max_level, smoother=JACOBI, relax=2.0 / 3.0, pre=3, post=3, wcycle=False, cg_max_iter=1000, cg_tol=1e-14):
+        """hyteg::GeometricMultigridSolver with WeightedJacobiSmoother( relax ) (the operator has no Gauss-Seidel sweep)"""
+        if smoother != JACOBI:
+            raise HytegHostError("EpsilonSolver.gmg: smoother JACOBI (gmg_chebyshev for the Chebyshev smoother)")
+        h = _vp()
+        _ck(lib().hyteg_host_epsilon_gmg_create(storage.h, min_level, max_level, float(relax), pre, post, int(bool(wcycle)), cg_max_iter,
+                                                float(cg_tol), C.byref(h)), "epsilon gmg_create")
+        return cls(storage, h)
+
+    @classmethod
+    def chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3):
+        """hyteg::ChebyshevSmoother< P1ElementwiseAffineEpsilonOperator > on its own (solve = one smoother call)"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_epsilon_chebyshev_create(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), C.byref(h)),
+            "epsilon chebyshev_create")
+        return cls(storage, h)
+
+    @classmethod
+    def gmg_chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3, pre=1, post=1, wcycle=False, cg_max_iter=1000,
+                      cg_tol=1e-14):
+        """the multigrid solver smoothing with ChebyshevSmoother( order ); radii: one spectral radius
+        (P1ElementwiseAffineEpsilonOperator.estimate_radius) or one per level"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_epsilon_gmg_create_chebyshev(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), pre,
+                                                          post, int(bool(wcycle)), cg_max_iter, float(cg_tol), C.byref(h)),
+            "epsilon gmg_create_chebyshev")
+        return cls(storage, h)
+
+    @classmethod
+    def smoother(cls, storage, min_level, max_level, smoother=JACOBI, relax=1.0):
+        """WeightedJacobiSmoother( relax ) (JACOBI) or IdentityPreconditioner (IDENTITY) on its own"""
+        if smoother not in (JACOBI, IDENTITY):
+            raise HytegHostError("EpsilonSolver.smoother: JACOBI or IDENTITY (the epsilon operator has no SOR sweep)")
+        h = _vp()
+        _ck(lib().hyteg_host_epsilon_smoother_create(storage.h, min_level, max_level, {JACOBI: 0, IDENTITY: -1}[smoother], float(relax),
+                                                     C.byref(h)), "epsilon smoother_create")
+        return cls(storage, h)
+
+    @property
+    def iterations(self) -> int:
+        """CGSolver::getIterations of the last solve (EpsilonSolver.cg)"""
+        n = _i(0)
+        _ck(lib().hyteg_host_epsilon_cg_iterations(self.h, C.byref(n)), "epsilon cg_iterations")
+        return n.value
+
+    def solve(self, op: P1ElementwiseAffineEpsilonOperator, xs, bs, level):
+        """xs, bs: three component functions each"""
+        _ck(lib().hyteg_host_epsilon_solver_solve(self.h, op.h, _handles3(xs), _handles3(bs), level), "epsilon solve")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_epsilon_solver_destroy(self.h)
             self.h = None
 
 
@@ -1572,14 +1676,34 @@ class EpsilonStokesSolver:
         self._keep = keep
 
     @classmethod
-    def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, preconditioner="pressure", mu=None):
+    def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, preconditioner="pressure", mu=None, velocity_cycles=1,
+               smoother="chebyshev", order=2, radii=None, relax=2.0 / 3.0, pre=1, post=1, cg_max_iter=1000, cg_tol=1e-14):
         """hyteg::MinResSolver< P1P1ElementwiseAffineEpsilonStokesOperator >; preconditioner "identity", "pressure"
-        (StokesPressureBlockPreconditioner with the lumped inverse mass operator, the reference's stokesMinResSolver) or
-        "pressure_viscosity" (pressure action x.p = mu .* invLumpedMass .* b.p; needs mu, the viscosity function)"""
-        kind = {"identity": 0, "pressure": 1, "pressure_viscosity": 2}[preconditioner]
-        if kind == 2 and mu is None:
-            raise HytegHostError("EpsilonStokesSolver.minres: the pressure_viscosity preconditioner needs mu")
+        (StokesPressureBlockPreconditioner with the lumped inverse mass operator, the reference's stokesMinResSolver),
+        "pressure_viscosity" (pressure action x.p = mu .* invLumpedMass .* b.p; needs mu, the viscosity function), or the
+        block-diagonal ones with a velocity action: "block" (velocity_cycles multigrid V-cycles on the epsilon operator, the lumped
+        inverse mass on the pressure) and "block_viscosity" (the same with the pressure action of "pressure_viscosity").  Both need
+        mu, the viscosity of the operator.  Their cycle smooths pre = post times with smoother "chebyshev" (of the given order; radii:
+        None = estimated per level at construction, one spectral radius, or one per level) or "jacobi" (relax), and solves the coarsest
+        level by CG to cg_tol: a symmetric positive definite action, as MINRES needs (any other smoother or pre != post raises)."""
+        kinds = {"identity": 0, "pressure": 1, "pressure_viscosity": 2, "block": 3, "block_viscosity": 4}
+        if preconditioner not in kinds:
+            raise HytegHostError(f"EpsilonStokesSolver.minres: unknown preconditioner {preconditioner!r}")
+        kind = kinds[preconditioner]
+        if kind in (2, 3, 4) and mu is None:
+            raise HytegHostError(f"EpsilonStokesSolver.minres: the {preconditioner} preconditioner needs mu")
         h = _vp()
+        if kind >= 3:
+            if smoother not in ("chebyshev", "jacobi"):
+                raise HytegHostError("EpsilonStokesSolver.minres: smoother 'chebyshev' or 'jacobi' (an SOR sweep is not symmetric)")
+            if pre != post:
+                raise HytegHostError("EpsilonStokesSolver.minres: a symmetric cycle needs pre == post")
+            keep, ptr, n = (None, None, 0) if radii is None else _radii(radii)
+            _ck(lib().hyteg_host_epsilon_stokes_minres_create_block(storage.h, min_level, max_level, int(max_iter), float(rel_tol), int(kind == 4),
+                                                                    mu.h, int(velocity_cycles), {"jacobi": 0, "chebyshev": 1}[smoother], int(order),
+                                                                    ptr, n, float(relax), int(pre), int(post), int(cg_max_iter), float(cg_tol),
+                                                                    C.byref(h)), "epsilon_stokes_minres_create_block")
+            return cls(h, keep=(mu,))
         _ck(lib().hyteg_host_epsilon_stokes_minres_create(storage.h, min_level, max_level, int(max_iter), float(rel_tol), kind,
                                                           mu.h if kind == 2 else None, C.byref(h)), "epsilon_stokes_minres_create")
         return cls(h, keep=(mu,))

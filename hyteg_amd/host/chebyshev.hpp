@@ -226,8 +226,8 @@ class ChebyshevSmoother : public Solver< OperatorType >
    {
       tmp1_.copyBoundaryConditionFromFunction( x );
       tmp2_.copyBoundaryConditionFromFunction( x );
-      const Selection             selected = x.effectiveFlag( flag_ );
-      std::optional< Selection >& last     = lastSelection_[level - minLevel_];
+      const SelectionType             selected = x.effectiveFlag( flag_ );
+      std::optional< SelectionType >& last     = lastSelection_[level - minLevel_];
       if ( last && *last != selected )
       {
          tmp1_.setToZero( level );
@@ -240,7 +240,9 @@ class ChebyshevSmoother : public Solver< OperatorType >
    uint_t                                    minLevel_, maxLevel_;
    FunctionType                              tmp1_, tmp2_;
    std::vector< std::vector< double > >      coefficients_;
-   std::vector< std::optional< Selection > > lastSelection_; // per level: what the temporaries were last written under
+   // a Selection, or one per component of a vector function
+   using SelectionType = decltype( std::declval< const FunctionType& >().effectiveFlag( std::declval< const Selection& >() ) );
+   std::vector< std::optional< SelectionType > > lastSelection_; // per level: what the temporaries were last written under
    bool                                      fused_ = true;
 };
 

@@ -1133,6 +1133,10 @@ HYTEG_HOST_API int hyteg_host_divkgrad_smooth_jac( hh_divkgrad_t op, hh_function
 {
    return guarded( [&] { DK( op ).smooth_jac( F( dst ), F( rhs ), F( src ), relax, (uint_t) level, DoFType( flag ) ); } );
 }
+HYTEG_HOST_API int hyteg_host_divkgrad_residual( hh_divkgrad_t op, hh_function_t x, hh_function_t b, hh_function_t r, int level, int flag )
+{
+   return guarded( [&] { DK( op ).residual( F( x ), F( b ), F( r ), (uint_t) level, DoFType( flag ) ); } );
+}
 HYTEG_HOST_API int hyteg_host_divkgrad_set_fused( hh_divkgrad_t op, int on )
 {
    return guarded( [&] { DK( op ).setFused( on != 0 ); } );
@@ -1699,11 +1703,22 @@ struct EpsilonStokesH
    std::shared_ptr< P1Function< double > > mu;
    std::shared_ptr< EpsilonStokes >        p;
 };
+struct EpsilonSolverH
+{
+   std::shared_ptr< Solver< Epsilon > > p;
+};
 struct EpsilonStokesSolverH
 {
    std::shared_ptr< P1Function< double > >        mu; // of the viscosity-weighted preconditioner, or null
    std::shared_ptr< Solver< EpsilonStokes > >     preconditioner;
    std::shared_ptr< MinResSolver< EpsilonStokes > > p;
+   bool                                           smoothsVelocity = false; // its preconditioner reads the velocity operator's inverse diagonals
+   // assembled on first use: the Stokes operator does not assemble them itself (the pressure preconditioners never read them)
+   void prepare( EpsilonStokes& op ) const
+   {
+      if ( smoothsVelocity && !op.viscOp.hasInverseDiagonalValues() )
+         op.viscOp.computeInverseDiagonalOperatorValues();
+   }
 };
 static Epsilon& EP( hh_epsilon_t op )
 {
@@ -1772,6 +1787,96 @@ HYTEG_HOST_API int hyteg_host_epsilon_set_fused( hh_epsilon_t op, int on )
 {
    return guarded( [&] { EP( op ).setFused( on != 0 ); } );
 }
+HYTEG_HOST_API int hyteg_host_epsilon_residual( hh_epsilon_t op, const hh_function_t* x, const hh_function_t* b, const hh_function_t* r, int level, int flag )
+{
+   return guarded( [&] { EP( op ).residual( vectorOf( x ), vectorOf( b ), vectorOf( r ), (uint_t) level, DoFType( flag ) ); } );
+}
+
+// ---- the solvers instantiated for the epsilon operator, acting on three component functions ----
+// a multigrid cycle on P1 vector functions: the linear P1 transfer on every component, CG on the coarsest level
+static std::shared_ptr< Solver< Epsilon > > epsilonGmg( hh_storage_t s, std::shared_ptr< Solver< Epsilon > > smoother, int minL, int maxL, int pre, int post,
+                                                        int wcycle, int cgMaxIter, double cgTol )
+{
+   return makeGmg< Epsilon, P1VectorFunctionLinearRestriction, P1VectorFunctionLinearProlongation >(
+       SP( s ), smoother, cgCoarse< Epsilon >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) );
+}
+// the operator has no Gauss-Seidel sweep: weighted Jacobi (0) and the identity (-1)
+static std::shared_ptr< Solver< Epsilon > > epsilonSmoother( const char* who, hh_storage_t s, int minL, int maxL, int code, double relax )
+{
+   if ( code == 0 )
+      return std::make_shared< WeightedJacobiSmoother< Epsilon > >( SP( s ), (uint_t) minL, (uint_t) maxL, relax );
+   if ( code == -1 )
+      return std::make_shared< IdentityPreconditioner< Epsilon > >();
+   throw std::runtime_error( std::string( who ) + ": smoother 0 (weighted Jacobi) or -1 (identity); the epsilon operator has no SOR sweep" );
+}
+// chebyshev::estimateRadius from a start vector of incommensurate waves (components along every eigenvector)
+static double epsilonRadius( const Epsilon& op, uint_t level, uint_t iterations )
+{
+   auto                       storage = op.getStorage();
+   P1VectorFunction< double > x( "epsilon_radius_x", storage, level, level ), tmp( "epsilon_radius_tmp", storage, level, level );
+   x.interpolate( { []( const Point3D& q ) { return std::sin( 7.3 * q[0] + 3.1 * q[1] + 1.7 * q[2] + 0.4 ); },
+                    []( const Point3D& q ) { return std::cos( 2.9 * q[0] - 6.1 * q[1] + 4.3 * q[2] ); },
+                    []( const Point3D& q ) { return std::sin( 5.3 * q[0] * q[1] - 3.7 * q[2] + 1.1 ); } },
+                  level, All );
+   return chebyshev::estimateRadius( op, level, iterations, storage, x, tmp );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_chebyshev_estimate_radius( hh_epsilon_t op, int level, int maxIter, double* radius )
+{
+   return guarded( [&] { *radius = epsilonRadius( EP( op ), (uint_t) level, (uint_t) maxIter ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_cg_create( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_epsilon_solver_t preconditioner,
+                                                 hh_epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      if ( preconditioner )
+         cgCreatePreconditioned< Epsilon, EpsilonSolverH >( "epsilon_cg_create", s, minL, maxL, maxIter, tol, preconditioner, out );
+      else
+         *out = new EpsilonSolverH{ std::make_shared< CGSolver< Epsilon > >( SP( s ), (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, tol, tol ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_cg_iterations( hh_epsilon_solver_t solver, int* iterations )
+{
+   return guarded( [&] { cgIterations< Epsilon, EpsilonSolverH >( "epsilon_cg_iterations", solver, iterations ); } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_smoother_create( hh_storage_t s, int minL, int maxL, int smoother, double relax, hh_epsilon_solver_t* out )
+{
+   return guarded( [&] { *out = new EpsilonSolverH{ epsilonSmoother( "epsilon_smoother_create", s, minL, maxL, smoother, relax ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_gmg_create( hh_storage_t s, int minL, int maxL, double relax, int pre, int post, int wcycle, int cgMaxIter,
+                                                  double cgTol, hh_epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      *out = new EpsilonSolverH{ epsilonGmg( s, epsilonSmoother( "epsilon_gmg_create", s, minL, maxL, 0, relax ), minL, maxL, pre, post, wcycle, cgMaxIter,
+                                             cgTol ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_chebyshev_create( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                        double lower, hh_epsilon_solver_t* out )
+{
+   return guarded( [&] { *out = new EpsilonSolverH{ makeChebyshev< Epsilon >( s, minL, maxL, order, radii, nRadii, upper, lower ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_gmg_create_chebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                            double lower, int pre, int post, int wcycle, int cgMaxIter, double cgTol,
+                                                            hh_epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      *out = new EpsilonSolverH{
+          epsilonGmg( s, makeChebyshev< Epsilon >( s, minL, maxL, order, radii, nRadii, upper, lower ), minL, maxL, pre, post, wcycle, cgMaxIter, cgTol ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_solver_solve( hh_epsilon_solver_t solver, hh_epsilon_t op, const hh_function_t* x, const hh_function_t* b, int level )
+{
+   return guarded( [&] {
+      if ( !solver )
+         throw std::runtime_error( "null epsilon solver" );
+      static_cast< EpsilonSolverH* >( solver )->p->solve( EP( op ), vectorOf( x ), vectorOf( b ), (uint_t) level );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_epsilon_solver_destroy( hh_epsilon_solver_t solver )
+{
+   return guarded( [&] { delete static_cast< EpsilonSolverH* >( solver ); } );
+}
+
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_create( hh_storage_t s, int minL, int maxL, hh_function_t mu, hh_epsilon_stokes_t* out )
 {
    return guarded( [&] {
@@ -1815,6 +1920,55 @@ HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_create( hh_storage_t s, int 
       *out = h.release();
    } );
 }
+// MinResSolver preconditioned with StokesVectorBlockDiagonalPreconditioner: velocityCycles multigrid V-cycles on the epsilon operator
+// (smoother 0 weighted Jacobi( relax ), 1 Chebyshev( order; radii: none = estimated per level here, one, or one per level ); pre = post
+// steps, CG on the coarsest level) and the lumped inverse mass on the pressure, weighted with mu if viscosityWeighted.  mu: the
+// viscosity of the operator the solver will be used with (the radii are estimated on an operator built from it).
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_create_block( hh_storage_t s, int minL, int maxL, int max_iter, double rel_tol, int viscosityWeighted,
+                                                                  hh_function_t mu, int velocityCycles, int smoother, int order, const double* radii,
+                                                                  int nRadii, double relax, int pre, int post, int cgMaxIter, double cgTol,
+                                                                  hh_epsilon_stokes_solver_t* out )
+{
+   return guarded( [&] {
+      const char* who     = "epsilon_stokes_minres_create_block";
+      auto        storage = SP( s );
+      auto        h       = std::make_unique< EpsilonStokesSolverH >();
+      // MINRES needs a symmetric positive definite preconditioner
+      if ( smoother != 0 && smoother != 1 )
+         throw std::runtime_error( std::string( who ) + ": smoother 0 (weighted Jacobi) or 1 (Chebyshev); an SOR sweep is not symmetric" );
+      if ( pre != post || pre < 1 )
+         throw std::runtime_error( std::string( who ) + ": a symmetric cycle needs pre = post >= 1 smoothing steps" );
+      if ( velocityCycles < 1 )
+         throw std::runtime_error( std::string( who ) + ": velocity_cycles >= 1" );
+      h->mu = viscosityOf( who, mu, minL, maxL );
+      std::shared_ptr< Solver< Epsilon > > sm;
+      if ( smoother == 0 )
+         sm = epsilonSmoother( who, s, minL, maxL, 0, relax );
+      else
+      {
+         std::vector< double > rho( radii, radii + ( radii ? nRadii : 0 ) );
+         if ( rho.empty() )
+         {
+            Epsilon probe( storage, (uint_t) minL, (uint_t) maxL, *h->mu );
+            probe.computeInverseDiagonalOperatorValues();
+            for ( int l = minL; l <= maxL; ++l )
+               rho.push_back( epsilonRadius( probe, (uint_t) l, 20 ) );
+         }
+         sm = makeChebyshev< Epsilon >( s, minL, maxL, order, rho.data(), (int) rho.size(), 1.2, 0.3 );
+      }
+      auto velocity      = epsilonGmg( s, sm, minL, maxL, pre, post, 0, cgMaxIter, cgTol );
+      h->smoothsVelocity = true;
+      if ( viscosityWeighted )
+         h->preconditioner = std::make_shared< StokesVectorBlockDiagonalPreconditioner< EpsilonStokes, Solver< Epsilon >, P1ViscosityWeightedLumpedInvMassOperator > >(
+             velocity, std::make_shared< P1ViscosityWeightedLumpedInvMassOperator >( storage, (uint_t) minL, (uint_t) maxL, *h->mu ), (uint_t) velocityCycles );
+      else
+         h->preconditioner = std::make_shared< StokesVectorBlockDiagonalPreconditioner< EpsilonStokes, Solver< Epsilon >, P1LumpedInvMassOperator > >(
+             velocity, std::make_shared< P1LumpedInvMassOperator >( storage, (uint_t) minL, (uint_t) maxL ), (uint_t) velocityCycles );
+      h->p = std::make_shared< MinResSolver< EpsilonStokes > >( storage, (uint_t) minL, (uint_t) maxL, (uint_t) max_iter, rel_tol, 1e-16,
+                                                                h->preconditioner );
+      *out = h.release();
+   } );
+}
 static EpsilonStokesSolverH& EPSS( hh_epsilon_stokes_solver_t solver )
 {
    if ( !solver )
@@ -1824,12 +1978,18 @@ static EpsilonStokesSolverH& EPSS( hh_epsilon_stokes_solver_t solver )
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_solve( hh_epsilon_stokes_solver_t solver, hh_epsilon_stokes_t op, hh_stokes_function_t x,
                                                            hh_stokes_function_t b, int level )
 {
-   return guarded( [&] { EPSS( solver ).p->solve( EPS( op ), P1P1::fn( x ), P1P1::fn( b ), (uint_t) level ); } );
+   return guarded( [&] {
+      EPSS( solver ).prepare( EPS( op ) );
+      EPSS( solver ).p->solve( EPS( op ), P1P1::fn( x ), P1P1::fn( b ), (uint_t) level );
+   } );
 }
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_precondition( hh_epsilon_stokes_solver_t solver, hh_epsilon_stokes_t op, hh_stokes_function_t x,
                                                                   hh_stokes_function_t b, int level )
 {
-   return guarded( [&] { EPSS( solver ).preconditioner->solve( EPS( op ), P1P1::fn( x ), P1P1::fn( b ), (uint_t) level ); } );
+   return guarded( [&] {
+      EPSS( solver ).prepare( EPS( op ) );
+      EPSS( solver ).preconditioner->solve( EPS( op ), P1P1::fn( x ), P1P1::fn( b ), (uint_t) level );
+   } );
 }
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_iterations( hh_epsilon_stokes_solver_t solver, int* iterations )
 {

@@ -157,6 +157,43 @@ class StokesBlockDiagonalPreconditioner : public Solver< OperatorType >
    std::shared_ptr< pressureBlockPreconditionerType >                     pressureBlockPreconditioner_;
 };
 
+// Block-diagonal preconditioner whose velocity action is ONE solver on the whole vector function: `velocitySteps` times
+// velocitySolver( A.getA(), x.uvw, b.uvw ) from x.uvw = 0, then the pressure action on p.  The reference's
+// StokesBlockDiagonalPreconditioner (StokesBlockDiagonalPreconditioner.hpp:54, above) loops a scalar solver over the velocity
+// components; that cannot take a velocity operator that couples them (the epsilon operator), whose solver acts on all three at
+// once.  x.uvw is zeroed on all points: the action is linear in b only with zero values on the fixed points.
+// For MINRES the action has to be symmetric positive definite: a multigrid cycle with as many post- as pre-smoothing steps of a
+// symmetric smoother (Jacobi, Chebyshev) and a coarse-grid solve to a tight tolerance; whoever builds the velocity solver checks that.
+template < class OperatorType, class VelocitySolver, class PressurePreconditioner >
+class StokesVectorBlockDiagonalPreconditioner : public Solver< OperatorType >
+{
+ public:
+   using FunctionType = typename OperatorType::srcType;
+   StokesVectorBlockDiagonalPreconditioner( std::shared_ptr< VelocitySolver > velocitySolver, std::shared_ptr< PressurePreconditioner > pressure,
+                                            uint_t velocitySteps = 1 )
+   : velocitySolver_( std::move( velocitySolver ) )
+   , pressure_( std::move( pressure ) )
+   , velocitySteps_( velocitySteps )
+   , flag_( Inner | NeumannBoundary | FreeslipBoundary )
+   {
+      if ( !velocitySolver_ || !pressure_ )
+         throw std::runtime_error( "StokesVectorBlockDiagonalPreconditioner: needs a velocity solver and a pressure preconditioner" );
+   }
+   void solve( const OperatorType& A, const FunctionType& x, const FunctionType& b, uint_t level ) override
+   {
+      x.uvw().interpolate( 0.0, level, All );
+      for ( uint_t i = 0; i < velocitySteps_; ++i )
+         velocitySolver_->solve( A.getA(), x.uvw(), b.uvw(), level );
+      pressure_->apply( b.p(), x.p(), level, flag_, Replace );
+   }
+
+ private:
+   std::shared_ptr< VelocitySolver >         velocitySolver_;
+   std::shared_ptr< PressurePreconditioner > pressure_;
+   uint_t                                    velocitySteps_;
+   DoFType                                   flag_;
+};
+
 // MinResSolver, MinresSolver.hpp:88-250, statement by statement.  The reference rotates its ten work functions by swapping
 // their data ( swap( …, level ) ); here the same rotation is done on pointers to them.
 template < class OperatorType >

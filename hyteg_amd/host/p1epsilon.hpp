@@ -8,6 +8,9 @@
 // (tests/hyteg/convergence/ElementwiseEpsilonMinResConvergenceTest.cpp).  The operator at level l reads mu at level l.
 // The reference composes the velocity block of nine P1ElementwiseOperator blocks (nine applies per macro-cell); here one C-ABI call
 // per macro-cell and kernel kind computes the three components (hyteg_hip_p1_elementwise_epsilon_*).
+// The operator also offers what GeometricMultigridSolver and ChebyshevSmoother look for (residual, chebyshevStart / Step / Finish, each
+// one fused launch on the inner points), so a multigrid cycle runs on it with P1VectorFunctionLinearRestriction / Prolongation
+// (stokes.hpp), and StokesVectorBlockDiagonalPreconditioner (minres.hpp) makes that cycle the velocity action of a MINRES preconditioner.
 #pragma once
 
 #include "stokes.hpp"
@@ -38,7 +41,7 @@ class P1ElementwiseAffineEpsilonOperator
    const P1Function< double >&         getViscosity() const { return mu_; }
    uint64_t                            uid() const { return uid_; }
 
-   // the fused Jacobi entry on the inner points (default), or the composed four passes everywhere (tests, measurements)
+   // the fused Jacobi, residual and Chebyshev entries on the inner points (default), or the composed passes everywhere (tests, measurements)
    void setFused( bool on ) { fused_ = on; }
    bool getFused() const { return fused_; }
 
@@ -97,6 +100,7 @@ class P1ElementwiseAffineEpsilonOperator
          }
       }
    }
+   bool                                          hasInverseDiagonalValues() const { return invDiag_ != nullptr; }
    std::shared_ptr< P1VectorFunction< double > > getInverseDiagonalValues() const
    {
       if ( !invDiag_ )
@@ -133,29 +137,106 @@ class P1ElementwiseAffineEpsilonOperator
          return;
       }
       checkDistinct( "smooth_jac", dst, { &src, &rhs } );
-      const P1Function< double >* out[3] = { &dst[0], &dst[1], &dst[2] };
-      storage_->forLocalCells(
-          [&]( uint_t c, const MacroCell& cell ) { kernel( out, src, c, cell, level, flag, HYTEG_HIP_MASK_SHELL, HYTEG_HIP_REPLACE ); } );
-      dst[0].beginSumSharedCopies( level, flag[0] );
-      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
-         if ( !( storage_->maskFor( cell, flag[0] ) & HYTEG_HIP_MASK_INNER ) || level < HYTEG_HIP_MIN_LEVEL )
-            return;
-         double cc[12];
-         coordsOf( cell, cc );
-         double*       d[3] = { dst[0].getCellPointer( c, level ), dst[1].getCellPointer( c, level ), dst[2].getCellPointer( c, level ) };
-         const double* s[3] = { src[0].getCellPointer( c, level ), src[1].getCellPointer( c, level ), src[2].getCellPointer( c, level ) };
-         const double* r[3] = { rhs[0].getCellPointer( c, level ), rhs[1].getCellPointer( c, level ), rhs[2].getCellPointer( c, level ) };
-         const double* i[3] = { invDiag[0].getCellPointer( c, level ), invDiag[1].getCellPointer( c, level ), invDiag[2].getCellPointer( c, level ) };
-         hipCheck( hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d( d, s, r, i, mu_.getCellPointer( c, level ), cc, int64_t( 1 ) << level, omega,
-                                                                     storage_->stream() ),
-                   "P1ElementwiseAffineEpsilonOperator::smooth_jac: cell" );
-      } );
-      dst[0].endSumSharedCopies( level, flag[0] );
-      for ( uint_t k = 1; k < 3; ++k )
-         dst[k].sumSharedCopies( level, flag[k] );
-      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+      sharesInnerShell(
+          dst, src, level, flag,
+          [&]( uint_t c, const double* cc, unsigned ) {
+             double*       d[3];
+             const double *s[3], *r[3], *i[3];
+             cellPointers( dst, c, level, d ), cellPointers( src, c, level, s ), cellPointers( rhs, c, level, r ), cellPointers( invDiag, c, level, i );
+             hipCheck( hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d( d, s, r, i, mu_.getCellPointer( c, level ), cc, int64_t( 1 ) << level, omega,
+                                                                         storage_->stream() ),
+                       "P1ElementwiseAffineEpsilonOperator::smooth_jac: cell" );
+          },
+          [&]( uint_t k, uint_t c, unsigned shell ) { smoothJacShellPasses( dst[k], rhs[k], invDiag[k], src[k], omega, c, level, shell ); } );
+   }
+
+   // r = b - A x as the multigrid cycle writes it (GeometricMultigridSolver.hpp:240-246: apply, then assign, over three components).
+   // Fused: the inner points of the three components in one launch per cell (hyteg_hip_p1_elementwise_epsilon_residual_macro_3d), the
+   // shell as in smooth_jac.  A component whose condition does not select a cell's inner points is left out of that launch (comps).
+   void residual( const srcType& x, const srcType& b, const dstType& r, uint_t level, const Selection& flagIn ) const
+   {
+      // views of the same functions are different VectorFunction objects (the C facade builds one per argument): compare components
+      bool inPlace = false;
+      for ( uint_t i = 0; i < 3; ++i )
+         for ( uint_t j = 0; j < 3; ++j )
+            inPlace = inPlace || &x[i] == &r[j];
+      if ( !fusedOn( level ) || inPlace )
+      {
+         apply( x, r, level, flagIn );
          for ( uint_t k = 0; k < 3; ++k )
-            smoothJacShellPasses( dst[k], rhs[k], invDiag[k], src[k], omega, c, level, storage_->maskFor( cell, flag[k] ) & HYTEG_HIP_MASK_SHELL );
+            r[k].assign( { 1.0, -1.0 }, { b[k], r[k] }, level, flagIn ); // the whole Selection, under r[k]'s condition as in the fused path
+         return;
+      }
+      ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1VectorFunction to P1VectorFunction" ), timerRes( storage_->getTimingTree(), "residual" );
+      checkDistinct( "residual", r, { &x, &b } );
+      const auto flag = r.effectiveFlag( flagIn );
+      sharesInnerShell(
+          r, x, level, flag.data(),
+          [&]( uint_t c, const double* cc, unsigned comps ) {
+             double*       d[3];
+             const double *s[3], *f[3];
+             cellPointers( r, c, level, d ), cellPointers( x, c, level, s ), cellPointers( b, c, level, f );
+             hipCheck( hyteg_hip_p1_elementwise_epsilon_residual_macro_3d( d, s, f, mu_.getCellPointer( c, level ), cc, int64_t( 1 ) << level, comps,
+                                                                           storage_->stream() ),
+                       "P1ElementwiseAffineEpsilonOperator::residual: cell" );
+          },
+          [&]( uint_t k, uint_t c, unsigned shell ) { fusedStepShellPasses( r[k], &b[k], nullptr, nullptr, 0.0, c, level, shell ); } );
+   }
+
+   // ---- the steps of ChebyshevSmoother::solve (ChebyshevSmoother.hpp:165-212) on the three components, with the semantics of
+   // P1ConstantOperator's (p1operator.hpp): one launch per step and cell on the inner points
+   // (hyteg_hip_p1_elementwise_epsilon_chebyshev_*_macro_3d), the shell as in smooth_jac.  Where chebyshevFusable is false the
+   // smoother runs its generic sequence.
+   bool chebyshevFusable( uint_t level ) const { return fusedOn( level ); }
+   // t = invDiag .* ( b - A x ); on the shell also x += c0 t.  On the inner points x is this launch's stencil source: its update
+   // is carried out by the following chebyshevStep( ..., hasPrev = true ) or by chebyshevFinish
+   void chebyshevStart( const dstType& t, const srcType& b, const srcType& x, double c0, uint_t level, const Selection& flagIn ) const
+   {
+      ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1VectorFunction to P1VectorFunction" ), timerCheb( storage_->getTimingTree(), "chebyshev" );
+      const auto& invDiag = *getInverseDiagonalValues();
+      checkDistinct( "chebyshevStart", t, { &b, &x, &invDiag } );
+      const auto flag = x.effectiveFlag( flagIn );
+      sharesInnerShell(
+          t, x, level, flag.data(),
+          [&]( uint_t c, const double* cc, unsigned comps ) {
+             double*       d[3];
+             const double *f[3], *s[3], *i[3];
+             cellPointers( t, c, level, d ), cellPointers( b, c, level, f ), cellPointers( x, c, level, s ), cellPointers( invDiag, c, level, i );
+             hipCheck( hyteg_hip_p1_elementwise_epsilon_chebyshev_start_macro_3d( d, f, s, i, mu_.getCellPointer( c, level ), cc, int64_t( 1 ) << level,
+                                                                                  comps, storage_->stream() ),
+                       "P1ElementwiseAffineEpsilonOperator::chebyshevStart: cell" );
+          },
+          [&]( uint_t k, uint_t c, unsigned shell ) { fusedStepShellPasses( t[k], &b[k], &invDiag[k], &x[k], c0, c, level, shell ); } );
+   }
+   // tOut = invDiag .* ( A tIn ); x = ( x + cPrev tIn ) + cCur tOut on the inner points (first term only if hasPrev: the update
+   // chebyshevStart left open), x += cCur tOut on the shell
+   void chebyshevStep( const dstType& tOut, const dstType& x, const srcType& tIn, double cPrev, double cCur, bool hasPrev, uint_t level,
+                       const Selection& flagIn ) const
+   {
+      ScopedTimer timerOp( storage_->getTimingTree(), "Operator P1VectorFunction to P1VectorFunction" ), timerCheb( storage_->getTimingTree(), "chebyshev" );
+      const auto& invDiag = *getInverseDiagonalValues();
+      checkDistinct( "chebyshevStep", tOut, { &x, &tIn, &invDiag } );
+      checkDistinct( "chebyshevStep", x, { &tIn, &invDiag } );
+      const auto flag = x.effectiveFlag( flagIn );
+      sharesInnerShell(
+          tOut, tIn, level, flag.data(),
+          [&]( uint_t c, const double* cc, unsigned comps ) {
+             double *      d[3], *u[3];
+             const double *s[3], *i[3];
+             cellPointers( tOut, c, level, d ), cellPointers( x, c, level, u ), cellPointers( tIn, c, level, s ), cellPointers( invDiag, c, level, i );
+             hipCheck( hyteg_hip_p1_elementwise_epsilon_chebyshev_step_macro_3d( d, u, s, i, mu_.getCellPointer( c, level ), cc, int64_t( 1 ) << level,
+                                                                                 cPrev, cCur, hasPrev ? 1 : 0, comps, storage_->stream() ),
+                       "P1ElementwiseAffineEpsilonOperator::chebyshevStep: cell" );
+          },
+          [&]( uint_t k, uint_t c, unsigned shell ) { fusedStepShellPasses( tOut[k], nullptr, &invDiag[k], &x[k], cCur, c, level, shell ); } );
+   }
+   // x += c t on the inner points: closes a smoother call of order 1 (no step follows the start)
+   void chebyshevFinish( const dstType& x, const srcType& t, double c, uint_t level, const Selection& flagIn ) const
+   {
+      const auto flag = x.effectiveFlag( flagIn );
+      storage_->forLocalCells( [&]( uint_t ci, const MacroCell& cell ) {
+         for ( uint_t k = 0; k < 3; ++k )
+            chebyshevFinishCell( x[k], t[k], c, ci, level, storage_->maskFor( cell, flag[k] ) & HYTEG_HIP_MASK_INNER );
       } );
    }
 
@@ -172,6 +253,42 @@ class P1ElementwiseAffineEpsilonOperator
       }
       if ( bad )
          throw std::runtime_error( std::string( "P1ElementwiseAffineEpsilonOperator::" ) + who + ": dst must differ from its inputs and from mu" );
+   }
+   // the fused entries act on the inner points: below level 2 there are none, and setFused( false ) composes everywhere
+   bool fusedOn( uint_t level ) const { return fused_ && level >= HYTEG_HIP_MIN_LEVEL; }
+   template < class T >
+   static void cellPointers( const srcType& f, uint_t c, uint_t level, T* ( &p )[3] )
+   {
+      for ( uint_t k = 0; k < 3; ++k )
+         p[k] = f[k].getCellPointer( c, level );
+   }
+   // the schedule of a fused step out = f( A src ): this cell's shares of A src on the shell classes, the additive exchange of the
+   // shares (the first overlaps the inner points) around inner( cell index, macro_vertex_coords, components whose inner points are
+   // selected ), then shell( component, cell index, shell classes )
+   template < class Inner, class Shell >
+   void sharesInnerShell( const dstType& out, const srcType& src, uint_t level, const Selection flag[3], Inner&& inner, Shell&& shell ) const
+   {
+      const P1Function< double >* o[3] = { &out[0], &out[1], &out[2] };
+      storage_->forLocalCells(
+          [&]( uint_t c, const MacroCell& cell ) { kernel( o, src, c, cell, level, flag, HYTEG_HIP_MASK_SHELL, HYTEG_HIP_REPLACE ); } );
+      out[0].beginSumSharedCopies( level, flag[0] );
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+         unsigned comps = 0;
+         for ( uint_t k = 0; k < 3; ++k )
+            comps |= ( storage_->maskFor( cell, flag[k] ) & HYTEG_HIP_MASK_INNER ) ? ( 1u << k ) : 0u;
+         if ( !comps || level < HYTEG_HIP_MIN_LEVEL )
+            return;
+         double cc[12];
+         coordsOf( cell, cc );
+         inner( c, cc, comps );
+      } );
+      out[0].endSumSharedCopies( level, flag[0] );
+      for ( uint_t k = 1; k < 3; ++k )
+         out[k].sumSharedCopies( level, flag[k] );
+      storage_->forLocalCells( [&]( uint_t c, const MacroCell& cell ) {
+         for ( uint_t k = 0; k < 3; ++k )
+            shell( k, c, storage_->maskFor( cell, flag[k] ) & HYTEG_HIP_MASK_SHELL );
+      } );
    }
    // one call for the classes of `classes` that the components' flags select on this cell
    void kernel( const P1Function< double >* const out[3], const srcType& src, uint_t c, const MacroCell& cell, uint_t level, const Selection flag[3],
@@ -242,19 +359,16 @@ class P1P1ElementwiseAffineEpsilonStokesOperator
    uint64_t                            uid_ = nextUid();
 };
 
-// StokesPressureBlockPreconditioner with the pressure action  x.p = mu .* invLumpedMass .* b.p : nodal quadrature of the
-// 1 / mu - weighted lumped mass matrix (the direction of the reference's commented-out varViscStokesMinResSolver,
-// src/hyteg/solvers/solvertemplates/StokesSolverTemplates.hpp).  The product is formed once, at construction.
-template < class OperatorType >
-class StokesViscosityWeightedPressureBlockPreconditioner : public Solver< OperatorType >
+// dst = mu .* invLumpedMass .* src pointwise: nodal quadrature of the 1 / mu - weighted lumped mass matrix (the direction of the
+// reference's commented-out varViscStokesMinResSolver, src/hyteg/solvers/solvertemplates/StokesSolverTemplates.hpp).  The pressure
+// action of the viscosity-weighted preconditioners; the product is formed once, at construction.
+class P1ViscosityWeightedLumpedInvMassOperator
 {
  public:
-   using FunctionType = typename OperatorType::srcType;
-   StokesViscosityWeightedPressureBlockPreconditioner( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel,
-                                                       const P1Function< double >& mu )
+   P1ViscosityWeightedLumpedInvMassOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel,
+                                             const P1Function< double >& mu )
    : scale_( "viscosity_weighted_lumped_inv_mass", storage, minLevel, maxLevel )
    , tmp_( "viscosity_weighted_lumped_inv_mass_tmp", storage, minLevel, maxLevel )
-   , flag_( Inner | NeumannBoundary | FreeslipBoundary )
    {
       scale_.setBoundaryConditionAllInner();
       tmp_.setBoundaryConditionAllInner();
@@ -262,15 +376,35 @@ class StokesViscosityWeightedPressureBlockPreconditioner : public Solver< Operat
       for ( uint_t l = minLevel; l <= maxLevel; ++l )
          scale_.multElementwise( { mu, lumped.getInverseLumpedMass() }, l, All );
    }
-   void solve( const OperatorType&, const FunctionType& x, const FunctionType& b, uint_t level ) override
+   void apply( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const
    {
-      x.assign( { 1.0 }, { b }, level, flag_ );
-      applyPointwiseScaling( scale_, tmp_, b.p(), x.p(), level, flag_, Replace );
+      applyPointwiseScaling( scale_, tmp_, src, dst, level, flag, updateType );
    }
 
  private:
    P1Function< double > scale_, tmp_;
-   DoFType              flag_;
+};
+
+// StokesPressureBlockPreconditioner with the pressure action above
+template < class OperatorType >
+class StokesViscosityWeightedPressureBlockPreconditioner : public Solver< OperatorType >
+{
+ public:
+   using FunctionType = typename OperatorType::srcType;
+   StokesViscosityWeightedPressureBlockPreconditioner( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel,
+                                                       const P1Function< double >& mu )
+   : pressure_( storage, minLevel, maxLevel, mu )
+   , flag_( Inner | NeumannBoundary | FreeslipBoundary )
+   {}
+   void solve( const OperatorType&, const FunctionType& x, const FunctionType& b, uint_t level ) override
+   {
+      x.assign( { 1.0 }, { b }, level, flag_ );
+      pressure_.apply( b.p(), x.p(), level, flag_, Replace );
+   }
+
+ private:
+   P1ViscosityWeightedLumpedInvMassOperator pressure_;
+   DoFType                                  flag_;
 };
 
 } // namespace hyteg

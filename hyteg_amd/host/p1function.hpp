@@ -598,4 +598,45 @@ inline void smoothJacShellPasses( const P1Function< double >& dst, const P1Funct
    hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, u, s2, (int) level, shell, stream ), "smooth_jac: shell update" );
 }
 
+// the vector passes of a residual or of a Chebyshev step that follow t = A src (GeometricMultigridSolver.hpp:240-246,
+// ChebyshevSmoother.hpp:165-212), each where its function is given,
+//   t = rhs - t ; t = invDiag .* t ; x = x + c t,   on the shell classes `shell` of cell ci
+inline void fusedStepShellPasses( const P1Function< double >& t, const P1Function< double >* rhs, const P1Function< double >* invDiag,
+                                  const P1Function< double >* x, double c, uint_t ci, uint_t level, unsigned shell )
+{
+   if ( !shell )
+      return;
+   const hyteg_hip_stream_t stream = t.getStorage()->stream();
+   double*                  d      = t.getCellPointer( ci, level );
+   if ( rhs )
+   {
+      const double* a[2]  = { rhs->getCellPointer( ci, level ), d };
+      const double  s1[2] = { 1.0, -1.0 };
+      hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, a, s1, (int) level, shell, stream ), "fused step: shell residual" );
+   }
+   if ( invDiag )
+   {
+      const double* m[2] = { invDiag->getCellPointer( ci, level ), d };
+      hipCheck( hyteg_hip_p1_vector_cell_masked( 2, d, 2, m, nullptr, (int) level, shell, stream ), "fused step: shell scale" );
+   }
+   if ( x )
+   {
+      double*       xd    = x->getCellPointer( ci, level );
+      const double* u[2]  = { xd, d };
+      const double  s2[2] = { 1.0, c };
+      hipCheck( hyteg_hip_p1_vector_cell_masked( 0, xd, 2, u, s2, (int) level, shell, stream ), "fused step: shell update" );
+   }
+}
+
+// x += c t on the inner points of cell ci: closes a Chebyshev smoother call of order 1 (no step follows the start)
+inline void chebyshevFinishCell( const P1Function< double >& x, const P1Function< double >& t, double c, uint_t ci, uint_t level, unsigned inner )
+{
+   if ( !inner || level < HYTEG_HIP_MIN_LEVEL )
+      return;
+   double*       d     = x.getCellPointer( ci, level );
+   const double* u[2]  = { d, t.getCellPointer( ci, level ) };
+   const double  sc[2] = { 1.0, c };
+   hipCheck( hyteg_hip_p1_vector_cell_masked( 0, d, 2, u, sc, (int) level, inner, x.getStorage()->stream() ), "chebyshevFinish" );
+}
+
 } // namespace hyteg

@@ -92,6 +92,24 @@ class VectorFunction
          s += comp_[k]->dotGlobal( rhs[k], level, flag );
       return s;
    }
+   // what the solver templates (solvers.hpp, chebyshev.hpp) ask of their FunctionType beyond the above, component by component
+   void multElementwise( const Refs& functions, uint_t level, const Selection& flag = All ) const
+   {
+      for ( uint_t k = 0; k < 3; ++k )
+         comp_[k]->multElementwise( componentRefs( functions, k ), level, flag );
+   }
+   void setToZero( uint_t level ) const
+   {
+      for ( auto& c : comp_ )
+         c->setToZero( level );
+   }
+   // the identity of the composite is that of its first component (as a Stokes function's is its pressure's)
+   uint64_t uid() const { return comp_[0]->uid(); }
+   // one selection per component: each under its own boundary condition
+   std::array< Selection, 3 > effectiveFlag( const Selection& s ) const
+   {
+      return { comp_[0]->effectiveFlag( s ), comp_[1]->effectiveFlag( s ), comp_[2]->effectiveFlag( s ) };
+   }
 
  private:
    static std::vector< std::reference_wrapper< const ScalarFunction > > componentRefs( const Refs& functions, uint_t k )
@@ -468,6 +486,45 @@ class StokesProlongation
    VelocityProlongation     pv_;
    P1toP1LinearProlongation pp_;
 };
+// P1VectorFunctionLinearRestriction.hpp / P1VectorFunctionLinearProlongation.hpp: the scalar transfer on every component of a
+// vector function (the grid transfer of a multigrid cycle on an operator that couples the components)
+template < class ScalarRestriction >
+class VectorFunctionRestriction
+{
+ public:
+   template < class FunctionType >
+   void restrict( const FunctionType& f, uint_t sourceLevel, DoFType flag ) const
+   {
+      for ( uint_t k = 0; k < f.getDimension(); ++k )
+         r_.restrict( f[k], sourceLevel, flag );
+   }
+
+ private:
+   ScalarRestriction r_;
+};
+template < class ScalarProlongation >
+class VectorFunctionProlongation
+{
+ public:
+   template < class FunctionType >
+   void prolongate( const FunctionType& f, uint_t sourceLevel, DoFType flag ) const
+   {
+      for ( uint_t k = 0; k < f.getDimension(); ++k )
+         p_.prolongate( f[k], sourceLevel, flag );
+   }
+   template < class FunctionType >
+   void prolongateAndAdd( const FunctionType& f, uint_t sourceLevel, DoFType flag ) const
+   {
+      for ( uint_t k = 0; k < f.getDimension(); ++k )
+         p_.prolongateAndAdd( f[k], sourceLevel, flag );
+   }
+
+ private:
+   ScalarProlongation p_;
+};
+using P1VectorFunctionLinearRestriction  = VectorFunctionRestriction< P1toP1LinearRestriction >;
+using P1VectorFunctionLinearProlongation = VectorFunctionProlongation< P1toP1LinearProlongation >;
+
 using P1P1StokesToP1P1StokesRestriction  = StokesRestriction< P1toP1LinearRestriction >;
 using P1P1StokesToP1P1StokesProlongation = StokesProlongation< P1toP1LinearProlongation >;
 

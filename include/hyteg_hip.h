@@ -1262,6 +1262,43 @@ HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_jacobi_macro_3d( double*    
                                                                      int64_t            micro_edges_per_macro_edge,
                                                                      double             omega,
                                                                      hyteg_hip_stream_t stream );
+/* Fused residual of a multigrid cycle for this operator, at the INNER points only:  dst = rhs - A src.  Replaces the apply and the
+ * assign of GeometricMultigridSolver::solveRecursively (src/hyteg/solvers/GeometricMultigridSolver.hpp:240-246): one pass over the
+ * arrays instead of two.  dst must alias neither src, rhs nor k, and neither input may be k (EINVAL).  Levels 0..8 (nothing to do
+ * below level 2). */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_residual_macro_3d( double*            dst,
+                                                                       const double*      src,
+                                                                       const double*      rhs,
+                                                                       const double*      k,
+                                                                       const double*      macro_vertex_coords,
+                                                                       int64_t            micro_edges_per_macro_edge,
+                                                                       hyteg_hip_stream_t stream );
+/* The steps of ChebyshevSmoother::solve (src/hyteg/solvers/ChebyshevSmoother.hpp:165-212) for this operator, fused, at the INNER
+ * points only, with the semantics of hyteg_hip_p1_chebyshev_start_cell / _step_cell above:
+ *   start:  t_out = inv_diag .* ( rhs - A x );  x is the stencil source and is not updated (x += c_0 t_out is deferred to the next
+ *           step, or to a vector pass for a smoother of order 1)
+ *   step:   t_out = inv_diag .* ( A t_in ),  x = ( x + c_prev t_in ) + c_cur t_out, the first summand only if has_prev != 0; x is
+ *           read and rewritten at the output points only.
+ * A written array (t_out, x) must alias no other array of the call, and no array may be k (EINVAL).  Levels 0..8. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_chebyshev_start_macro_3d( double*            t_out,
+                                                                              const double*      rhs,
+                                                                              const double*      x,
+                                                                              const double*      inv_diag,
+                                                                              const double*      k,
+                                                                              const double*      macro_vertex_coords,
+                                                                              int64_t            micro_edges_per_macro_edge,
+                                                                              hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_chebyshev_step_macro_3d( double*            t_out,
+                                                                             double*            x,
+                                                                             const double*      t_in,
+                                                                             const double*      inv_diag,
+                                                                             const double*      k,
+                                                                             const double*      macro_vertex_coords,
+                                                                             int64_t            micro_edges_per_macro_edge,
+                                                                             double             c_prev,
+                                                                             double             c_cur,
+                                                                             int                has_prev,
+                                                                             hyteg_hip_stream_t stream );
 /* Replaces computeInverseDiagonalOperatorValues_macro_3D of the same class: diag += sum over the adjacent micro-cells e of this
  * macro-cell of mean_k( e ) * K_e[i,i], at all points of the cell array. */
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d( double*            diag,
@@ -1315,6 +1352,48 @@ HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d( double* cons
                                                                     int64_t              micro_edges_per_macro_edge,
                                                                     double               omega,
                                                                     hyteg_hip_stream_t   stream );
+/* Fused residual of a multigrid cycle on the three components, at the INNER points only:  dst_i = rhs_i - ( A src )_i.  Replaces
+ * the apply and the assign of GeometricMultigridSolver::solveRecursively (src/hyteg/solvers/GeometricMultigridSolver.hpp:240-246)
+ * over three components: one pass over the arrays instead of seven.  comps: bit i set = component i is written (a component whose
+ * bit is off is computed and not stored; 0 launches nothing).  No dst may alias an input, mu or another dst, and no input may be
+ * mu (EINVAL).  Levels 0..8 (nothing to do below level 2). */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_residual_macro_3d( double* const*       dst,
+                                                                      const double* const* src,
+                                                                      const double* const* rhs,
+                                                                      const double*        mu,
+                                                                      const double*        macro_vertex_coords,
+                                                                      int64_t              micro_edges_per_macro_edge,
+                                                                      unsigned             comps,
+                                                                      hyteg_hip_stream_t   stream );
+/* The steps of ChebyshevSmoother::solve (src/hyteg/solvers/ChebyshevSmoother.hpp:165-212) on the three components, fused, at the
+ * INNER points only, with the semantics of hyteg_hip_p1_chebyshev_start_cell / _step_cell above:
+ *   start:  t_out_i = inv_diag_i .* ( rhs_i - ( A x )_i );  x is the stencil source and is not updated (x += c_0 t_out is deferred
+ *           to the next step, or to a vector pass for a smoother of order 1)
+ *   step:   t_out_i = inv_diag_i .* ( A t_in )_i,  x_i = ( x_i + c_prev t_in_i ) + c_cur t_out_i, the first summand only if
+ *           has_prev != 0; x is read and rewritten at the output points only.
+ * comps as above, for both store streams of the step.  A written array (t_out, x) must alias no other array of the call, and no
+ * array may be mu (EINVAL).  Levels 0..8. */
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_chebyshev_start_macro_3d( double* const*       t_out,
+                                                                             const double* const* rhs,
+                                                                             const double* const* x,
+                                                                             const double* const* inv_diag,
+                                                                             const double*        mu,
+                                                                             const double*        macro_vertex_coords,
+                                                                             int64_t              micro_edges_per_macro_edge,
+                                                                             unsigned             comps,
+                                                                             hyteg_hip_stream_t   stream );
+HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_chebyshev_step_macro_3d( double* const*       t_out,
+                                                                            double* const*       x,
+                                                                            const double* const* t_in,
+                                                                            const double* const* inv_diag,
+                                                                            const double*        mu,
+                                                                            const double*        macro_vertex_coords,
+                                                                            int64_t              micro_edges_per_macro_edge,
+                                                                            double               c_prev,
+                                                                            double               c_cur,
+                                                                            int                  has_prev,
+                                                                            unsigned             comps,
+                                                                            hyteg_hip_stream_t   stream );
 /* Replaces computeInverseDiagonalOperatorValues of the three diagonal blocks (what P1EpsilonOperator.hpp's extractInverseDiagonal
  * reads): diag[i] += sum over the adjacent micro-cells e of this macro-cell of A_e^{ii}[a][a], at all points of the cell array. */
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_diagonal_macro_3d( double* const*     diag,
@@ -1323,7 +1402,9 @@ HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_diagonal_macro_3d( double* co
                                                                       int64_t            micro_edges_per_macro_edge,
                                                                       hyteg_hip_stream_t stream );
 /* Tuning knobs as in b-4 (no counterpart in the reference): the brick shape of the inner-point z-march (0, 0 = the default of the
- * level; EINVAL for a shape that is not compiled in), and the inner points by the one-thread-per-point kernel instead. */
+ * level; EINVAL for a shape that is not compiled in), and the inner points by the one-thread-per-point kernel instead.  The
+ * Chebyshev step is not compiled at 2 x 4 (it would need scratch): with that shape set it marches ITS default shape of the level,
+ * so a timing of the step taken under set_shape( 2, 4 ) is a timing of 1 x 4 (levels <= 7) or 1 x 8 (level 8). */
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_set_shape( int ny, int lz );
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_epsilon_set_inner_by_points( int on );
 

@@ -257,7 +257,9 @@ HYTEG_HOST_API int hyteg_host_elementwise_smooth_jac( hh_elementwise_t op, hh_fu
  * tests/hyteg/convergence/ElementwiseDivKGradCGConvergenceTest.cpp:73-81): -div( k grad u ) with a P1 coefficient function that
  * holds values on every level min_level..max_level (levels 0..8).  The handle shares ownership of k.  apply / inverse diagonal /
  * smooth_jac as for the class above; smooth_jac is one fused launch on the inner points unless set_fused( 0 ) selects the four
- * composed passes of P1ElementwiseOperator.cpp:288-331 everywhere. */
+ * composed passes of P1ElementwiseOperator.cpp:288-331 everywhere.  residual: r = b - A x as a multigrid cycle forms it
+ * (GeometricMultigridSolver.hpp:240-246), one fused launch on the inner points as well; set_fused( 0 ) also composes the residual
+ * and the steps of the Chebyshev smoother. */
 typedef void* hh_divkgrad_t;
 typedef void* hh_divkgrad_solver_t;
 HYTEG_HOST_API int hyteg_host_divkgrad_create( hh_storage_t s, int min_level, int max_level, hh_function_t k, hh_divkgrad_t* out );
@@ -267,9 +269,10 @@ HYTEG_HOST_API int hyteg_host_divkgrad_compute_inverse_diagonal( hh_divkgrad_t o
 HYTEG_HOST_API int hyteg_host_divkgrad_inverse_diagonal( hh_divkgrad_t op, hh_function_t* out /* borrowed */ );
 HYTEG_HOST_API int hyteg_host_divkgrad_smooth_jac( hh_divkgrad_t op, hh_function_t dst, hh_function_t rhs, hh_function_t src, double relax, int level,
                                                    int flag );
+HYTEG_HOST_API int hyteg_host_divkgrad_residual( hh_divkgrad_t op, hh_function_t x, hh_function_t b, hh_function_t r, int level, int flag );
 HYTEG_HOST_API int hyteg_host_divkgrad_set_fused( hh_divkgrad_t op, int on );
 /* Solvers for this operator type: CGSolver (preconditioner: any solver of this group, or null), GeometricMultigridSolver with the
- * linear P1 transfer, a CG coarse-grid solver and WeightedJacobiSmoother( relax ) or ChebyshevSmoother (composed steps; radii: one
+ * linear P1 transfer, a CG coarse-grid solver and WeightedJacobiSmoother( relax ) or ChebyshevSmoother (fused steps; radii: one
  * spectral radius, or one per level) as its smoother, the two smoothers on their own (smoother: 0 weighted Jacobi, -1 identity),
  * and chebyshev::estimateRadius (ChebyshevSmoother.hpp:655-666). */
 HYTEG_HOST_API int hyteg_host_divkgrad_cg_create( hh_storage_t s, int min_level, int max_level, int max_iter, double tol,
@@ -295,8 +298,11 @@ HYTEG_HOST_API int hyteg_host_divkgrad_solver_destroy( hh_divkgrad_solver_t solv
  * of a degree-2 rule; here mu is a P1 function that holds values on every level min_level..max_level (levels 0..8): the same
  * operator where mu is linear per micro-cell.  The handle shares ownership of mu.  Every component is masked by its own boundary
  * condition.  inverse_diagonal: three borrowed handles (the diagonals of the diagonal blocks, extractInverseDiagonal); smooth_jac
- * is one fused launch on the inner points unless set_fused( 0 ) selects the composed passes of P1ElementwiseOperator.cpp:288-331. */
+ * is one fused launch on the inner points unless set_fused( 0 ) selects the composed passes of P1ElementwiseOperator.cpp:288-331.
+ * residual: r = b - A x as a multigrid cycle forms it (GeometricMultigridSolver.hpp:240-246), one fused launch on the inner points
+ * as well; set_fused( 0 ) also composes the residual and the steps of the Chebyshev smoother. */
 typedef void* hh_epsilon_t;
+typedef void* hh_epsilon_solver_t;
 typedef void* hh_epsilon_stokes_t;
 typedef void* hh_epsilon_stokes_solver_t;
 HYTEG_HOST_API int hyteg_host_epsilon_create( hh_storage_t s, int min_level, int max_level, hh_function_t mu, hh_epsilon_t* out );
@@ -308,18 +314,50 @@ HYTEG_HOST_API int hyteg_host_epsilon_inverse_diagonal( hh_epsilon_t op, hh_func
 HYTEG_HOST_API int hyteg_host_epsilon_smooth_jac( hh_epsilon_t op, const hh_function_t* dst, const hh_function_t* rhs, const hh_function_t* src,
                                                   double relax, int level, int flag );
 HYTEG_HOST_API int hyteg_host_epsilon_set_fused( hh_epsilon_t op, int on );
+HYTEG_HOST_API int hyteg_host_epsilon_residual( hh_epsilon_t op, const hh_function_t* x, const hh_function_t* b, const hh_function_t* r, int level,
+                                                int flag );
+/* Solvers for this operator type, acting on three component functions (x, b: arrays of three handles): CGSolver (preconditioner: any
+ * solver of this group, or null), GeometricMultigridSolver with the linear P1 transfer on every component
+ * (P1VectorFunctionLinearRestriction / Prolongation), a CG coarse-grid solver and WeightedJacobiSmoother( relax ) or ChebyshevSmoother
+ * (fused steps; radii: one spectral radius, or one per level) as its smoother, the smoothers on their own (smoother: 0 weighted
+ * Jacobi, -1 identity), and chebyshev::estimateRadius (ChebyshevSmoother.hpp:655-666) from a fixed start vector. */
+HYTEG_HOST_API int hyteg_host_epsilon_chebyshev_estimate_radius( hh_epsilon_t op, int level, int max_iter, double* radius );
+HYTEG_HOST_API int hyteg_host_epsilon_cg_create( hh_storage_t s, int min_level, int max_level, int max_iter, double tol,
+                                                 hh_epsilon_solver_t preconditioner /* or null */, hh_epsilon_solver_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_cg_iterations( hh_epsilon_solver_t solver, int* iterations );
+HYTEG_HOST_API int hyteg_host_epsilon_smoother_create( hh_storage_t s, int min_level, int max_level, int smoother, double relax,
+                                                       hh_epsilon_solver_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_gmg_create( hh_storage_t s, int min_level, int max_level, double relax, int pre, int post, int wcycle,
+                                                  int cg_max_iter, double cg_tol, hh_epsilon_solver_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_chebyshev_create( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                        double upper, double lower, hh_epsilon_solver_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_gmg_create_chebyshev( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                            double upper, double lower, int pre, int post, int wcycle, int cg_max_iter,
+                                                            double cg_tol, hh_epsilon_solver_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_solver_solve( hh_epsilon_solver_t solver, hh_epsilon_t op, const hh_function_t* x, const hh_function_t* b,
+                                                    int level );
+HYTEG_HOST_API int hyteg_host_epsilon_solver_destroy( hh_epsilon_solver_t solver );
 /* hyteg::P1P1ElementwiseAffineEpsilonStokesOperator( storage, minLevel, maxLevel, viscosity )
  * (src/mixed_operator/P1P1ElementwiseAffineEpsilonStokesOperator.hpp:32-92) on P1 Stokes functions: the operator above on the
  * velocity, the constant-stencil div / divT blocks and the PSPG block.  MinResSolver for it: preconditioner 0 identity, 1
  * StokesPressureBlockPreconditioner< ., P1LumpedInvMassOperator > (solvertemplates::stokesMinResSolver,
  * src/hyteg/solvers/solvertemplates/StokesSolverTemplates.hpp:54-69), 2 the same with the pressure action
  * x.p = mu .* invLumpedMass .* b.p (mu: the viscosity function; null for 0 and 1).  minres_precondition applies the solver's
- * preconditioner on its own: x = M^-1 b. */
+ * preconditioner on its own: x = M^-1 b.
+ * minres_create_block: MinResSolver with StokesVectorBlockDiagonalPreconditioner -- velocity_cycles multigrid V-cycles on the epsilon
+ * operator as the velocity action (smoother 0 weighted Jacobi( relax ), 1 Chebyshev( order ) with radii: none (n_radii 0) = estimated
+ * per level at construction, one, or one per level; pre = post smoothing steps; CG on the coarsest level), the lumped inverse mass on
+ * the pressure, weighted with mu if viscosity_weighted.  mu: the viscosity of the operator the solver is used with.  The action has
+ * to be symmetric positive definite: any other smoother, pre != post or velocity_cycles < 1 are errors. */
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_create( hh_storage_t s, int min_level, int max_level, hh_function_t mu, hh_epsilon_stokes_t* out );
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_destroy( hh_epsilon_stokes_t op );
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_apply( hh_epsilon_stokes_t op, hh_stokes_function_t src, hh_stokes_function_t dst, int level, int flag );
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_create( hh_storage_t s, int min_level, int max_level, int max_iter, double rel_tol,
                                                             int preconditioner, hh_function_t mu /* or null */, hh_epsilon_stokes_solver_t* out );
+HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_create_block( hh_storage_t s, int min_level, int max_level, int max_iter, double rel_tol,
+                                                                  int viscosity_weighted, hh_function_t mu, int velocity_cycles, int smoother, int order,
+                                                                  const double* radii /* or null */, int n_radii, double relax, int pre, int post,
+                                                                  int cg_max_iter, double cg_tol, hh_epsilon_stokes_solver_t* out );
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_solve( hh_epsilon_stokes_solver_t solver, hh_epsilon_stokes_t op, hh_stokes_function_t x,
                                                            hh_stokes_function_t b, int level );
 HYTEG_HOST_API int hyteg_host_epsilon_stokes_minres_precondition( hh_epsilon_stokes_solver_t solver, hh_epsilon_stokes_t op, hh_stokes_function_t x,

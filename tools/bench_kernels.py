@@ -2,7 +2,8 @@
 """Per-kernel timings of the whole P1 hot path on one GPU (level 8 by default) with algorithmic GB/s, plus V-cycle
 timings through the host layer.  Not the headline bench (that is bench.py); this is the evidence table for
 DESIGN.md section 3.  Usage: python tools/bench_kernels.py [--level 8] [--reps 200]
---only epsilon: the rows of the epsilon operator alone, levels 6..level."""
+--only epsilon: the rows of the epsilon operator alone, levels 6..level, with the fused residual and Chebyshev steps
+against the composed sequences they replace; --only divkgrad: the same pairs for div-k-grad."""
 import argparse
 import json
 import sys
@@ -58,7 +59,7 @@ def cpu_rows(L, w, rows):
         print(f"{'CPU 1 core: ' + name:58s} {us:12.1f} us  {nbytes / us * 1e-3:8.2f} GB/s  {updates / us * 1e-3:8.3f} GDoF/s", flush=True)
 
 
-def epsilon_rows(top_level, reps):
+def epsilon_rows(top_level, reps, from_level=6):
     """--only epsilon: one macro-cell, inner points, levels 6..top_level.  Per level, in the same run: the fused epsilon
     apply and Jacobi step (z-march), every compiled brick shape, the one-thread-per-point form, NINE div-k-grad applies (what a
     block-composed epsilon operator costs at the least) and a copy of the same seven arrays.  Every operand class is a ring of its
@@ -69,9 +70,9 @@ def epsilon_rows(top_level, reps):
     st.set_stream(sh)
     tet = [list(map(float, v)) for v in st.local_cell(0)[1]]
     rows = []
-    for L in range(6, top_level + 1):
+    for L in range(from_level, top_level + 1):
         n, inner = capi.cell_size(L), capi.cell_inner_size(L)
-        nbuf = max(6, -(-int(2.2 * 256 * 2**20) // (n * 8)))
+        nbuf = min(2049, max(6, -(-int(2.2 * 256 * 2**20) // (n * 8))))  # the cap binds below level 6 only: launch-bound there
         nbuf += -nbuf % 3  # three consecutive arrays per call
         S, D, X = ([torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)] for _ in range(3))
         M = [0.5 + 49.5 * torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf // 3)]  # the viscosity ring
@@ -122,14 +123,128 @@ def epsilon_rows(top_level, reps):
             capi.p1_assign_cell(d[2], [2.0], [s_[2]], L, sh)
 
         timeit("epsilon copy floor (assign: four arrays read, three written)", copy7, 56 * inner)
+
+        # the fused residual and Chebyshev steps, and on the same arrays the composed sequences they replace, built from
+        # the kernels that were there before: apply + assign, apply + assign + multElementwise, apply + multElementwise + assign per
+        # component.  Bytes: what the fused launch has to move (the composed sequences move more; their GB/s column is on that scale too)
+        inv = lambda k: p3(X, 2 * k, 3)  # noqa: E731
+        rhs = lambda k: p3(X, 2 * k)  # noqa: E731
+        timeit("epsilon residual fused (z-march)",
+               lambda k: capi.p1_elementwise_epsilon_residual_macro_3d(p3(D, k), p3(S, k), rhs(k), pm(k), tet, 1 << L, 7, sh), 80 * inner)
+
+        def residual_composed(k):
+            d, r = p3(D, k), rhs(k)
+            apply_(k)
+            for c in range(3):
+                capi.p1_assign_cell(d[c], [1.0, -1.0], [r[c], d[c]], L, sh)
+
+        timeit("epsilon residual composed (apply + 3 assign)", residual_composed, 80 * inner)
+        timeit("epsilon Chebyshev start fused (z-march)",
+               lambda k: capi.p1_elementwise_epsilon_chebyshev_start_macro_3d(p3(D, k), rhs(k), p3(S, k), inv(k), pm(k), tet, 1 << L, 7, sh),
+               104 * inner)
+
+        def start_composed(k):
+            d, r, i = p3(D, k), rhs(k), inv(k)
+            apply_(k)
+            for c in range(3):
+                capi.p1_assign_cell(d[c], [1.0, -1.0], [r[c], d[c]], L, sh)
+                capi.p1_mult_cell(d[c], [i[c], d[c]], L, sh)
+
+        timeit("epsilon Chebyshev start composed (apply + 3 assign + 3 mult)", start_composed, 104 * inner)
+        # x is the rhs ring here: read and rewritten at the inner points
+        timeit("epsilon Chebyshev step fused (z-march)",
+               lambda k: capi.p1_elementwise_epsilon_chebyshev_step_macro_3d(p3(D, k), rhs(k), p3(S, k), inv(k), pm(k), tet, 1 << L, 0.37, -0.21, 1, 7,
+                                                                             sh), 128 * inner)
+
+        step = lambda k: capi.p1_elementwise_epsilon_chebyshev_step_macro_3d(p3(D, k), rhs(k), p3(S, k), inv(k), pm(k), tet, 1 << L, 0.37, -0.21, 1,  # noqa: E731
+                                                                             7, sh)
+        for ny, lz in ((1, 4), (1, 8)):  # the step is not compiled at 2 x 4 (it would need scratch)
+            capi.p1_elementwise_epsilon_set_shape(ny, lz)
+            timeit(f"epsilon Chebyshev step fused (z-march, shape {ny} x {lz})", step, 128 * inner)
+        capi.p1_elementwise_epsilon_set_shape(0, 0)
+
+        def step_composed(k):
+            d, x, i = p3(D, k), rhs(k), inv(k)
+            apply_(k)
+            for c in range(3):
+                capi.p1_mult_cell(d[c], [i[c], d[c]], L, sh)
+                capi.p1_assign_cell(x[c], [1.0, -0.21], [x[c], d[c]], L, sh)
+
+        timeit("epsilon Chebyshev step composed (apply + 3 mult + 3 assign)", step_composed, 128 * inner)
         del S, D, X, M
-    print(json.dumps({"levels": list(range(6, top_level + 1)), "device": capi.device_name(), "kernels": rows}))
+    print(json.dumps({"levels": list(range(from_level, top_level + 1)), "device": capi.device_name(), "kernels": rows}))
+
+
+def divkgrad_mode_rows(top_level, reps, from_level=6):
+    """--only divkgrad: one macro-cell, inner points, levels 6..top_level.  Per level, in the same run: the fused residual
+    and Chebyshev steps of div-k-grad, the composed sequences they replace on the same arrays (apply + assign, apply + assign +
+    multElementwise, apply + multElementwise + assign), the apply alone and a copy floor.  Rings as for the epsilon rows."""
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    st = host.Storage.from_gmsh(ROOT / "hyteg_amd/data/meshes/tet_1el.msh")
+    st.set_stream(sh)
+    tet = [list(map(float, v)) for v in st.local_cell(0)[1]]
+    rows = []
+    for L in range(from_level, top_level + 1):
+        n, inner = capi.cell_size(L), capi.cell_inner_size(L)
+        nbuf = min(2048, max(4, -(-int(2.2 * 256 * 2**20) // (n * 8))))  # the cap binds below level 6 only: launch-bound there
+        S, D, R, I = ([torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)] for _ in range(4))
+        K = [1.0 + 0.5 * torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)]
+        p = lambda t, k: t[k % nbuf].data_ptr()  # noqa: E731
+
+        def timeit(name, fn, nbytes, r=reps):
+            for k in range(5):
+                fn(k)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for k in range(r):
+                fn(k)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) * 1e3 / r
+            rows.append(dict(kernel=name, level=L, us=us, GBps=nbytes / us * 1e-3, GDoFps=inner / us * 1e-3, algorithmic_bytes=nbytes))
+            print(f"level {L}  {name:62s} {us:10.2f} us  {nbytes / us * 1e-3:8.1f} GB/s  {inner / us * 1e-3:8.2f} GDoF/s", flush=True)
+
+        apply_ = lambda k: capi.p1_elementwise_divkgrad_apply_macro_3d_masked(p(D, k), p(S, k), p(K, k), tet, 1 << L, 1 << 14, 0, sh)  # noqa: E731
+        timeit("div-k-grad apply Replace, inner points (z-march)", apply_, 24 * inner)
+        timeit("div-k-grad residual fused (z-march)",
+               lambda k: capi.p1_elementwise_divkgrad_residual_macro_3d(p(D, k), p(S, k), p(R, k), p(K, k), tet, 1 << L, sh), 32 * inner)
+
+        def residual_composed(k):
+            apply_(k)
+            capi.p1_assign_cell(p(D, k), [1.0, -1.0], [p(R, k), p(D, k)], L, sh)
+
+        timeit("div-k-grad residual composed (apply + assign)", residual_composed, 32 * inner)
+        timeit("div-k-grad Chebyshev start fused (z-march)",
+               lambda k: capi.p1_elementwise_divkgrad_chebyshev_start_macro_3d(p(D, k), p(R, k), p(S, k), p(I, k), p(K, k), tet, 1 << L, sh), 40 * inner)
+
+        def start_composed(k):
+            residual_composed(k)
+            capi.p1_mult_cell(p(D, k), [p(I, k), p(D, k)], L, sh)
+
+        timeit("div-k-grad Chebyshev start composed (apply + assign + mult)", start_composed, 40 * inner)
+        timeit("div-k-grad Chebyshev step fused (z-march)",
+               lambda k: capi.p1_elementwise_divkgrad_chebyshev_step_macro_3d(p(D, k), p(R, k), p(S, k), p(I, k), p(K, k), tet, 1 << L, 0.37, -0.21, 1,
+                                                                              sh), 48 * inner)
+
+        def step_composed(k):
+            apply_(k)
+            capi.p1_mult_cell(p(D, k), [p(I, k), p(D, k)], L, sh)
+            capi.p1_assign_cell(p(R, k), [1.0, -0.21], [p(R, k), p(D, k)], L, sh)
+
+        timeit("div-k-grad Chebyshev step composed (apply + mult + assign)", step_composed, 48 * inner)
+        timeit("div-k-grad copy floor (assign 2 sources: two arrays read, one written)",
+               lambda k: capi.p1_assign_cell(p(D, k), [2.0, -1.0], [p(S, k), p(K, k)], L, sh), 24 * inner)
+        del S, D, R, I, K
+    print(json.dumps({"levels": list(range(from_level, top_level + 1)), "device": capi.device_name(), "kernels": rows}))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", type=int, default=8)
     ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--from-level", type=int, default=6, help="--only epsilon / divkgrad: the lowest level timed (2..level)")
     ap.add_argument("--only", default=None, help="time only the kernel rows whose name contains this text (skips the cycles)")
     ap.add_argument("--cpu", action="store_true",
                     help="also time the CPU restatement of the reference kernels (oracle/, gcc -O3 -march=native, 1 thread) for apply, "
@@ -137,7 +252,10 @@ def main():
     args = ap.parse_args()
     L, reps = args.level, args.reps
     if args.only == "epsilon":
-        epsilon_rows(min(L, 8), reps)
+        epsilon_rows(min(L, 8), reps, max(2, args.from_level))
+        return
+    if args.only == "divkgrad":
+        divkgrad_mode_rows(min(L, 8), reps, max(2, args.from_level))
         return
     n, inner = capi.cell_size(L), capi.cell_inner_size(L)
     nc = capi.cell_size(L - 1)
