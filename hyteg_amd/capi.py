@@ -179,6 +179,12 @@ SIGNATURES = {
     "hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d": (_i, [_vp, _vp, _dp, _i64, _vp]),
     "hyteg_hip_p1_elementwise_divkgrad_set_shape": (_i, [_i, _i]),
     "hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points": (_i, [_i]),
+    "hyteg_hip_p2_elementwise_divkgrad_geometry": (_i, [_dp, _i, _dp]),
+    "hyteg_hip_p2_elementwise_divkgrad_apply_cell_kinds": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _dp, _d, _i, C.c_uint, C.c_uint, _vp]),
+    "hyteg_hip_p2_elementwise_divkgrad_apply_cell_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _dp, _d, _i, C.c_uint, C.c_uint, _vp]),
+    "hyteg_hip_p2_elementwise_divkgrad_diagonal_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _vp]),
+    "hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level": (_i, [_i]),
+    "hyteg_hip_p2_elementwise_divkgrad_max_level": (_i, []),
     "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_masked": (_i, [_vp, _vp, _vp, _dp, _i64, C.c_uint, _i, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_component_masks": (_i, [_vp, _vp, _vp, _dp, _i64, C.POINTER(C.c_uint), _i, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _vp]),
@@ -951,6 +957,46 @@ DIVKGRAD_SHAPES = ((2, 4), (2, 8), (1, 8))  # the shapes compiled in (p1_divkgra
 
 def p1_elementwise_divkgrad_set_inner_by_points(on):
     check(lib().hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points(1 if on else 0), "p1_elementwise_divkgrad_set_inner_by_points")
+
+
+# ---- -div( k grad u ) on P2 with a P2 coefficient: the seam of the generated P2ElementwiseDivKGrad ----
+def p2_elementwise_divkgrad_geometry(coords, level):
+    """the 60 geometry numbers of a ( macro-cell, level ): |e| grad l_a . grad l_b / 840 of the six micro-cell types"""
+    a = (C.c_double * 12)(*_c12(coords))
+    out = (C.c_double * 60)()
+    check(lib().hyteg_hip_p2_elementwise_divkgrad_geometry(a, int(level), out), "p2_elementwise_divkgrad_geometry")
+    return list(out)
+
+
+def _geometry60(geometry):
+    if geometry is None:
+        return None
+    g = [float(v) for v in geometry]
+    if len(g) != 60:
+        raise ValueError("geometry: 60 doubles (p2_elementwise_divkgrad_geometry)")
+    return (C.c_double * 60)(*g)
+
+
+def p2_elementwise_divkgrad_apply_cell(dst_v, dst_e, src_v, src_e, k_v, k_e, level, geometry, alpha=1.0, update=REPLACE, mask=MASK_ALL,
+                                       kinds=0xFF, stream=0, gather=False):
+    """dst = alpha * A( k ) src (or +=) on the DoFs of `mask` and `kinds`; gather: the gather form on every DoF"""
+    fn = lib().hyteg_hip_p2_elementwise_divkgrad_apply_cell_gather if gather else lib().hyteg_hip_p2_elementwise_divkgrad_apply_cell_kinds
+    check(fn(dst_v, dst_e, src_v, src_e, k_v, k_e, int(level), _geometry60(geometry), float(alpha), update, mask, kinds, stream),
+          "p2_elementwise_divkgrad_apply_cell")
+
+
+def p2_elementwise_divkgrad_diagonal_cell(diag_v, diag_e, k_v, k_e, level, geometry, stream=0):
+    check(lib().hyteg_hip_p2_elementwise_divkgrad_diagonal_cell(diag_v, diag_e, k_v, k_e, int(level), _geometry60(geometry), stream),
+          "p2_elementwise_divkgrad_diagonal_cell")
+
+
+def p2_elementwise_divkgrad_set_inner_min_level(level):
+    """first level whose inner DoFs take the inner form (99: the gather form everywhere); returns the previous value"""
+    return lib().hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level(int(level))
+
+
+def p2_elementwise_divkgrad_max_level():
+    return lib().hyteg_hip_p2_elementwise_divkgrad_max_level()
 
 
 # ---- variable-viscosity epsilon operator -div( 2 mu eps(u) ): the nine blocks of P1ElementwiseAffineEpsilonOperator in one pass ----

@@ -3,6 +3,8 @@
 // (P2ElementwiseOperator::localMatrixVectorMultiply3D, src/hyteg/elementwiseoperators/P2ElementwiseOperator.cpp:66-223) visits them.
 #pragma once
 
+#include <mutex>
+
 #include "p2_common.hpp"
 
 namespace {
@@ -36,6 +38,43 @@ struct P2Args
    unsigned      kinds; // destination kinds to compute: bit 0 vertex DoFs, 1..7 edge DoFs X, Y, Z, XY, XZ, YZ, XYZ
    P2Tables      T;
 };
+
+// the tables, built once on the host: the local DoFs from c_local, and per destination kind the micro-cells that hold it
+inline const P2Tables& tables()
+{
+   static P2Tables       T;
+   static std::once_flag once;
+   std::call_once( once, [] {
+      for ( int t = 0; t < 6; ++t )
+         for ( int k = 0; k < 10; ++k )
+         {
+            const CLocal l = c_local( t, k );
+            T.local[t][k]  = LocalDof{ (signed char) l.kind, (signed char) l.ox, (signed char) l.oy, (signed char) l.oz };
+         }
+      for ( int c = 0; c < 8; ++c )
+      {
+         int n = 0;
+         for ( int t = 0; t < 6; ++t )
+         {
+            // cells of one type contribute in micro-cell iteration order (z, y, x ascending), i.e. offsets descending
+            int first = n;
+            for ( int k = 0; k < 10; ++k )
+               if ( T.local[t][k].kind == c )
+                  T.entries[c][n++] = Entry{ (signed char) t, (signed char) k, T.local[t][k].ox, T.local[t][k].oy, T.local[t][k].oz, { 0, 0, 0 } };
+            for ( int a = first; a < n; ++a )
+               for ( int b = a + 1; b < n; ++b )
+               {
+                  const Entry &A = T.entries[c][a], &B = T.entries[c][b];
+                  const bool   swap = B.oz > A.oz || ( B.oz == A.oz && ( B.oy > A.oy || ( B.oy == A.oy && B.ox > A.ox ) ) );
+                  if ( swap )
+                     std::swap( T.entries[c][a], T.entries[c][b] );
+               }
+         }
+         T.nentries[c] = (signed char) n;
+      }
+   } );
+   return T;
+}
 
 __constant__ int kRowDeficit[6]     = { 0, 1, 1, 2, 1, 1 }; // numCellsPerRowByType: n - deficit
 

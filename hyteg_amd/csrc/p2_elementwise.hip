@@ -27,42 +27,6 @@
 
 namespace {
 
-const P2Tables& tables()
-{
-   static P2Tables       T;
-   static std::once_flag once;
-   std::call_once( once, [] {
-      for ( int t = 0; t < 6; ++t )
-         for ( int k = 0; k < 10; ++k )
-         {
-            const CLocal l = c_local( t, k );
-            T.local[t][k]  = LocalDof{ (signed char) l.kind, (signed char) l.ox, (signed char) l.oy, (signed char) l.oz };
-         }
-      for ( int c = 0; c < 8; ++c )
-      {
-         int n = 0;
-         for ( int t = 0; t < 6; ++t )
-         {
-            // cells of one type contribute in micro-cell iteration order (z, y, x ascending), i.e. offsets descending
-            int first = n;
-            for ( int k = 0; k < 10; ++k )
-               if ( T.local[t][k].kind == c )
-                  T.entries[c][n++] = Entry{ (signed char) t, (signed char) k, T.local[t][k].ox, T.local[t][k].oy, T.local[t][k].oz, { 0, 0, 0 } };
-            for ( int a = first; a < n; ++a )
-               for ( int b = a + 1; b < n; ++b )
-               {
-                  const Entry &A = T.entries[c][a], &B = T.entries[c][b];
-                  const bool   swap = B.oz > A.oz || ( B.oz == A.oz && ( B.oy > A.oy || ( B.oy == A.oy && B.ox > A.ox ) ) );
-                  if ( swap )
-                     std::swap( T.entries[c][a], T.entries[c][b] );
-               }
-         }
-         T.nentries[c] = (signed char) n;
-      }
-   } );
-   return T;
-}
-
 // first level the row kernel with every point class is used at (HYTEG_HIP_P2_CLASS_ROWS_MIN_LEVEL, hyteg_hip_p2_set_class_rows_min_level: tests run it at small
 // levels, 99 = the row kernel of round 2 at every level)
 std::atomic< int >& class_rows_min_level()

@@ -195,6 +195,26 @@ SIGNATURES = {
     "hyteg_host_divkgrad_gmg_create_chebyshev": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_divkgrad_solver_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
     "hyteg_host_divkgrad_solver_destroy": (_i, [_vp]),
+    "hyteg_host_p2divkgrad_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_p2divkgrad_destroy": (_i, [_vp]),
+    "hyteg_host_p2divkgrad_apply": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "hyteg_host_p2divkgrad_gemv": (_i, [_vp, _d, _vp, _d, _vp, _i, _i]),
+    "hyteg_host_p2divkgrad_compute_inverse_diagonal": (_i, [_vp]),
+    "hyteg_host_p2divkgrad_inverse_diagonal_copy": (_i, [_vp, _vp, _i]),
+    "hyteg_host_p2divkgrad_smooth_jac": (_i, [_vp, _vp, _vp, _vp, _d, _i, _i]),
+    "hyteg_host_p2divkgrad_cg_create": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
+    "hyteg_host_p2divkgrad_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_p2divkgrad_smoother_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2divkgrad_gmg_create": (_i, [_vp, _i, _i, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2divkgrad_chebyshev_estimate_radius": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(_d)]),
+    "hyteg_host_p2divkgrad_chebyshev_create": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2divkgrad_gmg_create_chebyshev": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2divkgrad_fmg_create": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_uint), _i, C.POINTER(_vp)]),
+    "hyteg_host_p2divkgrad_solver_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_p2divkgrad_solver_destroy": (_i, [_vp]),
+    "hyteg_host_p2massoperator_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "hyteg_host_p2massoperator_apply": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "hyteg_host_p2massoperator_destroy": (_i, [_vp]),
     "hyteg_host_epsilon_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
     "hyteg_host_epsilon_destroy": (_i, [_vp]),
     "hyteg_host_epsilon_apply": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i]),
@@ -346,6 +366,8 @@ def estimate_radius(op, level: int, max_iter: int, x, tmp) -> float:
     fn = lib().hyteg_host_p2_chebyshev_estimate_radius if isinstance(op, P2ElementwiseLaplaceOperator) else lib().hyteg_host_chebyshev_estimate_radius
     if isinstance(op, P1ElementwiseDivKGrad):
         fn = lib().hyteg_host_divkgrad_chebyshev_estimate_radius
+    if isinstance(op, P2ElementwiseDivKGrad):
+        fn = lib().hyteg_host_p2divkgrad_chebyshev_estimate_radius
     _ck(fn(op.h, int(level), int(max_iter), x.h, tmp.h, C.byref(r)), "chebyshev_estimate_radius")
     return r.value
 
@@ -1922,6 +1944,139 @@ class P2Solver:
     def close(self):
         if self.h:
             lib().hyteg_host_p2_solver_destroy(self.h)
+            self.h = None
+
+
+class P2ElementwiseMassOperator:
+    """hyteg::P2ElementwiseMassOperator = P2ElementwiseOperator< forms::P2MassForm >: element matrix |e| times the universal P2 mass
+    constants"""
+
+    def __init__(self, storage: Storage, min_level: int, max_level: int):
+        self.storage = storage
+        h = _vp()
+        _ck(lib().hyteg_host_p2massoperator_create(storage.h, min_level, max_level, C.byref(h)), "P2ElementwiseMassOperator")
+        self.h = h
+
+    def apply(self, src: P2Function, dst: P2Function, level, flag, update=Replace):
+        _ck(lib().hyteg_host_p2massoperator_apply(self.h, src.h, dst.h, level, flag, update), "P2 mass apply")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_p2massoperator_destroy(self.h)
+            self.h = None
+
+
+class P2ElementwiseDivKGrad:
+    """hyteg::operatorgeneration::P2ElementwiseDivKGrad( storage, minLevel, maxLevel, k ): -div( k grad u ) on P2 with the P2 coefficient
+    function k, which the caller interpolates on every level it uses (the operator at level l reads k at level l).  Every apply goes
+    through the C-ABI seam hyteg_hip_p2_elementwise_divkgrad_apply_cell_kinds."""
+
+    def __init__(self, storage: Storage, min_level: int, max_level: int, k: P2Function):
+        self.storage, self.k = storage, k  # the coefficient must outlive the operator
+        h = _vp()
+        _ck(lib().hyteg_host_p2divkgrad_create(storage.h, min_level, max_level, k.h, C.byref(h)), "p2divkgrad_create")
+        self.h = h
+
+    def apply(self, src: P2Function, dst: P2Function, level, flag, update=Replace):
+        _ck(lib().hyteg_host_p2divkgrad_apply(self.h, src.h, dst.h, level, flag, update), "p2divkgrad apply")
+
+    def gemv(self, alpha, src: P2Function, beta, dst: P2Function, level, flag):
+        """dst = alpha A src + beta dst"""
+        _ck(lib().hyteg_host_p2divkgrad_gemv(self.h, float(alpha), src.h, float(beta), dst.h, level, flag), "p2divkgrad gemv")
+
+    def compute_inverse_diagonal(self):
+        _ck(lib().hyteg_host_p2divkgrad_compute_inverse_diagonal(self.h), "computeInverseDiagonalOperatorValues")
+
+    def inverse_diagonal_into(self, dst: P2Function, level):
+        _ck(lib().hyteg_host_p2divkgrad_inverse_diagonal_copy(self.h, dst.h, level), "p2divkgrad inverse diagonal")
+
+    def smooth_jac(self, dst: P2Function, rhs: P2Function, src: P2Function, relax, level, flag=Inner | NeumannBoundary):
+        _ck(lib().hyteg_host_p2divkgrad_smooth_jac(self.h, dst.h, rhs.h, src.h, float(relax), level, flag), "p2divkgrad smooth_jac")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_p2divkgrad_destroy(self.h)
+            self.h = None
+
+
+class P2DivKGradSolver:
+    """The solvers instantiated for P2ElementwiseDivKGrad: CGSolver, GeometricMultigridSolver (quadratic P2 transfer, CG on the coarsest
+    level) with a weighted-Jacobi or a Chebyshev smoother, FullMultigridSolver, and the smoothers on their own.  Built by the class
+    methods; mirrors DivKGradSolver and P2Solver."""
+
+    def __init__(self, storage, h, keep=None):
+        self.storage, self.h, self._keep = storage, h, keep
+
+    @classmethod
+    def cg(cls, storage, min_level, max_level, max_iter=1000, tol=1e-14, preconditioner=None):
+        """hyteg::CGSolver< P2ElementwiseDivKGrad >; preconditioner: a P2DivKGradSolver or None"""
+        h = _vp()
+        _ck(lib().hyteg_host_p2divkgrad_cg_create(storage.h, min_level, max_level, max_iter, float(tol),
+                                                  preconditioner.h if preconditioner is not None else None, C.byref(h)), "p2divkgrad cg_create")
+        return cls(storage, h, preconditioner)
+
+    @classmethod
+    def gmg(cls, storage, min_level, max_level, smoother=JACOBI, relax=2.0 / 3.0, pre=3, post=3, wcycle=False, cg_max_iter=1000, cg_tol=1e-14):
+        """hyteg::GeometricMultigridSolver with WeightedJacobiSmoother( relax ) (the operator has no Gauss-Seidel sweep)"""
+        if smoother != JACOBI:
+            raise HytegHostError("P2DivKGradSolver.gmg: smoother JACOBI (gmg_chebyshev for the Chebyshev smoother)")
+        h = _vp()
+        _ck(lib().hyteg_host_p2divkgrad_gmg_create(storage.h, min_level, max_level, float(relax), pre, post, int(bool(wcycle)), cg_max_iter,
+                                                   float(cg_tol), C.byref(h)), "p2divkgrad gmg_create")
+        return cls(storage, h)
+
+    @classmethod
+    def chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3):
+        """hyteg::ChebyshevSmoother< P2ElementwiseDivKGrad > on its own (solve = one smoother call)"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_p2divkgrad_chebyshev_create(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower),
+                                                         C.byref(h)), "p2divkgrad chebyshev_create")
+        return cls(storage, h)
+
+    @classmethod
+    def gmg_chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3, pre=1, post=1, wcycle=False, cg_max_iter=1000,
+                      cg_tol=1e-14):
+        """the multigrid solver smoothing with ChebyshevSmoother( order ); radii: one spectral radius (estimate_radius) or one per level"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_p2divkgrad_gmg_create_chebyshev(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), pre,
+                                                             post, int(bool(wcycle)), cg_max_iter, float(cg_tol), C.byref(h)),
+            "p2divkgrad gmg_create_chebyshev")
+        return cls(storage, h)
+
+    @classmethod
+    def fmg(cls, storage, gmg_solver, min_level, max_level, cycles_per_level=1):
+        """hyteg::FullMultigridSolver around the multigrid solver `gmg_solver`, prolongating with P2toP2QuadraticProlongation;
+        cycles_per_level: one count, or one per level"""
+        counts = [cycles_per_level] if isinstance(cycles_per_level, int) else list(cycles_per_level)
+        arr = (C.c_uint * len(counts))(*counts)
+        h = _vp()
+        _ck(lib().hyteg_host_p2divkgrad_fmg_create(storage.h, gmg_solver.h, min_level, max_level, arr, 0 if isinstance(cycles_per_level, int) else len(counts),
+                                                   C.byref(h)), "p2divkgrad fmg_create")
+        return cls(storage, h, gmg_solver)
+
+    @classmethod
+    def smoother(cls, storage, min_level, max_level, smoother=JACOBI, relax=1.0):
+        """WeightedJacobiSmoother( relax ) (JACOBI) or IdentityPreconditioner (IDENTITY) on its own"""
+        h = _vp()
+        _ck(lib().hyteg_host_p2divkgrad_smoother_create(storage.h, min_level, max_level, {JACOBI: 0, IDENTITY: -1}[smoother], float(relax),
+                                                        C.byref(h)), "p2divkgrad smoother_create")
+        return cls(storage, h)
+
+    @property
+    def iterations(self) -> int:
+        """CGSolver::getIterations of the last solve (P2DivKGradSolver.cg)"""
+        n = _i(0)
+        _ck(lib().hyteg_host_p2divkgrad_cg_iterations(self.h, C.byref(n)), "p2divkgrad cg_iterations")
+        return n.value
+
+    def solve(self, op: P2ElementwiseDivKGrad, x: P2Function, b: P2Function, level):
+        _ck(lib().hyteg_host_p2divkgrad_solver_solve(self.h, op.h, x.h, b.h, level), "p2divkgrad solve")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_p2divkgrad_solver_destroy(self.h)
             self.h = None
 
 

@@ -38,6 +38,7 @@
 #include "p1elementwise.hpp"
 #include "p1divkgrad.hpp"
 #include "p2operator.hpp"
+#include "p2divkgrad.hpp"
 #include "p2gridtransfer.hpp"
 #include "gridtransfer.hpp"
 #include "p1p2conversion.hpp"

@@ -2220,6 +2220,160 @@ HYTEG_HOST_API int hyteg_host_p2_cg_solve( hh_storage_t s, hh_p2operator_t op, h
 }
 }
 
+/* ---- the generated variable-coefficient P2 operator: P2ElementwiseDivKGrad with a P2 coefficient, the solvers instantiated for it, and
+ * P2ElementwiseMassOperator (p2divkgrad.hpp) ---- */
+namespace {
+using P2DivKGrad = operatorgeneration::P2ElementwiseDivKGrad;
+using P2DkGmg    = GeometricMultigridSolver< P2DivKGrad, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation >;
+struct P2DivKGradH
+{
+   std::shared_ptr< P2Function< double > > k; // the operator holds a reference: the handle keeps the function alive
+   std::shared_ptr< P2DivKGrad >           p;
+};
+struct P2DivKGradSolverH
+{
+   std::shared_ptr< Solver< P2DivKGrad > > p;
+};
+struct P2MassOperatorH
+{
+   std::shared_ptr< P2ElementwiseMassOperator > p;
+};
+P2DivKGrad& DK2( hh_p2divkgrad_t op )
+{
+   if ( !op )
+      throw std::runtime_error( "null p2divkgrad operator" );
+   return *static_cast< P2DivKGradH* >( op )->p;
+}
+std::shared_ptr< Solver< P2DivKGrad > > p2DivKGradSmoother( hh_storage_t s, int minL, int maxL, int code, double relax )
+{
+   if ( code == 0 )
+      return std::make_shared< WeightedJacobiSmoother< P2DivKGrad > >( SP( s ), (uint_t) minL, (uint_t) maxL, relax );
+   if ( code == -1 )
+      return std::make_shared< IdentityPreconditioner< P2DivKGrad > >();
+   throw std::runtime_error( "p2divkgrad_smoother_create: smoother 0 (weighted Jacobi) or -1 (identity)" );
+}
+} // namespace
+HYTEG_HOST_API int hyteg_host_p2divkgrad_create( hh_storage_t s, int minL, int maxL, hh_p2function_t k, hh_p2divkgrad_t* out )
+{
+   return guarded( [&] {
+      if ( !k || minL < 0 || maxL < minL )
+         throw std::runtime_error( "p2divkgrad_create: needs a coefficient function and 0 <= min_level <= max_level" );
+      auto h = std::make_unique< P2DivKGradH >();
+      h->k   = static_cast< P2FunctionH* >( k )->p;
+      h->p   = std::make_shared< P2DivKGrad >( SP( s ), (uint_t) minL, (uint_t) maxL, *h->k );
+      *out   = h.release();
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_destroy( hh_p2divkgrad_t op )
+{
+   return guarded( [&] { delete static_cast< P2DivKGradH* >( op ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_apply( hh_p2divkgrad_t op, hh_p2function_t src, hh_p2function_t dst, int level, int flag, int update )
+{
+   return guarded( [&] { DK2( op ).apply( F2( src ), F2( dst ), (uint_t) level, DoFType( flag ), update ? Add : Replace ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_gemv( hh_p2divkgrad_t op, double alpha, hh_p2function_t src, double beta, hh_p2function_t dst, int level,
+                                               int flag )
+{
+   return guarded( [&] { DK2( op ).gemv( alpha, F2( src ), beta, F2( dst ), (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_compute_inverse_diagonal( hh_p2divkgrad_t op )
+{
+   return guarded( [&] { DK2( op ).computeInverseDiagonalOperatorValues(); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_inverse_diagonal_copy( hh_p2divkgrad_t op, hh_p2function_t dst, int level )
+{
+   return guarded( [&] { F2( dst ).assign( { 1.0 }, { *DK2( op ).getInverseDiagonalValues() }, (uint_t) level, All ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_smooth_jac( hh_p2divkgrad_t op, hh_p2function_t dst, hh_p2function_t rhs, hh_p2function_t src, double relax,
+                                                     int level, int flag )
+{
+   return guarded( [&] { DK2( op ).smooth_jac( F2( dst ), F2( rhs ), F2( src ), relax, (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_cg_create( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_p2divkgrad_solver_t preconditioner,
+                                                    hh_p2divkgrad_solver_t* out )
+{
+   return guarded( [&] {
+      if ( preconditioner )
+         cgCreatePreconditioned< P2DivKGrad, P2DivKGradSolverH >( "p2divkgrad_cg_create", s, minL, maxL, maxIter, tol, preconditioner, out );
+      else
+         *out = new P2DivKGradSolverH{ std::make_shared< CGSolver< P2DivKGrad > >( SP( s ), (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, tol, tol ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_cg_iterations( hh_p2divkgrad_solver_t solver, int* iterations )
+{
+   return guarded( [&] { cgIterations< P2DivKGrad, P2DivKGradSolverH >( "p2divkgrad_cg_iterations", solver, iterations ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_smoother_create( hh_storage_t s, int minL, int maxL, int smoother, double relax, hh_p2divkgrad_solver_t* out )
+{
+   return guarded( [&] { *out = new P2DivKGradSolverH{ p2DivKGradSmoother( s, minL, maxL, smoother, relax ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_gmg_create( hh_storage_t s, int minL, int maxL, double relax, int pre, int post, int wcycle, int cgMaxIter,
+                                                     double cgTol, hh_p2divkgrad_solver_t* out )
+{
+   return guarded( [&] {
+      *out = new P2DivKGradSolverH{ makeGmg< P2DivKGrad, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation >(
+          SP( s ), p2DivKGradSmoother( s, minL, maxL, 0, relax ), cgCoarse< P2DivKGrad >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0,
+          cycleOf( wcycle ) ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_chebyshev_estimate_radius( hh_p2divkgrad_t op, int level, int maxIter, hh_p2function_t x, hh_p2function_t tmp,
+                                                                    double* radius )
+{
+   return guarded( [&] { *radius = chebyshev::estimateRadius( DK2( op ), (uint_t) level, (uint_t) maxIter, F2( x ).getStorage(), F2( x ), F2( tmp ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_chebyshev_create( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                           double lower, hh_p2divkgrad_solver_t* out )
+{
+   return guarded( [&] { *out = new P2DivKGradSolverH{ makeChebyshev< P2DivKGrad >( s, minL, maxL, order, radii, nRadii, upper, lower ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_gmg_create_chebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii,
+                                                               double upper, double lower, int pre, int post, int wcycle, int cgMaxIter, double cgTol,
+                                                               hh_p2divkgrad_solver_t* out )
+{
+   return guarded( [&] {
+      std::shared_ptr< Solver< P2DivKGrad > > sm = makeChebyshev< P2DivKGrad >( s, minL, maxL, order, radii, nRadii, upper, lower );
+      *out = new P2DivKGradSolverH{ makeGmg< P2DivKGrad, P2toP2QuadraticRestriction, P2toP2QuadraticProlongation >(
+          SP( s ), sm, cgCoarse< P2DivKGrad >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_fmg_create( hh_storage_t s, hh_p2divkgrad_solver_t gmg, int minL, int maxL, const unsigned* cyclesPerLevel,
+                                                     int nCycles, hh_p2divkgrad_solver_t* out )
+{
+   return guarded( [&] {
+      auto g = gmg ? std::dynamic_pointer_cast< P2DkGmg >( static_cast< P2DivKGradSolverH* >( gmg )->p ) : nullptr;
+      if ( !g )
+         throw std::runtime_error( "p2divkgrad_fmg_create: not a geometric multigrid solver" );
+      *out = new P2DivKGradSolverH{ std::make_shared< FullMultigridSolver< P2DivKGrad, P2DkGmg, P2toP2QuadraticProlongation > >(
+          SP( s ), g, std::make_shared< P2toP2QuadraticProlongation >(), (uint_t) minL, (uint_t) maxL,
+          fmgCycles( "p2divkgrad_fmg_create", minL, maxL, cyclesPerLevel, nCycles ), levelCallback( nullptr, nullptr ), levelCallback( nullptr, nullptr ) ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_solver_solve( hh_p2divkgrad_solver_t solver, hh_p2divkgrad_t op, hh_p2function_t x, hh_p2function_t b, int level )
+{
+   return guarded( [&] { static_cast< P2DivKGradSolverH* >( solver )->p->solve( DK2( op ), F2( x ), F2( b ), (uint_t) level ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_solver_destroy( hh_p2divkgrad_solver_t solver )
+{
+   return guarded( [&] { delete static_cast< P2DivKGradSolverH* >( solver ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2massoperator_create( hh_storage_t s, int minL, int maxL, hh_p2massoperator_t* out )
+{
+   return guarded( [&] { *out = new P2MassOperatorH{ std::make_shared< P2ElementwiseMassOperator >( SP( s ), (uint_t) minL, (uint_t) maxL ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_p2massoperator_apply( hh_p2massoperator_t op, hh_p2function_t src, hh_p2function_t dst, int level, int flag, int update )
+{
+   return guarded( [&] {
+      if ( !op )
+         throw std::runtime_error( "null p2 mass operator" );
+      static_cast< P2MassOperatorH* >( op )->p->apply( F2( src ), F2( dst ), (uint_t) level, DoFType( flag ), UpdateType( update ) );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2massoperator_destroy( hh_p2massoperator_t op )
+{
+   return guarded( [&] { delete static_cast< P2MassOperatorH* >( op ); } );
+}
+
 
 /* ---- P2-P1 Taylor-Hood Stokes (taylorhood.hpp) ---- */
 HYTEG_HOST_API int hyteg_host_th_function_create( hh_storage_t s, const char* name, int minL, int maxL, hh_th_function_t* out )

@@ -1312,6 +1312,67 @@ HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_diagonal_macro_3d( double*  
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_set_shape( int ny, int lz );
 HYTEG_HIP_API int hyteg_hip_p1_elementwise_divkgrad_set_inner_by_points( int on );
 
+/* ---- b-4 (P2): -div( k grad u ) on P2 with a P2 coefficient, the seam of the generated P2ElementwiseDivKGrad ----------------
+ * Replaces operatorgeneration::P2ElementwiseDivKGrad::apply of operatorgeneration::P2ElementwiseDivKGrad( storage, minLevel, maxLevel,
+ * const P2Function< real_t >& k ) (module hyteg_operators; in-tree use: tests/hyteg/convergence/ElementwiseDivKGradCGConvergenceTest.cpp:
+ * 192-221, runAllTestsP2).  The generated source is absent from the snapshot, so the arithmetic is pinned by the identity, not by the
+ * generated code: on a micro-cell e,  A_e[i][j] = sum_m k_m int_e phi_m grad phi_i . grad phi_j  over the ten DoFs m of e, integrated
+ * exactly (degree 4; forms::p2_div_k_grad_affine_q4 evaluates the same form with a degree-4 rule), local DoFs in the FEniCS order of
+ * P2Form::integrateAll.  Arrays, alpha, update, the 15-bit point-class mask and the 8-bit kind_mask are those of
+ * hyteg_hip_p2_elementwise_apply_cell_kinds (7-block edge array, XYZ block of tet( 2^level - 1 )); k_vertex / k_edge: the coefficient's
+ * arrays at the same level; entries outside mask and kinds are not written.  Levels 0..8 (32-bit indices).
+ * EINVAL before any GPU work: a level out of range, a null array, a written array that is a src or k array, a bad update type.
+ *
+ * hyteg_hip_p2_elementwise_divkgrad_geometry fills the 60 doubles the kernels need of a ( macro-cell, level ): |e| grad l_a . grad l_b / 840
+ * of the six micro-cell types (pairs a <= b: 00 01 02 03 11 12 13 22 23 33); a HOST array, passed to the kernels in their arguments. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_geometry( const double* macro_vertex_coords /* 12 */, int level, double* geometry /* 60 */ );
+/* Replaces operatorgeneration::P2ElementwiseDivKGrad::apply on one macro-cell (test file above).  Inner DoFs: the inner form
+ * (compile-time micro-cell lists) from the level of hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level on (default 6, where it
+ * measures faster), below it the gather form; boundary DoFs of every level: the gather form. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_apply_cell_kinds( double*            dst_vertex,
+                                                                      double*            dst_edge,
+                                                                      const double*      src_vertex,
+                                                                      const double*      src_edge,
+                                                                      const double*      k_vertex,
+                                                                      const double*      k_edge,
+                                                                      int                level,
+                                                                      const double*      geometry /* 60, host */,
+                                                                      double             alpha,
+                                                                      int                update,
+                                                                      unsigned           mask,
+                                                                      unsigned           kind_mask,
+                                                                      hyteg_hip_stream_t stream );
+/* The same operator (operatorgeneration::P2ElementwiseDivKGrad::apply, test file above) through the gather form on every DoF: the
+ * second implementation the inner form is tested and measured against. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_apply_cell_gather( double*            dst_vertex,
+                                                                       double*            dst_edge,
+                                                                       const double*      src_vertex,
+                                                                       const double*      src_edge,
+                                                                       const double*      k_vertex,
+                                                                       const double*      k_edge,
+                                                                       int                level,
+                                                                       const double*      geometry /* 60, host */,
+                                                                       double             alpha,
+                                                                       int                update,
+                                                                       unsigned           mask,
+                                                                       unsigned           kind_mask,
+                                                                       hyteg_hip_stream_t stream );
+/* Replaces the macro-cell part of operatorgeneration::P2ElementwiseDivKGrad::computeInverseDiagonalOperatorValues (test file above,
+ * through the smoothers): every DoF of the cell receives the sum of A_e[i][i] over its adjacent micro-cells of THIS macro-cell
+ * (Replace); the caller sums the shared copies and inverts.  diag arrays must not be k arrays. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_diagonal_cell( double*            diag_vertex,
+                                                                   double*            diag_edge,
+                                                                   const double*      k_vertex,
+                                                                   const double*      k_edge,
+                                                                   int                level,
+                                                                   const double*      geometry /* 60, host */,
+                                                                   hyteg_hip_stream_t stream );
+/* Tuning knob of operatorgeneration::P2ElementwiseDivKGrad::apply above (no counterpart in the reference; test file above): the first
+ * level whose inner DoFs take the inner form (at least 2; 99: the gather form everywhere).  Returns the previous value.
+ * hyteg_hip_p2_elementwise_divkgrad_max_level: the largest level of these entries. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level( int level );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_max_level( void );
+
 /* ---- b-5: variable-viscosity epsilon operator -div( 2 mu eps(u) ), eps(u) = ( grad u + grad u^T ) / 2 ------------------------
  * Replaces, in ONE pass over the three velocity components, the nine P1ElementwiseOperator::apply calls of
  * P1ElementwiseAffineEpsilonOperator::apply (src/mixed_operator/P1EpsilonOperator.hpp:89-164; forms::p1_epsilonvar_i_j_affine_q2)

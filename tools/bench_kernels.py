@@ -3,7 +3,8 @@
 timings through the host layer.  Not the headline bench (that is bench.py); this is the evidence table for
 DESIGN.md section 3.  Usage: python tools/bench_kernels.py [--level 8] [--reps 200]
 --only epsilon: the rows of the epsilon operator alone, levels 6..level, with the fused residual and Chebyshev steps
-against the composed sequences they replace; --only divkgrad: the same pairs for div-k-grad."""
+against the composed sequences they replace; --only divkgrad: the same pairs for div-k-grad; --only p2-divkgrad: the two
+forms of the P2 div-k-grad apply, the constant P2 apply and a copy, levels 4..7."""
 import argparse
 import json
 import sys
@@ -240,6 +241,68 @@ def divkgrad_mode_rows(top_level, reps, from_level=6):
     print(json.dumps({"levels": list(range(from_level, top_level + 1)), "device": capi.device_name(), "kernels": rows}))
 
 
+def p2_divkgrad_rows(top_level, reps, from_level=4, repeats=5):
+    """--only p2-divkgrad: the macro-cell of tet_1el, all DoFs, levels from_level..top_level.  Per level, in the same run and
+    alternating in every one of `repeats` rounds: the P2 div-k-grad apply with the inner form on the inner DoFs, the same through the gather
+    form on every DoF, the constant-coefficient P2 apply on the same cell, and a device copy that moves the bytes of the six arrays (four
+    read, two written).  Reported: the median of the rounds and their spread (min .. max); a form is faster only beyond that spread.
+    Rings: every array class exceeds the Infinity Cache 2.2 times, capped at 256 buffers (the small levels are launch-bound anyway)."""
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    st = host.Storage.from_gmsh(ROOT / "hyteg_amd/data/meshes/tet_1el.msh")
+    st.set_stream(sh)
+    tet = [list(map(float, v)) for v in st.local_cell(0)[1]]
+    rows = []
+    before = capi.p2_elementwise_divkgrad_set_inner_min_level(2)
+    for L in range(from_level, top_level + 1):
+        nv, ne = capi.cell_size(L), capi.p2_edge_array_size(L)
+        dofs = nv + ne
+        nbuf = min(256, max(4, -(-int(2.2 * 256 * 2**20) // (ne * 8))))
+        rnd = lambda n, lo=0.0: [lo + torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)]  # noqa: E731
+        DV, DE, SV, SE, KV, KE = rnd(nv), rnd(ne), rnd(nv), rnd(ne), rnd(nv, 0.5), rnd(ne, 0.5)
+        half = (3 * dofs) // 2
+        CA, CB = rnd(half), rnd(half)
+        geometry = capi.p2_elementwise_divkgrad_geometry(tet, L)
+        table = torch.from_numpy(np.asarray(capi.p2_build_operator_table(capi.p2_elementwise_diffusion_element_matrices(tet, 1 << L)))).to("cuda")
+        p = lambda t, k: t[k % nbuf].data_ptr()  # noqa: E731
+
+        def divkgrad(gather):
+            return lambda k: capi.p2_elementwise_divkgrad_apply_cell(p(DV, k), p(DE, k), p(SV, k), p(SE, k), p(KV, k), p(KE, k), L, geometry, 1.0, 0,
+                                                                     0x7FFF, 0xFF, sh, gather=gather)
+
+        table_rows = [
+            ("P2 div-k-grad apply: inner form (+ gather form on the boundary DoFs)", divkgrad(False), 48 * dofs),
+            ("P2 div-k-grad apply: gather form on every DoF", divkgrad(True), 48 * dofs),
+            ("constant-coefficient P2 apply on the same cell", lambda k: capi.p2_elementwise_apply_cell(p(DV, k), p(DE, k), p(SV, k), p(SE, k), L,
+                                                                                                     table.data_ptr(), 1.0, 0, 0x7FFF, sh), 16 * dofs),
+            ("device copy moving the bytes of the six arrays", lambda k: CA[k % nbuf].copy_(CB[k % nbuf]), 24 * dofs),
+        ]
+        for name, fn, nbytes in table_rows:  # warm every shape
+            for k in range(3):
+                fn(k)
+        torch.cuda.synchronize()
+        times = {name: [] for name, _, _ in table_rows}
+        for _ in range(repeats):
+            for name, fn, nbytes in table_rows:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for k in range(reps):
+                    fn(k)
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+        for name, fn, nbytes in table_rows:
+            t = sorted(times[name])
+            us = t[len(t) // 2]
+            rows.append(dict(kernel=name, level=L, us=us, us_min=t[0], us_max=t[-1], GBps=nbytes / us * 1e-3, GDoFps=dofs / us * 1e-3,
+                             algorithmic_bytes=nbytes, dofs=dofs))
+            print(f"level {L}  {name:70s} {us:10.2f} us  ({t[0]:.2f} .. {t[-1]:.2f})  {nbytes / us * 1e-3:8.1f} GB/s  {dofs / us * 1e-3:8.3f} GDoF/s",
+                  flush=True)
+        del DV, DE, SV, SE, KV, KE, CA, CB
+    capi.p2_elementwise_divkgrad_set_inner_min_level(before)
+    print(json.dumps({"levels": list(range(from_level, top_level + 1)), "device": capi.device_name(), "repeats": repeats, "kernels": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", type=int, default=8)
@@ -256,6 +319,9 @@ def main():
         return
     if args.only == "divkgrad":
         divkgrad_mode_rows(min(L, 8), reps, max(2, args.from_level))
+        return
+    if args.only == "p2-divkgrad":
+        p2_divkgrad_rows(min(L, 7), reps, min(4, max(0, args.from_level)))
         return
     n, inner = capi.cell_size(L), capi.cell_inner_size(L)
     nc = capi.cell_size(L - 1)
