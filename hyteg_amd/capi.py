@@ -185,6 +185,12 @@ SIGNATURES = {
     "hyteg_hip_p2_elementwise_divkgrad_diagonal_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _vp]),
     "hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level": (_i, [_i]),
     "hyteg_hip_p2_elementwise_divkgrad_max_level": (_i, []),
+    "hyteg_hip_p2_elementwise_epsilon_geometry": (_i, [_dp, _i, _dp]),
+    "hyteg_hip_p2_elementwise_epsilon_apply_cell_kinds": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint), _i, _dp, _d, _i, C.c_uint, _vp]),
+    "hyteg_hip_p2_elementwise_epsilon_apply_cell_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint), _i, _dp, _d, _i, C.c_uint, _vp]),
+    "hyteg_hip_p2_elementwise_epsilon_diagonal_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _vp]),
+    "hyteg_hip_p2_elementwise_epsilon_set_inner_min_level": (_i, [_i]),
+    "hyteg_hip_p2_elementwise_epsilon_max_level": (_i, []),
     "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_masked": (_i, [_vp, _vp, _vp, _dp, _i64, C.c_uint, _i, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_component_masks": (_i, [_vp, _vp, _vp, _dp, _i64, C.POINTER(C.c_uint), _i, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _vp]),
@@ -997,6 +1003,55 @@ def p2_elementwise_divkgrad_set_inner_min_level(level):
 
 def p2_elementwise_divkgrad_max_level():
     return lib().hyteg_hip_p2_elementwise_divkgrad_max_level()
+
+
+# ---- -div( 2 mu eps(u) ) on P2 with a P2 viscosity: the seam of P2ViscousBlockEpsilonOperator, three components in one pass ----
+def p2_elementwise_epsilon_geometry(coords, level):
+    """the 72 geometry numbers of a ( macro-cell, level ): sqrt( |e| / 840 ) d_r l_a of the six micro-cell types at [12 t + 3 a + r]"""
+    a = (C.c_double * 12)(*_c12(coords))
+    out = (C.c_double * 72)()
+    check(lib().hyteg_hip_p2_elementwise_epsilon_geometry(a, int(level), out), "p2_elementwise_epsilon_geometry")
+    return list(out)
+
+
+def _geometry72(geometry):
+    if geometry is None:
+        return None
+    g = [float(v) for v in geometry]
+    if len(g) != 72:
+        raise ValueError("geometry: 72 doubles (p2_elementwise_epsilon_geometry)")
+    return (C.c_double * 72)(*g)
+
+
+def _masks3(mask):
+    if mask is None:
+        return None
+    m = [int(x) for x in mask] if isinstance(mask, (tuple, list)) else [int(mask)] * 3
+    return (C.c_uint * 3)(*m)
+
+
+def p2_elementwise_epsilon_apply_cell(dst_v, dst_e, src_v, src_e, mu_v, mu_e, level, geometry, alpha=1.0, update=REPLACE, mask=MASK_ALL,
+                                      kinds=0xFF, stream=0, gather=False):
+    """dst = alpha * A( mu ) src (or +=) on the DoFs of `mask` and `kinds`; dst_*, src_*: three device pointers each (u, v, w); mask: one
+    15-bit class mask, or three (one per destination component); gather: the gather form on every DoF"""
+    fn = lib().hyteg_hip_p2_elementwise_epsilon_apply_cell_gather if gather else lib().hyteg_hip_p2_elementwise_epsilon_apply_cell_kinds
+    check(fn(_ptr3(dst_v), _ptr3(dst_e), _ptr3(src_v), _ptr3(src_e), mu_v, mu_e, _masks3(mask), int(level), _geometry72(geometry), float(alpha),
+             update, kinds, stream), "p2_elementwise_epsilon_apply_cell")
+
+
+def p2_elementwise_epsilon_diagonal_cell(diag_v, diag_e, mu_v, mu_e, level, geometry, stream=0):
+    """component i of every DoF: the sum of A_e^{ii}[row][row] over its adjacent micro-cells; diag_v, diag_e: three device pointers each"""
+    check(lib().hyteg_hip_p2_elementwise_epsilon_diagonal_cell(_ptr3(diag_v), _ptr3(diag_e), mu_v, mu_e, int(level), _geometry72(geometry), stream),
+          "p2_elementwise_epsilon_diagonal_cell")
+
+
+def p2_elementwise_epsilon_set_inner_min_level(level):
+    """first level whose inner DoFs take the inner form (99: the gather form everywhere); returns the previous value"""
+    return lib().hyteg_hip_p2_elementwise_epsilon_set_inner_min_level(int(level))
+
+
+def p2_elementwise_epsilon_max_level():
+    return lib().hyteg_hip_p2_elementwise_epsilon_max_level()
 
 
 # ---- variable-viscosity epsilon operator -div( 2 mu eps(u) ): the nine blocks of P1ElementwiseAffineEpsilonOperator in one pass ----

@@ -57,9 +57,8 @@ struct DkGatherArgs
 constexpr int kDkPair[4][4]  = { { 0, 1, 2, 3 }, { 1, 4, 5, 6 }, { 2, 5, 7, 8 }, { 3, 6, 8, 9 } };
 constexpr int kDkLocal[4][4] = { { 0, 9, 8, 7 }, { 9, 1, 6, 5 }, { 8, 6, 2, 4 }, { 7, 5, 4, 3 } }; // fenics::P2DoFMap
 
-// row `row` of A_e times u, without the factor alpha.  g: the ten geometry numbers of the micro-cell's type.  Every loop has
-// constant bounds and is unrolled; with a compile-time row the entries of S that the row does not need are never computed.
-__device__ __forceinline__ double dk_element_row( const double* __restrict__ g, const double ( &k )[10], const double ( &u )[10], int row )
+// 840 Q_cd / |e| from the ten coefficient values of a micro-cell (shared with the P2 epsilon kernels, kernels_p2_epsilon.hpp)
+__device__ __forceinline__ void dk_moments( const double ( &k )[10], double ( &Q )[4][4] )
 {
    double K[4][4], r[4];
 #pragma unroll
@@ -79,7 +78,6 @@ __device__ __forceinline__ double dk_element_row( const double* __restrict__ g, 
       tr += K[a][a];
    }
    const double st = s + tr;
-   double       Q[4][4];
 #pragma unroll
    for ( int c = 0; c < 4; ++c )
    {
@@ -88,12 +86,24 @@ __device__ __forceinline__ double dk_element_row( const double* __restrict__ g, 
       for ( int d = c + 1; d < 4; ++d )
          Q[c][d] = Q[d][c] = st + 2.0 * ( r[c] + r[d] ) + 2.0 * ( K[c][d] + ( K[c][c] + K[d][d] ) );
    }
-   double w[4][4];
+}
+// grad u = sum_b ( sum_d w_bd l_d ) g_b from the ten values of u
+__device__ __forceinline__ void dk_weights( const double ( &u )[10], double ( &w )[4][4] )
+{
 #pragma unroll
    for ( int b = 0; b < 4; ++b )
 #pragma unroll
       for ( int d = 0; d < 4; ++d )
          w[b][d] = b == d ? 3.0 * u[b] : 4.0 * u[kDkLocal[b][d]] - u[b];
+}
+
+// row `row` of A_e times u, without the factor alpha.  g: the ten geometry numbers of the micro-cell's type.  Every loop has
+// constant bounds and is unrolled; with a compile-time row the entries of S that the row does not need are never computed.
+__device__ __forceinline__ double dk_element_row( const double* __restrict__ g, const double ( &k )[10], const double ( &u )[10], int row )
+{
+   double Q[4][4], w[4][4];
+   dk_moments( k, Q );
+   dk_weights( u, w );
    double S[4][4];
 #pragma unroll
    for ( int c = 0; c < 4; ++c )

@@ -215,6 +215,28 @@ SIGNATURES = {
     "hyteg_host_p2massoperator_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "hyteg_host_p2massoperator_apply": (_i, [_vp, _vp, _vp, _i, _i, _i]),
     "hyteg_host_p2massoperator_destroy": (_i, [_vp]),
+    "hyteg_host_p2epsilon_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_p2epsilon_destroy": (_i, [_vp]),
+    "hyteg_host_p2epsilon_apply": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i]),
+    "hyteg_host_p2epsilon_gemv": (_i, [_vp, _d, C.POINTER(_vp), _d, C.POINTER(_vp), _i, _i]),
+    "hyteg_host_p2epsilon_compute_inverse_diagonal": (_i, [_vp]),
+    "hyteg_host_p2epsilon_inverse_diagonal": (_i, [_vp, C.POINTER(_vp)]),
+    "hyteg_host_p2epsilon_smooth_jac": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _d, _i, _i]),
+    "hyteg_host_p2epsilon_cg_create": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
+    "hyteg_host_p2epsilon_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_p2epsilon_smoother_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2epsilon_chebyshev_estimate_radius": (_i, [_vp, _i, _i, C.POINTER(_d)]),
+    "hyteg_host_p2epsilon_chebyshev_create": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2epsilon_solver_solve": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _i]),
+    "hyteg_host_p2epsilon_solver_destroy": (_i, [_vp]),
+    "hyteg_host_th_epsilon_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_th_epsilon_destroy": (_i, [_vp]),
+    "hyteg_host_th_epsilon_apply": (_i, [_vp, _vp, _vp, _i, _i]),
+    "hyteg_host_th_epsilon_minres_create": (_i, [_vp, _i, _i, _i, _d, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_th_epsilon_minres_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_th_epsilon_minres_precondition": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "hyteg_host_th_epsilon_minres_iterations": (_i, [_vp, C.POINTER(_i)]),
+    "hyteg_host_th_epsilon_minres_destroy": (_i, [_vp]),
     "hyteg_host_epsilon_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
     "hyteg_host_epsilon_destroy": (_i, [_vp]),
     "hyteg_host_epsilon_apply": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i]),
@@ -2189,6 +2211,161 @@ class TaylorHoodSolver:
         if self.h:
             lib().hyteg_host_th_solver_destroy(self.h)
             self.h = None
+
+
+class P2ViscousBlockEpsilonOperator:
+    """hyteg::operatorgeneration::P2ViscousBlockEpsilonOperator( storage, minLevel, maxLevel, mu ): -div( 2 mu eps(u) ) on a P2 vector
+    function, given as its three component functions (for instance TaylorHoodFunction.velocity), with the P2 viscosity function mu,
+    which the caller interpolates on every level it uses (the operator at level l reads mu at level l; levels 0..8).  Every component is
+    masked by its own boundary condition.  Every apply goes through the C-ABI seam hyteg_hip_p2_elementwise_epsilon_apply_cell_kinds."""
+
+    def __init__(self, storage: Storage, min_level: int, max_level: int, mu: P2Function):
+        self.storage, self.mu = storage, mu  # the viscosity must outlive the operator
+        self.min_level, self.max_level = min_level, max_level
+        h = _vp()
+        _ck(lib().hyteg_host_p2epsilon_create(storage.h, min_level, max_level, mu.h, C.byref(h)), "p2epsilon_create")
+        self.h = h
+
+    def apply(self, src, dst, level, flag, update=Replace):
+        _ck(lib().hyteg_host_p2epsilon_apply(self.h, _handles3(src), _handles3(dst), level, flag, update), "p2epsilon apply")
+
+    def gemv(self, alpha, src, beta, dst, level, flag):
+        """dst = alpha A src + beta dst"""
+        _ck(lib().hyteg_host_p2epsilon_gemv(self.h, float(alpha), _handles3(src), float(beta), _handles3(dst), level, flag), "p2epsilon gemv")
+
+    def compute_inverse_diagonal(self):
+        _ck(lib().hyteg_host_p2epsilon_compute_inverse_diagonal(self.h), "p2epsilon computeInverseDiagonalOperatorValues")
+
+    def inverse_diagonal(self):
+        """the inverse diagonals of the three diagonal blocks: three P2Functions (borrowed: they live as long as the operator)"""
+        hs = (_vp * 3)()
+        _ck(lib().hyteg_host_p2epsilon_inverse_diagonal(self.h, hs), "p2epsilon getInverseDiagonalValues")
+        return [P2Function(self.storage, "invdiag", self.min_level, self.max_level, _borrowed=_vp(hs[k])) for k in range(3)]
+
+    def smooth_jac(self, dst, rhs, src, relax, level, flag=Inner | NeumannBoundary):
+        _ck(lib().hyteg_host_p2epsilon_smooth_jac(self.h, _handles3(dst), _handles3(rhs), _handles3(src), float(relax), level, flag),
+            "p2epsilon smooth_jac")
+
+    def estimate_radius(self, level: int, iterations: int) -> float:
+        """chebyshev::estimateRadius: spectral radius of D^-1 A by power iterations from a fixed start vector (inverse diagonal
+        computed)"""
+        r = _d()
+        _ck(lib().hyteg_host_p2epsilon_chebyshev_estimate_radius(self.h, int(level), int(iterations), C.byref(r)), "p2epsilon estimate_radius")
+        return r.value
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_p2epsilon_destroy(self.h)
+            self.h = None
+
+
+class P2EpsilonSolver:
+    """The solvers instantiated for P2ViscousBlockEpsilonOperator, acting on three component functions: CGSolver, ChebyshevSmoother and
+    WeightedJacobiSmoother / IdentityPreconditioner on their own.  Built by the class methods; mirrors EpsilonSolver."""
+
+    def __init__(self, storage, h, keep=None):
+        self.storage, self.h, self._keep = storage, h, keep
+
+    @classmethod
+    def cg(cls, storage, min_level, max_level, max_iter=1000, tol=1e-14, preconditioner=None):
+        """hyteg::CGSolver< P2ViscousBlockEpsilonOperator >; preconditioner: a P2EpsilonSolver or None"""
+        h = _vp()
+        _ck(lib().hyteg_host_p2epsilon_cg_create(storage.h, min_level, max_level, max_iter, float(tol),
+                                                 preconditioner.h if preconditioner is not None else None, C.byref(h)), "p2epsilon cg_create")
+        return cls(storage, h, preconditioner)
+
+    @classmethod
+    def chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3):
+        """hyteg::ChebyshevSmoother< P2ViscousBlockEpsilonOperator > on its own (solve = one smoother call)"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_p2epsilon_chebyshev_create(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower),
+                                                        C.byref(h)), "p2epsilon chebyshev_create")
+        return cls(storage, h)
+
+    @classmethod
+    def smoother(cls, storage, min_level, max_level, smoother=JACOBI, relax=1.0):
+        """WeightedJacobiSmoother( relax ) (JACOBI) or IdentityPreconditioner (IDENTITY) on its own"""
+        h = _vp()
+        _ck(lib().hyteg_host_p2epsilon_smoother_create(storage.h, min_level, max_level, {JACOBI: 0, IDENTITY: -1}[smoother], float(relax),
+                                                       C.byref(h)), "p2epsilon smoother_create")
+        return cls(storage, h)
+
+    @property
+    def iterations(self) -> int:
+        """CGSolver::getIterations of the last solve (P2EpsilonSolver.cg)"""
+        n = _i(0)
+        _ck(lib().hyteg_host_p2epsilon_cg_iterations(self.h, C.byref(n)), "p2epsilon cg_iterations")
+        return n.value
+
+    def solve(self, op: P2ViscousBlockEpsilonOperator, xs, bs, level):
+        _ck(lib().hyteg_host_p2epsilon_solver_solve(self.h, op.h, _handles3(xs), _handles3(bs), level), "p2epsilon solve")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_p2epsilon_solver_destroy(self.h)
+            self.h = None
+
+
+class TaylorHoodEpsilonStokesOperator:
+    """hyteg::operatorgeneration::P2P1StokesEpsilonOperator( storage, minLevel, maxLevel, mu ): the P2 epsilon operator on the velocity and
+    the div / divT blocks of the Taylor-Hood operator (no stabilisation); mu: a P2Function as for P2ViscousBlockEpsilonOperator"""
+
+    def __init__(self, storage: Storage, min_level: int, max_level: int, mu: P2Function):
+        self.storage, self.mu = storage, mu
+        h = _vp()
+        _ck(lib().hyteg_host_th_epsilon_create(storage.h, min_level, max_level, mu.h, C.byref(h)), "th_epsilon_create")
+        self.h = h
+
+    def apply(self, src: TaylorHoodFunction, dst: TaylorHoodFunction, level, flag):
+        _ck(lib().hyteg_host_th_epsilon_apply(self.h, src.h, dst.h, level, flag), "th_epsilon_apply")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_th_epsilon_destroy(self.h)
+        self.h = None
+
+
+class TaylorHoodEpsilonSolver:
+    """The solver instantiated for TaylorHoodEpsilonStokesOperator: MinResSolver (class method minres)"""
+
+    def __init__(self, handle, keep=()):
+        self.h = handle
+        self._keep = keep
+
+    @classmethod
+    def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, preconditioner="pressure", mu=None):
+        """hyteg::MinResSolver< P2P1StokesEpsilonOperator >; preconditioner "identity", "pressure" (StokesPressureBlockPreconditioner with
+        the lumped inverse mass operator, the reference's stokesMinResSolver) or "pressure_viscosity" (pressure action
+        x.p = mu .* invLumpedMass .* b.p with mu at the vertex DoFs; needs mu, the viscosity function)"""
+        kinds = {"identity": 0, "pressure": 1, "pressure_viscosity": 2}
+        if preconditioner not in kinds:
+            raise HytegHostError(f"TaylorHoodEpsilonSolver.minres: unknown preconditioner {preconditioner!r}")
+        kind = kinds[preconditioner]
+        if kind == 2 and mu is None:
+            raise HytegHostError(f"TaylorHoodEpsilonSolver.minres: the {preconditioner} preconditioner needs mu")
+        h = _vp()
+        _ck(lib().hyteg_host_th_epsilon_minres_create(storage.h, min_level, max_level, int(max_iter), float(rel_tol), kind,
+                                                      mu.h if kind == 2 else None, C.byref(h)), "th_epsilon_minres_create")
+        return cls(h, keep=(mu,))
+
+    @property
+    def minres_iterations(self) -> int:
+        n = _i(0)
+        _ck(lib().hyteg_host_th_epsilon_minres_iterations(self.h, C.byref(n)), "th_epsilon_minres_iterations")
+        return n.value
+
+    def solve(self, op: TaylorHoodEpsilonStokesOperator, x: TaylorHoodFunction, b: TaylorHoodFunction, level: int):
+        _ck(lib().hyteg_host_th_epsilon_minres_solve(self.h, op.h, x.h, b.h, level), "th_epsilon_minres_solve")
+
+    def precondition(self, op: TaylorHoodEpsilonStokesOperator, x: TaylorHoodFunction, b: TaylorHoodFunction, level: int):
+        """the solver's preconditioner on its own: x = M^-1 b"""
+        _ck(lib().hyteg_host_th_epsilon_minres_precondition(self.h, op.h, x.h, b.h, level), "th_epsilon_minres_precondition")
+
+    def close(self):
+        if self.h:
+            lib().hyteg_host_th_epsilon_minres_destroy(self.h)
+        self.h = None
 
 
 def taylor_hood_form_element_matrix(which, k, coords):

@@ -47,4 +47,5 @@
 #include "stokes.hpp"
 #include "p1epsilon.hpp"
 #include "taylorhood.hpp"
+#include "p2epsilon.hpp"
 #include "projectnormal.hpp"

@@ -2477,3 +2477,223 @@ HYTEG_HOST_API int hyteg_host_th_form_element_matrix( int which, int k, const do
          k == 0 ? forms::P1ToP2DivTForm< 0 >::integrateAll( c, out100 ) : ( k == 1 ? forms::P1ToP2DivTForm< 1 >::integrateAll( c, out100 ) : forms::P1ToP2DivTForm< 2 >::integrateAll( c, out100 ) );
    } );
 }
+
+/* ---- variable-viscosity Taylor-Hood Stokes: P2ViscousBlockEpsilonOperator, P2P1StokesEpsilonOperator and the solvers instantiated for
+ * them (p2epsilon.hpp) ---- */
+namespace {
+using P2Epsilon       = operatorgeneration::P2ViscousBlockEpsilonOperator;
+using P2EpsilonStokes = operatorgeneration::P2P1StokesEpsilonOperator;
+struct P2EpsilonH
+{
+   std::shared_ptr< P2Function< double > > mu; // the operator holds a reference: the handle keeps the function alive
+   std::shared_ptr< P2Epsilon >            p;
+   P2FunctionH                             invDiag[3]; // borrowed views
+};
+struct P2EpsilonSolverH
+{
+   std::shared_ptr< Solver< P2Epsilon > > p;
+};
+struct P2EpsilonStokesH
+{
+   std::shared_ptr< P2Function< double > > mu;
+   std::shared_ptr< P2EpsilonStokes >      p;
+};
+struct P2EpsilonStokesSolverH
+{
+   std::shared_ptr< P2Function< double > >            mu; // of the viscosity-weighted preconditioner, or null
+   std::shared_ptr< Solver< P2EpsilonStokes > >       preconditioner;
+   std::shared_ptr< MinResSolver< P2EpsilonStokes > > p;
+};
+P2Epsilon& EP2( hh_p2epsilon_t op )
+{
+   if ( !op )
+      throw std::runtime_error( "null p2 epsilon operator" );
+   return *static_cast< P2EpsilonH* >( op )->p;
+}
+P2EpsilonStokes& EPS2( hh_th_epsilon_t op )
+{
+   if ( !op )
+      throw std::runtime_error( "null Taylor-Hood epsilon Stokes operator" );
+   return *static_cast< P2EpsilonStokesH* >( op )->p;
+}
+P2EpsilonStokesSolverH& EPSS2( hh_th_epsilon_solver_t solver )
+{
+   if ( !solver )
+      throw std::runtime_error( "null Taylor-Hood epsilon Stokes solver" );
+   return *static_cast< P2EpsilonStokesSolverH* >( solver );
+}
+// three function handles as one P2VectorFunction (a view: the handles keep the components)
+P2VectorFunction< double > vectorOf2( const hh_p2function_t* f )
+{
+   if ( !f || !f[0] || !f[1] || !f[2] )
+      throw std::runtime_error( "p2 epsilon: three component functions" );
+   return P2VectorFunction< double >(
+       { static_cast< P2FunctionH* >( f[0] )->p, static_cast< P2FunctionH* >( f[1] )->p, static_cast< P2FunctionH* >( f[2] )->p } );
+}
+std::shared_ptr< P2Function< double > > viscosityOf2( const char* who, hh_p2function_t mu, int minL, int maxL )
+{
+   if ( !mu || minL < 0 || maxL < minL )
+      throw std::runtime_error( std::string( who ) + ": needs a viscosity function and 0 <= min_level <= max_level" );
+   return static_cast< P2FunctionH* >( mu )->p;
+}
+} // namespace
+HYTEG_HOST_API int hyteg_host_p2epsilon_create( hh_storage_t s, int minL, int maxL, hh_p2function_t mu, hh_p2epsilon_t* out )
+{
+   return guarded( [&] {
+      auto h = std::make_unique< P2EpsilonH >();
+      h->mu  = viscosityOf2( "p2epsilon_create", mu, minL, maxL );
+      h->p   = std::make_shared< P2Epsilon >( SP( s ), (uint_t) minL, (uint_t) maxL, *h->mu );
+      *out   = h.release();
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_destroy( hh_p2epsilon_t op )
+{
+   return guarded( [&] { delete static_cast< P2EpsilonH* >( op ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_apply( hh_p2epsilon_t op, const hh_p2function_t* src, const hh_p2function_t* dst, int level, int flag, int update )
+{
+   return guarded( [&] { EP2( op ).apply( vectorOf2( src ), vectorOf2( dst ), (uint_t) level, DoFType( flag ), update ? Add : Replace ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_gemv( hh_p2epsilon_t op, double alpha, const hh_p2function_t* src, double beta, const hh_p2function_t* dst,
+                                              int level, int flag )
+{
+   return guarded( [&] { EP2( op ).gemv( alpha, vectorOf2( src ), beta, vectorOf2( dst ), (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_compute_inverse_diagonal( hh_p2epsilon_t op )
+{
+   return guarded( [&] { EP2( op ).computeInverseDiagonalOperatorValues(); } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_inverse_diagonal( hh_p2epsilon_t op, hh_p2function_t* out )
+{
+   return guarded( [&] {
+      auto*      h = static_cast< P2EpsilonH* >( op );
+      const auto d = EP2( op ).getInverseDiagonalValues();
+      for ( int k = 0; k < 3; ++k )
+      {
+         h->invDiag[k].p = viewOf( d, ( *d )[(uint_t) k] );
+         out[k]          = &h->invDiag[k];
+      }
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_smooth_jac( hh_p2epsilon_t op, const hh_p2function_t* dst, const hh_p2function_t* rhs, const hh_p2function_t* src,
+                                                    double relax, int level, int flag )
+{
+   return guarded( [&] { EP2( op ).smooth_jac( vectorOf2( dst ), vectorOf2( rhs ), vectorOf2( src ), relax, (uint_t) level, DoFType( flag ) ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_cg_create( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_p2epsilon_solver_t preconditioner,
+                                                   hh_p2epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      if ( preconditioner )
+         cgCreatePreconditioned< P2Epsilon, P2EpsilonSolverH >( "p2epsilon_cg_create", s, minL, maxL, maxIter, tol, preconditioner, out );
+      else
+         *out = new P2EpsilonSolverH{ std::make_shared< CGSolver< P2Epsilon > >( SP( s ), (uint_t) minL, (uint_t) maxL, (uint_t) maxIter, tol, tol ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_cg_iterations( hh_p2epsilon_solver_t solver, int* iterations )
+{
+   return guarded( [&] { cgIterations< P2Epsilon, P2EpsilonSolverH >( "p2epsilon_cg_iterations", solver, iterations ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_smoother_create( hh_storage_t s, int minL, int maxL, int smoother, double relax, hh_p2epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      if ( smoother == 0 )
+         *out = new P2EpsilonSolverH{ std::make_shared< WeightedJacobiSmoother< P2Epsilon > >( SP( s ), (uint_t) minL, (uint_t) maxL, relax ) };
+      else if ( smoother == -1 )
+         *out = new P2EpsilonSolverH{ std::make_shared< IdentityPreconditioner< P2Epsilon > >() };
+      else
+         throw std::runtime_error( "p2epsilon_smoother_create: smoother 0 (weighted Jacobi) or -1 (identity); the operator has no SOR sweep" );
+   } );
+}
+// chebyshev::estimateRadius from a start vector of incommensurate waves (components along every eigenvector)
+HYTEG_HOST_API int hyteg_host_p2epsilon_chebyshev_estimate_radius( hh_p2epsilon_t op, int level, int maxIter, double* radius )
+{
+   return guarded( [&] {
+      auto                       storage = EP2( op ).getStorage();
+      P2VectorFunction< double > x( "p2epsilon_radius_x", storage, (uint_t) level, (uint_t) level ), tmp( "p2epsilon_radius_tmp", storage, (uint_t) level, (uint_t) level );
+      x.interpolate( { []( const Point3D& q ) { return std::sin( 7.3 * q[0] + 3.1 * q[1] + 1.7 * q[2] + 0.4 ); },
+                       []( const Point3D& q ) { return std::cos( 2.9 * q[0] - 6.1 * q[1] + 4.3 * q[2] ); },
+                       []( const Point3D& q ) { return std::sin( 5.3 * q[0] * q[1] - 3.7 * q[2] + 1.1 ); } },
+                     (uint_t) level, All );
+      *radius = chebyshev::estimateRadius( EP2( op ), (uint_t) level, (uint_t) maxIter, storage, x, tmp );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_chebyshev_create( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                          double lower, hh_p2epsilon_solver_t* out )
+{
+   return guarded( [&] { *out = new P2EpsilonSolverH{ makeChebyshev< P2Epsilon >( s, minL, maxL, order, radii, nRadii, upper, lower ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_solver_solve( hh_p2epsilon_solver_t solver, hh_p2epsilon_t op, const hh_p2function_t* x, const hh_p2function_t* b,
+                                                      int level )
+{
+   return guarded( [&] {
+      if ( !solver )
+         throw std::runtime_error( "null p2 epsilon solver" );
+      static_cast< P2EpsilonSolverH* >( solver )->p->solve( EP2( op ), vectorOf2( x ), vectorOf2( b ), (uint_t) level );
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_solver_destroy( hh_p2epsilon_solver_t solver )
+{
+   return guarded( [&] { delete static_cast< P2EpsilonSolverH* >( solver ); } );
+}
+
+HYTEG_HOST_API int hyteg_host_th_epsilon_create( hh_storage_t s, int minL, int maxL, hh_p2function_t mu, hh_th_epsilon_t* out )
+{
+   return guarded( [&] {
+      auto h = std::make_unique< P2EpsilonStokesH >();
+      h->mu  = viscosityOf2( "th_epsilon_create", mu, minL, maxL );
+      h->p   = std::make_shared< P2EpsilonStokes >( SP( s ), (uint_t) minL, (uint_t) maxL, *h->mu );
+      *out   = h.release();
+   } );
+}
+HYTEG_HOST_API int hyteg_host_th_epsilon_destroy( hh_th_epsilon_t op )
+{
+   return guarded( [&] { delete static_cast< P2EpsilonStokesH* >( op ); } );
+}
+HYTEG_HOST_API int hyteg_host_th_epsilon_apply( hh_th_epsilon_t op, hh_th_function_t src, hh_th_function_t dst, int level, int flag )
+{
+   return guarded( [&] { EPS2( op ).apply( TH::fn( src ), TH::fn( dst ), (uint_t) level, DoFType( flag ) ); } );
+}
+// MinResSolver< P2P1StokesEpsilonOperator >; preconditioner 0 identity, 1 StokesPressureBlockPreconditioner< ., P1LumpedInvMassOperator >
+// (solvertemplates::stokesMinResSolver, StokesSolverTemplates.hpp:54-69), 2 the same weighted with mu at the vertex DoFs
+HYTEG_HOST_API int hyteg_host_th_epsilon_minres_create( hh_storage_t s, int minL, int maxL, int max_iter, double rel_tol, int preconditioner,
+                                                        hh_p2function_t mu, hh_th_epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      auto storage = SP( s );
+      auto h       = std::make_unique< P2EpsilonStokesSolverH >();
+      if ( preconditioner == 0 )
+         h->preconditioner = std::make_shared< IdentityPreconditioner< P2EpsilonStokes > >();
+      else if ( preconditioner == 1 )
+         h->preconditioner =
+             std::make_shared< StokesPressureBlockPreconditioner< P2EpsilonStokes, P1LumpedInvMassOperator > >( storage, (uint_t) minL, (uint_t) maxL );
+      else if ( preconditioner == 2 )
+      {
+         h->mu             = viscosityOf2( "th_epsilon_minres_create (viscosity-weighted preconditioner)", mu, minL, maxL );
+         h->preconditioner = std::make_shared< StokesViscosityWeightedPressureBlockPreconditioner< P2EpsilonStokes > >(
+             storage, (uint_t) minL, (uint_t) maxL, h->mu->getVertexDoFFunction() );
+      }
+      else
+         throw std::runtime_error( "th_epsilon_minres_create: unknown preconditioner" );
+      h->p = std::make_shared< MinResSolver< P2EpsilonStokes > >( storage, (uint_t) minL, (uint_t) maxL, (uint_t) max_iter, rel_tol, 1e-16,
+                                                                  h->preconditioner );
+      *out = h.release();
+   } );
+}
+HYTEG_HOST_API int hyteg_host_th_epsilon_minres_solve( hh_th_epsilon_solver_t solver, hh_th_epsilon_t op, hh_th_function_t x, hh_th_function_t b, int level )
+{
+   return guarded( [&] { EPSS2( solver ).p->solve( EPS2( op ), TH::fn( x ), TH::fn( b ), (uint_t) level ); } );
+}
+HYTEG_HOST_API int hyteg_host_th_epsilon_minres_precondition( hh_th_epsilon_solver_t solver, hh_th_epsilon_t op, hh_th_function_t x, hh_th_function_t b,
+                                                              int level )
+{
+   return guarded( [&] { EPSS2( solver ).preconditioner->solve( EPS2( op ), TH::fn( x ), TH::fn( b ), (uint_t) level ); } );
+}
+HYTEG_HOST_API int hyteg_host_th_epsilon_minres_iterations( hh_th_epsilon_solver_t solver, int* iterations )
+{
+   return guarded( [&] { *iterations = (int) EPSS2( solver ).p->getIterations(); } );
+}
+HYTEG_HOST_API int hyteg_host_th_epsilon_minres_destroy( hh_th_epsilon_solver_t solver )
+{
+   return guarded( [&] { delete static_cast< P2EpsilonStokesSolverH* >( solver ); } );
+}

@@ -1,0 +1,243 @@
+// p2epsilon.hpp -- part of the C++ host layer above the C-ABI (see hyteg_host.hpp for the data model).
+// Variable-viscosity Stokes on P2-P1 (Taylor-Hood):
+//   operatorgeneration::P2ViscousBlockEpsilonOperator( storage, minLevel, maxLevel, const P2Function< real_t >& mu )
+//   operatorgeneration::P2P1StokesEpsilonOperator( storage, minLevel, maxLevel, mu )
+// of module hyteg_operators: the operators the reference's convection apps instantiate.  Their mu = 1 case is the in-tree
+// P2ElementwiseAffineEpsilonOperator / P2P1ElementwiseAffineEpsilonStokesOperator (src/mixed_operator/
+// P2P1ElementwiseAffineEpsilonStokesOperator.hpp:33-88, apply :61-70), the P2 half of
+// tests/hyteg/convergence/ElementwiseEpsilonMinResConvergenceTest.cpp:156-163, 366-412.  The viscosity is a P2Function that the caller
+// interpolates on every level used (the operator at level l reads mu at level l), as the coefficient of P2ElementwiseDivKGrad.
+// The reference composes the velocity block of nine P2 elementwise blocks; here one C-ABI call per macro-cell computes the three
+// components (hyteg_hip_p2_elementwise_epsilon_apply_cell_kinds) with the schedule of P2ElementwiseDivKGrad::gemv: every cell adds the
+// contributions of its own micro-cells, the additive exchange completes the shared DoFs.  No smooth_sor, no fused steps: the solver
+// templates run their composed sequences.
+#pragma once
+
+#include "p1epsilon.hpp"
+#include "p2divkgrad.hpp"
+#include "taylorhood.hpp"
+
+namespace hyteg {
+namespace operatorgeneration {
+
+class P2ViscousBlockEpsilonOperator
+{
+ public:
+   using srcType = P2VectorFunction< double >;
+   using dstType = P2VectorFunction< double >;
+
+   P2ViscousBlockEpsilonOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel, const P2Function< double >& mu )
+   : storage_( storage )
+   , minLevel_( minLevel )
+   , maxLevel_( maxLevel )
+   , mu_( mu )
+   {
+      if ( (int) maxLevel > hyteg_hip_p2_elementwise_epsilon_max_level() )
+         throw std::runtime_error( "P2ViscousBlockEpsilonOperator: levels 0..8" );
+      storage->markInUse(); // the mesh boundary flags are fixed from here on
+      for ( uint_t l = minLevel; l <= maxLevel; ++l )
+         for ( uint_t lc = 0; lc < storage->getNumberOfLocalCells(); ++lc )
+         {
+            double                   cc[12];
+            std::array< double, 72 > g;
+            coordsOf( storage->getLocalCell( lc ), cc );
+            hipCheck( hyteg_hip_p2_elementwise_epsilon_geometry( cc, (int) l, g.data() ), "P2ViscousBlockEpsilonOperator: geometry" );
+            geometry_[l].push_back( g );
+         }
+   }
+   std::shared_ptr< PrimitiveStorage > getStorage() const { return storage_; }
+   uint_t                              getMinLevel() const { return minLevel_; }
+   uint_t                              getMaxLevel() const { return maxLevel_; }
+   const P2Function< double >&         getViscosity() const { return mu_; }
+   uint64_t                            uid() const { return uid_; }
+
+   // Operator::apply = gemv( 1, src, updateType == Replace ? 0 : 1, dst )
+   void apply( const srcType& src, const dstType& dst, uint_t level, const Selection& flag, UpdateType updateType = Replace ) const
+   {
+      gemv( 1.0, src, updateType == Replace ? 0.0 : 1.0, dst, level, flag );
+   }
+   // the schedule of P2ElementwiseDivKGrad::gemv on the three components in one pass.  Every component has its own boundary condition
+   // (VectorToVectorOperator applies block ( i, j ) with the flag on dst[i]): the kernels take a class mask per component
+   void gemv( double alpha, const srcType& src, double beta, const dstType& dst, uint_t level, const Selection& flagIn ) const
+   {
+      checkDistinct( "gemv", dst, src );
+      const std::array< Selection, 3 > flag   = dst.effectiveFlag( flagIn );
+      const bool                       shared = storage_->getCells().size() > 1;
+      if ( !shared )
+      {
+         if ( beta != 0.0 && beta != 1.0 )
+            for ( uint_t k = 0; k < 3; ++k )
+               dst[k].assign( { beta }, { dst[k] }, level, flag[k] );
+         launch( alpha, src, dst, level, flag, beta == 0.0 ? HYTEG_HIP_REPLACE : HYTEG_HIP_ADD );
+         return;
+      }
+      if ( beta == 0.0 )
+      {
+         launch( alpha, src, dst, level, flag, HYTEG_HIP_REPLACE );
+         sumShared( dst, level, flag );
+         return;
+      }
+      P2VectorFunction< double > tmp( "p2_epsilon_gemv_tmp", storage_, level, level );
+      launch( alpha, src, tmp, level, flag, HYTEG_HIP_REPLACE );
+      sumShared( tmp, level, flag );
+      for ( uint_t k = 0; k < 3; ++k )
+         dst[k].assign( { beta, 1.0 }, { dst[k], tmp[k] }, level, flag[k] );
+   }
+
+   // VectorToVectorOperator::computeInverseDiagonalOperatorValues + extractInverseDiagonal: the inverse diagonals of the three diagonal
+   // blocks.  Per cell the diagonal kernel, the additive exchange, and the reciprocal on the host (set-up time, once per operator)
+   void computeInverseDiagonalOperatorValues()
+   {
+      invDiag_.reset( new P2VectorFunction< double >( "inverse diagonal entries", storage_, minLevel_, maxLevel_ ) );
+      const P2VectorFunction< double >& d = *invDiag_;
+      for ( uint_t l = minLevel_; l <= maxLevel_; ++l )
+      {
+         for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
+         {
+            double* dv[3];
+            double* de[3];
+            for ( uint_t k = 0; k < 3; ++k )
+               dv[k] = d[k].getVertexDoFFunction().getCellPointer( c, l ), de[k] = d[k].getEdgeCellPointer( c, l );
+            hipCheck( hyteg_hip_p2_elementwise_epsilon_diagonal_cell( dv, de, mu_.getVertexDoFFunction().getCellPointer( c, l ), mu_.getEdgeCellPointer( c, l ),
+                                                                      (int) l, geometry_.at( l ).at( c ).data(), storage_->stream() ),
+                      "P2ViscousBlockEpsilonOperator: diagonal" );
+         }
+         const size_t          nv = (size_t) layout::cellSize( (int) l ), ne = std::max< size_t >( 1, d[0].getNumberOfEdgeDoFs( l ) );
+         std::vector< double > hv( nv ), he( ne );
+         for ( uint_t k = 0; k < 3; ++k )
+         {
+            if ( storage_->getCells().size() > 1 )
+            {
+               d[k].getVertexDoFFunction().sumSharedCopies( l, All );
+               d[k].sumSharedEdgeCopies( l, All );
+            }
+            for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
+            {
+               d[k].getVertexDoFFunction().copyCellToHost( c, l, hv.data() );
+               d[k].copyEdgeToHost( c, l, he.data() );
+               hipCheck( hyteg_hip_stream_synchronize( storage_->stream() ), "P2ViscousBlockEpsilonOperator: inverse diagonal" );
+               for ( auto& v : hv )
+                  v = v != 0.0 ? 1.0 / v : 0.0;
+               for ( auto& v : he )
+                  v = v != 0.0 ? 1.0 / v : 0.0;
+               d[k].getVertexDoFFunction().copyCellFromHost( c, l, hv.data() );
+               d[k].copyEdgeFromHost( c, l, he.data() );
+            }
+         }
+      }
+   }
+   bool                                          hasInverseDiagonalValues() const { return invDiag_ != nullptr; }
+   std::shared_ptr< P2VectorFunction< double > > getInverseDiagonalValues() const
+   {
+      if ( !invDiag_ )
+         throw std::runtime_error( "Inverse diagonal values have not been assembled, call computeInverseDiagonalOperatorValues() "
+                                   "to set up this function." );
+      return invDiag_;
+   }
+
+   // P2ElementwiseOperator::smooth_jac (P2ElementwiseOperator.cpp:344-374) on the three components, statement by statement:
+   //   dst = A src;  dst = rhs - dst;  dst = D^-1 dst;  dst = src + relax dst
+   void smooth_jac( const dstType& dst, const srcType& rhs, const srcType& src, double relax, uint_t level, const Selection& flag ) const
+   {
+      const auto& invDiag = *getInverseDiagonalValues();
+      apply( src, dst, level, flag );
+      for ( uint_t k = 0; k < 3; ++k )
+      {
+         dst[k].assign( { 1.0, -1.0 }, { rhs[k], dst[k] }, level, flag );
+         dst[k].multElementwise( { invDiag[k], dst[k] }, level, flag );
+         dst[k].assign( { 1.0, relax }, { src[k], dst[k] }, level, flag );
+      }
+   }
+
+ private:
+   // views of the same functions are different VectorFunction objects (the C facade builds one per argument): compare components
+   void checkDistinct( const char* who, const dstType& dst, const srcType& src ) const
+   {
+      bool bad = false;
+      for ( uint_t i = 0; i < 3; ++i )
+      {
+         bad = bad || &dst[i] == &mu_ || &dst[i] == &dst[( i + 1 ) % 3];
+         for ( uint_t j = 0; j < 3; ++j )
+            bad = bad || &dst[i] == &src[j];
+      }
+      if ( bad )
+         throw std::runtime_error( std::string( "P2ViscousBlockEpsilonOperator::" ) + who + ": dst must differ from src and from mu" );
+   }
+   void sumShared( const dstType& f, uint_t level, const std::array< Selection, 3 >& flag ) const
+   {
+      for ( uint_t k = 0; k < 3; ++k )
+      {
+         f[k].getVertexDoFFunction().sumSharedCopies( level, flag[k] );
+         f[k].sumSharedEdgeCopies( level, flag[k] );
+      }
+   }
+   void launch( double alpha, const srcType& src, const dstType& dst, uint_t level, const std::array< Selection, 3 >& flag, int update ) const
+   {
+      const std::vector< unsigned > masks[3] = { storage_->masksFor( flag[0], false, HYTEG_HIP_MASK_ALL ), storage_->masksFor( flag[1], false, HYTEG_HIP_MASK_ALL ),
+                                                 storage_->masksFor( flag[2], false, HYTEG_HIP_MASK_ALL ) };
+      for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
+      {
+         double *       dv[3], *de[3];
+         const double * sv[3], *se[3];
+         const unsigned m[3] = { masks[0][c], masks[1][c], masks[2][c] };
+         for ( uint_t k = 0; k < 3; ++k )
+         {
+            dv[k] = dst[k].getVertexDoFFunction().getCellPointer( c, level ), de[k] = dst[k].getEdgeCellPointer( c, level );
+            sv[k] = src[k].getVertexDoFFunction().getCellPointer( c, level ), se[k] = src[k].getEdgeCellPointer( c, level );
+         }
+         hipCheck( hyteg_hip_p2_elementwise_epsilon_apply_cell_kinds( dv, de, sv, se, mu_.getVertexDoFFunction().getCellPointer( c, level ),
+                                                                      mu_.getEdgeCellPointer( c, level ), m, (int) level,
+                                                                      geometry_.at( level ).at( c ).data(), alpha, update, 0xFFu, storage_->stream() ),
+                   "P2ViscousBlockEpsilonOperator::gemv" );
+      }
+   }
+
+   std::shared_ptr< PrimitiveStorage >                         storage_;
+   uint_t                                                      minLevel_, maxLevel_;
+   const P2Function< double >&                                 mu_;
+   std::map< uint_t, std::vector< std::array< double, 72 > > > geometry_; // per level and local cell
+   uint64_t                                                    uid_ = nextUid();
+   std::shared_ptr< P2VectorFunction< double > >               invDiag_;
+};
+
+// P2P1ElementwiseAffineEpsilonStokesOperator.hpp:61-70: viscOp Replace, divT Add, div Replace; no stabilisation block.  The mixed blocks
+// are those of P2P1TaylorHoodStokesOperator (taylorhood.hpp); StokesOperator (stokes.hpp) builds its velocity block from a scalar
+// operator without a coefficient, so the composition is written out here, as P1P1ElementwiseAffineEpsilonStokesOperator is.
+class P2P1StokesEpsilonOperator
+{
+ public:
+   using srcType            = P2P1TaylorHoodFunction< double >;
+   using dstType            = srcType;
+   using VelocityOperator_T = P2ViscousBlockEpsilonOperator;
+   static constexpr bool hasPspgBlock = false;
+
+   P2P1StokesEpsilonOperator( const std::shared_ptr< PrimitiveStorage >& storage, uint_t minLevel, uint_t maxLevel, const P2Function< double >& mu )
+   : viscOp( storage, minLevel, maxLevel, mu )
+   , div( storage, minLevel, maxLevel )
+   , divT( storage, minLevel, maxLevel )
+   , storage_( storage )
+   {}
+
+   void apply( const srcType& src, const dstType& dst, uint_t level, DoFType flag, UpdateType = Replace ) const
+   {
+      if ( &src == &dst )
+         throw std::runtime_error( "P2P1StokesEpsilonOperator::apply: src and dst must differ" );
+      viscOp.apply( src.uvw(), dst.uvw(), level, flag, Replace );
+      divT.apply( src.p(), dst.uvw(), level, flag, Add );
+      div.apply( src.uvw(), dst.p(), level, flag, Replace );
+   }
+   const VelocityOperator_T&           getA() const { return viscOp; }
+   std::shared_ptr< PrimitiveStorage > getStorage() const { return storage_; }
+   uint64_t                            uid() const { return uid_; }
+
+   P2ViscousBlockEpsilonOperator viscOp;
+   P2ToP1DivOperator             div;
+   P1ToP2DivTOperator            divT;
+
+ private:
+   std::shared_ptr< PrimitiveStorage > storage_;
+   uint64_t                            uid_ = nextUid();
+};
+
+} // namespace operatorgeneration
+} // namespace hyteg

@@ -1373,6 +1373,72 @@ HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_diagonal_cell( double*      
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level( int level );
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_max_level( void );
 
+/* ---- b-4 (P2 epsilon): variable-viscosity epsilon operator -div( 2 mu eps(u) ) on P2 with a P2 viscosity -----------------------
+ * Replaces, in ONE pass over the three velocity components, the nine P2 elementwise block applies of
+ * operatorgeneration::P2ViscousBlockEpsilonOperator::apply (module hyteg_operators; the velocity block of
+ * operatorgeneration::P2P1StokesEpsilonOperator, which the reference's convection apps instantiate; for mu = 1 the in-tree
+ * P2ElementwiseAffineEpsilonOperator of tests/hyteg/convergence/ElementwiseEpsilonMinResConvergenceTest.cpp:156-163, 366-412 and
+ * src/mixed_operator/P2P1ElementwiseAffineEpsilonStokesOperator.hpp:61-70).  The generated source is absent from the snapshot, so the
+ * arithmetic is pinned by the identity: on a micro-cell e, block ( i, j ) of the element matrix is
+ * int_e mu ( delta_ij grad phi_b . grad phi_a + d_j phi_a d_i phi_b ), mu the P2 interpolant of its ten values on e, integrated exactly
+ * (degree 4), local DoFs in the FEniCS order of P2Form::integrateAll.  dst_* / src_*: HOST arrays of three device pointers (the
+ * components' vertex arrays and 7-block edge arrays as in hyteg_hip_p2_elementwise_apply_cell_kinds); mu_vertex / mu_edge: the viscosity's
+ * arrays at the same level; mask[3]: a 15-bit point-class mask per destination component (the components of a P2VectorFunction may carry
+ * different boundary conditions: a DoF that mask[i] excludes is not written in component i); kind_mask: the 8 destination kinds.
+ * Levels 0..8 (32-bit indices).  EINVAL before any GPU work: a level out of range, a null array, a written array that is a src, mu or
+ * another written array, a bad update type.
+ *
+ * hyteg_hip_p2_elementwise_epsilon_geometry fills the 72 doubles the kernels need of a ( macro-cell, level ):
+ * sqrt( |e| / 840 ) d_r l_a of the six micro-cell types at [12 t + 3 a + r]; a HOST array, passed to the kernels in their arguments. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_geometry( const double* macro_vertex_coords /* 12 */, int level, double* geometry /* 72 */ );
+/* Replaces operatorgeneration::P2ViscousBlockEpsilonOperator::apply on one macro-cell (test file above).  Inner DoFs: the inner form
+ * (compile-time micro-cell lists) from the level of hyteg_hip_p2_elementwise_epsilon_set_inner_min_level on, below it the gather form;
+ * boundary DoFs of every level: the gather form. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_apply_cell_kinds( double* const*       dst_vertex /* 3 */,
+                                                                     double* const*       dst_edge /* 3 */,
+                                                                     const double* const* src_vertex /* 3 */,
+                                                                     const double* const* src_edge /* 3 */,
+                                                                     const double*        mu_vertex,
+                                                                     const double*        mu_edge,
+                                                                     const unsigned*      mask /* 3 */,
+                                                                     int                  level,
+                                                                     const double*        geometry /* 72, host */,
+                                                                     double               alpha,
+                                                                     int                  update,
+                                                                     unsigned             kind_mask,
+                                                                     hyteg_hip_stream_t   stream );
+/* The same operator (operatorgeneration::P2ViscousBlockEpsilonOperator::apply, test file above) through the gather form on every DoF:
+ * the second implementation the inner form is tested and measured against. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_apply_cell_gather( double* const*       dst_vertex /* 3 */,
+                                                                      double* const*       dst_edge /* 3 */,
+                                                                      const double* const* src_vertex /* 3 */,
+                                                                      const double* const* src_edge /* 3 */,
+                                                                      const double*        mu_vertex,
+                                                                      const double*        mu_edge,
+                                                                      const unsigned*      mask /* 3 */,
+                                                                      int                  level,
+                                                                      const double*        geometry /* 72, host */,
+                                                                      double               alpha,
+                                                                      int                  update,
+                                                                      unsigned             kind_mask,
+                                                                      hyteg_hip_stream_t   stream );
+/* Replaces the macro-cell part of operatorgeneration::P2ViscousBlockEpsilonOperator::computeInverseDiagonalOperatorValues (the inverse
+ * diagonals of the three diagonal blocks, test file above through the smoothers): component i of every DoF of the cell receives the sum
+ * of A_e^{ii}[row][row] over its adjacent micro-cells of THIS macro-cell (Replace); the caller sums the shared copies and inverts.  diag
+ * arrays must not be mu arrays. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_diagonal_cell( double* const*     diag_vertex /* 3 */,
+                                                                  double* const*     diag_edge /* 3 */,
+                                                                  const double*      mu_vertex,
+                                                                  const double*      mu_edge,
+                                                                  int                level,
+                                                                  const double*      geometry /* 72, host */,
+                                                                  hyteg_hip_stream_t stream );
+/* Tuning knob of operatorgeneration::P2ViscousBlockEpsilonOperator::apply above (no counterpart in the reference; test file above): the
+ * first level whose inner DoFs take the inner form (at least 2; 99: the gather form everywhere).  Returns the previous value.
+ * hyteg_hip_p2_elementwise_epsilon_max_level: the largest level of these entries. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_set_inner_min_level( int level );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_max_level( void );
+
 /* ---- b-5: variable-viscosity epsilon operator -div( 2 mu eps(u) ), eps(u) = ( grad u + grad u^T ) / 2 ------------------------
  * Replaces, in ONE pass over the three velocity components, the nine P1ElementwiseOperator::apply calls of
  * P1ElementwiseAffineEpsilonOperator::apply (src/mixed_operator/P1EpsilonOperator.hpp:89-164; forms::p1_epsilonvar_i_j_affine_q2)

@@ -4,7 +4,8 @@ timings through the host layer.  Not the headline bench (that is bench.py); this
 DESIGN.md section 3.  Usage: python tools/bench_kernels.py [--level 8] [--reps 200]
 --only epsilon: the rows of the epsilon operator alone, levels 6..level, with the fused residual and Chebyshev steps
 against the composed sequences they replace; --only divkgrad: the same pairs for div-k-grad; --only p2-divkgrad: the two
-forms of the P2 div-k-grad apply, the constant P2 apply and a copy, levels 4..7."""
+forms of the P2 div-k-grad apply, the constant P2 apply and a copy, levels 4..7; --only p2-epsilon: the fused P2 epsilon
+apply in its forms against three P2 div-k-grad applies on the same arrays, levels 4..7."""
 import argparse
 import json
 import sys
@@ -303,6 +304,81 @@ def p2_divkgrad_rows(top_level, reps, from_level=4, repeats=5):
     print(json.dumps({"levels": list(range(from_level, top_level + 1)), "device": capi.device_name(), "repeats": repeats, "kernels": rows}))
 
 
+def p2_epsilon_rows(top_level, reps, from_level=4, repeats=5):
+    """--only p2-epsilon: the macro-cell of tet_1el, all DoFs of the three components, levels from_level..top_level.  Per level,
+    in the same run and alternating in every one of `repeats` rounds: the fused P2 epsilon apply with the inner form on the inner DoFs, the
+    same through the gather form on every DoF, the apply as shipped (the default inner_min_level), and the yardstick: three
+    P2ElementwiseDivKGrad applies (as shipped) on the same arrays -- the three diagonal blocks alone, a lower bound of any block
+    composition.  Reported: the median of the rounds and their spread (min .. max); a form is faster only beyond that spread.
+    Rings as for p2-divkgrad: every array class exceeds the Infinity Cache 2.2 times, capped at 256 buffers."""
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    st = host.Storage.from_gmsh(ROOT / "hyteg_amd/data/meshes/tet_1el.msh")
+    st.set_stream(sh)
+    tet = [list(map(float, v)) for v in st.local_cell(0)[1]]
+    rows = []
+    shipped = capi.p2_elementwise_epsilon_set_inner_min_level(2)
+    capi.p2_elementwise_epsilon_set_inner_min_level(shipped)
+    for L in range(from_level, top_level + 1):
+        nv, ne = capi.cell_size(L), capi.p2_edge_array_size(L)
+        dofs = 3 * (nv + ne)
+        nbuf = min(256, max(4, -(-int(2.2 * 256 * 2**20) // (ne * 8))))
+        rnd = lambda n, lo=0.0: [lo + torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)]  # noqa: E731
+        DV, DE, SV, SE = ([rnd(n) for _ in range(3)] for n in (nv, ne, nv, ne))
+        MV, ME = rnd(nv, 0.5), rnd(ne, 0.5)
+        geometry = capi.p2_elementwise_epsilon_geometry(tet, L)
+        geometry_dk = capi.p2_elementwise_divkgrad_geometry(tet, L)
+        p = lambda t, k: t[k % nbuf].data_ptr()  # noqa: E731
+        p3 = lambda ts, k: [t[k % nbuf].data_ptr() for t in ts]  # noqa: E731
+
+        def epsilon(gather, inner_min_level):
+            def fn(k):
+                capi.p2_elementwise_epsilon_apply_cell(p3(DV, k), p3(DE, k), p3(SV, k), p3(SE, k), p(MV, k), p(ME, k), L, geometry, 1.0, 0, 0x7FFF,
+                                                       0xFF, sh, gather=gather)
+            return fn, inner_min_level
+
+        def three_divkgrad(k):
+            for c in range(3):
+                capi.p2_elementwise_divkgrad_apply_cell(p(DV[c], k), p(DE[c], k), p(SV[c], k), p(SE[c], k), p(MV, k), p(ME, k), L, geometry_dk, 1.0, 0,
+                                                        0x7FFF, 0xFF, sh)
+
+        nbytes = 8 * (2 * dofs + nv + ne)  # three components read, three written, the viscosity read
+        table_rows = [
+            ("P2 epsilon apply: inner form (+ gather form on the boundary DoFs)", *epsilon(False, 2)),
+            ("P2 epsilon apply: gather form on every DoF", *epsilon(True, shipped)),
+            ("P2 epsilon apply as shipped", *epsilon(False, shipped)),
+            ("yardstick: three P2 div-k-grad applies on the same arrays", three_divkgrad, shipped),
+        ]
+
+        for name, fn, sw in table_rows:  # warm every shape
+            capi.p2_elementwise_epsilon_set_inner_min_level(sw)
+            for k in range(3):
+                fn(k)
+        torch.cuda.synchronize()
+        times = {name: [] for name, _, _ in table_rows}
+        for _ in range(repeats):
+            for name, fn, sw in table_rows:
+                capi.p2_elementwise_epsilon_set_inner_min_level(sw)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for k in range(reps):
+                    fn(k)
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+        for name, fn, sw in table_rows:
+            t = sorted(times[name])
+            us = t[len(t) // 2]
+            rows.append(dict(kernel=name, level=L, us=us, us_min=t[0], us_max=t[-1], GBps=nbytes / us * 1e-3, GDoFps=dofs / us * 1e-3,
+                             algorithmic_bytes=nbytes, dofs=dofs))
+            print(f"level {L}  {name:70s} {us:10.2f} us  ({t[0]:.2f} .. {t[-1]:.2f})  {nbytes / us * 1e-3:8.1f} GB/s  {dofs / us * 1e-3:8.3f} GDoF/s",
+                  flush=True)
+        del DV, DE, SV, SE, MV, ME
+    capi.p2_elementwise_epsilon_set_inner_min_level(shipped)
+    print(json.dumps({"levels": list(range(from_level, top_level + 1)), "device": capi.device_name(), "repeats": repeats,
+                      "shipped_inner_min_level": shipped, "kernels": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", type=int, default=8)
@@ -322,6 +398,9 @@ def main():
         return
     if args.only == "p2-divkgrad":
         p2_divkgrad_rows(min(L, 7), reps, min(4, max(0, args.from_level)))
+        return
+    if args.only == "p2-epsilon":
+        p2_epsilon_rows(min(L, 7), reps, min(4, max(0, args.from_level)))
         return
     n, inner = capi.cell_size(L), capi.cell_inner_size(L)
     nc = capi.cell_size(L - 1)
