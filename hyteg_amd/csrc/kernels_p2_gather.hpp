@@ -78,6 +78,70 @@ inline const P2Tables& tables()
 
 __constant__ int kRowDeficit[6]     = { 0, 1, 1, 2, 1, 1 }; // numCellsPerRowByType: n - deficit
 
+// ---- the skeleton of a gather kernel, as device functions: the decode of a group index and the lane-group sum.  gather_kernel of
+// kernels_p2_varcoef.hpp is built from them.  p2_elementwise_kernel below keeps its own copy of the same lines: built from these
+// functions it computes the same but compiles to another instruction order (profiles/p2_varcoef_checks.txt). -------------------------
+// group q as entry q of a tetrahedral array of width W; false: past its end
+__device__ __forceinline__ bool p2_decode_all( int W, int q, int& x, int& y, int& z )
+{
+   if ( q >= (int) tet32( (unsigned) W ) )
+      return false;
+   z           = slice_of( W, q );
+   const int j = q - slice_start( W, z );
+   y           = row_of( W - z, j );
+   x           = j - row_start( W - z, y );
+   return true;
+}
+// group q of the boundary walk (see p2_elementwise_kernel): q -> face, ( i, j ), a point kept at its lowest-numbered face.  false: past
+// the end, or a point that a lower face holds
+__device__ __forceinline__ bool p2_decode_boundary( int W, int q, int& x, int& y, int& z )
+{
+   const int T = tri( W );
+   if ( q >= 4 * T )
+      return false;
+   const int f = q / T, r = q - f * T;
+   const int j = row_of( W, r );
+   const int k = r - row_start( W, j );
+   switch ( f )
+   {
+   case 0:
+      x = k, y = j, z = 0;
+      break;
+   case 1:
+      x = k, y = 0, z = j;
+      break;
+   case 2:
+      x = 0, y = k, z = j;
+      break;
+   default:
+      x = k, y = j, z = W - 1 - k - j;
+      break;
+   }
+   const int lowest = ( z == 0 ) ? 0 : ( y == 0 ) ? 1 : ( x == 0 ) ? 2 : 3;
+   return lowest == f;
+}
+// The lane-group sum.  The G lanes of a DoF share its (at most 24) adjacent micro-cells, 24 / G each: lane l has evaluated entries
+// l, l + G, l + 2 G, ... of the table into part[slot][NC], and vmask[slot] is the ballot of the lanes whose entry lies inside the
+// macro-cell.  Every lane adds all contributions in the order of the table: one lane per DoF walks 24 dependent round trips (pure
+// latency below level 7), G = 8 keeps three.  Every lane of a DoF's group must take part, or none.
+template < int G, int NC >
+__device__ __forceinline__ void p2_group_sum( const double ( &part )[24 / G][NC], const unsigned long long ( &vmask )[24 / G], double ( &acc )[NC] )
+{
+   const int base = ( threadIdx.x & 63 ) & ~( G - 1 ); // first lane of this DoF's group inside the wave
+#pragma unroll
+   for ( int l = 0; l < 24; ++l )
+   {
+      const bool on = ( vmask[l / G] >> ( base + ( l % G ) ) ) & 1ull;
+#pragma unroll
+      for ( int j = 0; j < NC; ++j )
+      {
+         const double p = __shfl( part[l / G][j], base + ( l % G ), 64 );
+         if ( on )
+            acc[j] += p;
+      }
+   }
+}
+
 // Boundary DoFs only, densely enumerated: the non-inner DoFs of a kind lie on faces of that kind's own tetrahedral array
 // (all four for vertex DoFs, two for X .. YZ edge DoFs, none for XYZ), so thread q walks the four triangular faces
 // (q -> face, (i,j)) and keeps a point at its lowest-numbered face.

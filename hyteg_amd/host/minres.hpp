@@ -79,19 +79,11 @@ class P1LumpedInvMassOperator
    {
       P1ConstantMassOperator mass( storage, minLevel, maxLevel );
       P1Function< double >   one( "lumped_inv_mass_one", storage, minLevel, maxLevel );
-      std::vector< double >  h;
       for ( uint_t l = minLevel; l <= maxLevel; ++l )
       {
          one.interpolate( 1.0, l, All );
          mass.apply( one, invLumped_, l, All, Replace ); // row sums; the shares of shared points are summed by the apply
-         h.resize( (size_t) hyteg_hip_cell_size( (int) l ) );
-         for ( uint_t c = 0; c < storage->getNumberOfLocalCells(); ++c )
-         {
-            invLumped_.copyCellToHost( c, l, h.data() );
-            for ( double& v : h )
-               v = v != 0.0 ? 1.0 / v : 0.0;
-            invLumped_.copyCellFromHost( c, l, h.data() );
-         }
+         invertElementwise( invLumped_, l );
       }
    }
    void apply( const P1Function< double >& src, const P1Function< double >& dst, uint_t level, DoFType flag, UpdateType updateType = Replace ) const

@@ -102,8 +102,6 @@ class P2ViscousBlockEpsilonOperator
                                                                       (int) l, geometry_.at( l ).at( c ).data(), storage_->stream() ),
                       "P2ViscousBlockEpsilonOperator: diagonal" );
          }
-         const size_t          nv = (size_t) layout::cellSize( (int) l ), ne = std::max< size_t >( 1, d[0].getNumberOfEdgeDoFs( l ) );
-         std::vector< double > hv( nv ), he( ne );
          for ( uint_t k = 0; k < 3; ++k )
          {
             if ( storage_->getCells().size() > 1 )
@@ -111,18 +109,7 @@ class P2ViscousBlockEpsilonOperator
                d[k].getVertexDoFFunction().sumSharedCopies( l, All );
                d[k].sumSharedEdgeCopies( l, All );
             }
-            for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
-            {
-               d[k].getVertexDoFFunction().copyCellToHost( c, l, hv.data() );
-               d[k].copyEdgeToHost( c, l, he.data() );
-               hipCheck( hyteg_hip_stream_synchronize( storage_->stream() ), "P2ViscousBlockEpsilonOperator: inverse diagonal" );
-               for ( auto& v : hv )
-                  v = v != 0.0 ? 1.0 / v : 0.0;
-               for ( auto& v : he )
-                  v = v != 0.0 ? 1.0 / v : 0.0;
-               d[k].getVertexDoFFunction().copyCellFromHost( c, l, hv.data() );
-               d[k].copyEdgeFromHost( c, l, he.data() );
-            }
+            invertElementwise( d[k], l );
          }
       }
    }

@@ -390,4 +390,23 @@ class P2Function
    uint64_t                                               uid_ = nextUid();
 };
 
+// P2Function::invertElementwise of an assembled diagonal: set-up time, on the host (as invertElementwise of p1function.hpp)
+inline void invertElementwise( const P2Function< double >& f, uint_t level )
+{
+   const auto            storage = f.getStorage();
+   std::vector< double > hv( (size_t) hyteg_hip_cell_size( (int) level ) ), he( std::max< size_t >( 1, f.getNumberOfEdgeDoFs( level ) ) );
+   for ( uint_t c = 0; c < storage->getNumberOfLocalCells(); ++c )
+   {
+      f.getVertexDoFFunction().copyCellToHost( c, level, hv.data() );
+      f.copyEdgeToHost( c, level, he.data() );
+      hipCheck( hyteg_hip_stream_synchronize( storage->stream() ), "P2Function: invertElementwise" );
+      for ( auto& v : hv )
+         v = v != 0.0 ? 1.0 / v : 0.0;
+      for ( auto& v : he )
+         v = v != 0.0 ? 1.0 / v : 0.0;
+      f.getVertexDoFFunction().copyCellFromHost( c, level, hv.data() );
+      f.copyEdgeFromHost( c, level, he.data() );
+   }
+}
+
 } // namespace hyteg

@@ -206,20 +206,7 @@ class P2ElementwiseOperator
             d.getVertexDoFFunction().sumSharedCopies( l, All );
             d.sumSharedEdgeCopies( l, All );
          }
-         const size_t          nv = (size_t) layout::cellSize( (int) l ), ne = std::max< size_t >( 1, d.getNumberOfEdgeDoFs( l ) );
-         std::vector< double > hv( nv ), he( ne );
-         for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
-         {
-            d.getVertexDoFFunction().copyCellToHost( c, l, hv.data() );
-            d.copyEdgeToHost( c, l, he.data() );
-            hipCheck( hyteg_hip_stream_synchronize( storage_->stream() ), "P2ElementwiseOperator: inverse diagonal" );
-            for ( auto& v : hv )
-               v = v != 0.0 ? 1.0 / v : 0.0;
-            for ( auto& v : he )
-               v = v != 0.0 ? 1.0 / v : 0.0;
-            d.getVertexDoFFunction().copyCellFromHost( c, l, hv.data() );
-            d.copyEdgeFromHost( c, l, he.data() );
-         }
+         invertElementwise( d, l );
       }
    }
    std::shared_ptr< P2Function< double > > getInverseDiagonalValues() const

@@ -152,10 +152,7 @@ def test_constant_source_gives_zero(env, level, form):
     assert np.abs(got).max() <= 1e-12 * k.max() * laplace * 3.0  # the source is the constant 3
 
 
-@pytest.mark.parametrize("level", [5, 6])
-def test_inner_form_equals_gather_form(env, level):
-    """levels the restatement is not run at; level 6 has rows longer than a wave.  The two forms differ in the order of the micro-cells
-    only: max difference <= 1e-13 * max|dst|, the bound of tests/test_gpu_p2_class_rows.py for two P2 kernels with different partial sums"""
+def _check_inner_form_equals_gather_form(env, level):
     torch, capi = env
     rng = np.random.default_rng(level)
     nv, ne = pu.vertex_size(level), pu.edge_size(level)
@@ -175,3 +172,16 @@ def test_inner_form_equals_gather_form(env, level):
         assert np.array_equal(av == 0.25, bv == 0.25) and np.array_equal(ae == -0.5, be == -0.5)  # untouched entries are untouched in both
         if update == 0:  # exactly the DoFs of the mask were written
             assert np.array_equal(np.concatenate([av != 0.25, ae != -0.5]), pu.dof_mask(level, mask))
+
+
+@pytest.mark.parametrize("level", [5, 6])
+def test_inner_form_equals_gather_form(env, level):
+    """levels the restatement is not run at; level 6 has rows longer than a wave.  The two forms differ in the order of the micro-cells
+    only: max difference <= 1e-13 * max|dst|, the bound of tests/test_gpu_p2_class_rows.py for two P2 kernels with different partial sums"""
+    _check_inner_form_equals_gather_form(env, level)
+
+
+def test_inner_form_equals_gather_form_at_level_6(env):
+    """the one-lane gather form: level 6 is the smallest level at which "every DoF" is dispatched with one lane per DoF (47,905 vertex
+    and about 318,000 edge entries).  Same cases and bound as above; the parent commit holds 1e-13 (profiles/p2_varcoef_checks.txt)"""
+    _check_inner_form_equals_gather_form(env, 6)

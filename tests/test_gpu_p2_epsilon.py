@@ -188,11 +188,8 @@ def test_rigid_rotation_gives_zero(env, level, form):
     assert np.abs(got).max() <= 1e-12 * mu.max() * np.abs(u).max() * pe.max_entry(tet(), level)
 
 
-def test_inner_form_equals_gather_form_at_level_5(env):
-    """a level the restatement is not run at.  The two forms differ in the order of the micro-cells only: max difference
-    <= 1e-13 * max|dst|, the bound of tests/test_gpu_p2_divkgrad.py for form against form"""
+def _check_inner_form_equals_gather_form(env, level):
     torch, capi = env
-    level = 5
     rng = np.random.default_rng(level)
     n = pu.size(level)
     src, mu = rng.standard_normal((3, n)), rng.uniform(0.5, 2.0, n)
@@ -210,3 +207,16 @@ def test_inner_form_equals_gather_form_at_level_5(env):
         assert np.array_equal(out[False] == filled, out[True] == filled)  # untouched entries are untouched in both
         if update == 0:  # exactly the DoFs of the masks were written
             assert np.array_equal(out[False] != filled, pe.dof_masks(level, mask))
+
+
+def test_inner_form_equals_gather_form_at_level_5(env):
+    """a level the restatement is not run at.  The two forms differ in the order of the micro-cells only: max difference
+    <= 1e-13 * max|dst|, the bound of tests/test_gpu_p2_divkgrad.py for form against form"""
+    _check_inner_form_equals_gather_form(env, 5)
+
+
+def test_inner_form_equals_gather_form_at_level_6(env):
+    """the one-lane gather form: level 6 is the smallest level at which "every DoF" is dispatched with one lane per DoF (47,905 vertex
+    and about 318,000 edge entries per component).  Same cases and bound as at level 5; the parent commit holds 1e-13
+    (profiles/p2_varcoef_checks.txt)"""
+    _check_inner_form_equals_gather_form(env, 6)
