@@ -191,6 +191,13 @@ SIGNATURES = {
     "hyteg_hip_p2_elementwise_epsilon_diagonal_cell": (_i, [_vp, _vp, _vp, _vp, _i, _dp, _vp]),
     "hyteg_hip_p2_elementwise_epsilon_set_inner_min_level": (_i, [_i]),
     "hyteg_hip_p2_elementwise_epsilon_max_level": (_i, []),
+    **{f"hyteg_hip_p2_elementwise_divkgrad_{what}_cell{form}": (_i, [_vp] * (2 * pairs + 2) + [_i, _dp] + scalars + [C.c_uint, C.c_uint, _vp])
+       for form in ("", "_gather")
+       for what, pairs, scalars in (("residual", 3, []), ("jacobi", 4, [_d]), ("chebyshev_start", 4, []), ("chebyshev_step", 4, [_d, _d, _i]))},
+    **{f"hyteg_hip_p2_elementwise_epsilon_{what}_cell{form}":
+       (_i, [_vp] * (2 * pairs + 2) + [C.POINTER(C.c_uint), _i, _dp] + scalars + [C.c_uint, _vp])
+       for form in ("", "_gather")
+       for what, pairs, scalars in (("residual", 3, []), ("jacobi", 4, [_d]), ("chebyshev_start", 4, []), ("chebyshev_step", 4, [_d, _d, _i]))},
     "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_masked": (_i, [_vp, _vp, _vp, _dp, _i64, C.c_uint, _i, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_apply_macro_3d_component_masks": (_i, [_vp, _vp, _vp, _dp, _i64, C.POINTER(C.c_uint), _i, _vp]),
     "hyteg_hip_p1_elementwise_epsilon_jacobi_macro_3d": (_i, [_vp, _vp, _vp, _vp, _vp, _dp, _i64, _d, _vp]),
@@ -1052,6 +1059,42 @@ def p2_elementwise_epsilon_set_inner_min_level(level):
 
 def p2_elementwise_epsilon_max_level():
     return lib().hyteg_hip_p2_elementwise_epsilon_max_level()
+
+
+# ---- the fused modes of the two P2 variable-coefficient operators: residual, Jacobi step, Chebyshev start and step ----
+def _p2_varcoef_mode(op, what, operands, coef, level, geometry, scalars, mask, kinds, stream, gather):
+    """one call of hyteg_hip_p2_elementwise_{op}_{what}_cell[_gather]; operands: ( vertex, edge ) pairs in the entry's order, device pointers
+    for div-k-grad and three device pointers each for the epsilon operator"""
+    name = f"p2_elementwise_{op}_{what}_cell" + ("_gather" if gather else "")
+    fn = getattr(lib(), "hyteg_hip_" + name)
+    if op == "epsilon":
+        arrays = [_ptr3(a) for pair in operands for a in pair]
+        check(fn(*arrays, *coef, _masks3(mask), int(level), _geometry72(geometry), *scalars, kinds, stream), name)
+    else:
+        arrays = [a for pair in operands for a in pair]
+        check(fn(*arrays, *coef, int(level), _geometry60(geometry), *scalars, mask, kinds, stream), name)
+
+
+def p2_varcoef_residual_cell(op, dst, src, rhs, coef, level, geometry, mask=MASK_ALL, kinds=0xFF, stream=0, gather=False):
+    """dst = rhs - A( coef ) src on the DoFs of `mask` and `kinds`; op: "epsilon" or "divkgrad"; dst, src, rhs, coef: ( vertex, edge )"""
+    _p2_varcoef_mode(op, "residual", (dst, src, rhs), coef, level, geometry, (), mask, kinds, stream, gather)
+
+
+def p2_varcoef_jacobi_cell(op, dst, src, rhs, inv_diag, coef, level, geometry, relax, mask=MASK_ALL, kinds=0xFF, stream=0, gather=False):
+    """dst = src + relax * inv_diag * ( rhs - A( coef ) src )"""
+    _p2_varcoef_mode(op, "jacobi", (dst, src, rhs, inv_diag), coef, level, geometry, (float(relax),), mask, kinds, stream, gather)
+
+
+def p2_varcoef_chebyshev_start_cell(op, t_out, x, rhs, inv_diag, coef, level, geometry, mask=MASK_ALL, kinds=0xFF, stream=0, gather=False):
+    """t_out = inv_diag * ( rhs - A( coef ) x ); x is not updated"""
+    _p2_varcoef_mode(op, "chebyshev_start", (t_out, x, rhs, inv_diag), coef, level, geometry, (), mask, kinds, stream, gather)
+
+
+def p2_varcoef_chebyshev_step_cell(op, t_out, x, t_in, inv_diag, coef, level, geometry, c_prev, c_cur, has_prev, mask=MASK_ALL, kinds=0xFF,
+                                   stream=0, gather=False):
+    """t_out = inv_diag * A( coef ) t_in; x = ( x + c_prev * t_in ) + c_cur * t_out, the first summand only if has_prev"""
+    _p2_varcoef_mode(op, "chebyshev_step", (t_out, x, t_in, inv_diag), coef, level, geometry, (float(c_prev), float(c_cur), int(bool(has_prev))),
+                     mask, kinds, stream, gather)
 
 
 # ---- variable-viscosity epsilon operator -div( 2 mu eps(u) ): the nine blocks of P1ElementwiseAffineEpsilonOperator in one pass ----

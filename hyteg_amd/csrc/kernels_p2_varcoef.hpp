@@ -17,6 +17,10 @@
 // compile-time list, so a thread is straight-line code whose lanes run along x.  Both add the micro-cells' contributions in a fixed
 // order; no atomics, no LDS, no scratch.  Every component has a point-class mask of its own: a component whose mask excludes a DoF is
 // computed but not stored.  32-bit indices: levels 0 .. kMaxLevel.
+//
+// Fused modes.  At its store a thread (or the first lane of a group) holds the complete ( A src )_j of its DoF.  The kernels whose
+// arguments carry an Epilogue replace the plain store by one of four epilogues, selected by a wave-uniform run-time mode, so that each
+// form is compiled once more and not four times (`epilogue` below).  rhs, invdiag and x are read at the DoF's own index only.
 #pragma once
 
 #include "kernels_p2_gather.hpp"
@@ -47,6 +51,95 @@ struct GatherArgs
    Args< OP > A;
    P2Tables   T;
 };
+
+// what replaces the store of ( A src )_j (alpha = 1, Replace); dst, src: the arrays of Args
+//    kResidual    dst = rhs - A src
+//    kJacobi      dst = src + relax invdiag ( rhs - A src )              smooth_jac's four statements in their order; the compiler may
+//                 contract the last multiply-add (here and in kChebStep) into one FMA, which the composed passes do not
+//    kChebStart   dst = invdiag ( rhs - A src )                          src is x, which is not updated here
+//    kChebStep    dst = invdiag A src;  x = ( x + cPrev src ) + cCur dst, the first summand only if hasPrev (src is t_in, dst t_out;
+//                 x is read and written at the DoF's own index by the thread that owns it: it is not a source of the operator)
+enum Mode : int
+{
+   kResidual  = 0,
+   kJacobi    = 1,
+   kChebStart = 2,
+   kChebStep  = 3
+};
+struct Plain
+{};
+template < class OP >
+struct Epilogue
+{
+   static constexpr int NC = OP::NC;
+   const double*        rhsV[NC]; // null where the mode does not read them
+   const double*        rhsE[NC];
+   const double*        invV[NC];
+   const double*        invE[NC];
+   double*              xV[NC];
+   double*              xE[NC];
+   double               relax, cPrev, cCur;
+   int                  mode, hasPrev;
+};
+// the arguments of the fused kernels: those of the plain kernels first, at their offsets
+template < class OP >
+struct FusedArgs
+{
+   Args< OP >     A;
+   Epilogue< OP > E;
+};
+template < class OP >
+struct FusedGatherArgs
+{
+   Args< OP >     A;
+   P2Tables       T;
+   Epilogue< OP > E;
+};
+template < class OP >
+__device__ __forceinline__ const Args< OP >& args_of( const Args< OP >& K )
+{
+   return K;
+}
+template < class OP >
+__device__ __forceinline__ const Args< OP >& args_of( const FusedArgs< OP >& K )
+{
+   return K.A;
+}
+template < class OP >
+__device__ __forceinline__ Plain epilogue_of( const Args< OP >& )
+{
+   return Plain{};
+}
+template < class OP >
+__device__ __forceinline__ const Epilogue< OP >& epilogue_of( const FusedArgs< OP >& K )
+{
+   return K.E;
+}
+
+// component j of the DoF at entry `at` of the vertex array or of the edge array: v = ( A src )_j, complete.  Every branch is
+// wave-uniform.  Both store streams of kChebStep are behind the caller's mask test.
+template < class OP >
+__device__ __forceinline__ void epilogue( const Args< OP >& A, const Epilogue< OP >& E, bool vertex, int j, int at, double v )
+{
+   double* out = ( vertex ? A.dstV[j] : A.dstE[j] ) + at;
+   if ( E.mode == kResidual )
+   {
+      *out = ( vertex ? E.rhsV[j] : E.rhsE[j] )[at] - v;
+      return;
+   }
+   const double inv = ( vertex ? E.invV[j] : E.invE[j] )[at];
+   if ( E.mode == kChebStep )
+   {
+      double*      x = ( vertex ? E.xV[j] : E.xE[j] ) + at;
+      const double t = inv * v;
+      const double p = E.hasPrev ? *x + E.cPrev * ( vertex ? A.srcV[j] : A.srcE[j] )[at] : *x;
+      *out           = t;
+      *x             = p + E.cCur * t;
+      return;
+   }
+   const double d = inv * ( ( vertex ? E.rhsV[j] : E.rhsE[j] )[at] - v );
+   *out           = E.mode == kJacobi ? ( vertex ? A.srcV[j] : A.srcE[j] )[at] + E.relax * d : d;
+}
 
 constexpr int kLocal[4][4] = { { 0, 9, 8, 7 }, { 9, 1, 6, 5 }, { 8, 6, 2, 4 }, { 7, 5, 4, 3 } }; // fenics::P2DoFMap
 
@@ -95,10 +188,13 @@ __device__ inline int block_start( int n, int kind ) { return ( kind - 1 ) * (in
 // ALL: group q is entry q of the kind's array; otherwise the boundary DoFs only (p2_decode_boundary).
 // DIAG: component i of every DoF receives the sum of A_e^{ii}[row][row] (src is not read): the row function on the unit vector of
 // the DoF in component i alone, once per component.
-template < class OP, bool ALL, int G, bool DIAG >
-__global__ __launch_bounds__( kThreads ) void gather_kernel( const GatherArgs< OP > GA )
+// KA = FusedGatherArgs< OP >: the epilogue of GA.E.mode in place of the store.
+template < class OP, bool ALL, int G, bool DIAG, class KA = GatherArgs< OP > >
+__global__ __launch_bounds__( kThreads ) void gather_kernel( const KA GA )
 {
-   constexpr int     NC = OP::NC;
+   constexpr int  NC    = OP::NC;
+   constexpr bool FUSED = !std::is_same_v< KA, GatherArgs< OP > >;
+   static_assert( !( FUSED && DIAG ), "the diagonal has no fused mode" );
    const Args< OP >& A  = GA.A;
    const int         c  = blockIdx.y; // destination kind
    const int         N = A.N, n = N - 1;
@@ -208,8 +304,13 @@ __global__ __launch_bounds__( kThreads ) void gather_kernel( const GatherArgs< O
    {
       if ( !( ( A.mask[j] >> cls ) & 1u ) )
          continue;
-      double* out = ( c == 0 ? A.dstV[j] : A.dstE[j] ) + at;
-      *out        = A.update == HYTEG_HIP_ADD ? *out + acc[j] : acc[j];
+      if constexpr ( FUSED )
+         epilogue( A, GA.E, c == 0, j, at, acc[j] );
+      else
+      {
+         double* out = ( c == 0 ? A.dstV[j] : A.dstE[j] ) + at;
+         *out        = A.update == HYTEG_HIP_ADD ? *out + acc[j] : acc[j];
+      }
    }
 }
 
@@ -334,8 +435,8 @@ __device__ __forceinline__ void inner_cell( const Args< OP >& A, const Base& B, 
    __builtin_amdgcn_sched_barrier( 0 );
 }
 
-template < class OP, int C >
-__device__ __forceinline__ void inner_body( const Args< OP >& A )
+template < class OP, int C, class EP >
+__device__ __forceinline__ void inner_body( const Args< OP >& A, const EP& E )
 {
    constexpr int NC     = OP::NC;
    constexpr int NCELLS = CellsOf< C >::value.n; // forced constant evaluation: none of the table code may run on the device
@@ -367,25 +468,32 @@ __device__ __forceinline__ void inner_body( const Args< OP >& A )
       if constexpr ( NC > 1 ) // one component: the launch layer starts this kernel only for a mask with the inner class
          if ( !( ( A.mask[k] >> 14 ) & 1u ) ) // inner DoFs are point class 14
             continue;
-      double* out = ( C == 0 ? A.dstV[k] : A.dstE[k] ) + at;
-      *out        = A.update == HYTEG_HIP_ADD ? *out + acc[k] : acc[k];
+      if constexpr ( !std::is_same_v< EP, Plain > )
+         epilogue( A, E, C == 0, k, at, acc[k] );
+      else
+      {
+         double* out = ( C == 0 ? A.dstV[k] : A.dstE[k] ) + at;
+         *out        = A.update == HYTEG_HIP_ADD ? *out + acc[k] : acc[k];
+      }
    }
 }
 
 // the inner vertex DoFs (24 micro-cells each, the most registers) and, blockIdx.y + 1 = destination kind, the inner edge DoFs of the
-// kinds of A.kinds: two launches, so that the edge kinds are not held to the vertex kind's occupancy
-template < class OP >
-__global__ __launch_bounds__( kThreads ) void inner_vertex_kernel( const Args< OP > A )
+// kinds of A.kinds: two launches, so that the edge kinds are not held to the vertex kind's occupancy.  KA = FusedArgs< OP >: the
+// epilogue of K.E.mode in place of the store
+template < class OP, class KA = Args< OP > >
+__global__ __launch_bounds__( kThreads ) void inner_vertex_kernel( const KA K )
 {
-   inner_body< OP, 0 >( A );
+   inner_body< OP, 0 >( args_of< OP >( K ), epilogue_of< OP >( K ) );
 }
-template < class OP >
-__global__ __launch_bounds__( kThreads ) void inner_edge_kernel( const Args< OP > A )
+template < class OP, class KA = Args< OP > >
+__global__ __launch_bounds__( kThreads ) void inner_edge_kernel( const KA K )
 {
-   const int c = blockIdx.y + 1;
+   const Args< OP >& A = args_of< OP >( K );
+   const int         c = blockIdx.y + 1;
    if ( !( ( A.kinds >> c ) & 1u ) )
       return;
-   [&]< int... C >( std::integer_sequence< int, C... > ) { ( ( c == C + 1 ? inner_body< OP, C + 1 >( A ) : void() ), ... ); }
+   [&]< int... C >( std::integer_sequence< int, C... > ) { ( ( c == C + 1 ? inner_body< OP, C + 1 >( A, epilogue_of< OP >( K ) ) : void() ), ... ); }
    ( std::make_integer_sequence< int, 7 >{} );
 }
 

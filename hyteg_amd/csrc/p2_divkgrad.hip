@@ -79,6 +79,48 @@ HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_diagonal_cell( double*      
    return p2varcoef::diagonal< L >( "p2_elementwise_divkgrad_diagonal_cell", &diag_vertex, &diag_edge, k_vertex, k_edge, level, geometry, as_stream( stream ) );
 }
 
+// The fused modes: the arguments of apply_cell_kinds plus the mode's operands; the _gather entries run the gather form on every DoF.
+#define HH_P2_DIVKGRAD_MODE_ENTRIES( SUFFIX, GATHER )                                                                                                  \
+   HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_residual_cell##SUFFIX(                                                                          \
+       double* dst_vertex, double* dst_edge, const double* src_vertex, const double* src_edge, const double* rhs_vertex, const double* rhs_edge,       \
+       const double* k_vertex, const double* k_edge, int level, const double* geometry, unsigned mask, unsigned kind_mask,                             \
+       hyteg_hip_stream_t stream )                                                                                                                     \
+   {                                                                                                                                                   \
+      return p2varcoef::residual< L >( "p2_elementwise_divkgrad_residual_cell" #SUFFIX, GATHER, { &dst_vertex, &dst_edge },                            \
+                                       { &src_vertex, &src_edge }, { &rhs_vertex, &rhs_edge }, k_vertex, k_edge, &mask, level, geometry, kind_mask,    \
+                                       as_stream( stream ) );                                                                                          \
+   }                                                                                                                                                   \
+   HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_jacobi_cell##SUFFIX(                                                                            \
+       double* dst_vertex, double* dst_edge, const double* src_vertex, const double* src_edge, const double* rhs_vertex, const double* rhs_edge,       \
+       const double* invdiag_vertex, const double* invdiag_edge, const double* k_vertex, const double* k_edge, int level, const double* geometry,      \
+       double relax, unsigned mask, unsigned kind_mask, hyteg_hip_stream_t stream )                                                                    \
+   {                                                                                                                                                   \
+      return p2varcoef::jacobi< L >( "p2_elementwise_divkgrad_jacobi_cell" #SUFFIX, GATHER, { &dst_vertex, &dst_edge }, { &src_vertex, &src_edge },    \
+                                     { &rhs_vertex, &rhs_edge }, { &invdiag_vertex, &invdiag_edge }, k_vertex, k_edge, &mask, level, geometry, relax,  \
+                                     kind_mask, as_stream( stream ) );                                                                                 \
+   }                                                                                                                                                   \
+   HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_chebyshev_start_cell##SUFFIX(                                                                   \
+       double* t_out_vertex, double* t_out_edge, const double* x_vertex, const double* x_edge, const double* rhs_vertex, const double* rhs_edge,       \
+       const double* invdiag_vertex, const double* invdiag_edge, const double* k_vertex, const double* k_edge, int level, const double* geometry,      \
+       unsigned mask, unsigned kind_mask, hyteg_hip_stream_t stream )                                                                                  \
+   {                                                                                                                                                   \
+      return p2varcoef::chebyshev_start< L >( "p2_elementwise_divkgrad_chebyshev_start_cell" #SUFFIX, GATHER, { &t_out_vertex, &t_out_edge },          \
+                                              { &x_vertex, &x_edge }, { &rhs_vertex, &rhs_edge }, { &invdiag_vertex, &invdiag_edge }, k_vertex,        \
+                                              k_edge, &mask, level, geometry, kind_mask, as_stream( stream ) );                                        \
+   }                                                                                                                                                   \
+   HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_chebyshev_step_cell##SUFFIX(                                                                    \
+       double* t_out_vertex, double* t_out_edge, double* x_vertex, double* x_edge, const double* t_in_vertex, const double* t_in_edge,                 \
+       const double* invdiag_vertex, const double* invdiag_edge, const double* k_vertex, const double* k_edge, int level, const double* geometry,      \
+       double c_prev, double c_cur, int has_prev, unsigned mask, unsigned kind_mask, hyteg_hip_stream_t stream )                                       \
+   {                                                                                                                                                   \
+      return p2varcoef::chebyshev_step< L >( "p2_elementwise_divkgrad_chebyshev_step_cell" #SUFFIX, GATHER, { &t_out_vertex, &t_out_edge },            \
+                                             { &x_vertex, &x_edge }, { &t_in_vertex, &t_in_edge }, { &invdiag_vertex, &invdiag_edge }, k_vertex,       \
+                                             k_edge, &mask, level, geometry, c_prev, c_cur, has_prev, kind_mask, as_stream( stream ) );                \
+   }
+HH_P2_DIVKGRAD_MODE_ENTRIES(, false )
+HH_P2_DIVKGRAD_MODE_ENTRIES( _gather, true )
+#undef HH_P2_DIVKGRAD_MODE_ENTRIES
+
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level( int level ) { return p2varcoef::set_inner_min_level< L >( level ); }
 
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_max_level( void ) { return p2varcoef::kMaxLevel; }

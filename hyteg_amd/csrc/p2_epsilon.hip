@@ -81,6 +81,50 @@ HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_diagonal_cell( double* const*
    return p2varcoef::diagonal< L >( "p2_elementwise_epsilon_diagonal_cell", diag_vertex, diag_edge, mu_vertex, mu_edge, level, geometry, as_stream( stream ) );
 }
 
+// The fused modes: the arguments of apply_cell_kinds plus the mode's operands; the _gather entries run the gather form on every DoF.
+#define HH_P2_EPSILON_MODE_ENTRIES( SUFFIX, GATHER )                                                                                                   \
+   HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_residual_cell##SUFFIX(                                                                           \
+       double* const* dst_vertex, double* const* dst_edge, const double* const* src_vertex, const double* const* src_edge,                            \
+       const double* const* rhs_vertex, const double* const* rhs_edge, const double* mu_vertex, const double* mu_edge, const unsigned* mask,           \
+       int level, const double* geometry, unsigned kind_mask, hyteg_hip_stream_t stream )                                                             \
+   {                                                                                                                                                   \
+      return p2varcoef::residual< L >( "p2_elementwise_epsilon_residual_cell" #SUFFIX, GATHER, { dst_vertex, dst_edge }, { src_vertex, src_edge },     \
+                                       { rhs_vertex, rhs_edge }, mu_vertex, mu_edge, mask, level, geometry, kind_mask, as_stream( stream ) );          \
+   }                                                                                                                                                   \
+   HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_jacobi_cell##SUFFIX(                                                                             \
+       double* const* dst_vertex, double* const* dst_edge, const double* const* src_vertex, const double* const* src_edge,                            \
+       const double* const* rhs_vertex, const double* const* rhs_edge, const double* const* invdiag_vertex, const double* const* invdiag_edge,         \
+       const double* mu_vertex, const double* mu_edge, const unsigned* mask, int level, const double* geometry, double relax, unsigned kind_mask,      \
+       hyteg_hip_stream_t stream )                                                                                                                     \
+   {                                                                                                                                                   \
+      return p2varcoef::jacobi< L >( "p2_elementwise_epsilon_jacobi_cell" #SUFFIX, GATHER, { dst_vertex, dst_edge }, { src_vertex, src_edge },         \
+                                     { rhs_vertex, rhs_edge }, { invdiag_vertex, invdiag_edge }, mu_vertex, mu_edge, mask, level, geometry, relax,     \
+                                     kind_mask, as_stream( stream ) );                                                                                 \
+   }                                                                                                                                                   \
+   HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_chebyshev_start_cell##SUFFIX(                                                                    \
+       double* const* t_out_vertex, double* const* t_out_edge, const double* const* x_vertex, const double* const* x_edge,                            \
+       const double* const* rhs_vertex, const double* const* rhs_edge, const double* const* invdiag_vertex, const double* const* invdiag_edge,         \
+       const double* mu_vertex, const double* mu_edge, const unsigned* mask, int level, const double* geometry, unsigned kind_mask,                    \
+       hyteg_hip_stream_t stream )                                                                                                                     \
+   {                                                                                                                                                   \
+      return p2varcoef::chebyshev_start< L >( "p2_elementwise_epsilon_chebyshev_start_cell" #SUFFIX, GATHER, { t_out_vertex, t_out_edge },             \
+                                              { x_vertex, x_edge }, { rhs_vertex, rhs_edge }, { invdiag_vertex, invdiag_edge }, mu_vertex, mu_edge,    \
+                                              mask, level, geometry, kind_mask, as_stream( stream ) );                                                 \
+   }                                                                                                                                                   \
+   HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_chebyshev_step_cell##SUFFIX(                                                                     \
+       double* const* t_out_vertex, double* const* t_out_edge, double* const* x_vertex, double* const* x_edge, const double* const* t_in_vertex,      \
+       const double* const* t_in_edge, const double* const* invdiag_vertex, const double* const* invdiag_edge, const double* mu_vertex,                \
+       const double* mu_edge, const unsigned* mask, int level, const double* geometry, double c_prev, double c_cur, int has_prev,                      \
+       unsigned kind_mask, hyteg_hip_stream_t stream )                                                                                                 \
+   {                                                                                                                                                   \
+      return p2varcoef::chebyshev_step< L >( "p2_elementwise_epsilon_chebyshev_step_cell" #SUFFIX, GATHER, { t_out_vertex, t_out_edge },               \
+                                             { x_vertex, x_edge }, { t_in_vertex, t_in_edge }, { invdiag_vertex, invdiag_edge }, mu_vertex, mu_edge,   \
+                                             mask, level, geometry, c_prev, c_cur, has_prev, kind_mask, as_stream( stream ) );                         \
+   }
+HH_P2_EPSILON_MODE_ENTRIES(, false )
+HH_P2_EPSILON_MODE_ENTRIES( _gather, true )
+#undef HH_P2_EPSILON_MODE_ENTRIES
+
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_set_inner_min_level( int level ) { return p2varcoef::set_inner_min_level< L >( level ); }
 
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_max_level( void ) { return p2varcoef::kMaxLevel; }

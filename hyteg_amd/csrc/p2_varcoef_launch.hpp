@@ -83,29 +83,73 @@ unsigned any_mask( const Args< OP >& A )
 // L::kGatherLanes lanes per DoF where the launch is latency-bound (the boundary walk, all DoFs up to L::kGatherLanesMaxLevel, and the
 // diagonal, which runs once per operator); one lane per DoF above, where repeating the index decode eight times costs more than the
 // round trips (tools/bench_kernels.py --only p2-divkgrad / p2-epsilon)
-template < class L, bool DIAG = false >
-int launch_gather( const Args< typename L::OP >& A, int level, hipStream_t s )
+// E: Plain, or the Epilogue of a fused mode (the kernels that take FusedGatherArgs)
+template < class L, bool DIAG = false, class EP = Plain >
+int launch_gather( const Args< typename L::OP >& A, int level, hipStream_t s, const EP& E = EP{} )
 {
-   using OP         = typename L::OP;
-   constexpr int GL = L::kGatherLanes;
-   GatherArgs< OP > G;
+   using OP             = typename L::OP;
+   constexpr int  GL    = L::kGatherLanes;
+   constexpr bool FUSED = !std::is_same_v< EP, Plain >;
+   using GA             = std::conditional_t< FUSED, FusedGatherArgs< OP >, GatherArgs< OP > >;
+   GA G;
    G.A = A, G.T = tables();
+   if constexpr ( FUSED )
+      G.E = E;
    const unsigned all = tet32( (unsigned) A.N ), shell = (unsigned) ( 4 * tri( A.N ) );
    const auto     grid = []( unsigned dofs, int lanes ) { return dim3( ( dofs * lanes + kThreads - 1 ) / kThreads, 8 ); };
    if constexpr ( DIAG )
       hipLaunchKernelGGL( ( gather_kernel< OP, true, GL, true > ), grid( all, GL ), dim3( kThreads ), 0, s, G );
    else if ( !( any_mask( A ) & HYTEG_HIP_MASK_INNER ) )
-      hipLaunchKernelGGL( ( gather_kernel< OP, false, GL, false > ), grid( shell, GL ), dim3( kThreads ), 0, s, G );
+      hipLaunchKernelGGL( ( gather_kernel< OP, false, GL, false, GA > ), grid( shell, GL ), dim3( kThreads ), 0, s, G );
    else if ( level <= L::kGatherLanesMaxLevel )
-      hipLaunchKernelGGL( ( gather_kernel< OP, true, GL, false > ), grid( all, GL ), dim3( kThreads ), 0, s, G );
+      hipLaunchKernelGGL( ( gather_kernel< OP, true, GL, false, GA > ), grid( all, GL ), dim3( kThreads ), 0, s, G );
    else
-      hipLaunchKernelGGL( ( gather_kernel< OP, true, 1, false > ), grid( all, 1 ), dim3( kThreads ), 0, s, G );
+      hipLaunchKernelGGL( ( gather_kernel< OP, true, 1, false, GA > ), grid( all, 1 ), dim3( kThreads ), 0, s, G );
    HH_CHECK_HIP( hipGetLastError() );
    return HYTEG_HIP_OK;
 }
 
-// dst = alpha A src or dst += alpha A src on the DoFs of the masks and kinds.  gather_only: the gather form on every DoF; otherwise
-// the gather form on the shell and, from the operator's first inner level, the inner vertex and inner edge launches
+// The shape split of an apply or of a fused mode on the DoFs of A.mask and A.kinds (not all empty).  gather_only: the gather form on
+// every DoF; otherwise the gather form on the shell and, from the operator's first inner level, the inner vertex and inner edge launches
+template < class L, class EP >
+int launch( const Args< typename L::OP >& A, const EP& E, bool gather_only, int level, hipStream_t s )
+{
+   using OP                 = typename L::OP;
+   const unsigned any       = any_mask( A );
+   const bool     inner =
+       !gather_only && ( any & HYTEG_HIP_MASK_INNER ) && level >= 2 && level >= inner_min_level< L >().load( std::memory_order_relaxed );
+   if ( !inner )
+      return launch_gather< L, false, EP >( A, level, s, E );
+   if ( any & HYTEG_HIP_MASK_SHELL )
+   {
+      Args< OP > B = A;
+      for ( int j = 0; j < OP::NC; ++j )
+         B.mask[j] = A.mask[j] & HYTEG_HIP_MASK_SHELL;
+      const int rs = launch_gather< L, false, EP >( B, level, s, E );
+      if ( rs != HYTEG_HIP_OK )
+         return rs;
+   }
+   const unsigned nb = ( tet32( (unsigned) A.N ) + kThreads - 1 ) / kThreads;
+   if constexpr ( std::is_same_v< EP, Plain > )
+   {
+      if ( A.kinds & 1u )
+         hipLaunchKernelGGL( inner_vertex_kernel< OP >, dim3( nb ), dim3( kThreads ), 0, s, A );
+      if ( A.kinds & 0xFEu )
+         hipLaunchKernelGGL( inner_edge_kernel< OP >, dim3( nb, 7 ), dim3( kThreads ), 0, s, A );
+   }
+   else
+   {
+      const FusedArgs< OP > F{ A, E };
+      if ( A.kinds & 1u )
+         hipLaunchKernelGGL( ( inner_vertex_kernel< OP, FusedArgs< OP > > ), dim3( nb ), dim3( kThreads ), 0, s, F );
+      if ( A.kinds & 0xFEu )
+         hipLaunchKernelGGL( ( inner_edge_kernel< OP, FusedArgs< OP > > ), dim3( nb, 7 ), dim3( kThreads ), 0, s, F );
+   }
+   HH_CHECK_HIP( hipGetLastError() );
+   return HYTEG_HIP_OK;
+}
+
+// dst = alpha A src or dst += alpha A src on the DoFs of the masks and kinds
 template < class L >
 int apply( const char* who, bool gather_only, double* const* dstV, double* const* dstE, const double* const* srcV, const double* const* srcE,
            const double* kV, const double* kE, const unsigned* mask, int level, const double* geometry, double alpha, int update, unsigned kinds,
@@ -122,27 +166,107 @@ int apply( const char* who, bool gather_only, double* const* dstV, double* const
    kinds &= 0xFFu;
    if ( any == 0 || kinds == 0 )
       return HYTEG_HIP_OK;
-   Args< OP > A = make_args< OP >( dstV, dstE, srcV, srcE, kV, kE, level, geometry, alpha, update, m, kinds );
-   const bool inner =
-       !gather_only && ( any & HYTEG_HIP_MASK_INNER ) && level >= 2 && level >= inner_min_level< L >().load( std::memory_order_relaxed );
-   if ( !inner )
-      return launch_gather< L >( A, level, s );
-   if ( any & HYTEG_HIP_MASK_SHELL )
+   return launch< L >( make_args< OP >( dstV, dstE, srcV, srcE, kV, kE, level, geometry, alpha, update, m, kinds ), Plain{}, gather_only, level, s );
+}
+
+// ---- the fused modes (kernels_p2_varcoef.hpp, Mode): the arguments of apply plus the mode's operands ----------------------------
+// An operand is a pair ( vertex arrays, edge arrays ) of NC pointers each; a pair the mode does not have is { nullptr, nullptr }.
+template < class T >
+struct Operand
+{
+   T* const* v;
+   T* const* e;
+};
+// Before any launch: no null pointer among the mode's operands, the level, no written array (dst, t_out, x) equal to another array of
+// the call, no array equal to the coefficient.
+template < class L >
+int fused( const char* who, Mode mode, bool gather_only, Operand< double > dst, Operand< const double > src, Operand< const double > rhs,
+           Operand< const double > inv, Operand< double > x, const double* kV, const double* kE, const unsigned* mask, int level,
+           const double* geometry, double relax, double cPrev, double cCur, int hasPrev, unsigned kinds, hipStream_t s )
+{
+   using OP         = typename L::OP;
+   constexpr int NC = OP::NC;
+   const bool    hasRhs = mode != kChebStep, hasInv = mode != kResidual, hasX = mode == kChebStep;
+   const std::string w = who;
+   HH_REQUIRE( mask && kV && kE && geometry && dst.v && dst.e && src.v && src.e, w + ": null pointer" );
+   HH_REQUIRE( ( !hasRhs || ( rhs.v && rhs.e ) ) && ( !hasInv || ( inv.v && inv.e ) ) && ( !hasX || ( x.v && x.e ) ), w + ": null pointer" );
+   const double* written[4 * NC];
+   const double* read[6 * NC];
+   int           nw = 0, nr = 0;
+   for ( int j = 0; j < NC; ++j )
    {
-      Args< OP > B = A;
-      for ( int j = 0; j < OP::NC; ++j )
-         B.mask[j] = m[j] & HYTEG_HIP_MASK_SHELL;
-      const int rs = launch_gather< L >( B, level, s );
-      if ( rs != HYTEG_HIP_OK )
-         return rs;
+      written[nw++] = dst.v[j], written[nw++] = dst.e[j];
+      read[nr++] = src.v[j], read[nr++] = src.e[j];
+      if ( hasX )
+         written[nw++] = x.v[j], written[nw++] = x.e[j];
+      if ( hasRhs )
+         read[nr++] = rhs.v[j], read[nr++] = rhs.e[j];
+      if ( hasInv )
+         read[nr++] = inv.v[j], read[nr++] = inv.e[j];
    }
-   const unsigned nb = ( tet32( (unsigned) A.N ) + kThreads - 1 ) / kThreads;
-   if ( kinds & 1u )
-      hipLaunchKernelGGL( inner_vertex_kernel< OP >, dim3( nb ), dim3( kThreads ), 0, s, A );
-   if ( kinds & 0xFEu )
-      hipLaunchKernelGGL( inner_edge_kernel< OP >, dim3( nb, 7 ), dim3( kThreads ), 0, s, A );
-   HH_CHECK_HIP( hipGetLastError() );
-   return HYTEG_HIP_OK;
+   for ( int a = 0; a < nw; ++a )
+      HH_REQUIRE( written[a], w + ": null pointer" );
+   for ( int a = 0; a < nr; ++a )
+      HH_REQUIRE( read[a], w + ": null pointer" );
+   HH_REQUIRE( level >= 0 && level <= kMaxLevel, w + ": level out of range [0,8]" );
+   const std::string alias = w + ": a written array must not alias another array of the call, and no array the coefficient";
+   for ( int a = 0; a < nw; ++a )
+   {
+      HH_REQUIRE( written[a] != kV && written[a] != kE, alias );
+      for ( int b = 0; b < nr; ++b )
+         HH_REQUIRE( written[a] != read[b], alias );
+      for ( int b = a + 1; b < nw; ++b )
+         HH_REQUIRE( written[a] != written[b], alias );
+   }
+   for ( int b = 0; b < nr; ++b )
+      HH_REQUIRE( read[b] != kV && read[b] != kE, alias );
+   unsigned m[NC], any = 0;
+   for ( int j = 0; j < NC; ++j )
+      any |= m[j] = mask[j] & HYTEG_HIP_MASK_ALL;
+   kinds &= 0xFFu;
+   if ( any == 0 || kinds == 0 )
+      return HYTEG_HIP_OK;
+   Epilogue< OP > E{};
+   for ( int j = 0; j < NC; ++j )
+   {
+      E.rhsV[j] = hasRhs ? rhs.v[j] : nullptr, E.rhsE[j] = hasRhs ? rhs.e[j] : nullptr;
+      E.invV[j] = hasInv ? inv.v[j] : nullptr, E.invE[j] = hasInv ? inv.e[j] : nullptr;
+      E.xV[j] = hasX ? x.v[j] : nullptr, E.xE[j] = hasX ? x.e[j] : nullptr;
+   }
+   E.relax = relax, E.cPrev = cPrev, E.cCur = cCur, E.mode = mode, E.hasPrev = hasPrev != 0;
+   return launch< L >( make_args< OP >( dst.v, dst.e, src.v, src.e, kV, kE, level, geometry, 1.0, HYTEG_HIP_REPLACE, m, kinds ), E, gather_only, level, s );
+}
+
+// dst = rhs - A src
+template < class L >
+int residual( const char* who, bool gather_only, Operand< double > dst, Operand< const double > src, Operand< const double > rhs, const double* kV,
+              const double* kE, const unsigned* mask, int level, const double* geometry, unsigned kinds, hipStream_t s )
+{
+   return fused< L >( who, kResidual, gather_only, dst, src, rhs, {}, {}, kV, kE, mask, level, geometry, 0.0, 0.0, 0.0, 0, kinds, s );
+}
+// dst = src + relax invdiag ( rhs - A src )
+template < class L >
+int jacobi( const char* who, bool gather_only, Operand< double > dst, Operand< const double > src, Operand< const double > rhs,
+            Operand< const double > inv, const double* kV, const double* kE, const unsigned* mask, int level, const double* geometry, double relax,
+            unsigned kinds, hipStream_t s )
+{
+   return fused< L >( who, kJacobi, gather_only, dst, src, rhs, inv, {}, kV, kE, mask, level, geometry, relax, 0.0, 0.0, 0, kinds, s );
+}
+// t_out = invdiag ( rhs - A x ); x is not updated
+template < class L >
+int chebyshev_start( const char* who, bool gather_only, Operand< double > tOut, Operand< const double > x, Operand< const double > rhs,
+                     Operand< const double > inv, const double* kV, const double* kE, const unsigned* mask, int level, const double* geometry,
+                     unsigned kinds, hipStream_t s )
+{
+   return fused< L >( who, kChebStart, gather_only, tOut, x, rhs, inv, {}, kV, kE, mask, level, geometry, 0.0, 0.0, 0.0, 0, kinds, s );
+}
+// t_out = invdiag A t_in; x = ( x + c_prev t_in ) + c_cur t_out, the first summand only if has_prev
+template < class L >
+int chebyshev_step( const char* who, bool gather_only, Operand< double > tOut, Operand< double > x, Operand< const double > tIn,
+                    Operand< const double > inv, const double* kV, const double* kE, const unsigned* mask, int level, const double* geometry,
+                    double cPrev, double cCur, int hasPrev, unsigned kinds, hipStream_t s )
+{
+   return fused< L >( who, kChebStep, gather_only, tOut, tIn, {}, inv, x, kV, kE, mask, level, geometry, 0.0, cPrev, cCur, hasPrev, kinds, s );
 }
 
 // every DoF of the NC diag arrays receives the diagonal entry of its component's diagonal block

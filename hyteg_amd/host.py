@@ -202,6 +202,9 @@ SIGNATURES = {
     "hyteg_host_p2divkgrad_compute_inverse_diagonal": (_i, [_vp]),
     "hyteg_host_p2divkgrad_inverse_diagonal_copy": (_i, [_vp, _vp, _i]),
     "hyteg_host_p2divkgrad_smooth_jac": (_i, [_vp, _vp, _vp, _vp, _d, _i, _i]),
+    "hyteg_host_p2divkgrad_set_fused": (_i, [_vp, _i]),
+    "hyteg_host_p2divkgrad_chebyshev_fusable": (_i, [_vp, _i, C.POINTER(_i)]),
+    "hyteg_host_p2divkgrad_residual": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
     "hyteg_host_p2divkgrad_cg_create": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
     "hyteg_host_p2divkgrad_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
     "hyteg_host_p2divkgrad_smoother_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
@@ -222,6 +225,11 @@ SIGNATURES = {
     "hyteg_host_p2epsilon_compute_inverse_diagonal": (_i, [_vp]),
     "hyteg_host_p2epsilon_inverse_diagonal": (_i, [_vp, C.POINTER(_vp)]),
     "hyteg_host_p2epsilon_smooth_jac": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _d, _i, _i]),
+    "hyteg_host_p2epsilon_set_fused": (_i, [_vp, _i]),
+    "hyteg_host_p2epsilon_chebyshev_fusable": (_i, [_vp, _i, C.POINTER(_i)]),
+    "hyteg_host_p2epsilon_residual": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i]),
+    "hyteg_host_p2epsilon_gmg_create": (_i, [_vp, _i, _i, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
+    "hyteg_host_p2epsilon_gmg_create_chebyshev": (_i, [_vp, _i, _i, _i, _dp, _i, _d, _d, _i, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_p2epsilon_cg_create": (_i, [_vp, _i, _i, _i, _d, _vp, C.POINTER(_vp)]),
     "hyteg_host_p2epsilon_cg_iterations": (_i, [_vp, C.POINTER(_i)]),
     "hyteg_host_p2epsilon_smoother_create": (_i, [_vp, _i, _i, _i, _d, C.POINTER(_vp)]),
@@ -233,6 +241,7 @@ SIGNATURES = {
     "hyteg_host_th_epsilon_destroy": (_i, [_vp]),
     "hyteg_host_th_epsilon_apply": (_i, [_vp, _vp, _vp, _i, _i]),
     "hyteg_host_th_epsilon_minres_create": (_i, [_vp, _i, _i, _i, _d, _i, _vp, C.POINTER(_vp)]),
+    "hyteg_host_th_epsilon_minres_create_block": (_i, [_vp, _i, _i, _i, _d, _i, _vp, _i, _i, _i, _i, _dp, _i, _d, _i, _i, _i, _d, C.POINTER(_vp)]),
     "hyteg_host_th_epsilon_minres_solve": (_i, [_vp, _vp, _vp, _vp, _i]),
     "hyteg_host_th_epsilon_minres_precondition": (_i, [_vp, _vp, _vp, _vp, _i]),
     "hyteg_host_th_epsilon_minres_iterations": (_i, [_vp, C.POINTER(_i)]),
@@ -2015,6 +2024,20 @@ class P2ElementwiseDivKGrad:
     def smooth_jac(self, dst: P2Function, rhs: P2Function, src: P2Function, relax, level, flag=Inner | NeumannBoundary):
         _ck(lib().hyteg_host_p2divkgrad_smooth_jac(self.h, dst.h, rhs.h, src.h, float(relax), level, flag), "p2divkgrad smooth_jac")
 
+    def set_fused(self, on: bool):
+        """the fused residual / Jacobi / Chebyshev launches (default), or the composed passes everywhere"""
+        _ck(lib().hyteg_host_p2divkgrad_set_fused(self.h, int(bool(on))), "p2divkgrad set_fused")
+
+    def chebyshev_fusable(self, level) -> bool:
+        """chebyshevFusable( level ): does ChebyshevSmoother take the fused steps on this level?"""
+        n = _i(0)
+        _ck(lib().hyteg_host_p2divkgrad_chebyshev_fusable(self.h, int(level), C.byref(n)), "p2divkgrad chebyshev_fusable")
+        return bool(n.value)
+
+    def residual(self, x, b, r, level, flag=Inner | NeumannBoundary):
+        """r = b - A x as the multigrid cycle writes it"""
+        _ck(lib().hyteg_host_p2divkgrad_residual(self.h, x.h, b.h, r.h, level, flag), "p2divkgrad residual")
+
     def close(self):
         if self.h:
             lib().hyteg_host_p2divkgrad_destroy(self.h)
@@ -2246,6 +2269,20 @@ class P2ViscousBlockEpsilonOperator:
         _ck(lib().hyteg_host_p2epsilon_smooth_jac(self.h, _handles3(dst), _handles3(rhs), _handles3(src), float(relax), level, flag),
             "p2epsilon smooth_jac")
 
+    def set_fused(self, on: bool):
+        """the fused residual / Jacobi / Chebyshev launches (default), or the composed passes everywhere"""
+        _ck(lib().hyteg_host_p2epsilon_set_fused(self.h, int(bool(on))), "p2epsilon set_fused")
+
+    def chebyshev_fusable(self, level) -> bool:
+        """chebyshevFusable( level ): does ChebyshevSmoother take the fused steps on this level?"""
+        n = _i(0)
+        _ck(lib().hyteg_host_p2epsilon_chebyshev_fusable(self.h, int(level), C.byref(n)), "p2epsilon chebyshev_fusable")
+        return bool(n.value)
+
+    def residual(self, x, b, r, level, flag=Inner | NeumannBoundary):
+        """r = b - A x as the multigrid cycle writes it; x, b, r: three component functions each"""
+        _ck(lib().hyteg_host_p2epsilon_residual(self.h, _handles3(x), _handles3(b), _handles3(r), level, flag), "p2epsilon residual")
+
     def estimate_radius(self, level: int, iterations: int) -> float:
         """chebyshev::estimateRadius: spectral radius of D^-1 A by power iterations from a fixed start vector (inverse diagonal
         computed)"""
@@ -2260,7 +2297,8 @@ class P2ViscousBlockEpsilonOperator:
 
 
 class P2EpsilonSolver:
-    """The solvers instantiated for P2ViscousBlockEpsilonOperator, acting on three component functions: CGSolver, ChebyshevSmoother and
+    """The solvers instantiated for P2ViscousBlockEpsilonOperator, acting on three component functions: CGSolver,
+    GeometricMultigridSolver (quadratic P2 transfer on every component, CG on the coarsest level), ChebyshevSmoother and
     WeightedJacobiSmoother / IdentityPreconditioner on their own.  Built by the class methods; mirrors EpsilonSolver."""
 
     def __init__(self, storage, h, keep=None):
@@ -2281,6 +2319,28 @@ class P2EpsilonSolver:
         keep, ptr, n = _radii(radii)
         _ck(lib().hyteg_host_p2epsilon_chebyshev_create(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower),
                                                         C.byref(h)), "p2epsilon chebyshev_create")
+        return cls(storage, h)
+
+    @classmethod
+    def gmg(cls, storage, min_level, max_level, smoother=JACOBI, relax=2.0 / 3.0, pre=3, post=3, wcycle=False, cg_max_iter=1000, cg_tol=1e-14):
+        """hyteg::GeometricMultigridSolver with WeightedJacobiSmoother( relax ) (the operator has no Gauss-Seidel sweep)"""
+        if smoother != JACOBI:
+            raise HytegHostError("P2EpsilonSolver.gmg: smoother JACOBI (gmg_chebyshev for the Chebyshev smoother)")
+        h = _vp()
+        _ck(lib().hyteg_host_p2epsilon_gmg_create(storage.h, min_level, max_level, float(relax), pre, post, int(bool(wcycle)), cg_max_iter,
+                                                  float(cg_tol), C.byref(h)), "p2epsilon gmg_create")
+        return cls(storage, h)
+
+    @classmethod
+    def gmg_chebyshev(cls, storage, min_level, max_level, order, radii, upper=1.2, lower=0.3, pre=1, post=1, wcycle=False, cg_max_iter=1000,
+                      cg_tol=1e-14):
+        """the multigrid solver smoothing with ChebyshevSmoother( order ); radii: one spectral radius
+        (P2ViscousBlockEpsilonOperator.estimate_radius) or one per level"""
+        h = _vp()
+        keep, ptr, n = _radii(radii)
+        _ck(lib().hyteg_host_p2epsilon_gmg_create_chebyshev(storage.h, min_level, max_level, int(order), ptr, n, float(upper), float(lower), pre,
+                                                            post, int(bool(wcycle)), cg_max_iter, float(cg_tol), C.byref(h)),
+            "p2epsilon gmg_create_chebyshev")
         return cls(storage, h)
 
     @classmethod
@@ -2334,17 +2394,39 @@ class TaylorHoodEpsilonSolver:
         self._keep = keep
 
     @classmethod
-    def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, preconditioner="pressure", mu=None):
+    def minres(cls, storage, min_level, max_level, max_iter=1000, rel_tol=1e-16, preconditioner="pressure", mu=None, velocity_cycles=1,
+               smoother="chebyshev", order=2, radii=None, relax=2.0 / 3.0, pre=1, post=1, velocity_min_level=None, cg_max_iter=1000,
+               cg_tol=1e-14):
         """hyteg::MinResSolver< P2P1StokesEpsilonOperator >; preconditioner "identity", "pressure" (StokesPressureBlockPreconditioner with
-        the lumped inverse mass operator, the reference's stokesMinResSolver) or "pressure_viscosity" (pressure action
-        x.p = mu .* invLumpedMass .* b.p with mu at the vertex DoFs; needs mu, the viscosity function)"""
-        kinds = {"identity": 0, "pressure": 1, "pressure_viscosity": 2}
+        the lumped inverse mass operator, the reference's stokesMinResSolver), "pressure_viscosity" (pressure action
+        x.p = mu .* invLumpedMass .* b.p with mu at the vertex DoFs; needs mu, the viscosity function), or the block-diagonal ones with a
+        velocity action: "block" (velocity_cycles multigrid V-cycles on the P2 epsilon operator over the levels velocity_min_level (default
+        min_level) .. max_level, the lumped inverse mass on the pressure) and "block_viscosity" (the same with the pressure action of
+        "pressure_viscosity").  Both need mu, the viscosity of the operator.  Their cycle smooths pre = post times with smoother
+        "chebyshev" (of the given order; radii: None = estimated per level at construction, one spectral radius, or one per level) or
+        "jacobi" (relax), and solves the coarsest level by CG to cg_tol: a symmetric positive definite action, as MINRES needs (any other
+        smoother, pre != post or a looser coarse solve raises)."""
+        kinds = {"identity": 0, "pressure": 1, "pressure_viscosity": 2, "block": 3, "block_viscosity": 4}
         if preconditioner not in kinds:
             raise HytegHostError(f"TaylorHoodEpsilonSolver.minres: unknown preconditioner {preconditioner!r}")
         kind = kinds[preconditioner]
-        if kind == 2 and mu is None:
+        if kind in (2, 3, 4) and mu is None:
             raise HytegHostError(f"TaylorHoodEpsilonSolver.minres: the {preconditioner} preconditioner needs mu")
         h = _vp()
+        if kind >= 3:
+            if smoother not in ("chebyshev", "jacobi"):
+                raise HytegHostError("TaylorHoodEpsilonSolver.minres: smoother 'chebyshev' or 'jacobi' (an SOR sweep is not symmetric)")
+            if pre != post:
+                raise HytegHostError("TaylorHoodEpsilonSolver.minres: a symmetric cycle needs pre == post")
+            if cg_tol > 1e-14:
+                raise HytegHostError("TaylorHoodEpsilonSolver.minres: the coarse CG of a MINRES preconditioner runs to 1e-14")
+            keep, ptr, n = (None, None, 0) if radii is None else _radii(radii)
+            vmin = min_level if velocity_min_level is None else int(velocity_min_level)
+            _ck(lib().hyteg_host_th_epsilon_minres_create_block(storage.h, min_level, max_level, int(max_iter), float(rel_tol), int(kind == 4), mu.h,
+                                                                vmin, int(velocity_cycles), {"jacobi": 0, "chebyshev": 1}[smoother], int(order), ptr,
+                                                                n, float(relax), int(pre), int(post), int(cg_max_iter), float(cg_tol), C.byref(h)),
+                "th_epsilon_minres_create_block")
+            return cls(h, keep=(mu,))
         _ck(lib().hyteg_host_th_epsilon_minres_create(storage.h, min_level, max_level, int(max_iter), float(rel_tol), kind,
                                                       mu.h if kind == 2 else None, C.byref(h)), "th_epsilon_minres_create")
         return cls(h, keep=(mu,))

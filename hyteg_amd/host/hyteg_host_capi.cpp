@@ -2290,6 +2290,18 @@ HYTEG_HOST_API int hyteg_host_p2divkgrad_smooth_jac( hh_p2divkgrad_t op, hh_p2fu
 {
    return guarded( [&] { DK2( op ).smooth_jac( F2( dst ), F2( rhs ), F2( src ), relax, (uint_t) level, DoFType( flag ) ); } );
 }
+HYTEG_HOST_API int hyteg_host_p2divkgrad_set_fused( hh_p2divkgrad_t op, int on )
+{
+   return guarded( [&] { DK2( op ).setFused( on != 0 ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_chebyshev_fusable( hh_p2divkgrad_t op, int level, int* fusable )
+{
+   return guarded( [&] { *fusable = DK2( op ).chebyshevFusable( (uint_t) level ) ? 1 : 0; } );
+}
+HYTEG_HOST_API int hyteg_host_p2divkgrad_residual( hh_p2divkgrad_t op, hh_p2function_t x, hh_p2function_t b, hh_p2function_t r, int level, int flag )
+{
+   return guarded( [&] { DK2( op ).residual( F2( x ), F2( b ), F2( r ), (uint_t) level, DoFType( flag ) ); } );
+}
 HYTEG_HOST_API int hyteg_host_p2divkgrad_cg_create( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_p2divkgrad_solver_t preconditioner,
                                                     hh_p2divkgrad_solver_t* out )
 {
@@ -2503,6 +2515,13 @@ struct P2EpsilonStokesSolverH
    std::shared_ptr< P2Function< double > >            mu; // of the viscosity-weighted preconditioner, or null
    std::shared_ptr< Solver< P2EpsilonStokes > >       preconditioner;
    std::shared_ptr< MinResSolver< P2EpsilonStokes > > p;
+   bool                                               smoothsVelocity = false; // its preconditioner reads the velocity operator's inverse diagonals
+   // assembled on first use: the Stokes operator does not assemble them itself (the pressure preconditioners never read them)
+   void prepare( P2EpsilonStokes& op ) const
+   {
+      if ( smoothsVelocity && !op.viscOp.hasInverseDiagonalValues() )
+         op.viscOp.computeInverseDiagonalOperatorValues();
+   }
 };
 P2Epsilon& EP2( hh_p2epsilon_t op )
 {
@@ -2535,6 +2554,24 @@ std::shared_ptr< P2Function< double > > viscosityOf2( const char* who, hh_p2func
    if ( !mu || minL < 0 || maxL < minL )
       throw std::runtime_error( std::string( who ) + ": needs a viscosity function and 0 <= min_level <= max_level" );
    return static_cast< P2FunctionH* >( mu )->p;
+}
+// a multigrid cycle on P2 vector functions: the quadratic P2 transfer on every component, CG on the coarsest level
+std::shared_ptr< Solver< P2Epsilon > > p2EpsilonGmg( hh_storage_t s, std::shared_ptr< Solver< P2Epsilon > > smoother, int minL, int maxL, int pre, int post,
+                                                     int wcycle, int cgMaxIter, double cgTol )
+{
+   return makeGmg< P2Epsilon, P2toP2QuadraticVectorRestriction, P2toP2QuadraticVectorProlongation >(
+       SP( s ), smoother, cgCoarse< P2Epsilon >( SP( s ), minL, cgMaxIter, cgTol ), minL, maxL, pre, post, 0, cycleOf( wcycle ) );
+}
+// chebyshev::estimateRadius from a start vector of incommensurate waves (components along every eigenvector)
+double p2EpsilonRadius( const P2Epsilon& op, uint_t level, uint_t iterations )
+{
+   auto                       storage = op.getStorage();
+   P2VectorFunction< double > x( "p2epsilon_radius_x", storage, level, level ), tmp( "p2epsilon_radius_tmp", storage, level, level );
+   x.interpolate( { []( const Point3D& q ) { return std::sin( 7.3 * q[0] + 3.1 * q[1] + 1.7 * q[2] + 0.4 ); },
+                    []( const Point3D& q ) { return std::cos( 2.9 * q[0] - 6.1 * q[1] + 4.3 * q[2] ); },
+                    []( const Point3D& q ) { return std::sin( 5.3 * q[0] * q[1] - 3.7 * q[2] + 1.1 ); } },
+                  level, All );
+   return chebyshev::estimateRadius( op, level, iterations, storage, x, tmp );
 }
 } // namespace
 HYTEG_HOST_API int hyteg_host_p2epsilon_create( hh_storage_t s, int minL, int maxL, hh_p2function_t mu, hh_p2epsilon_t* out )
@@ -2580,6 +2617,19 @@ HYTEG_HOST_API int hyteg_host_p2epsilon_smooth_jac( hh_p2epsilon_t op, const hh_
 {
    return guarded( [&] { EP2( op ).smooth_jac( vectorOf2( dst ), vectorOf2( rhs ), vectorOf2( src ), relax, (uint_t) level, DoFType( flag ) ); } );
 }
+HYTEG_HOST_API int hyteg_host_p2epsilon_set_fused( hh_p2epsilon_t op, int on )
+{
+   return guarded( [&] { EP2( op ).setFused( on != 0 ); } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_chebyshev_fusable( hh_p2epsilon_t op, int level, int* fusable )
+{
+   return guarded( [&] { *fusable = EP2( op ).chebyshevFusable( (uint_t) level ) ? 1 : 0; } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_residual( hh_p2epsilon_t op, const hh_p2function_t* x, const hh_p2function_t* b, const hh_p2function_t* r, int level,
+                                                  int flag )
+{
+   return guarded( [&] { EP2( op ).residual( vectorOf2( x ), vectorOf2( b ), vectorOf2( r ), (uint_t) level, DoFType( flag ) ); } );
+}
 HYTEG_HOST_API int hyteg_host_p2epsilon_cg_create( hh_storage_t s, int minL, int maxL, int maxIter, double tol, hh_p2epsilon_solver_t preconditioner,
                                                    hh_p2epsilon_solver_t* out )
 {
@@ -2605,23 +2655,31 @@ HYTEG_HOST_API int hyteg_host_p2epsilon_smoother_create( hh_storage_t s, int min
          throw std::runtime_error( "p2epsilon_smoother_create: smoother 0 (weighted Jacobi) or -1 (identity); the operator has no SOR sweep" );
    } );
 }
-// chebyshev::estimateRadius from a start vector of incommensurate waves (components along every eigenvector)
 HYTEG_HOST_API int hyteg_host_p2epsilon_chebyshev_estimate_radius( hh_p2epsilon_t op, int level, int maxIter, double* radius )
 {
-   return guarded( [&] {
-      auto                       storage = EP2( op ).getStorage();
-      P2VectorFunction< double > x( "p2epsilon_radius_x", storage, (uint_t) level, (uint_t) level ), tmp( "p2epsilon_radius_tmp", storage, (uint_t) level, (uint_t) level );
-      x.interpolate( { []( const Point3D& q ) { return std::sin( 7.3 * q[0] + 3.1 * q[1] + 1.7 * q[2] + 0.4 ); },
-                       []( const Point3D& q ) { return std::cos( 2.9 * q[0] - 6.1 * q[1] + 4.3 * q[2] ); },
-                       []( const Point3D& q ) { return std::sin( 5.3 * q[0] * q[1] - 3.7 * q[2] + 1.1 ); } },
-                     (uint_t) level, All );
-      *radius = chebyshev::estimateRadius( EP2( op ), (uint_t) level, (uint_t) maxIter, storage, x, tmp );
-   } );
+   return guarded( [&] { *radius = p2EpsilonRadius( EP2( op ), (uint_t) level, (uint_t) maxIter ); } );
 }
 HYTEG_HOST_API int hyteg_host_p2epsilon_chebyshev_create( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
                                                           double lower, hh_p2epsilon_solver_t* out )
 {
    return guarded( [&] { *out = new P2EpsilonSolverH{ makeChebyshev< P2Epsilon >( s, minL, maxL, order, radii, nRadii, upper, lower ) }; } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_gmg_create( hh_storage_t s, int minL, int maxL, double relax, int pre, int post, int wcycle, int cgMaxIter,
+                                                    double cgTol, hh_p2epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      std::shared_ptr< Solver< P2Epsilon > > sm = std::make_shared< WeightedJacobiSmoother< P2Epsilon > >( SP( s ), (uint_t) minL, (uint_t) maxL, relax );
+      *out = new P2EpsilonSolverH{ p2EpsilonGmg( s, sm, minL, maxL, pre, post, wcycle, cgMaxIter, cgTol ) };
+   } );
+}
+HYTEG_HOST_API int hyteg_host_p2epsilon_gmg_create_chebyshev( hh_storage_t s, int minL, int maxL, int order, const double* radii, int nRadii, double upper,
+                                                              double lower, int pre, int post, int wcycle, int cgMaxIter, double cgTol,
+                                                              hh_p2epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      *out = new P2EpsilonSolverH{
+          p2EpsilonGmg( s, makeChebyshev< P2Epsilon >( s, minL, maxL, order, radii, nRadii, upper, lower ), minL, maxL, pre, post, wcycle, cgMaxIter, cgTol ) };
+   } );
 }
 HYTEG_HOST_API int hyteg_host_p2epsilon_solver_solve( hh_p2epsilon_solver_t solver, hh_p2epsilon_t op, const hh_p2function_t* x, const hh_p2function_t* b,
                                                       int level )
@@ -2680,14 +2738,75 @@ HYTEG_HOST_API int hyteg_host_th_epsilon_minres_create( hh_storage_t s, int minL
       *out = h.release();
    } );
 }
+// MinResSolver preconditioned with StokesVectorBlockDiagonalPreconditioner: velocityCycles multigrid V-cycles on the P2 epsilon operator
+// (smoother 0 weighted Jacobi( relax ), 1 Chebyshev( order; radii: none = estimated per level here, one, or one per level ); pre = post
+// steps, CG on the coarsest level, levels velocityMinL .. maxL) and the lumped inverse mass on the pressure, weighted with mu at the vertex
+// DoFs if viscosityWeighted.  mu: the viscosity of the operator the solver will be used with (the radii are estimated on an operator
+// built from it).
+HYTEG_HOST_API int hyteg_host_th_epsilon_minres_create_block( hh_storage_t s, int minL, int maxL, int max_iter, double rel_tol, int viscosityWeighted,
+                                                              hh_p2function_t mu, int velocityMinL, int velocityCycles, int smoother, int order,
+                                                              const double* radii, int nRadii, double relax, int pre, int post, int cgMaxIter,
+                                                              double cgTol, hh_th_epsilon_solver_t* out )
+{
+   return guarded( [&] {
+      const char* who     = "th_epsilon_minres_create_block";
+      auto        storage = SP( s );
+      auto        h       = std::make_unique< P2EpsilonStokesSolverH >();
+      // MINRES needs a symmetric positive definite preconditioner
+      if ( smoother != 0 && smoother != 1 )
+         throw std::runtime_error( std::string( who ) + ": smoother 0 (weighted Jacobi) or 1 (Chebyshev); an SOR sweep is not symmetric" );
+      if ( pre != post || pre < 1 )
+         throw std::runtime_error( std::string( who ) + ": a symmetric cycle needs pre = post >= 1 smoothing steps" );
+      if ( velocityCycles < 1 )
+         throw std::runtime_error( std::string( who ) + ": velocity_cycles >= 1" );
+      if ( velocityMinL < minL || velocityMinL > maxL )
+         throw std::runtime_error( std::string( who ) + ": min_level <= velocity_min_level <= max_level" );
+      h->mu = viscosityOf2( who, mu, minL, maxL );
+      std::shared_ptr< Solver< P2Epsilon > > sm;
+      if ( smoother == 0 )
+         sm = std::make_shared< WeightedJacobiSmoother< P2Epsilon > >( storage, (uint_t) velocityMinL, (uint_t) maxL, relax );
+      else
+      {
+         std::vector< double > rho( radii, radii + ( radii ? nRadii : 0 ) );
+         if ( rho.empty() )
+         {
+            P2Epsilon probe( storage, (uint_t) velocityMinL, (uint_t) maxL, *h->mu );
+            probe.computeInverseDiagonalOperatorValues();
+            for ( int l = velocityMinL; l <= maxL; ++l )
+               rho.push_back( p2EpsilonRadius( probe, (uint_t) l, 20 ) );
+         }
+         sm = makeChebyshev< P2Epsilon >( s, velocityMinL, maxL, order, rho.data(), (int) rho.size(), 1.2, 0.3 );
+      }
+      auto velocity      = p2EpsilonGmg( s, sm, velocityMinL, maxL, pre, post, 0, cgMaxIter, cgTol );
+      h->smoothsVelocity = true;
+      if ( viscosityWeighted )
+         h->preconditioner =
+             std::make_shared< StokesVectorBlockDiagonalPreconditioner< P2EpsilonStokes, Solver< P2Epsilon >, P1ViscosityWeightedLumpedInvMassOperator > >(
+                 velocity,
+                 std::make_shared< P1ViscosityWeightedLumpedInvMassOperator >( storage, (uint_t) minL, (uint_t) maxL, h->mu->getVertexDoFFunction() ),
+                 (uint_t) velocityCycles );
+      else
+         h->preconditioner = std::make_shared< StokesVectorBlockDiagonalPreconditioner< P2EpsilonStokes, Solver< P2Epsilon >, P1LumpedInvMassOperator > >(
+             velocity, std::make_shared< P1LumpedInvMassOperator >( storage, (uint_t) minL, (uint_t) maxL ), (uint_t) velocityCycles );
+      h->p = std::make_shared< MinResSolver< P2EpsilonStokes > >( storage, (uint_t) minL, (uint_t) maxL, (uint_t) max_iter, rel_tol, 1e-16,
+                                                                  h->preconditioner );
+      *out = h.release();
+   } );
+}
 HYTEG_HOST_API int hyteg_host_th_epsilon_minres_solve( hh_th_epsilon_solver_t solver, hh_th_epsilon_t op, hh_th_function_t x, hh_th_function_t b, int level )
 {
-   return guarded( [&] { EPSS2( solver ).p->solve( EPS2( op ), TH::fn( x ), TH::fn( b ), (uint_t) level ); } );
+   return guarded( [&] {
+      EPSS2( solver ).prepare( EPS2( op ) );
+      EPSS2( solver ).p->solve( EPS2( op ), TH::fn( x ), TH::fn( b ), (uint_t) level );
+   } );
 }
 HYTEG_HOST_API int hyteg_host_th_epsilon_minres_precondition( hh_th_epsilon_solver_t solver, hh_th_epsilon_t op, hh_th_function_t x, hh_th_function_t b,
                                                               int level )
 {
-   return guarded( [&] { EPSS2( solver ).preconditioner->solve( EPS2( op ), TH::fn( x ), TH::fn( b ), (uint_t) level ); } );
+   return guarded( [&] {
+      EPSS2( solver ).prepare( EPS2( op ) );
+      EPSS2( solver ).preconditioner->solve( EPS2( op ), TH::fn( x ), TH::fn( b ), (uint_t) level );
+   } );
 }
 HYTEG_HOST_API int hyteg_host_th_epsilon_minres_iterations( hh_th_epsilon_solver_t solver, int* iterations )
 {

@@ -189,25 +189,29 @@ class P1Function
    }
 
    // ---- assign / add / multElementwise ( VertexDoFFunction.cpp:1130-1221, :1408-1484, :1487-1563 ) ----
+   // `keep`: further restriction to point classes (HYTEG_HIP_MASK_INNER: inside the macro-cells, HYTEG_HIP_MASK_SHELL: on shared primitives)
    void assign( const std::vector< ValueType >&                                           scalars,
                 const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions,
                 uint_t                                                                    level,
-                const Selection&                                                          flag = All ) const
+                const Selection&                                                          flag = All,
+                unsigned                                                                  keep = HYTEG_HIP_MASK_ALL ) const
    {
-      vectorOp( 0, scalars, functions, level, flag );
+      vectorOp( 0, scalars, functions, level, flag, keep );
    }
    void add( const std::vector< ValueType >&                                           scalars,
              const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions,
              uint_t                                                                    level,
-             const Selection&                                                          flag = All ) const
+             const Selection&                                                          flag = All,
+             unsigned                                                                  keep = HYTEG_HIP_MASK_ALL ) const
    {
-      vectorOp( 1, scalars, functions, level, flag );
+      vectorOp( 1, scalars, functions, level, flag, keep );
    }
    void multElementwise( const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions,
                          uint_t                                                                    level,
-                         const Selection&                                                          flag = All ) const
+                         const Selection&                                                          flag = All,
+                         unsigned                                                                  keep = HYTEG_HIP_MASK_ALL ) const
    {
-      vectorOp( 2, {}, functions, level, flag );
+      vectorOp( 2, {}, functions, level, flag, keep );
    }
    void setToZero( uint_t level ) const { interpolate( ValueType( 0 ), level, All ); }
 
@@ -462,7 +466,8 @@ class P1Function
                   const std::vector< ValueType >&                                           scalars,
                   const std::vector< std::reference_wrapper< const P1Function< ValueType > > >& functions,
                   uint_t                                                                    level,
-                  const Selection&                                                          flagIn ) const
+                  const Selection&                                                          flagIn,
+                  unsigned                                                                  keep = HYTEG_HIP_MASK_ALL ) const
    {
       const Selection flag = effectiveFlag( flagIn ); // the function's boundary condition decides what `Inner` means
       static const char* kOpNames[3] = { "Assign", "Add", "Multiply elementwise" };
@@ -471,7 +476,7 @@ class P1Function
          throw std::runtime_error( "P1Function::assign/add/multElementwise: bad number of functions or scalars" );
       if ( storage_->useBatch( level ) )
       {
-         const auto masks = storage_->masksFor( flag );
+         const auto masks = storage_->masksFor( flag, false, keep );
          storage_->forCellChunks( [&]( int first, int count ) {
             const auto             dst = cellPointers( level, first, count );
             std::vector< double* > srcs; // [function][cell]
@@ -489,7 +494,7 @@ class P1Function
          for ( uint_t k = 0; k < functions.size(); ++k )
             srcs[k] = functions[k].get().getCellPointer( c, level );
          hipCheck( hyteg_hip_p1_vector_cell_masked( op, getCellPointer( c, level ), (int) functions.size(), srcs,
-                                                    op == 2 ? nullptr : scalars.data(), (int) level, storage_->maskFor( cell, flag ),
+                                                    op == 2 ? nullptr : scalars.data(), (int) level, storage_->maskFor( cell, flag ) & keep,
                                                     storage_->stream() ),
                    "P1Function vector op" );
       } );

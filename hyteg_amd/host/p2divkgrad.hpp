@@ -6,10 +6,12 @@
 // side with.  The operator has the interface and the schedules of P2ElementwiseOperator (p2operator.hpp): per cell the C-ABI seam
 // hyteg_hip_p2_elementwise_divkgrad_apply_cell_kinds, then the additive exchange of the shares of the shared DoFs.  The operator at
 // level l reads k at level l: the caller interpolates k on every level it uses, as the reference test does.  No smooth_sor, no constant
-// stencils, no fused steps: the solver templates run their composed sequences.
+// stencils.  The operator offers what GeometricMultigridSolver and ChebyshevSmoother look for (residual, chebyshevStart / Step /
+// Finish) and a fused smooth_jac: one launch per step and cell (hyteg_hip_p2_elementwise_divkgrad_*_cell, schedule: p2varcoefsteps.hpp).
 #pragma once
 
 #include "p2operator.hpp"
+#include "p2varcoefsteps.hpp"
 
 namespace hyteg {
 
@@ -84,6 +86,10 @@ class P2ElementwiseDivKGrad
    const P2Function< double >&         getCoefficient() const { return k_; }
    uint64_t                            uid() const { return uid_; }
 
+   // the fused Jacobi, residual and Chebyshev entries (default), or the composed passes everywhere (tests, measurements)
+   void setFused( bool on ) { fused_ = on; }
+   bool getFused() const { return fused_; }
+
    // Operator::apply = gemv( 1, src, updateType == Replace ? 0 : 1, dst ), as P2ElementwiseOperator
    void apply( const P2Function< double >& src, const P2Function< double >& dst, uint_t level, const Selection& flag, UpdateType updateType = Replace ) const
    {
@@ -149,21 +155,113 @@ class P2ElementwiseDivKGrad
 
    // P2ElementwiseOperator::smooth_jac (P2ElementwiseOperator.cpp:344-374), statement by statement:
    //   dst = A src;  dst = rhs - dst;  dst = D^-1 dst;  dst = src + relax dst
+   // Fused: the four statements in the epilogue of the apply kernels (hyteg_hip_p2_elementwise_divkgrad_jacobi_cell)
    void smooth_jac( const P2Function< double >& dst, const P2Function< double >& rhs, const P2Function< double >& src, double relax, uint_t level,
                     const Selection& flag ) const
    {
       if ( &dst == &src )
          throw std::runtime_error( "P2ElementwiseDivKGrad::smooth_jac: src and dst must differ" );
+      const auto& invDiag = *getInverseDiagonalValues();
+      if ( fused_ && &dst != &rhs && &dst != &invDiag && &dst != &k_ )
+      {
+         step( p2varcoef::Step::Jacobi, { { &dst }, { &src }, { &rhs }, { &invDiag }, { nullptr } }, dst.effectiveFlag( flag ), level, relax, 0.0, false );
+         return;
+      }
       apply( src, dst, level, flag );
       dst.assign( { 1.0, -1.0 }, { rhs, dst }, level, flag );
-      dst.multElementwise( { *getInverseDiagonalValues(), dst }, level, flag );
+      dst.multElementwise( { invDiag, dst }, level, flag );
       dst.assign( { 1.0, relax }, { src, dst }, level, flag );
    }
 
- private:
-   void launch( double alpha, const P2Function< double >& src, const P2Function< double >& dst, uint_t level, const Selection& flag, int update ) const
+   // r = b - A x as the multigrid cycle writes it (GeometricMultigridSolver.hpp:240-246: apply, then assign).  Fused: one launch per cell
+   // (hyteg_hip_p2_elementwise_divkgrad_residual_cell); composed where r is x or b, and with setFused( false )
+   void residual( const P2Function< double >& x, const P2Function< double >& b, const P2Function< double >& r, uint_t level, const Selection& flag ) const
    {
-      const std::vector< unsigned > masks = storage_->masksFor( flag, false, HYTEG_HIP_MASK_ALL );
+      if ( !fused_ || &r == &x || &r == &b )
+      {
+         apply( x, r, level, flag );
+         r.assign( { 1.0, -1.0 }, { b, r }, level, flag );
+         return;
+      }
+      step( p2varcoef::Step::Residual, { { &r }, { &x }, { &b }, { nullptr }, { nullptr } }, r.effectiveFlag( flag ), level, 0.0, 0.0, false );
+   }
+
+   // ---- the steps of ChebyshevSmoother::solve (ChebyshevSmoother.hpp:165-212) with the semantics of P1ConstantOperator's
+   // (p1operator.hpp): one launch per step and cell (hyteg_hip_p2_elementwise_divkgrad_chebyshev_*_cell).  Where chebyshevFusable is
+   // false the smoother runs its generic sequence.
+   bool chebyshevFusable( uint_t ) const { return fused_; }
+   // t = invDiag .* ( b - A x ); on the shell of several cells also x += c0 t.  Elsewhere x is this launch's source: its update is carried
+   // out by the following chebyshevStep( ..., hasPrev = true ) or by chebyshevFinish
+   void chebyshevStart( const P2Function< double >& t, const P2Function< double >& b, const P2Function< double >& x, double c0, uint_t level,
+                        const Selection& flag ) const
+   {
+      const auto& invDiag = *getInverseDiagonalValues();
+      checkOutput( "chebyshevStart", t, { &b, &x, &invDiag } );
+      step( p2varcoef::Step::ChebStart, { { &t }, { &x }, { &b }, { &invDiag }, { &x } }, x.effectiveFlag( flag ), level, c0, 0.0, false );
+   }
+   // tOut = invDiag .* ( A tIn ); x = ( x + cPrev tIn ) + cCur tOut (first term only if hasPrev: the update chebyshevStart left open); on the
+   // shell of several cells x += cCur tOut
+   void chebyshevStep( const P2Function< double >& tOut, const P2Function< double >& x, const P2Function< double >& tIn, double cPrev, double cCur,
+                       bool hasPrev, uint_t level, const Selection& flag ) const
+   {
+      const auto& invDiag = *getInverseDiagonalValues();
+      checkOutput( "chebyshevStep", tOut, { &x, &tIn, &invDiag } );
+      checkOutput( "chebyshevStep", x, { &tIn, &invDiag } );
+      step( p2varcoef::Step::ChebStep, { { &tOut }, { &tIn }, { nullptr }, { &invDiag }, { &x } }, x.effectiveFlag( flag ), level, cCur, cPrev, hasPrev );
+   }
+   // x += c t where the start deferred it: closes a smoother call of order 1 (no step follows the start)
+   void chebyshevFinish( const P2Function< double >& x, const P2Function< double >& t, double c, uint_t level, const Selection& flag ) const
+   {
+      p2varcoef::chebyshevFinish< 1 >( storage_, { &x }, { &t }, { x.effectiveFlag( flag ) }, c, level );
+   }
+
+ private:
+   void checkOutput( const char* who, const P2Function< double >& out, std::initializer_list< const P2Function< double >* > inputs ) const
+   {
+      bool bad = &out == &k_;
+      for ( const P2Function< double >* f : inputs )
+         bad = bad || &out == f;
+      if ( bad )
+         throw std::runtime_error( std::string( "P2ElementwiseDivKGrad::" ) + who + ": an output must differ from the inputs and from k" );
+   }
+   // one fused step (p2varcoefsteps.hpp): a = relax, c0 or cCur
+   void step( p2varcoef::Step what, const p2varcoef::Operands< 1 >& f, const Selection& flag, uint_t level, double a, double cPrev, bool hasPrev ) const
+   {
+      p2varcoef::fusedStep< 1 >(
+          storage_, what, f, { flag }, level, a, [&] { launch( 1.0, *f.src[0], *f.out[0], level, flag, HYTEG_HIP_REPLACE, HYTEG_HIP_MASK_SHELL ); },
+          [&]( uint_t c, const std::array< unsigned, 1 >& m ) {
+             const auto v = [&]( const P2Function< double >* g ) -> double* { return g ? g->getVertexDoFFunction().getCellPointer( c, level ) : nullptr; };
+             const auto e = [&]( const P2Function< double >* g ) -> double* { return g ? g->getEdgeCellPointer( c, level ) : nullptr; };
+             const double *kv = v( &k_ ), *ke = e( &k_ ), *geo = geometry_.at( level ).at( c ).data();
+             const int     l = (int) level;
+             hyteg_hip_stream_t s  = storage_->stream();
+             int         rc = 0;
+             switch ( what )
+             {
+             case p2varcoef::Step::Residual:
+                rc = hyteg_hip_p2_elementwise_divkgrad_residual_cell( v( f.out[0] ), e( f.out[0] ), v( f.src[0] ), e( f.src[0] ), v( f.rhs[0] ), e( f.rhs[0] ), kv, ke,
+                                                                      l, geo, m[0], 0xFFu, s );
+                break;
+             case p2varcoef::Step::Jacobi:
+                rc = hyteg_hip_p2_elementwise_divkgrad_jacobi_cell( v( f.out[0] ), e( f.out[0] ), v( f.src[0] ), e( f.src[0] ), v( f.rhs[0] ), e( f.rhs[0] ),
+                                                                    v( f.inv[0] ), e( f.inv[0] ), kv, ke, l, geo, a, m[0], 0xFFu, s );
+                break;
+             case p2varcoef::Step::ChebStart:
+                rc = hyteg_hip_p2_elementwise_divkgrad_chebyshev_start_cell( v( f.out[0] ), e( f.out[0] ), v( f.src[0] ), e( f.src[0] ), v( f.rhs[0] ),
+                                                                             e( f.rhs[0] ), v( f.inv[0] ), e( f.inv[0] ), kv, ke, l, geo, m[0], 0xFFu, s );
+                break;
+             case p2varcoef::Step::ChebStep:
+                rc = hyteg_hip_p2_elementwise_divkgrad_chebyshev_step_cell( v( f.out[0] ), e( f.out[0] ), v( f.x[0] ), e( f.x[0] ), v( f.src[0] ), e( f.src[0] ),
+                                                                            v( f.inv[0] ), e( f.inv[0] ), kv, ke, l, geo, cPrev, a, hasPrev ? 1 : 0, m[0], 0xFFu, s );
+                break;
+             }
+             hipCheck( rc, "P2ElementwiseDivKGrad: fused step" );
+          } );
+   }
+   void launch( double alpha, const P2Function< double >& src, const P2Function< double >& dst, uint_t level, const Selection& flag, int update,
+                unsigned keep = HYTEG_HIP_MASK_ALL ) const
+   {
+      const std::vector< unsigned > masks = storage_->masksFor( flag, false, keep );
       for ( uint_t c = 0; c < storage_->getNumberOfLocalCells(); ++c )
          hipCheck( hyteg_hip_p2_elementwise_divkgrad_apply_cell_kinds(
                        dst.getVertexDoFFunction().getCellPointer( c, level ), dst.getEdgeCellPointer( c, level ),
@@ -179,6 +277,7 @@ class P2ElementwiseDivKGrad
    std::map< uint_t, std::vector< std::array< double, 60 > > >  geometry_; // per level and local cell
    uint64_t                                                     uid_ = nextUid();
    std::shared_ptr< P2Function< double > >                      invDiag_;
+   bool                                                         fused_ = true;
 };
 
 } // namespace operatorgeneration

@@ -346,11 +346,11 @@ class P2Function
       if ( kinds & 1u )
       {
          if ( op == 0 )
-            vertexDoFFunction_.assign( scalars, vs, level, flag );
+            vertexDoFFunction_.assign( scalars, vs, level, flag, keep );
          else if ( op == 1 )
-            vertexDoFFunction_.add( scalars, vs, level, flag );
+            vertexDoFFunction_.add( scalars, vs, level, flag, keep );
          else
-            vertexDoFFunction_.multElementwise( vs, level, flag );
+            vertexDoFFunction_.multElementwise( vs, level, flag, keep );
       }
       if ( ( kinds & 0xFEu ) == 0 )
          return;

@@ -1373,6 +1373,75 @@ HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_diagonal_cell( double*      
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level( int level );
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_max_level( void );
 
+/* b-4 (P2), fused modes: in the kernels of hyteg_hip_p2_elementwise_divkgrad_apply_cell_kinds every DoF holds its complete ( A src )
+ * at the store; these entries replace the store by the arithmetic that follows the apply in the reference, read at the DoF's own index:
+ *   residual          dst = rhs - A src: the apply and the assign of GeometricMultigridSolver::solveRecursively
+ *                     (src/hyteg/solvers/GeometricMultigridSolver.hpp:240-246) on operatorgeneration::P2ElementwiseDivKGrad
+ *   jacobi            dst = src + relax invdiag ( rhs - A src ): P2ElementwiseOperator::smooth_jac
+ *                     (src/hyteg/elementwiseoperators/P2ElementwiseOperator.cpp:344-374) as its four statements (the last
+ *                     multiply-add may contract to an FMA)
+ *   chebyshev_start   t_out = invdiag ( rhs - A x ) and
+ *   chebyshev_step    t_out = invdiag ( A t_in ), x = ( x + c_prev t_in ) + c_cur t_out (the first summand only if has_prev != 0): the
+ *                     steps of ChebyshevSmoother::solve (src/hyteg/solvers/ChebyshevSmoother.hpp:165-212) with the semantics of
+ *                     hyteg_hip_p1_chebyshev_start_cell / hyteg_hip_p1_chebyshev_step_cell, the deferred x += c_0 t after a start
+ *                     included; x is read and written at the DoF's own index only and is not a source of the operator.
+ * Arrays, level, geometry, mask and kind_mask as in apply_cell_kinds (alpha = 1, Replace); invdiag: the inverse diagonal's arrays.  A
+ * DoF outside mask or kind_mask is written in no output array (t_out and x alike).  The shell / inner split and
+ * hyteg_hip_p2_elementwise_divkgrad_set_inner_min_level act as in apply_cell_kinds; the _gather entries run the gather form on every DoF
+ * (the second implementation).  EINVAL before any GPU work: a null array, a level outside 0..8, a written array (dst, t_out, x) that is
+ * another array of the call, any array that is a k array.  An empty mask or kind_mask returns OK. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_residual_cell( double* dst_vertex, double* dst_edge, const double* src_vertex,
+                                                                   const double* src_edge, const double* rhs_vertex, const double* rhs_edge,
+                                                                   const double* k_vertex, const double* k_edge, int level,
+                                                                   const double* geometry /* 60, host */, unsigned mask, unsigned kind_mask,
+                                                                   hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_residual_cell_gather( double* dst_vertex, double* dst_edge, const double* src_vertex,
+                                                                          const double* src_edge, const double* rhs_vertex,
+                                                                          const double* rhs_edge, const double* k_vertex, const double* k_edge,
+                                                                          int level, const double* geometry /* 60, host */, unsigned mask,
+                                                                          unsigned kind_mask, hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_jacobi_cell( double* dst_vertex, double* dst_edge, const double* src_vertex,
+                                                                 const double* src_edge, const double* rhs_vertex, const double* rhs_edge,
+                                                                 const double* invdiag_vertex, const double* invdiag_edge,
+                                                                 const double* k_vertex, const double* k_edge, int level,
+                                                                 const double* geometry /* 60, host */, double relax, unsigned mask,
+                                                                 unsigned kind_mask, hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_jacobi_cell_gather( double* dst_vertex, double* dst_edge, const double* src_vertex,
+                                                                        const double* src_edge, const double* rhs_vertex,
+                                                                        const double* rhs_edge, const double* invdiag_vertex,
+                                                                        const double* invdiag_edge, const double* k_vertex,
+                                                                        const double* k_edge, int level, const double* geometry /* 60, host */,
+                                                                        double relax, unsigned mask, unsigned kind_mask,
+                                                                        hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_chebyshev_start_cell( double* t_out_vertex, double* t_out_edge, const double* x_vertex,
+                                                                          const double* x_edge, const double* rhs_vertex,
+                                                                          const double* rhs_edge, const double* invdiag_vertex,
+                                                                          const double* invdiag_edge, const double* k_vertex,
+                                                                          const double* k_edge, int level, const double* geometry /* 60, host */,
+                                                                          unsigned mask, unsigned kind_mask, hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_chebyshev_start_cell_gather( double* t_out_vertex, double* t_out_edge,
+                                                                                 const double* x_vertex, const double* x_edge,
+                                                                                 const double* rhs_vertex, const double* rhs_edge,
+                                                                                 const double* invdiag_vertex, const double* invdiag_edge,
+                                                                                 const double* k_vertex, const double* k_edge, int level,
+                                                                                 const double* geometry /* 60, host */, unsigned mask,
+                                                                                 unsigned kind_mask, hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_chebyshev_step_cell( double* t_out_vertex, double* t_out_edge, double* x_vertex,
+                                                                         double* x_edge, const double* t_in_vertex, const double* t_in_edge,
+                                                                         const double* invdiag_vertex, const double* invdiag_edge,
+                                                                         const double* k_vertex, const double* k_edge, int level,
+                                                                         const double* geometry /* 60, host */, double c_prev, double c_cur,
+                                                                         int has_prev, unsigned mask, unsigned kind_mask,
+                                                                         hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_divkgrad_chebyshev_step_cell_gather( double* t_out_vertex, double* t_out_edge, double* x_vertex,
+                                                                                double* x_edge, const double* t_in_vertex,
+                                                                                const double* t_in_edge, const double* invdiag_vertex,
+                                                                                const double* invdiag_edge, const double* k_vertex,
+                                                                                const double* k_edge, int level,
+                                                                                const double* geometry /* 60, host */, double c_prev,
+                                                                                double c_cur, int has_prev, unsigned mask, unsigned kind_mask,
+                                                                                hyteg_hip_stream_t stream );
+
 /* ---- b-4 (P2 epsilon): variable-viscosity epsilon operator -div( 2 mu eps(u) ) on P2 with a P2 viscosity -----------------------
  * Replaces, in ONE pass over the three velocity components, the nine P2 elementwise block applies of
  * operatorgeneration::P2ViscousBlockEpsilonOperator::apply (module hyteg_operators; the velocity block of
@@ -1438,6 +1507,101 @@ HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_diagonal_cell( double* const*
  * hyteg_hip_p2_elementwise_epsilon_max_level: the largest level of these entries. */
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_set_inner_min_level( int level );
 HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_max_level( void );
+
+/* b-4 (P2 epsilon), fused modes: in the kernels of hyteg_hip_p2_elementwise_epsilon_apply_cell_kinds every DoF holds the complete
+ * ( A src )_j of its three components at the store; these entries replace the store by the arithmetic that follows the apply in the
+ * reference, read at the DoF's own index:
+ *   residual          dst = rhs - A src: the apply and the assign of GeometricMultigridSolver::solveRecursively
+ *                     (src/hyteg/solvers/GeometricMultigridSolver.hpp:240-246) on operatorgeneration::P2ViscousBlockEpsilonOperator
+ *   jacobi            dst = src + relax invdiag ( rhs - A src ): P2ElementwiseOperator::smooth_jac
+ *                     (src/hyteg/elementwiseoperators/P2ElementwiseOperator.cpp:344-374) per component as its four statements (the
+ *                     last multiply-add may contract to an FMA)
+ *   chebyshev_start   t_out = invdiag ( rhs - A x ) and
+ *   chebyshev_step    t_out = invdiag ( A t_in ), x = ( x + c_prev t_in ) + c_cur t_out (the first summand only if has_prev != 0): the
+ *                     steps of ChebyshevSmoother::solve (src/hyteg/solvers/ChebyshevSmoother.hpp:165-212) with the semantics of
+ *                     hyteg_hip_p1_chebyshev_start_cell / hyteg_hip_p1_chebyshev_step_cell, the deferred x += c_0 t after a start
+ *                     included; x is read and written at the DoF's own index only and is not a source of the operator.
+ * Every array argument but mu is a HOST array of three device pointers; level, geometry, mask[3] and kind_mask as in apply_cell_kinds
+ * (alpha = 1, Replace); invdiag: the inverse diagonals of the three diagonal blocks.  mask[i] = 0 switches component i off; a DoF that
+ * mask[i] or kind_mask excludes is written in no output array of component i (t_out and x alike).  The shell / inner split and
+ * hyteg_hip_p2_elementwise_epsilon_set_inner_min_level act as in apply_cell_kinds; the _gather entries run the gather form on every DoF
+ * (the second implementation).  EINVAL before any GPU work: a null array, a level outside 0..8, a written array (dst, t_out, x) that is
+ * another array of the call, any array that is a mu array.  Empty masks or an empty kind_mask return OK. */
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_residual_cell( double* const* dst_vertex /* 3 */, double* const* dst_edge /* 3 */,
+                                                                  const double* const* src_vertex /* 3 */, const double* const* src_edge /* 3 */,
+                                                                  const double* const* rhs_vertex /* 3 */, const double* const* rhs_edge /* 3 */,
+                                                                  const double* mu_vertex, const double* mu_edge, const unsigned* mask /* 3 */,
+                                                                  int level, const double* geometry /* 72, host */, unsigned kind_mask,
+                                                                  hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_residual_cell_gather( double* const* dst_vertex /* 3 */, double* const* dst_edge /* 3 */,
+                                                                         const double* const* src_vertex /* 3 */,
+                                                                         const double* const* src_edge /* 3 */,
+                                                                         const double* const* rhs_vertex /* 3 */,
+                                                                         const double* const* rhs_edge /* 3 */, const double* mu_vertex,
+                                                                         const double* mu_edge, const unsigned* mask /* 3 */, int level,
+                                                                         const double* geometry /* 72, host */, unsigned kind_mask,
+                                                                         hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_jacobi_cell( double* const* dst_vertex /* 3 */, double* const* dst_edge /* 3 */,
+                                                                const double* const* src_vertex /* 3 */, const double* const* src_edge /* 3 */,
+                                                                const double* const* rhs_vertex /* 3 */, const double* const* rhs_edge /* 3 */,
+                                                                const double* const* invdiag_vertex /* 3 */,
+                                                                const double* const* invdiag_edge /* 3 */, const double* mu_vertex,
+                                                                const double* mu_edge, const unsigned* mask /* 3 */, int level,
+                                                                const double* geometry /* 72, host */, double relax, unsigned kind_mask,
+                                                                hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_jacobi_cell_gather( double* const* dst_vertex /* 3 */, double* const* dst_edge /* 3 */,
+                                                                       const double* const* src_vertex /* 3 */,
+                                                                       const double* const* src_edge /* 3 */,
+                                                                       const double* const* rhs_vertex /* 3 */,
+                                                                       const double* const* rhs_edge /* 3 */,
+                                                                       const double* const* invdiag_vertex /* 3 */,
+                                                                       const double* const* invdiag_edge /* 3 */, const double* mu_vertex,
+                                                                       const double* mu_edge, const unsigned* mask /* 3 */, int level,
+                                                                       const double* geometry /* 72, host */, double relax, unsigned kind_mask,
+                                                                       hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_chebyshev_start_cell( double* const* t_out_vertex /* 3 */, double* const* t_out_edge /* 3 */,
+                                                                         const double* const* x_vertex /* 3 */,
+                                                                         const double* const* x_edge /* 3 */,
+                                                                         const double* const* rhs_vertex /* 3 */,
+                                                                         const double* const* rhs_edge /* 3 */,
+                                                                         const double* const* invdiag_vertex /* 3 */,
+                                                                         const double* const* invdiag_edge /* 3 */, const double* mu_vertex,
+                                                                         const double* mu_edge, const unsigned* mask /* 3 */, int level,
+                                                                         const double* geometry /* 72, host */, unsigned kind_mask,
+                                                                         hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_chebyshev_start_cell_gather( double* const* t_out_vertex /* 3 */,
+                                                                                double* const* t_out_edge /* 3 */,
+                                                                                const double* const* x_vertex /* 3 */,
+                                                                                const double* const* x_edge /* 3 */,
+                                                                                const double* const* rhs_vertex /* 3 */,
+                                                                                const double* const* rhs_edge /* 3 */,
+                                                                                const double* const* invdiag_vertex /* 3 */,
+                                                                                const double* const* invdiag_edge /* 3 */,
+                                                                                const double* mu_vertex, const double* mu_edge,
+                                                                                const unsigned* mask /* 3 */, int level,
+                                                                                const double* geometry /* 72, host */, unsigned kind_mask,
+                                                                                hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_chebyshev_step_cell( double* const* t_out_vertex /* 3 */, double* const* t_out_edge /* 3 */,
+                                                                        double* const* x_vertex /* 3 */, double* const* x_edge /* 3 */,
+                                                                        const double* const* t_in_vertex /* 3 */,
+                                                                        const double* const* t_in_edge /* 3 */,
+                                                                        const double* const* invdiag_vertex /* 3 */,
+                                                                        const double* const* invdiag_edge /* 3 */, const double* mu_vertex,
+                                                                        const double* mu_edge, const unsigned* mask /* 3 */, int level,
+                                                                        const double* geometry /* 72, host */, double c_prev, double c_cur,
+                                                                        int has_prev, unsigned kind_mask, hyteg_hip_stream_t stream );
+HYTEG_HIP_API int hyteg_hip_p2_elementwise_epsilon_chebyshev_step_cell_gather( double* const* t_out_vertex /* 3 */,
+                                                                               double* const* t_out_edge /* 3 */,
+                                                                               double* const* x_vertex /* 3 */, double* const* x_edge /* 3 */,
+                                                                               const double* const* t_in_vertex /* 3 */,
+                                                                               const double* const* t_in_edge /* 3 */,
+                                                                               const double* const* invdiag_vertex /* 3 */,
+                                                                               const double* const* invdiag_edge /* 3 */,
+                                                                               const double* mu_vertex, const double* mu_edge,
+                                                                               const unsigned* mask /* 3 */, int level,
+                                                                               const double* geometry /* 72, host */, double c_prev,
+                                                                               double c_cur, int has_prev, unsigned kind_mask,
+                                                                               hyteg_hip_stream_t stream );
 
 /* ---- b-5: variable-viscosity epsilon operator -div( 2 mu eps(u) ), eps(u) = ( grad u + grad u^T ) / 2 ------------------------
  * Replaces, in ONE pass over the three velocity components, the nine P1ElementwiseOperator::apply calls of

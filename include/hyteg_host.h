@@ -595,6 +595,11 @@ HYTEG_HOST_API int hyteg_host_p2divkgrad_compute_inverse_diagonal( hh_p2divkgrad
 HYTEG_HOST_API int hyteg_host_p2divkgrad_inverse_diagonal_copy( hh_p2divkgrad_t op, hh_p2function_t dst, int level );
 HYTEG_HOST_API int hyteg_host_p2divkgrad_smooth_jac( hh_p2divkgrad_t op, hh_p2function_t dst, hh_p2function_t rhs, hh_p2function_t src, double relax,
                                                      int level, int flag );
+/* setFused: the fused residual / Jacobi / Chebyshev entries of the operator (default on), or the composed passes; residual: r = b - A x
+ * as a multigrid cycle writes it (GeometricMultigridSolver.hpp:240-246) */
+HYTEG_HOST_API int hyteg_host_p2divkgrad_set_fused( hh_p2divkgrad_t op, int on );
+HYTEG_HOST_API int hyteg_host_p2divkgrad_chebyshev_fusable( hh_p2divkgrad_t op, int level, int* fusable ); /* chebyshevFusable( level ) */
+HYTEG_HOST_API int hyteg_host_p2divkgrad_residual( hh_p2divkgrad_t op, hh_p2function_t x, hh_p2function_t b, hh_p2function_t r, int level, int flag );
 HYTEG_HOST_API int hyteg_host_p2divkgrad_cg_create( hh_storage_t s, int min_level, int max_level, int max_iter, double tol,
                                                     hh_p2divkgrad_solver_t preconditioner /* or null */, hh_p2divkgrad_solver_t* out );
 HYTEG_HOST_API int hyteg_host_p2divkgrad_cg_iterations( hh_p2divkgrad_solver_t solver, int* iterations );
@@ -675,6 +680,20 @@ HYTEG_HOST_API int hyteg_host_p2epsilon_compute_inverse_diagonal( hh_p2epsilon_t
 HYTEG_HOST_API int hyteg_host_p2epsilon_inverse_diagonal( hh_p2epsilon_t op, hh_p2function_t* out /* 3 */ );
 HYTEG_HOST_API int hyteg_host_p2epsilon_smooth_jac( hh_p2epsilon_t op, const hh_p2function_t* dst, const hh_p2function_t* rhs, const hh_p2function_t* src,
                                                     double relax, int level, int flag );
+/* setFused: the fused residual / Jacobi / Chebyshev entries of the operator (default on), or the composed passes; residual: r = b - A x
+ * as a multigrid cycle writes it (GeometricMultigridSolver.hpp:240-246), on three component functions each */
+HYTEG_HOST_API int hyteg_host_p2epsilon_set_fused( hh_p2epsilon_t op, int on );
+HYTEG_HOST_API int hyteg_host_p2epsilon_chebyshev_fusable( hh_p2epsilon_t op, int level, int* fusable ); /* chebyshevFusable( level ) */
+HYTEG_HOST_API int hyteg_host_p2epsilon_residual( hh_p2epsilon_t op, const hh_p2function_t* x, const hh_p2function_t* b, const hh_p2function_t* r,
+                                                  int level, int flag );
+/* GeometricMultigridSolver on the operator with the quadratic P2 transfer on every component (P2toP2QuadraticVectorRestriction /
+ * Prolongation), a CG coarse-grid solver and WeightedJacobiSmoother( relax ) or ChebyshevSmoother (fused steps; radii: one spectral
+ * radius, or one per level) as its smoother */
+HYTEG_HOST_API int hyteg_host_p2epsilon_gmg_create( hh_storage_t s, int min_level, int max_level, double relax, int pre, int post, int wcycle,
+                                                    int cg_max_iter, double cg_tol, hh_p2epsilon_solver_t* out );
+HYTEG_HOST_API int hyteg_host_p2epsilon_gmg_create_chebyshev( hh_storage_t s, int min_level, int max_level, int order, const double* radii, int n_radii,
+                                                              double upper, double lower, int pre, int post, int wcycle, int cg_max_iter,
+                                                              double cg_tol, hh_p2epsilon_solver_t* out );
 HYTEG_HOST_API int hyteg_host_p2epsilon_cg_create( hh_storage_t s, int min_level, int max_level, int max_iter, double tol,
                                                    hh_p2epsilon_solver_t preconditioner /* or null */, hh_p2epsilon_solver_t* out );
 HYTEG_HOST_API int hyteg_host_p2epsilon_cg_iterations( hh_p2epsilon_solver_t solver, int* iterations );
@@ -691,6 +710,15 @@ HYTEG_HOST_API int hyteg_host_th_epsilon_destroy( hh_th_epsilon_t op );
 HYTEG_HOST_API int hyteg_host_th_epsilon_apply( hh_th_epsilon_t op, hh_th_function_t src, hh_th_function_t dst, int level, int flag );
 HYTEG_HOST_API int hyteg_host_th_epsilon_minres_create( hh_storage_t s, int min_level, int max_level, int max_iter, double rel_tol, int preconditioner,
                                                         hh_p2function_t mu /* or null */, hh_th_epsilon_solver_t* out );
+/* MinResSolver with StokesVectorBlockDiagonalPreconditioner: velocity_cycles multigrid V-cycles on the P2 epsilon operator on the levels
+ * velocity_min_level .. max_level (smoother 0 weighted Jacobi( relax ), 1 Chebyshev( order; radii null: estimated per level at
+ * construction ), pre = post steps, CG on the coarsest level) and the lumped inverse pressure mass, weighted with mu at the vertex DoFs if
+ * viscosity_weighted.  The action has to be symmetric positive definite: any other smoother, pre != post or velocity_cycles < 1 are
+ * errors.  The velocity operator's inverse diagonals are assembled on first use. */
+HYTEG_HOST_API int hyteg_host_th_epsilon_minres_create_block( hh_storage_t s, int min_level, int max_level, int max_iter, double rel_tol,
+                                                              int viscosity_weighted, hh_p2function_t mu, int velocity_min_level, int velocity_cycles,
+                                                              int smoother, int order, const double* radii /* or null */, int n_radii, double relax,
+                                                              int pre, int post, int cg_max_iter, double cg_tol, hh_th_epsilon_solver_t* out );
 HYTEG_HOST_API int hyteg_host_th_epsilon_minres_solve( hh_th_epsilon_solver_t solver, hh_th_epsilon_t op, hh_th_function_t x, hh_th_function_t b,
                                                        int level );
 /* x = P b: the preconditioner of the solver alone (tests restate MINRES around it) */

@@ -5,7 +5,9 @@ DESIGN.md section 3.  Usage: python tools/bench_kernels.py [--level 8] [--reps 2
 --only epsilon: the rows of the epsilon operator alone, levels 6..level, with the fused residual and Chebyshev steps
 against the composed sequences they replace; --only divkgrad: the same pairs for div-k-grad; --only p2-divkgrad: the two
 forms of the P2 div-k-grad apply, the constant P2 apply and a copy, levels 4..7; --only p2-epsilon: the fused P2 epsilon
-apply in its forms against three P2 div-k-grad applies on the same arrays, levels 4..7."""
+apply in its forms against three P2 div-k-grad applies on the same arrays, levels 4..7; --only p2-epsilon-modes /
+p2-divkgrad-modes: the fused residual, Jacobi and Chebyshev steps of the P2 operators against the composed sequences, levels 2..7
+(DESIGN 3.21)."""
 import argparse
 import json
 import sys
@@ -379,6 +381,90 @@ def p2_epsilon_rows(top_level, reps, from_level=4, repeats=5):
                       "shipped_inner_min_level": shipped, "kernels": rows}))
 
 
+def p2_varcoef_mode_rows(op, top_level, reps, from_level=2, repeats=5):
+    """--only p2-epsilon-modes / p2-divkgrad-modes: the fused residual, Jacobi step, Chebyshev start and Chebyshev step of a P2
+    variable-coefficient operator on the macro-cell of tet_1el, all DoFs, as shipped (the default inner_min_level), each against the
+    composed sequence on the same arrays in the same run: the apply as shipped plus the vector passes the host layer ran before the fused
+    steps (per component a vertex launch and an edge launch per pass).  Rows alternate in every one of `repeats` rounds; reported: the
+    median and the spread (min .. max).  Rings as for p2-divkgrad."""
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    st = host.Storage.from_gmsh(ROOT / "hyteg_amd/data/meshes/tet_1el.msh")
+    st.set_stream(sh)
+    tet = [list(map(float, v)) for v in st.local_cell(0)[1]]
+    nc = 3 if op == "epsilon" else 1
+    rows = []
+    for L in range(from_level, top_level + 1):
+        nv, ne = capi.cell_size(L), capi.p2_edge_array_size(L)
+        dofs = nc * (nv + ne)
+        nbuf = min(256, max(4, -(-int(2.2 * 256 * 2**20) // (ne * 8))))
+        rnd = lambda n, lo=0.0: [lo + torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(nbuf)]  # noqa: E731
+        ring = lambda lo=0.0: ([rnd(nv, lo) for _ in range(nc)], [rnd(ne, lo) for _ in range(nc)])  # noqa: E731
+        D, S, R, I, X = ring(), ring(), ring(), ring(0.5), ring()
+        KV, KE = rnd(nv, 0.5), rnd(ne, 0.5)
+        geometry = getattr(capi, f"p2_elementwise_{op}_geometry")(tet, L)
+        ptr = lambda t, k: t[k % nbuf].data_ptr()  # noqa: E731
+        arg = lambda F, k: [[ptr(t, k) for t in half] if nc == 3 else ptr(half[0], k) for half in F]  # noqa: E731
+        coef = lambda k: [ptr(KV, k), ptr(KE, k)]  # noqa: E731
+
+        def apply_(k):
+            getattr(capi, f"p2_elementwise_{op}_apply_cell")(*arg(D, k), *arg(S, k), *coef(k), L, geometry, 1.0, 0, 0x7FFF, 0xFF, sh)
+
+        def passes(k, *ops):
+            """( what, dst ring, scalars or None, source rings ): per component a vertex launch and an edge launch"""
+            for what, dst, scalars, srcs in ops:
+                for c in range(nc):
+                    sv, se = [ptr(s[0][c], k) for s in srcs], [ptr(s[1][c], k) for s in srcs]
+                    if what == "assign":
+                        capi.p1_assign_cell(ptr(dst[0][c], k), scalars, sv, L, sh)
+                    else:
+                        capi.p1_mult_cell(ptr(dst[0][c], k), sv, L, sh)
+                    capi.p2_edge_vector_cell_masked(0 if what == "assign" else 2, ptr(dst[1][c], k), se, scalars, L, 0x7FFF, sh)
+
+        def composed(*ops):
+            def fn(k):
+                apply_(k)
+                passes(k, *ops)
+            return fn
+
+        table_rows = [
+            ("residual fused", lambda k: capi.p2_varcoef_residual_cell(op, arg(D, k), arg(S, k), arg(R, k), coef(k), L, geometry, stream=sh)),
+            ("residual composed (apply + assign)", composed(("assign", D, [1.0, -1.0], [R, D]))),
+            ("Jacobi step fused",
+             lambda k: capi.p2_varcoef_jacobi_cell(op, arg(D, k), arg(S, k), arg(R, k), arg(I, k), coef(k), L, geometry, 0.6, stream=sh)),
+            ("Jacobi step composed (apply + assign + mult + assign)",
+             composed(("assign", D, [1.0, -1.0], [R, D]), ("mult", D, None, [I, D]), ("assign", D, [1.0, 0.6], [S, D]))),
+            ("Chebyshev start fused",
+             lambda k: capi.p2_varcoef_chebyshev_start_cell(op, arg(D, k), arg(S, k), arg(R, k), arg(I, k), coef(k), L, geometry, stream=sh)),
+            ("Chebyshev start composed (apply + assign + mult)", composed(("assign", D, [1.0, -1.0], [R, D]), ("mult", D, None, [I, D]))),
+            ("Chebyshev step fused", lambda k: capi.p2_varcoef_chebyshev_step_cell(op, arg(D, k), arg(X, k), arg(S, k), arg(I, k), coef(k), L, geometry,
+                                                                                     0.37, -0.21, 1, stream=sh)),
+            ("Chebyshev step composed (apply + mult + assign)", composed(("mult", D, None, [I, D]), ("assign", X, [1.0, -0.21], [X, D]))),
+            ("apply as shipped", apply_),
+        ]
+        for name, fn in table_rows:  # warm every shape
+            for k in range(3):
+                fn(k)
+        torch.cuda.synchronize()
+        times = {name: [] for name, _ in table_rows}
+        for _ in range(repeats):
+            for name, fn in table_rows:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for k in range(reps):
+                    fn(k)
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+        for name, fn in table_rows:
+            t = sorted(times[name])
+            us = t[len(t) // 2]
+            rows.append(dict(kernel=f"P2 {op} {name}", level=L, us=us, us_min=t[0], us_max=t[-1], dofs=dofs))
+            print(f"level {L}  P2 {op:9s} {name:56s} {us:10.2f} us  ({t[0]:.2f} .. {t[-1]:.2f})", flush=True)
+        del D, S, R, I, X, KV, KE
+    print(json.dumps({"levels": list(range(from_level, top_level + 1)), "device": capi.device_name(), "repeats": repeats, "kernels": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", type=int, default=8)
@@ -401,6 +487,9 @@ def main():
         return
     if args.only == "p2-epsilon":
         p2_epsilon_rows(min(L, 7), reps, min(4, max(0, args.from_level)))
+        return
+    if args.only in ("p2-epsilon-modes", "p2-divkgrad-modes"):
+        p2_varcoef_mode_rows(args.only.split("-")[1], min(L, 7), reps, min(7, max(2, args.from_level)))
         return
     n, inner = capi.cell_size(L), capi.cell_inner_size(L)
     nc = capi.cell_size(L - 1)
